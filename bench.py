@@ -5,7 +5,7 @@ One "step" = one frame of the hot path = `spp` static frames of the megakernel (
 a temporal framebuffer that starts from zero (ptamd_launch.reset_accumulation), with every input resident in HBM before the timed region starts.  1 sample = one
 execution of the reference kernel() for one pixel.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  Started as `python bench.py --gpus N` this script launches the ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, spawned before anything touches the GPU; its
@@ -47,10 +47,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# HIP maps streams onto 4 hardware queues by default; two frames-in-flight streams sharing a queue would serialise
-# (measured: -30 %; with 8 queues five frame streams collapse the same way, with 16 they do not).  Frames + RCCL's
-# streams + torch's own need more than 4: ask for 16 before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 WIDTH, HEIGHT, SPP, BOUNCES = 1920, 1080, 4, 4
 MAX_FRAMES_PER_LAUNCH = 4   # ptamd_api.cpp: kMaxFramesPerSlab — a batch of more frames is issued as consecutive launches of four
@@ -111,7 +107,36 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_latest.json"),
                     help="per-dispatch PMC averages of this workload written by scripts/summarize_pmc.py (optional)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "surface (the RGBA8 frame; the gathered frame on several GPUs) and accum (rank 0's accumulator), "
+                         f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all (beyond that a fixed, seeded sample of pixels)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(directory, arrays):
+    """Writes every (name, array) as directory/<name>.npy in float32.  When the float32 arrays together exceed
+    DUMP_LIMIT_BYTES, each array keeps the same fixed share of its pixels (first axes flattened, last axis = channels),
+    drawn with DUMP_SAMPLE_SEED and kept in pixel order: the same shapes give the same sample in every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = [(name, np.ascontiguousarray(a, dtype=np.float32)) for name, a in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    # (each .npy carries a 128-byte header)
+    keep = 1.0 if total + 128 * len(arrays) <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - 128 * len(arrays)) / total
+    for name, a in arrays:
+        if keep < 1.0:
+            px = a.reshape(-1, a.shape[-1])
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(px), int(len(px) * keep), replace=False))
+            a = px[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------- N > 1 without a launcher: start the ranks ourselves
@@ -360,6 +385,14 @@ class Workload:
     def checksum(self):
         return int(self.slots[0][0].surface.to(self.torch.int64).sum().item())
 
+    def last_outputs(self):
+        """What the last step handed its caller, as host arrays: the RGBA8 surface (the gathered frame when the step ended in
+        an all-gather of several ranks) and this rank's accumulator."""
+        fr, bg, _ = self.slots[(self.counter - 1) % self.n_slots]
+        self.torch.cuda.synchronize()
+        surface = bg.assemble() if (bg is not None and self.world > 1) else fr.surface
+        return [("surface", surface.cpu().numpy()), ("accum", fr.accum.cpu().numpy())]
+
     def close(self):
         self.slots = []
         self.ctx.close()
@@ -506,6 +539,8 @@ def main():
                   local_rank, world, rank, gather, rows, interleave, machine_share=args.machine_share)
     proxy = rows is not None or (interleave is not None and world == 1)
     dt, step_ms = wl.run(args.steps, args.warmup, args.settle_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.last_outputs())
     gather_ms = wl.gather_ms() if (world > 1 or force_gather) else None
     frames_per_launch = wl.frames_per_launch
     launches_per_step = -(-spp // frames_per_launch)

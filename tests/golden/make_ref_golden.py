@@ -12,6 +12,8 @@ they lie under /root/reference).  The fixture holds only outputs (digests and bi
   resize_sha256         sha256 over stbir_resize_float's outputs for the seeded cases of test_ref_thirdparty.resize_cases
 
 so that the loader / decoder stay pinned where /root/reference is absent (tests/test_ref_thirdparty.py).
+The library's outputs for the inputs of tests/test_ref_thirdparty.py itself are recorded in ref_thirdparty_calls.json
+by that module (PTAMD_RECORD_REF_CALLS=1).
 """
 import glob
 import hashlib
