@@ -326,6 +326,7 @@ struct KParams {
   uint32_t xcd_regions;           // restart kernel: != 0: tickets map to tiles through XCD-local regions (pt_kernels.hip: region_tile); needs n_static % 8 == 0 and tiles_per_ticket == 1
   uint32_t brute_walk;            // restart kernel: the launch wants the instantiation that tests every triangle record instead of walking the tree (far origin)
   unsigned long long* timeline;   // restart kernel: != nullptr selects the instantiation that records 4 time stamps per wave (ptamd_set_timeline)
+  uint32_t generic_round;         // restart kernel: != 0 sends a resident scene's launch to the generic instantiation even when the shipped one serves it (PTAMD_RS_GENERIC)
 };
 // LDS bytes of one wave's pool of fresh paths (restart kernel: 64 entries x 9 dwords)
 #define PT_POOL_LDS_BYTES 2304u

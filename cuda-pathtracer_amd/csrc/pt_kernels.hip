@@ -786,13 +786,15 @@ PT_DEV void path_begin(const KParams& p, uint32_t x, uint32_t y, Path& st, uint3
 // so that the search can run in another lane (workgroup ray compaction):
 //   r1 = path_pre(st);  n = trace_nearest(st.o, st.d);  done = path_post(st, r1, n);
 // When the camera moved, the "iteration" is the whole preview sample (raytrace.cu:54-62).
+// STATIC: the instantiation only ever runs launches with is_static set (restart kernel, PT_RS_PLAIN on an LDS-resident scene)
+template <bool STATIC = false>
 PT_DEV float path_pre(const KParams& p, Path& st)
 {
-  return p.is_static ? xorwow_uniform(st.rng) : 0.0f; // raytrace.cu:70: drawn before tracing
+  return (STATIC || p.is_static) ? xorwow_uniform(st.rng) : 0.0f; // raytrace.cu:70: drawn before tracing
 }
 
 // Returns true when the path is complete (st.acc is final).
-template <bool STATS>
+template <bool STATS, bool STATIC = false>
 PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Counters& cnt)
 {
   Hit inter;
@@ -807,7 +809,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
     if (PT_WAVE_ONE()) cnt.cyc[8] += (unsigned long long)(ts1 - ts0);
   }
 
-  if (!p.is_static) {
+  if (!STATIC && !p.is_static) {
     st.acc = found ? inter.diffuse_col : env_lookup(p, st.d);
     return true;
   }
@@ -2022,6 +2024,7 @@ PT_DEV bool region_tile(const KParams& p, uint32_t ticket, uint32_t& col, uint32
 #define PT_RS_BRUTE 3
 #define PT_RS_WIDE8 4   /* scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one */
 #define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
+#define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
 
 template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
@@ -2029,6 +2032,10 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
 {
   constexpr bool STATS = VARIANT == PT_RS_STATS;
   constexpr uint32_t THREADS = LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS;
+  // The shipped instantiation (LDS-resident scene, PT_RS_PLAIN) serves only the common launch, which fixes four launch constants:
+  // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
+  // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
+  constexpr bool LEAN = LDS_RESIDENT && VARIANT == PT_RS_PLAIN;
   extern __shared__ float4 s_mem[];
   const float4* s_nodes;
   const float4* s_tris;
@@ -2079,7 +2086,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   uint32_t tile_row_delta = 0;   // (frame row) - (row of the launch's buffers + row_begin): non-zero for interleaved bands
   uint32_t tile = 0, tile_end = 0;
   // XCD-local regions (KParams::xcd_regions): the waves of XCD x take the tickets = x (mod 8), their first ones without an atomic
-  uint32_t ticket = PT_KARG(p, xcd_regions) ? ((blockIdx.x >> 3) * (THREADS / 64u) + (threadIdx.x >> 6)) * 8u + (blockIdx.x & 7u) : gwave;
+  uint32_t ticket = (!LEAN && PT_KARG(p, xcd_regions)) ? ((blockIdx.x >> 3) * (THREADS / 64u) + (threadIdx.x >> 6)) * 8u + (blockIdx.x & 7u) : gwave;
   ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);   // wave-uniform: the tile arithmetic stays scalar
   uint32_t reg_col = 0, reg_row = 0, reg_k = 0;
   uint32_t head = blockIdx.x & 7u, dry = 0;
@@ -2106,12 +2113,12 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
               ticket = PT_KARG(p, n_static) + t * 8u + head;
             }
             have_ticket = false;
-            if (PT_KARG(p, xcd_regions) ? region_tile(p, ticket, reg_col, reg_row, reg_k) : ((unsigned long long)ticket * tiles_per_ticket < total)) break;
+            if ((!LEAN && PT_KARG(p, xcd_regions)) ? region_tile(p, ticket, reg_col, reg_row, reg_k) : ((unsigned long long)ticket * tiles_per_ticket < total)) break;
             head = (head + 1u) & 7u;
             if (++dry == 8u) break;
           }
           if (dry == 8u) { exhausted = true; PT_STAMP(2); break; }
-          if (PT_KARG(p, xcd_regions)) { tile = ticket; tile_end = ticket + 1u; }
+          if (!LEAN && PT_KARG(p, xcd_regions)) { tile = ticket; tile_end = ticket + 1u; }
           else {
             tile = ticket * tiles_per_ticket;
             tile_end = tile + tiles_per_ticket;
@@ -2121,7 +2128,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         {
           const uint32_t n_tiles = PT_KARG(p, n_tiles), tiles_x = PT_KARG(p, tiles_x), row_begin = PT_KARG(p, row_begin);
           uint32_t local_y0;                                      // row inside this launch's share of the frame
-          if (PT_KARG(p, xcd_regions)) {
+          if (!LEAN && PT_KARG(p, xcd_regions)) {
             tile_k = reg_k; tile_x0 = reg_col * PT_TILE_W; local_y0 = reg_row * PT_TILE_H;
           } else {
             tile_k = tile / n_tiles;
@@ -2129,7 +2136,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
             tile_x0 = (tl % tiles_x) * PT_TILE_W;
             local_y0 = (tl / tiles_x) * PT_TILE_H;
           }
-          const uint32_t ilv_ranks = PT_KARG(p, ilv_ranks);
+          const uint32_t ilv_ranks = LEAN ? 0u : PT_KARG(p, ilv_ranks);
           if (ilv_ranks > 1u) {
             // interleaved bands: band j of ilv_rows rows belongs to rank j % ilv_ranks; this launch renders
             // the bands of rank ilv_rank and stores them one after the other
@@ -2147,11 +2154,11 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
           if (x < p.width && y < p.y_limit) {
             Path fresh;
             path_begin(p, x, y, fresh, tile_k);
-            if (p.pool_lds_offset) pool_store_lds(lds_pool, lane, fresh);
+            if (LEAN || p.pool_lds_offset) pool_store_lds(lds_pool, lane, fresh);
             else pool_store(slab, lane, fresh);
           }
           // the stores have reached L2 (LDS: are ordered before this wave's later reads) before any lane reads them back
-          if (!p.pool_lds_offset) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          if (!LEAN && !p.pool_lds_offset) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         pool_rd = 0u;
       }
@@ -2161,7 +2168,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         const uint32_t e = pool_rd + rank;
         const uint32_t x = tile_x0 + (e & (PT_TILE_W - 1u)), y = tile_y0 + (e >> PT_TILE_W_LOG2);
         if (x < p.width && y < p.y_limit) {   // entries of pixels outside the frame were never written: skip them
-          if (p.pool_lds_offset) pool_load_lds(lds_pool, e, st);
+          if (LEAN || p.pool_lds_offset) pool_load_lds(lds_pool, e, st);
           else pool_load(slab, e, st);
           st.throughput = mk3(1.0f);
           st.acc = mk3(0.0f);
@@ -2212,14 +2219,14 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         // path's random stream is the same, and r1 need not live (in scratch, as it turned out) across the walk
         long long tl0 = 0;
         if (STATS) tl0 = clock64();
-        const float r1 = path_pre(p, st);
+        const float r1 = path_pre<LEAN>(p, st);
         Nearest n;
         n.t = best.t; n.u = best.u; n.v = best.v; n.idx = best.idx;
         n = nearest_lights(p, st.o, st.d, n);
         walking = false;
         long long tl1 = 0;
         if (STATS) { asm volatile("" : "+v"(n.t), "+v"(n.idx)); tl1 = clock64(); if (PT_WAVE_ONE()) cnt.cyc[3] += (unsigned long long)(tl1 - tl0); }   // [3]: r1 + light loop
-        if (path_post<STATS>(p, st, r1, n, cnt)) {
+        if (path_post<STATS, LEAN>(p, st, r1, n, cnt)) {
           path_finish_sample(p, st);
           idle = true;
           if (STATS) samples++;
@@ -2905,6 +2912,7 @@ static const void* restart_entry(int variant)
   switch (variant) {
 #ifdef PT_FMA_BUILD
     case PT_RS_BRUTE: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_BRUTE>);
+    case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);
     default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
   }
 }
@@ -2918,14 +2926,18 @@ static const void* restart_entry_unused(int variant)
     case PT_RS_BRUTE: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_BRUTE>);
     case PT_RS_WIDE8: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE8>);   // (only ever a non-resident scene)
     case PT_RS_WIDE4Q: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE4Q>);
+    case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);   // (only ever a resident scene)
     default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
   }
 }
 
-// variant: instrumented build when counters are wanted, else the far-origin form, else the time-stamp form, else the shipped kernel
+// variant: instrumented build when counters are wanted, else the far-origin form, else the time-stamp form, else the shipped kernel —
+// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form
 static const void* restart_select(bool lds_resident, bool stats, const KParams* p = nullptr)
 {
-  const int variant = stats ? PT_RS_STATS : (p && p->brute_walk ? PT_RS_BRUTE : (p && p->timeline ? PT_RS_STAMPS : (p && p->wide8 && !lds_resident ? (p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8) : PT_RS_PLAIN)));
+  const bool lean = !p || (p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !p->generic_round);
+  const int variant = stats ? PT_RS_STATS : (p && p->brute_walk ? PT_RS_BRUTE : (p && p->timeline ? PT_RS_STAMPS : (p && p->wide8 && !lds_resident ? (p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8) :
+                      (lds_resident && !lean ? PT_RS_GENERIC : PT_RS_PLAIN))));
   return lds_resident ? restart_entry<true>(variant) : restart_entry<false>(variant);
 }
 
@@ -3077,7 +3089,7 @@ hipError_t resolve_kernels()
     persistent_select(true, false), persistent_select(false, false), persistent_select(true, true), persistent_select(false, true),
     split_select(true, false), split_select(false, false), blockwise_select(true, false), blockwise_select(false, false),
     restart_entry<true>(PT_RS_PLAIN), restart_entry<false>(PT_RS_PLAIN), restart_entry<true>(PT_RS_STATS), restart_entry<false>(PT_RS_STATS),
-    restart_entry<true>(PT_RS_STAMPS), restart_entry<false>(PT_RS_STAMPS), restart_entry<true>(PT_RS_BRUTE), restart_entry<false>(PT_RS_BRUTE), restart_entry<false>(PT_RS_WIDE8), restart_entry<false>(PT_RS_WIDE4Q),
+    restart_entry<true>(PT_RS_STAMPS), restart_entry<false>(PT_RS_STAMPS), restart_entry<true>(PT_RS_BRUTE), restart_entry<false>(PT_RS_BRUTE), restart_entry<false>(PT_RS_WIDE8), restart_entry<false>(PT_RS_WIDE4Q), restart_entry<true>(PT_RS_GENERIC),
     reinterpret_cast<const void*>(pt_megakernel<1, true, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<1, false, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<2, true, false, PT_TILE_THREADS>),

@@ -115,6 +115,7 @@ struct ptamd_context {
   hipStream_t internal[2] = { nullptr, nullptr };
   bool overlap = true;                    // PTAMD_OVERLAP=0 (tuning): everything on the caller's stream
   bool wide4q = false;                    // PTAMD_WIDE4Q=1 (tuning): big scenes walk the 64-byte quantised four-wide nodes instead of the float ones (ahead by 2.8 % while the walk's LDS accesses went out as FLAT instructions, level since they are LDS instructions: profiles/r03_notes.md)
+  bool generic_round = false;             // PTAMD_RS_GENERIC=1 (tuning): resident scenes take the restart kernel's generic instantiation (launch constants read at run time), for A/B and tests
   bool wide8 = false;                     // PTAMD_WIDE8=1 (tuning): big scenes walk the eight-wide quantised nodes (measured 8 % slower: DESIGN.md §4)
   uint2* d_trace_spill = nullptr;             // ptamd_trace_rays_queue: global continuation of the walk-only kernel's stacks (grown on demand)
   struct { uint32_t config = ~0u; size_t lds = 0; int resident = 0; } trace_queue_cache;   // ... its last configuration: dynamic-LDS attribute set, blocks resident per CU
@@ -374,6 +375,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     if (which == PTAMD_KERNEL_BVH_RESTART) p.brute_walk = 1u;
     else which = PTAMD_KERNEL_BRUTE_FORCE;
   }
+  p.generic_round = ctx->generic_round ? 1u : 0u;
   // only the restart kernel maps its tiles to the rows of interleaved bands; every other kernel would render the whole
   // frame into the band-local buffers (PTAMD_DEFAULT_KERNEL behind PTAMD_KERNEL_AUTO can ask for one)
   if (l->interleave_ranks > 1u && which != PTAMD_KERNEL_BVH_RESTART) {
@@ -792,6 +794,7 @@ int ptamd_create(int32_t device_ordinal, ptamd_context** out)
   }
   if (const char* e = tuning_env("PTAMD_SHORT_RCP")) ctx->short_rcp = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_WIDE8")) ctx->wide8 = std::atoi(e) != 0; // tuning knob
+  if (const char* e = tuning_env("PTAMD_RS_GENERIC")) ctx->generic_round = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_WIDE4Q")) ctx->wide4q = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS")) ctx->pool_in_lds = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS_WIDE")) ctx->pool_in_lds_wide = std::atoi(e) != 0; // tuning knob

@@ -32,3 +32,9 @@ with P.Context(0) as ctx:
         if name == "restart":
             print("  rounds per wave-tile %.2f, walks completed per round %.1f" % (
                 s["fetch_events"] * 64.0 / s["samples"], s["fetch_rays"] / max(s["fetch_events"], 1)))
+            # shader-clock cycles of the waves by phase (instrumented build: shares, not absolutes); the shading half of a round
+            # is refill [0], r1 + lights [3], record fetch [8], path_post + parking [9] ([10] up to the BSDF, [11] the BSDF)
+            c = ctx.phase_cycles()
+            tot = max(c["round_loop"], 1)
+            print("  phase cycles (share of the round loop): " + ", ".join("%s %.3f" % (k, v / tot) for k, v in c.items() if k != "round_loop"))
+            print("  phase cycles per sample: " + ", ".join("%s %.0f" % (k, v / s["samples"]) for k, v in c.items()))

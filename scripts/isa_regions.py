@@ -2,7 +2,8 @@
 """Static instruction counts of the restart kernel per source region: compiles a scratch copy of pt_kernels.hip with
 assembler-comment markers at the region boundaries and counts VALU / SALU / LDS / scratch / lane-spill instructions between
 them in the ISA listing (block placement follows the source closely enough for this to be a useful map; the markers are
-scheduling barriers, so the listing differs slightly from the shipped code).   python3 scripts/isa_regions.py [--dump REGION]"""
+scheduling barriers, so the listing differs slightly from the shipped code).   python3 scripts/isa_regions.py [--dump REGION]
+VARIANT=6 counts the generic instantiation of a resident scene (PT_RS_GENERIC) instead of the shipped one (0)."""
 import os, re, subprocess, sys, tempfile, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")
@@ -10,9 +11,9 @@ MARKS = [  # (unique source anchor, marker name) — the marker goes in front of
     ("    if (!idle) {\n      if (!walking) {\n        best.t = PT_MAX_DIST;", "round_begin"),
     ("      } else if (WIDE) {\n        traverse_round4<STATS, VARIANT == PT_RS_WIDE8", "traverse_begin"),
     ("      if (node == PT_END) {\n        // the iteration's first variate", "traverse_end"),
-    ("        if (path_post<STATS>(p, st, r1, n, cnt)) {\n          path_finish_sample(p, st);", "lights_end"),
+    ("        if (path_post<STATS, LEAN>(p, st, r1, n, cnt)) {\n          path_finish_sample(p, st);", "lights_end"),
     ("          path_finish_sample(p, st);\n          idle = true;\n          if (STATS) samples++;", "post_end"),
-    ("  if (!p.is_static) {\n    st.acc = found ? inter.diffuse_col : env_lookup(p, st.d);", "resolve_end"),
+    ("  if (!STATIC && !p.is_static) {\n    st.acc = found ? inter.diffuse_col : env_lookup(p, st.d);", "resolve_end"),
     ("  const f3 d = st.d;\n  const float cos_theta = dot(inter.normal, d);", "miss_end"),
     ("  const float pmax = __builtin_fmaxf(st.throughput.x, __builtin_fmaxf(st.throughput.y, st.throughput.z));\n  if (r1 > pmax && st.b() > 1u) return true;\n  st.throughput = st.throughput * rcp_hot(pmax);\n  ++st.bk;\n  return", "bsdf_end"),
 ]
@@ -28,7 +29,7 @@ with tempfile.TemporaryDirectory() as td:
                            "-I" + os.path.join(ROOT, "cuda-pathtracer_amd", "csrc"), "-x", "hip", "--cuda-device-only", "-S", "-o", out, src],
                           stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")
-start = [i for i, l in enumerate(lines) if l.startswith("_ZN5ptamd21pt_megakernel_restartILb1ELi0EEEvNS_7KParamsE:")][0]
+start = [i for i, l in enumerate(lines) if l.startswith("_ZN5ptamd21pt_megakernel_restartILb1ELi%sEEEvNS_7KParamsE:" % os.environ.get("VARIANT", "0"))][0]
 end = [i for i, l in enumerate(lines) if i > start and re.match(r"\.Lfunc_end\d+:", l)][0]
 marks = [(i, re.search(r"; PT_MARK (\w+)", lines[i]).group(1)) for i in range(start, end) if "; PT_MARK" in lines[i]]
 bounds = [(start, "prologue")] + marks + [(end, "end")]
