@@ -18,22 +18,25 @@ namespace ptamd {
 struct f3 { float x, y, z; };
 
 #define PT_DEV __device__ __forceinline__
+// arithmetic shared by the device code and the host mirror of the denoiser (pt_denoise.h, ptamd_host_denoise): the same float
+// operations on both sides (both are compiled with -ffp-contract=off)
+#define PT_HD __host__ __device__ __forceinline__
 
-PT_DEV f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
-PT_DEV f3 mk3(float s) { return mk3(s, s, s); }
-PT_DEV f3 operator+(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-PT_DEV f3 operator+(f3 a, float b) { return mk3(a.x + b, a.y + b, a.z + b); }
-PT_DEV f3 operator-(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-PT_DEV f3 operator-(f3 a, float b) { return mk3(a.x - b, a.y - b, a.z - b); }
-PT_DEV f3 operator-(f3 a) { return mk3(-a.x, -a.y, -a.z); }
-PT_DEV f3 operator*(f3 a, f3 b) { return mk3(a.x * b.x, a.y * b.y, a.z * b.z); }
-PT_DEV f3 operator*(f3 a, float b) { return mk3(a.x * b, a.y * b, a.z * b); }
-PT_DEV f3 operator*(float b, f3 a) { return mk3(b * a.x, b * a.y, b * a.z); }
-PT_DEV f3 operator/(f3 a, f3 b) { return mk3(a.x / b.x, a.y / b.y, a.z / b.z); }
-PT_DEV f3 operator/(f3 a, float b) { return mk3(a.x / b, a.y / b, a.z / b); }
-PT_DEV f3 operator/(float b, f3 a) { return mk3(b / a.x, b / a.y, b / a.z); }
-PT_DEV float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-PT_DEV f3 cross(f3 a, f3 b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+PT_HD f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
+PT_HD f3 mk3(float s) { return mk3(s, s, s); }
+PT_HD f3 operator+(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
+PT_HD f3 operator+(f3 a, float b) { return mk3(a.x + b, a.y + b, a.z + b); }
+PT_HD f3 operator-(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
+PT_HD f3 operator-(f3 a, float b) { return mk3(a.x - b, a.y - b, a.z - b); }
+PT_HD f3 operator-(f3 a) { return mk3(-a.x, -a.y, -a.z); }
+PT_HD f3 operator*(f3 a, f3 b) { return mk3(a.x * b.x, a.y * b.y, a.z * b.z); }
+PT_HD f3 operator*(f3 a, float b) { return mk3(a.x * b, a.y * b, a.z * b); }
+PT_HD f3 operator*(float b, f3 a) { return mk3(b * a.x, b * a.y, b * a.z); }
+PT_HD f3 operator/(f3 a, f3 b) { return mk3(a.x / b.x, a.y / b.y, a.z / b.z); }
+PT_HD f3 operator/(f3 a, float b) { return mk3(a.x / b, a.y / b, a.z / b); }
+PT_HD f3 operator/(float b, f3 a) { return mk3(b / a.x, b / a.y, b / a.z); }
+PT_HD float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+PT_HD f3 cross(f3 a, f3 b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 // cutils_math.h:70-74,1557: v * (1.0f / sqrtf(dot))
 PT_DEV f3 normalize(f3 v) { float inv_len = 1.0f / __builtin_sqrtf(dot(v, v)); return v * inv_len; }
 
@@ -96,7 +99,7 @@ PT_DEV f3 reflect(f3 i, f3 n) { return i - (2.0f * n) * dot(n, i); }
 // cutils_math.h:1722
 PT_DEV f3 mix(f3 x, f3 y, float a) { return (x * (1.0f - a)) + y * a; }
 // cutils_math.h:44-56,1357: NaN-propagating-to-1 clamp
-PT_DEV float clamp01(float f) { float m = f < 1.0f ? f : 1.0f; return 0.0f > m ? 0.0f : m; }
+PT_HD float clamp01(float f) { float m = f < 1.0f ? f : 1.0f; return 0.0f > m ? 0.0f : m; }
 
 PT_DEV uint32_t f_as_u(float f) { return __float_as_uint(f); }
 PT_DEV float u_as_f(uint32_t u) { return __uint_as_float(u); }
@@ -136,8 +139,24 @@ __constant__ double kPowExp[14] = { 1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 /
                                     1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0,
                                     1.0 / 24.0, 1.0 / 6.0, 0.5, 1.0, 1.0 };
 
+#ifndef __HIP_DEVICE_COMPILE__
+// the host mirror's copy of the two tables (same values)
+static constexpr double kPowLogHost[9] = { 1.0 / 17.0, 1.0 / 15.0, 1.0 / 13.0, 1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0, 1.0 / 5.0, 1.0 / 3.0, 1.0 };
+static constexpr double kPowExpHost[14] = { 1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0,
+                                            1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0,
+                                            1.0 / 24.0, 1.0 / 6.0, 0.5, 1.0, 1.0 };
+#define kPowLog kPowLogHost
+#define kPowExp kPowExpHost
+#define __double_as_longlong(x) __builtin_bit_cast(long long, (double)(x))
+#define __longlong_as_double(x) __builtin_bit_cast(double, (long long)(x))
+#endif
+
 // powf evaluated in binary64: 2^(y*log2 x)
-__device__ __noinline__ float pt_powf(float xf, float yf)
+#ifdef __HIP_DEVICE_COMPILE__
+__host__ __device__ __noinline__ float pt_powf(float xf, float yf)
+#else
+static __host__ __device__ __noinline__ float pt_powf(float xf, float yf)   // (one copy per translation unit on the host)
+#endif
 {
   if (yf == 0.0f || xf == 1.0f) return 1.0f;
   if (xf != xf || yf != yf) return __builtin_nanf("");
@@ -189,13 +208,91 @@ __device__ __noinline__ float pt_powf(float xf, float yf)
   }
   return (float)(negate ? -res : res);
 }
+#ifndef __HIP_DEVICE_COMPILE__
+#undef kPowLog
+#undef kPowExp
+#undef __double_as_longlong
+#undef __longlong_as_double
+#endif
 
 // cvt.rzi.u32.f32 semantics of the reference's bit-field stores (raytrace.cu:266-268)
-PT_DEV uint32_t pt_f2u(float v)
+PT_HD uint32_t pt_f2u(float v)
 {
   if (!(v > 0.0f)) return 0u;
   if (v >= 4294967296.0f) return 0xffffffffu;
   return (uint32_t)v;
+}
+
+// ---------------------------------------------------------------- the resolve pass's output stage (raytrace.cu:259-268)
+// Shared by the resolve kernels (pt_kernels.hip), the denoiser's last pass and its host mirror (pt_denoise.h).
+
+PT_HD f3 uncharted_tonemap(f3 x) // post_process.cuh:14-25
+{
+  const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
+  return ((x * (A * x + C * B) + D * E) / (x * (A * x + B) + D * F)) - E / F;
+}
+
+PT_HD f3 exposure(f3 color) // post_process.cuh:31-41
+{
+  const float exposure_bias = 2.0f;
+  const f3 curr = uncharted_tonemap(exposure_bias * color);
+  const f3 W = mk3(11.2f);
+  const f3 white_scale = 1.0f / uncharted_tonemap(W);
+  return curr * white_scale;
+}
+
+PT_HD f3 post_process(uint32_t id, f3 c) // raytrace.cu:327-352
+{
+  if (id == 1) {
+    const float gray = (float)((double)c.x * 0.3 + (double)c.y * 0.59 + (double)c.z * 0.11);
+    return mk3(gray, gray, gray);
+  }
+  if (id == 2)
+    return mk3((float)((double)c.x * 0.393 + (double)c.y * 0.769 + (double)c.z * 0.189),
+               (float)((double)c.x * 0.349 + (double)c.y * 0.686 + (double)c.z * 0.168),
+               (float)((double)c.x * 0.272 + (double)c.y * 0.534 + (double)c.z * 0.131));
+  if (id == 3)
+    return mk3((float)(1.0 - (double)c.x), (float)(1.0 - (double)c.y), (float)(1.0 - (double)c.z));
+  return c;
+}
+
+// the gamma step of the tonemap: the definition, and (device code only) its table form (pt_kernels.hip: "the gamma step of the
+// tonemap as a table")
+PT_HD uint32_t gamma_byte_exact(float x)   // the definition (post_id 0): what the reference's store sequence produces
+{
+  return pt_f2u(pt_powf(x, 1.0f / 2.2f) * 255.0f) & 0xffu;
+}
+PT_HD uint32_t gamma_value_exact(float x) { return pt_f2u(pt_powf(x, 1.0f / 2.2f) * 255.0f); }
+
+// T points at 258 floats (LDS copy in the resolve kernels).  Valid for every x: values at or above T[256], and NaN, take the
+// pt_powf form; negative values and zero give 0 either way (pt_powf: NaN or 0 -> pt_f2u -> 0).
+template <typename TablePtr>
+PT_DEV uint32_t gamma_byte(float x, TablePtr T)
+{
+  if (!(x < T[256])) return gamma_byte_exact(x);
+  if (!(x > 0.0f)) return 0u;
+  const float est = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 2.2f)) * 255.0f;
+  int k = (int)est;
+  k = k < 0 ? 0 : (k > 255 ? 255 : k);
+  k = x < T[k] ? k - 1 : k;          // T[0] = 0 < x: k stays >= 0
+  k = x >= T[k + 1] ? k + 1 : k;     // x < T[256]: k stays <= 255
+  return (uint32_t)k;
+}
+
+// colour / frame number -> RGBA8: tonemap, gamma (read off the gamma table when `use_table` — the resolve passes set it for
+// post_id 0 when the context has a table —, else pt_powf), post-process, pack.  The host side always takes the pt_powf form,
+// which the table reproduces for every input (ptamd_gamma_table_selftest).
+template <typename TablePtr>
+PT_HD uint32_t output_pixel(f3 rad, uint32_t post_id, bool use_table, TablePtr T)
+{
+  rad = exposure(rad);
+#ifdef __HIP_DEVICE_COMPILE__
+  if (use_table) return gamma_byte(rad.x, T) | (gamma_byte(rad.y, T) << 8) | (gamma_byte(rad.z, T) << 16);
+#endif
+  const float g = 1.0f / 2.2f;
+  rad = mk3(pt_powf(rad.x, g), pt_powf(rad.y, g), pt_powf(rad.z, g));
+  rad = post_process(post_id, rad);
+  return (pt_f2u(rad.x * 255.0f) & 0xffu) | ((pt_f2u(rad.y * 255.0f) & 0xffu) << 8) | ((pt_f2u(rad.z * 255.0f) & 0xffu) << 16);
 }
 
 // ---------------------------------------------------------------- RNG (cuRAND XORWOW restated)

@@ -20,6 +20,9 @@
 //     raytrace.cu:194-199), so its remaining iterations skip the walk — exact.
 #include "pt_device.h"
 #include "pt_launch.h"
+#ifndef PT_FMA_BUILD
+#include "pt_denoise.h"
+#endif
 
 namespace ptamd {
 
@@ -900,35 +903,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
 
 // ---------------------------------------------------------------- post process
 
-PT_DEV f3 uncharted_tonemap(f3 x) // post_process.cuh:14-25
-{
-  const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
-  return ((x * (A * x + C * B) + D * E) / (x * (A * x + B) + D * F)) - E / F;
-}
-
-PT_DEV f3 exposure(f3 color) // post_process.cuh:31-41
-{
-  const float exposure_bias = 2.0f;
-  const f3 curr = uncharted_tonemap(exposure_bias * color);
-  const f3 W = mk3(11.2f);
-  const f3 white_scale = 1.0f / uncharted_tonemap(W);
-  return curr * white_scale;
-}
-
-PT_DEV f3 post_process(uint32_t id, f3 c) // raytrace.cu:327-352
-{
-  if (id == 1) {
-    const float gray = (float)((double)c.x * 0.3 + (double)c.y * 0.59 + (double)c.z * 0.11);
-    return mk3(gray, gray, gray);
-  }
-  if (id == 2)
-    return mk3((float)((double)c.x * 0.393 + (double)c.y * 0.769 + (double)c.z * 0.189),
-               (float)((double)c.x * 0.349 + (double)c.y * 0.686 + (double)c.z * 0.168),
-               (float)((double)c.x * 0.272 + (double)c.y * 0.534 + (double)c.z * 0.131));
-  if (id == 3)
-    return mk3((float)(1.0 - (double)c.x), (float)(1.0 - (double)c.y), (float)(1.0 - (double)c.z));
-  return c;
-}
+// (uncharted_tonemap, exposure, post_process: pt_device.h, shared with the host mirror of the denoiser)
 
 // ---------------------------------------------------------------- LDS staging
 
@@ -956,26 +931,7 @@ PT_DEV bool path_step(const KParams& p, const float4* s_nodes, const float4* s_t
 // over bit patterns per step) and the byte is read off them: a 3-instruction estimate (v_log, v_mul, v_exp) that is
 // within one step of the answer, corrected by two comparisons against the table.  ptamd_gamma_table_selftest compares the
 // result with the pt_powf form for EVERY binary32 value below T[256] on the device.
-PT_DEV uint32_t gamma_byte_exact(float x)   // the definition (post_id 0): what the reference's store sequence produces
-{
-  return pt_f2u(pt_powf(x, 1.0f / 2.2f) * 255.0f) & 0xffu;
-}
-PT_DEV uint32_t gamma_value_exact(float x) { return pt_f2u(pt_powf(x, 1.0f / 2.2f) * 255.0f); }
-
-// T points at 258 floats (LDS copy in the resolve kernels).  Valid for every x: values at or above T[256], and NaN, take the
-// pt_powf form; negative values and zero give 0 either way (pt_powf: NaN or 0 -> pt_f2u -> 0).
-template <typename TablePtr>
-PT_DEV uint32_t gamma_byte(float x, TablePtr T)
-{
-  if (!(x < T[256])) return gamma_byte_exact(x);
-  if (!(x > 0.0f)) return 0u;
-  const float est = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 2.2f)) * 255.0f;
-  int k = (int)est;
-  k = k < 0 ? 0 : (k > 255 ? 255 : k);
-  k = x < T[k] ? k - 1 : k;          // T[0] = 0 < x: k stays >= 0
-  k = x >= T[k + 1] ? k + 1 : k;     // x < T[256]: k stays <= 255
-  return (uint32_t)k;
-}
+// (gamma_byte_exact, gamma_byte: pt_device.h, beside the output stage that uses them)
 
 // kernel() epilogue: clamp, temporal accumulation, tonemap, gamma, post-process, RGBA8 store
 // (raytrace.cu:248-270)
@@ -2678,18 +2634,10 @@ __global__ void __launch_bounds__(256) pt_resolve_kernel4(PT_KERNEL_PARAMS)
   }
   tp[0] = make_float4(t[0], t[1], t[2], t[3]); tp[1] = make_float4(t[4], t[5], t[6], t[7]); tp[2] = make_float4(t[8], t[9], t[10], t[11]);
   uint32_t px[4];
-  const float g22 = 1.0f / 2.2f;
   for (int q = 0; q < 4; ++q) {
     const f3 tq = mk3(t[q * 3 + 0], t[q * 3 + 1], t[q * 3 + 2]);
-    f3 rad = p.frame_nb_inv != 0.0f ? tq * p.frame_nb_inv : tq / p.frame_nb_f;   // KParams::frame_nb_inv
-    rad = exposure(rad);
-    if (use_table) {
-      px[q] = gamma_byte(rad.x, s_gamma) | (gamma_byte(rad.y, s_gamma) << 8) | (gamma_byte(rad.z, s_gamma) << 16);
-      continue;
-    }
-    rad = mk3(pt_powf(rad.x, g22), pt_powf(rad.y, g22), pt_powf(rad.z, g22));
-    rad = post_process(p.post_id, rad);
-    px[q] = (pt_f2u(rad.x * 255.0f) & 0xffu) | ((pt_f2u(rad.y * 255.0f) & 0xffu) << 8) | ((pt_f2u(rad.z * 255.0f) & 0xffu) << 16);
+    const f3 rad = p.frame_nb_inv != 0.0f ? tq * p.frame_nb_inv : tq / p.frame_nb_f;   // KParams::frame_nb_inv
+    px[q] = output_pixel(rad, p.post_id, use_table, s_gamma);
   }
   *reinterpret_cast<uint4*>(p.surface + (size_t)(y - p.surf_row0) * p.width + x0) = make_uint4(px[0], px[1], px[2], px[3]);
 }
@@ -2829,6 +2777,76 @@ __global__ void __launch_bounds__(256) pt_trace_rays_kernel(PT_KERNEL_PARAMS, co
   const int index = kind == 0 ? -1 : (int)(nr.idx & ~PT_LIGHT);
   out[i] = make_int4(kind, index, (int)f_as_u(nr.t), 0);
 }
+
+#ifndef PT_FMA_BUILD   /* (not in the contracted translation unit: pt_kernels_fma.hip) */
+// ---------------------------------------------------------------- denoiser (ptamd_denoise, ptamd_render_features; pt_denoise.h)
+
+// Feature pass: per pixel of a full frame, the camera ray path_begin builds with the aperture offset zero (origin cam_pos,
+// direction normalize_hot(focus_dist * dir): with aperture 0 the ray of a preview launch, bit for bit), its nearest hit through
+// the binary tree from L2 (KIND 2) or every face (KIND 1: origins outside the tree's margins), decoded by resolve_hit.  Writes the
+// two feature records of the pixel (pt_denoise.h) and, when `rays` is set, the ray {dir, origin}.  16x16 pixels per block.
+template <int KIND>
+__global__ void __launch_bounds__(256) pt_features_kernel(PT_KERNEL_PARAMS, float4* feat, float* rays)
+{
+  const uint32_t x = blockIdx.x * 16u + (threadIdx.x & 15u), y = blockIdx.y * 16u + (threadIdx.x >> 4);
+  if (x >= p.width || y >= p.height) return;
+  const int half_w = (int)(p.width / 2u), half_h = (int)(p.height / 2u);
+  const f3 screen_pos = (p.cam_p0 + (p.cam_u * (float)((int)x - half_w))) + (p.cam_v * (float)((int)y - half_h));
+  const f3 dir = normalize_hot(screen_pos - p.cam_pos);
+  const f3 d = normalize_hot(p.focus_dist * dir);
+  const f3 o = p.cam_pos;
+  Counters cnt = {};
+  const Nearest n = trace_nearest<KIND, false>(p, p.nodes, KIND == 1 ? p.tris_brute : p.tris_bvh, o, d, cnt);
+  Hit hit;
+  hit.normal = mk3(0.f); hit.diffuse_col = mk3(0.f);
+  hit.dist = 0.f; hit.specular_col = 0.f; hit.ior = 0.f; hit.light = -1; hit.emission = 0.f;
+  const bool found = resolve_hit<false>(p, d, n, hit, cnt);
+  const uint32_t kind = !found ? PT_FEAT_MISS : ((n.idx & PT_LIGHT) ? PT_FEAT_LIGHT : PT_FEAT_MESH);
+  const uint32_t index = kind == PT_FEAT_MISS ? PT_FEAT_NO_INDEX : (n.idx & ~PT_LIGHT);
+  const f3 albedo = found ? hit.diffuse_col : env_lookup(p, d);
+  const f3 nrm = found ? hit.normal : mk3(0.f);
+  const size_t i = (size_t)y * p.width + x;
+  feat[2 * i] = make_float4(nrm.x, nrm.y, nrm.z, n.t);
+  feat[2 * i + 1] = make_float4(albedo.x, albedo.y, albedo.z, u_as_f(kind << 30 | index));
+  if (rays) {
+    float* r = rays + i * 6;
+    r[0] = d.x; r[1] = d.y; r[2] = d.z; r[3] = o.x; r[4] = o.y; r[5] = o.z;
+  }
+}
+
+// The filter's passes (pt_denoise.h), one thread per pixel, 16x16 pixels per block.  PASS: 0 prepare, 1 variance, 2 a-trous
+// level, 3 plain output (levels == 0).
+template <int PASS>
+__global__ void __launch_bounds__(256) pt_denoise_kernel(const DenoiseParams q)
+{
+  const uint32_t x = blockIdx.x * 16u + (threadIdx.x & 15u), y = blockIdx.y * 16u + (threadIdx.x >> 4);
+  if (x >= q.width || y >= q.height) return;
+  if (PASS == 0) dn_prepare(q, x, y);
+  else if (PASS == 1) dn_variance(q, x, y);
+  else if (PASS == 2) dn_level(q, x, y);
+  else dn_plain(q, x, y);
+}
+
+hipError_t launch_features(const KParams& p, int kind, float4* feat_dev, float* rays_dev, hipStream_t stream)
+{
+  const dim3 grid((p.width + 15u) / 16u, (p.height + 15u) / 16u);
+  if (kind == 1) hipLaunchKernelGGL(pt_features_kernel<1>, grid, dim3(256), 0, stream, p, feat_dev, rays_dev);
+  else hipLaunchKernelGGL(pt_features_kernel<2>, grid, dim3(256), 0, stream, p, feat_dev, rays_dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t stream)
+{
+  const dim3 grid((q.width + 15u) / 16u, (q.height + 15u) / 16u);
+  switch (pass) {
+  case 0: hipLaunchKernelGGL(pt_denoise_kernel<0>, grid, dim3(256), 0, stream, q); break;
+  case 1: hipLaunchKernelGGL(pt_denoise_kernel<1>, grid, dim3(256), 0, stream, q); break;
+  case 2: hipLaunchKernelGGL(pt_denoise_kernel<2>, grid, dim3(256), 0, stream, q); break;
+  default: hipLaunchKernelGGL(pt_denoise_kernel<3>, grid, dim3(256), 0, stream, q); break;
+  }
+  return hipGetLastError();
+}
+#endif
 
 // ---------------------------------------------------------------- launchers
 
@@ -3098,6 +3116,9 @@ hipError_t resolve_kernels()
     reinterpret_cast<const void*>(pt_trace_rays_kernel<1>), reinterpret_cast<const void*>(pt_trace_rays_kernel<2>),
     reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<0>), reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<1>),
     reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<2>),
+    reinterpret_cast<const void*>(pt_features_kernel<1>), reinterpret_cast<const void*>(pt_features_kernel<2>),
+    reinterpret_cast<const void*>(pt_denoise_kernel<0>), reinterpret_cast<const void*>(pt_denoise_kernel<1>),
+    reinterpret_cast<const void*>(pt_denoise_kernel<2>), reinterpret_cast<const void*>(pt_denoise_kernel<3>),
   };
   for (const void* fn : fns) {
     hipFuncAttributes attr;

@@ -7,6 +7,7 @@
 namespace ptamd {
 
 struct KParams;
+struct DenoiseParams;
 
 // kind: 1 brute force, 2 BVH.  lds_bytes: dynamic LDS needed when lds_resident.
 hipError_t launch_megakernel(const KParams& p, int kind, bool lds_resident, size_t lds_bytes, bool stats,
@@ -39,5 +40,9 @@ hipError_t launch_trace_queue(const KParams& p, uint32_t config, size_t lds_byte
                               uint32_t* head_dev, int* resident_blocks_per_cu, hipStream_t stream);
 hipError_t launch_trace_rays(const KParams& p, int kind, const float* rays_dev, uint32_t n, int4* out_dev,
                              hipStream_t stream);
+// denoiser (pt_denoise.h): the feature pass (kind 1 every face, 2 the binary tree from L2) and one pass of the filter
+// (0 prepare, 1 variance, 2 a-trous level, 3 plain output), full frames
+hipError_t launch_features(const KParams& p, int kind, float4* feat_dev, float* rays_dev, hipStream_t stream);
+hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t stream);
 
 } // namespace ptamd

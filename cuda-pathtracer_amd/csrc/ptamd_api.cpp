@@ -9,6 +9,7 @@
 // computed here once per launch with the same float operations the kernel would do.
 #include "../host/ptamd_internal.h"
 #include "pt_device.h"
+#include "pt_denoise.h"
 #include "pt_launch.h"
 
 #include <algorithm>
@@ -137,6 +138,10 @@ struct ptamd_context {
   uint32_t walk_min4 = 16;                // the same threshold for the four-wide walk (PTAMD_WALK_MIN4; 1/4/8/16/24: 813/902/960/994/971 Msamples/s)
   bool short_rcp = true;                  // restart kernel: 7-instruction exact 1/det where the scene allows it (PTAMD_SHORT_RCP=0: always the full division)
   uint32_t tiles_per_ticket = 1;
+  // denoiser workspace (ptamd_denoise): feature records, geometry records, two ping-pong images — 96 bytes per pixel in one
+  // allocation, grown at the first call of a larger frame
+  float4* d_denoise = nullptr;
+  size_t denoise_pixels = 0;
   uint32_t xcd_regions = 0;               // restart kernel: XCD-local tile regions (0 never, 1 for scenes walked from L2, 2 always; PTAMD_XCD_REGIONS).  Off: measured -0.5 % on the atrium, -0.7 % on the headline (profiles/r04_notes.md)
 };
 
@@ -253,6 +258,22 @@ inline f3 hnormalize(f3 v)
   return hmuls(v, inv_len);
 }
 
+// generateRay's pixel-invariant part (intersection.cuh:79-89) into p.cam_*; returns screen_dist
+float camera_terms(const ptamd_camera& cam, uint32_t width, KParams& p)
+{
+  const int half_w = (int)(width / 2u);
+  const float screen_dist = (float)half_w / tanf(cam.fov_x * 0.5f);
+  f3 down; down.x = 0.0f; down.y = -1.0f; down.z = 0.0f;
+  f3 u = hnormalize(hcross(hf3(cam.dir), down));
+  f3 v = hnormalize(hcross(u, hf3(cam.dir)));
+  u = hmuls(u, -1.0f);
+  p.cam_pos = hf3(cam.position);
+  p.cam_p0 = hadd(hf3(cam.position), hmuls(hf3(cam.dir), screen_dist));
+  p.cam_u = u; p.cam_v = v;
+  p.focus_dist = cam.focus_dist; p.aperture = cam.aperture;
+  return screen_dist;
+}
+
 int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
 {
   if (!ctx || !l) { set_error("ptamd_raytrace: null context or launch"); return PTAMD_ERR_ARG; }
@@ -332,16 +353,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
 
   // generateRay's pixel-invariant part (intersection.cuh:79-89)
   const ptamd_camera& cam = l->camera;
-  const int half_w = (int)(l->width / 2u);
-  const float screen_dist = (float)half_w / tanf(cam.fov_x * 0.5f);
-  f3 down; down.x = 0.0f; down.y = -1.0f; down.z = 0.0f;
-  f3 u = hnormalize(hcross(hf3(cam.dir), down));
-  f3 v = hnormalize(hcross(u, hf3(cam.dir)));
-  u = hmuls(u, -1.0f);
-  p.cam_pos = hf3(cam.position);
-  p.cam_p0 = hadd(hf3(cam.position), hmuls(hf3(cam.dir), screen_dist));
-  p.cam_u = u; p.cam_v = v;
-  p.focus_dist = cam.focus_dist; p.aperture = cam.aperture;
+  camera_terms(cam, l->width, p);
 
   p.width = l->width; p.height = l->height; p.row_begin = l->row_begin; p.row_end = l->row_end;
   p.hash_seed = ptamd_wang_hash(l->frame_nb);
@@ -694,6 +706,62 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
   return PTAMD_OK;
 }
 
+// ---------------------------------------------------------------- denoiser (pt_denoise.h)
+
+// the checks every denoiser entry point shares: frame, divisor, output stage, levels and sigmas; fills the filter's constants
+int denoise_params(const char* who, const ptamd_denoise_desc* d, DenoiseParams& q, KParams& p)
+{
+  auto fail = [&](const char* what) { set_error(std::string(who) + ": " + what); return PTAMD_ERR_ARG; };
+  if (d->width == 0 || d->height == 0 || d->width > 65536 || d->height > 65536) return fail("bad frame size (1..65536 per side)");
+  if (d->frame_nb == 0) return fail("frame_nb must be >= 1");
+  if (d->post_id > 3) return fail("post_id out of range (0..3)");
+  if (d->levels > PT_DN_MAX_LEVELS) return fail("levels out of range (0..8)");
+  uint32_t n_sq = 7;
+  if (d->sigma_n != 0.0f) {
+    int e = 0;
+    const float m = std::frexp(d->sigma_n, &e);
+    if (!(d->sigma_n >= 1.0f && d->sigma_n <= 65536.0f) || m != 0.5f) return fail("sigma_n must be 0 or a power of two in 1..65536");
+    n_sq = (uint32_t)(e - 1);
+  }
+  if (!(d->sigma_l >= 0.0f) || !(d->sigma_x >= 0.0f) || std::isinf(d->sigma_l) || std::isinf(d->sigma_x))
+    return fail("sigma_l and sigma_x must be 0 (default) or positive and finite");
+  std::memset(&q, 0, sizeof q);
+  std::memset(&p, 0, sizeof p);
+  q.width = d->width; q.height = d->height; q.post_id = d->post_id;
+  q.frame_nb_f = (float)(int)d->frame_nb;
+  q.frame_nb_inv = frame_nb_inverse(q.frame_nb_f);
+  p.width = d->width; p.height = d->height; p.row_begin = 0; p.row_end = d->height;
+  q.screen_dist = camera_terms(d->camera, d->width, p);
+  q.cam_pos = p.cam_pos; q.cam_p0 = p.cam_p0; q.cam_u = p.cam_u; q.cam_v = p.cam_v; q.focus_dist = p.focus_dist;
+  q.n_squarings = n_sq;
+  q.sigma_l = d->sigma_l != 0.0f ? d->sigma_l : PT_DN_SIGMA_L;
+  q.sigma_x = d->sigma_x != 0.0f ? d->sigma_x : PT_DN_SIGMA_X;
+  return PTAMD_OK;
+}
+
+// the scene and environment part of the feature pass's KParams; returns the walk (1 every face, 2 the binary tree)
+int feature_scene(const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, const ptamd_camera& cam, KParams& p)
+{
+  const DeviceScene& s = ctx->scenes[scene_id];
+  const DeviceCubemap& cm = ctx->cubemaps[cubemap_id];
+  p.nodes = s.nodes; p.tris_bvh = s.tris_bvh; p.tris_brute = s.tris_brute; p.shade = s.shade;
+  p.materials = s.materials; p.lights = s.lights; p.textures = s.textures; p.texels = s.texels;
+  p.cubemap = cm.faces; p.cubemap_size = cm.size;
+  p.env_uniform = cm.uniform ? 1u : 0u; p.env_r = cm.color[0]; p.env_g = cm.color[1]; p.env_b = cm.color[2];
+  p.n_faces = s.n_faces; p.n_lights = s.n_lights; p.n_nodes = s.n_nodes; p.n_bvh_tris = s.n_bvh_tris;
+  // the same rule as do_launch: an origin beyond what the boxes' margins cover tests every face
+  const float cam_far = std::fmax(std::fabs(cam.position.x), std::fmax(std::fabs(cam.position.y), std::fabs(cam.position.z)));
+  const bool far_origin = !((cam_far + s.extent) * (1.0f / 2097152.0f) <= s.margin_floor) && s.n_faces != 0;
+  return far_origin ? 1 : 2;
+}
+
+int denoise_ids(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id)
+{
+  if (scene_id >= ctx->scenes.size()) { set_error(std::string(who) + ": scene_id out of range"); return PTAMD_ERR_ARG; }
+  if (cubemap_id >= ctx->cubemaps.size()) { set_error(std::string(who) + ": cubemap_id out of range"); return PTAMD_ERR_ARG; }
+  return PTAMD_OK;
+}
+
 } // namespace
 } // namespace ptamd
 
@@ -835,6 +903,7 @@ void ptamd_destroy(ptamd_context* ctx)
   for (hipStream_t is : ctx->internal) if (is) (void)hipStreamDestroy(is);
   (void)hipFree(ctx->d_timeline);
   (void)hipFree(ctx->d_trace_spill);
+  (void)hipFree(ctx->d_denoise);
   delete ctx;
 }
 
@@ -1263,6 +1332,128 @@ int ptamd_stream_synchronize(ptamd_context* ctx, void* stream)
   if (!ctx) { set_error("ptamd_stream_synchronize: null context"); return PTAMD_ERR_ARG; }
   PT_HIP(hipSetDevice(ctx->device));
   PT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  return PTAMD_OK;
+}
+
+int ptamd_get_frame_counter(ptamd_context* ctx, uint32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_get_frame_counter: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->frame_counter;
+  return PTAMD_OK;
+}
+
+int ptamd_render_features(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, const ptamd_camera* camera,
+                          uint32_t width, uint32_t height, void* features_dev, float* rays_dev, void* stream)
+{
+  if (!ctx || !camera || !features_dev) { set_error("ptamd_render_features: null argument"); return PTAMD_ERR_ARG; }
+  if (width == 0 || height == 0 || width > 65536 || height > 65536) { set_error("ptamd_render_features: bad frame size (1..65536 per side)"); return PTAMD_ERR_ARG; }
+  int rc = denoise_ids("ptamd_render_features", ctx, scene_id, cubemap_id);
+  if (rc != PTAMD_OK) return rc;
+  PT_HIP(hipSetDevice(ctx->device));
+  KParams p;
+  std::memset(&p, 0, sizeof p);
+  p.width = width; p.height = height; p.row_begin = 0; p.row_end = height;
+  camera_terms(*camera, width, p);
+  const int kind = feature_scene(ctx, scene_id, cubemap_id, *camera, p);
+  PT_HIP(launch_features(p, kind, static_cast<float4*>(features_dev), rays_dev, static_cast<hipStream_t>(stream)));
+  return PTAMD_OK;
+}
+
+int ptamd_denoise(ptamd_context* ctx, const ptamd_denoise_desc* d)
+{
+  if (!ctx || !d) { set_error("ptamd_denoise: null argument"); return PTAMD_ERR_ARG; }
+  if (!d->temporal_framebuffer || !d->surface_rgba8) { set_error("ptamd_denoise: null accumulator or surface"); return PTAMD_ERR_ARG; }
+  int rc = denoise_ids("ptamd_denoise", ctx, d->scene_id, d->cubemap_id);
+  if (rc != PTAMD_OK) return rc;
+  DenoiseParams q;
+  KParams p;
+  if ((rc = denoise_params("ptamd_denoise", d, q, p)) != PTAMD_OK) return rc;
+  PT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  q.acc = d->temporal_framebuffer;
+  q.surface = static_cast<uint32_t*>(d->surface_rgba8);
+  q.linear = d->linear_rgb;
+  q.gamma_table = ctx->d_gamma;
+  q.use_table = ctx->d_gamma != nullptr && d->post_id == 0u ? 1u : 0u;
+  if (d->levels == 0) {   // the plain resolve's output: no features, no workspace
+    PT_HIP(launch_denoise_pass(q, 3, stream));
+    return PTAMD_OK;
+  }
+  const size_t n = (size_t)d->width * d->height;
+  if (ctx->denoise_pixels < n) {
+    // (hipFree waits for the work in flight that may still use the old workspace)
+    (void)hipFree(ctx->d_denoise);
+    ctx->d_denoise = nullptr;
+    ctx->denoise_pixels = 0;
+    PT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_denoise), n * 96u));
+    ctx->denoise_pixels = n;
+  }
+  float4* feat = ctx->d_denoise;
+  q.feat = feat;
+  q.geo_n = feat + 2 * n;
+  q.geo_x = feat + 3 * n;
+  float4* img[2] = { feat + 4 * n, feat + 5 * n };
+  const int kind = feature_scene(ctx, d->scene_id, d->cubemap_id, d->camera, p);
+  PT_HIP(launch_features(p, kind, feat, nullptr, stream));
+  q.c_out = img[0];
+  PT_HIP(launch_denoise_pass(q, 0, stream));
+  q.h = 1u; q.c_in = img[0]; q.c_out = img[1];
+  PT_HIP(launch_denoise_pass(q, 1, stream));
+  for (uint32_t i = 0; i < d->levels; ++i) {
+    q.h = 1u << i;
+    q.c_in = img[(i + 1u) & 1u];
+    q.c_out = img[i & 1u];
+    q.last = i + 1u == d->levels ? 1u : 0u;
+    PT_HIP(launch_denoise_pass(q, 2, stream));
+  }
+  return PTAMD_OK;
+}
+
+int ptamd_host_denoise(const float* features, const float* temporal_framebuffer, const ptamd_denoise_desc* d,
+                       float* linear_rgb, uint8_t* rgba8)
+{
+  if (!features || !temporal_framebuffer || !d || !rgba8) { set_error("ptamd_host_denoise: null argument"); return PTAMD_ERR_ARG; }
+  DenoiseParams q;
+  KParams p;
+  int rc = denoise_params("ptamd_host_denoise", d, q, p);
+  if (rc != PTAMD_OK) return rc;
+  const size_t n = (size_t)d->width * d->height;
+  std::vector<float4> ws;
+  std::vector<uint32_t> surface;
+  try {
+    ws.resize(d->levels ? n * 4 : 0);
+    surface.resize(n);
+  } catch (const std::bad_alloc&) {
+    set_error("ptamd_host_denoise: out of memory");
+    return PTAMD_ERR_LIMIT;
+  }
+  q.feat = reinterpret_cast<const float4*>(features);
+  q.acc = temporal_framebuffer;
+  q.surface = surface.data();
+  q.linear = linear_rgb;
+  auto each = [&](void (*pass)(const DenoiseParams&, uint32_t, uint32_t)) {
+    for (uint32_t y = 0; y < d->height; ++y)
+      for (uint32_t x = 0; x < d->width; ++x) pass(q, x, y);
+  };
+  if (d->levels == 0) {
+    each(dn_plain);
+  } else {
+    q.geo_n = ws.data();
+    q.geo_x = ws.data() + n;
+    float4* img[2] = { ws.data() + 2 * n, ws.data() + 3 * n };
+    q.c_out = img[0];
+    each(dn_prepare);
+    q.h = 1u; q.c_in = img[0]; q.c_out = img[1];
+    each(dn_variance);
+    for (uint32_t i = 0; i < d->levels; ++i) {
+      q.h = 1u << i;
+      q.c_in = img[(i + 1u) & 1u];
+      q.c_out = img[i & 1u];
+      q.last = i + 1u == d->levels ? 1u : 0u;
+      each(dn_level);
+    }
+  }
+  std::memcpy(rgba8, surface.data(), n * 4);   // RGBA8 little-endian: byte 0 red
   return PTAMD_OK;
 }
 

@@ -91,6 +91,18 @@ class SceneInfo(C.Structure):
                                           "n_nodes4", "depth4")]
 
 
+class DenoiseDesc(C.Structure):   # ptamd_denoise_desc (include/ptamd.h)
+    _fields_ = [("temporal_framebuffer", C.c_void_p), ("frame_nb", C.c_uint32), ("camera", Camera),
+                ("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("surface_rgba8", C.c_void_p), ("linear_rgb", C.c_void_p), ("stream", C.c_void_p),
+                ("post_id", C.c_uint32), ("levels", C.c_uint32),
+                ("sigma_n", C.c_float), ("sigma_l", C.c_float), ("sigma_x", C.c_float)]
+
+
+FEATURE_MISS, FEATURE_MESH, FEATURE_LIGHT = 0, 1, 2   # kind of a feature record (code >> 30)
+FEATURE_BYTES = 32                                    # per pixel: {normal.xyz, t} {albedo.rgb, kind << 30 | index}
+DENOISE_MAX_LEVELS = 8
+
 assert C.sizeof(Face) == 112 and C.sizeof(Material) == 16 and C.sizeof(Light) == 32 and C.sizeof(Camera) == 64
 
 IMAGE_LOAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -154,6 +166,11 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "ptamd_trace_rays_queue": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.POINTER(C.c_uint32)]),
+    "ptamd_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseDesc)]),
+    "ptamd_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptamd_host_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseDesc), C.c_void_p, C.c_void_p]),
+    "ptamd_get_frame_counter": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ptamd_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "ptamd_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_device_memset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),

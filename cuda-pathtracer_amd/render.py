@@ -141,6 +141,37 @@ class Context:
     def raytrace_ex(self, launch: N.Launch) -> None:
         N.check(self._lib.ptamd_raytrace_ex(self._h, C.byref(launch)))
 
+    # ---- the denoiser (include/ptamd.h: ptamd_denoise)
+    def frame_counter(self) -> int:
+        """The frame number of the last raytrace(): the divisor of its resolve."""
+        out = C.c_uint32()
+        N.check(self._lib.ptamd_get_frame_counter(self._h, C.byref(out)))
+        return out.value
+
+    def denoise(self, surface, temporal_framebuffer, scene_id: int, cubemap_id: int, cam: N.Camera, width: int, height: int,
+                frame_nb: int, levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_l: float = 0.0,
+                sigma_x: float = 0.0, linear=None, stream=None) -> None:
+        """Edge-aware a-trous denoise of a full-frame accumulator (left unchanged) into `surface` (uint8[height, width, 4]) and,
+        optionally, `linear` (float32[height, width, 3]); asynchronous on `stream`.  A sigma of 0 takes the default."""
+        d = N.DenoiseDesc()
+        d.temporal_framebuffer = _ptr(temporal_framebuffer)
+        d.frame_nb = frame_nb
+        d.camera = cam
+        d.scene_id, d.cubemap_id, d.width, d.height = scene_id, cubemap_id, width, height
+        d.surface_rgba8 = _ptr(surface)
+        d.linear_rgb = _ptr(linear) if linear is not None else None
+        d.stream = _stream_handle(stream)
+        d.post_id, d.levels = post_id, levels
+        d.sigma_n, d.sigma_l, d.sigma_x = sigma_n, sigma_l, sigma_x
+        N.check(self._lib.ptamd_denoise(self._h, C.byref(d)))
+
+    def render_features(self, scene_id: int, cubemap_id: int, cam: N.Camera, width: int, height: int, features,
+                        rays=None, stream=None) -> None:
+        """The denoiser's feature pass alone: features float32[height, width, 8] (two float4 per pixel, include/ptamd.h),
+        rays (optional) float32[height, width, 6] = {dir, origin}; device tensors, asynchronous on `stream`."""
+        N.check(self._lib.ptamd_render_features(self._h, scene_id, cubemap_id, C.byref(cam), width, height, _ptr(features),
+                                                _ptr(rays) if rays is not None else None, _stream_handle(stream)))
+
     def trace_rays_queue(self, scene_id: int, rays, out, config: int = 0, refill_min: int = 8, stream=None) -> int:
         """The walk-only kernel fed from a ray queue (ptamd_trace_rays_queue): rays float32[n, 6] and out int32[n, 4] are device
         tensors; asynchronous on `stream`.  Returns the waves resident per CU."""
@@ -251,6 +282,25 @@ def host_bvh8_trace(scene: HostScene, rays: np.ndarray):
     return out, counters[0], counters[1], counters[2], counters[5]
 
 
+def host_denoise(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_nb: int, levels: int = 5,
+                 post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_l: float = 0.0, sigma_x: float = 0.0):
+    """Host mirror of the device filter (ptamd_host_denoise): features float32[H, W, 8], accum float32[H, W, 3] (accumulator
+    row order, as the device holds it).  Returns (linear float32[H, W, 3], rgba uint8[H, W, 4]), both with row 0 = top."""
+    features = np.ascontiguousarray(features, dtype=np.float32)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    h, w = accum.shape[:2]
+    if features.shape != (h, w, 8):
+        raise ValueError(f"features must be float32[{h}, {w}, 8]")
+    d = N.DenoiseDesc()
+    d.frame_nb, d.camera, d.width, d.height = frame_nb, cam, w, h
+    d.post_id, d.levels = post_id, levels
+    d.sigma_n, d.sigma_l, d.sigma_x = sigma_n, sigma_l, sigma_x
+    linear = np.zeros((h, w, 3), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    N.check(N.load().ptamd_host_denoise(features.ctypes.data, accum.ctypes.data, C.byref(d), linear.ctypes.data, rgba.ctypes.data))
+    return linear, rgba
+
+
 def interleaved_rows(height: int, ranks: int, rank: int, band_rows: int) -> int:
     """Rows the interleaved bands of `rank` hold (ptamd_interleaved_rows)."""
     return N.load().ptamd_interleaved_rows(height, ranks, rank, band_rows)
@@ -293,6 +343,7 @@ class FrameRenderer:
         else:
             self.surface = torch.zeros((n_rows, width, 4), dtype=torch.uint8, device=dev)
         self.accum = torch.zeros((n_rows, width, 3), dtype=torch.float32, device=dev)
+        self.last_frame_nb = 0   # frame number of the last launch (the divisor denoise() hands on)
 
     def reset(self) -> None:
         self.accum.zero_()
@@ -312,6 +363,7 @@ class FrameRenderer:
                                      band_local_buffers=self.band_local, frame_count=spp, machine_share=self.machine_share,
                                      interleave=self.interleave, reset_accumulation=reset)
             self.ctx.raytrace_ex(l)
+            self.last_frame_nb = first_frame + spp - 1
             return
         for k in range(first_frame, first_frame + spp):
             l = self.ctx.make_launch(self.surface, self.accum, self.scene_id, self.cubemap_id, self.cam,
@@ -320,3 +372,16 @@ class FrameRenderer:
                                      band_local_buffers=self.band_local, machine_share=self.machine_share,
                                      interleave=self.interleave, reset_accumulation=reset and k == first_frame)
             self.ctx.raytrace_ex(l)
+            self.last_frame_nb = k
+
+    def denoise(self, levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_l: float = 0.0,
+                sigma_x: float = 0.0, linear=None, stream=None, surface=None) -> None:
+        """Denoises the accumulator of the last render() into the renderer's surface (or `surface`); the accumulator is left as
+        it is, so render() can go on converging it.  Full frames only."""
+        if self.rows != (0, self.height) or self.band_local or self.interleave is not None:
+            raise ValueError("denoise() needs a full-frame renderer (no row band, band-local or interleaved buffers)")
+        if self.last_frame_nb == 0:
+            raise ValueError("denoise() before any render(): the accumulator holds no frame")
+        self.ctx.denoise(self.surface if surface is None else surface, self.accum, self.scene_id, self.cubemap_id, self.cam,
+                         self.width, self.height, self.last_frame_nb, levels=levels, post_id=post_id, sigma_n=sigma_n,
+                         sigma_l=sigma_l, sigma_x=sigma_x, linear=linear, stream=stream)

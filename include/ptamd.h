@@ -405,6 +405,62 @@ int ptamd_host_bvh4q_trace(const ptamd_face* faces, uint32_t n_faces, const floa
 int ptamd_host_bvh8_trace(const ptamd_face* faces, uint32_t n_faces, const float* rays, uint32_t n,
                           int32_t* out, uint64_t* counters);
 
+/* ---- Edge-aware denoiser -------------------------------------------------------------------------------
+ * An opt-in pass behind the accumulator: the spatial half of SVGF over an edge-avoiding a-trous wavelet, guided by a first-hit
+ * feature pass.  It reads the accumulator and writes a surface; it changes nothing any other entry point computes.
+ *
+ * Feature records (ptamd_render_features): 32 bytes per pixel, surface row order (row 0 = top), two float4:
+ *   [0] {normal.x, normal.y, normal.z, t}    the hit normal exactly as the integrator decodes it (interpolated, normal-mapped;
+ *                                            not renormalised), 0 on a miss; t the hit distance (100000 on a miss)
+ *   [1] {albedo.r, albedo.g, albedo.b, code} albedo: the diffuse colour of the mesh or light hit, the environment on a miss (what a
+ *                                            preview launch stores); code, as uint32 bits: kind << 30 | index, kind 0 miss, 1 mesh
+ *                                            face, 2 light sphere, index the face or light (0x3fffffff on a miss)
+ * One ray per pixel, no RNG: origin camera.position, direction normalize(focus_dist * dir) with dir from generateRay (the camera
+ * ray with the aperture offset zero; at aperture 0 the ray of a moved launch, bit for bit). */
+#define PTAMD_FEATURE_MISS 0u
+#define PTAMD_FEATURE_MESH 1u
+#define PTAMD_FEATURE_LIGHT 2u
+#define PTAMD_DENOISE_MAX_LEVELS 8u
+
+typedef struct {
+  const float* temporal_framebuffer;   /* accumulator of a full frame (read only, left unchanged), as ptamd_raytrace writes it */
+  uint32_t frame_nb;                   /* the frame number of its last launch: the divisor of the resolve (ptamd_get_frame_counter) */
+  ptamd_camera camera;
+  uint32_t scene_id, cubemap_id;
+  uint32_t width, height;              /* full frames only: no row bands, no band-local or interleaved buffers */
+  void* surface_rgba8;                 /* out: width x height RGBA8, row 0 = top */
+  float* linear_rgb;                   /* optional out: width x height x 3 floats, row 0 = top: the denoised colour before the output stage */
+  void* stream;                        /* hipStream_t; NULL = default stream */
+  uint32_t post_id;                    /* 0..3, as ptamd_raytrace */
+  uint32_t levels;                     /* a-trous levels, 0..8; 0: the plain resolve's bytes (no filtering) */
+  float sigma_n;                       /* normal exponent, a power of two 1..65536 (0: 128) */
+  float sigma_l;                       /* luminance scale, > 0 (0: 2) */
+  float sigma_x;                       /* plane-distance scale, > 0 (0: 1) */
+} ptamd_denoise_desc;
+
+/* Denoises the accumulator into surface_rgba8 (and linear_rgb): asynchronous on `stream`.  Call it after ptamd_raytrace /
+ * ptamd_raytrace_ex on the same stream (stream order makes the accumulator complete).  Errors: PTAMD_ERR_ARG for null pointers,
+ * ids or post_id out of range, levels > 8, a sigma out of range, frame_nb 0, frames outside 1..65536 per side.
+ * Workspace: the feature records, the geometry records and two ping-pong images (96 bytes per pixel) belong to the context.  They
+ * are sized at the first call of a frame size (hipMalloc, a device synchronisation); later calls of the same or a smaller size only
+ * enqueue.  Calls on ONE context share them: order them (one stream, or an event between streams). */
+int ptamd_denoise(ptamd_context* ctx, const ptamd_denoise_desc* desc);
+
+/* The feature pass alone, for tests and hosts that want the buffers: features_dev receives width x height x 32 bytes (layout above);
+ * rays_dev, optional, width x height x {dir.xyz, origin.xyz} floats.  Device pointers, asynchronous on `stream`. */
+int ptamd_render_features(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, const ptamd_camera* camera,
+                          uint32_t width, uint32_t height, void* features_dev, float* rays_dev, void* stream);
+
+/* Host mirror of the filter (the device kernels and this function execute the same binary32 operations): from feature records
+ * and an accumulator in host memory, the denoised colour (linear_rgb, optional) and the RGBA8 bytes.  desc supplies camera, width,
+ * height, frame_nb, post_id, levels and the sigmas (temporal_framebuffer / surface_rgba8 / linear_rgb / stream / ids of desc are
+ * ignored).  Allocates its workspace per call. */
+int ptamd_host_denoise(const float* features, const float* temporal_framebuffer, const ptamd_denoise_desc* desc,
+                       float* linear_rgb, uint8_t* rgba8);
+
+/* The frame number of the context's last ptamd_raytrace (raytrace.cu:296's `seed`): the divisor of its resolve. */
+int ptamd_get_frame_counter(ptamd_context* ctx, uint32_t* out);
+
 /* Plain device-memory helpers so that C/C++ hosts need not link HIP themselves. */
 int ptamd_device_alloc(ptamd_context* ctx, size_t bytes, void** out);
 int ptamd_device_free(ptamd_context* ctx, void* p);
