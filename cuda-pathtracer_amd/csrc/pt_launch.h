@@ -8,6 +8,7 @@ namespace ptamd {
 
 struct KParams;
 struct DenoiseParams;
+struct TemporalParams;
 
 // kind: 1 brute force, 2 BVH.  lds_bytes: dynamic LDS needed when lds_resident.
 hipError_t launch_megakernel(const KParams& p, int kind, bool lds_resident, size_t lds_bytes, bool stats,
@@ -44,5 +45,7 @@ hipError_t launch_trace_rays(const KParams& p, int kind, const float* rays_dev, 
 // (0 prepare, 1 variance, 2 a-trous level, 3 plain output), full frames
 hipError_t launch_features(const KParams& p, int kind, float4* feat_dev, float* rays_dev, hipStream_t stream);
 hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t stream);
+// temporal half (pt_denoise_temporal.hip): 0 reproject and blend, 1 temporal variance, 2 capture, 3 plain output
+hipError_t launch_temporal_pass(const DenoiseParams& q, const TemporalParams& t, int pass, hipStream_t stream);
 
 } // namespace ptamd

@@ -99,6 +99,20 @@ class DenoiseDesc(C.Structure):   # ptamd_denoise_desc (include/ptamd.h)
                 ("sigma_n", C.c_float), ("sigma_l", C.c_float), ("sigma_x", C.c_float)]
 
 
+class DenoiseTemporalDesc(C.Structure):   # ptamd_denoise_temporal_desc (include/ptamd.h)
+    _fields_ = [("base", DenoiseDesc), ("history", C.c_void_p), ("alpha_color", C.c_float), ("alpha_moments", C.c_float),
+                ("reset_history", C.c_uint32), ("history_length", C.c_void_p)]
+
+
+class DenoiseHistoryView(C.Structure):    # ptamd_denoise_history_view (include/ptamd.h)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("valid", C.c_uint32), ("frame_nb", C.c_uint32),
+                ("camera", Camera), ("color", C.c_void_p), ("moments", C.c_void_p), ("normal", C.c_void_p),
+                ("position", C.c_void_p)]
+
+
+DENOISE_HISTORY_BYTES = 100                           # per pixel of a device history
+
+
 FEATURE_MISS, FEATURE_MESH, FEATURE_LIGHT = 0, 1, 2   # kind of a feature record (code >> 30)
 FEATURE_BYTES = 32                                    # per pixel: {normal.xyz, t} {albedo.rgb, kind << 30 | index}
 DENOISE_MAX_LEVELS = 8
@@ -171,6 +185,13 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptamd_host_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseDesc), C.c_void_p, C.c_void_p]),
     "ptamd_get_frame_counter": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ptamd_denoise_history_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ptamd_denoise_history_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ptamd_denoise_history_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptamd_denoise_history_view_of": (C.c_int, [C.c_void_p, C.POINTER(DenoiseHistoryView)]),
+    "ptamd_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(DenoiseTemporalDesc)]),
+    "ptamd_host_denoise_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseTemporalDesc), C.POINTER(DenoiseHistoryView),
+                                              C.c_void_p, C.c_void_p]),
     "ptamd_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "ptamd_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_device_memset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),

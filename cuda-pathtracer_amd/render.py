@@ -165,6 +165,37 @@ class Context:
         d.sigma_n, d.sigma_l, d.sigma_x = sigma_n, sigma_l, sigma_x
         N.check(self._lib.ptamd_denoise(self._h, C.byref(d)))
 
+    def denoise_history(self, width: int, height: int) -> "DenoiseHistory":
+        """A temporal history of width x height pixels on this context (ptamd_denoise_history_create)."""
+        return DenoiseHistory(self, width, height)
+
+    def denoise_temporal(self, surface, temporal_framebuffer, scene_id: int, cubemap_id: int, cam: N.Camera, width: int,
+                         height: int, frame_nb: int, history: "DenoiseHistory", levels: int = 5, post_id: int = POST_NONE,
+                         sigma_n: float = 0.0, sigma_l: float = 0.0, sigma_x: float = 0.0, alpha_color: float = 0.0,
+                         alpha_moments: float = 0.0, reset_history: bool = False, history_length=None, linear=None,
+                         stream=None) -> None:
+        """Temporal + spatial denoise (ptamd_denoise_temporal): as denoise(), blended with what `history`
+        integrated over the previous calls, which it then updates.  The accumulator must be an independent estimate (a new
+        accumulation since the last call on this history); history_length (optional) float32[height, width] receives n'."""
+        if history.ctx is not self:
+            raise ValueError("the history belongs to another context")
+        d = N.DenoiseTemporalDesc()
+        b = d.base
+        b.temporal_framebuffer = _ptr(temporal_framebuffer)
+        b.frame_nb = frame_nb
+        b.camera = cam
+        b.scene_id, b.cubemap_id, b.width, b.height = scene_id, cubemap_id, width, height
+        b.surface_rgba8 = _ptr(surface)
+        b.linear_rgb = _ptr(linear) if linear is not None else None
+        b.stream = _stream_handle(stream)
+        b.post_id, b.levels = post_id, levels
+        b.sigma_n, b.sigma_l, b.sigma_x = sigma_n, sigma_l, sigma_x
+        d.history = history.handle
+        d.alpha_color, d.alpha_moments = alpha_color, alpha_moments
+        d.reset_history = 1 if reset_history else 0
+        d.history_length = _ptr(history_length) if history_length is not None else None
+        N.check(self._lib.ptamd_denoise_temporal(self._h, C.byref(d)))
+
     def render_features(self, scene_id: int, cubemap_id: int, cam: N.Camera, width: int, height: int, features,
                         rays=None, stream=None) -> None:
         """The denoiser's feature pass alone: features float32[height, width, 8] (two float4 per pixel, include/ptamd.h),
@@ -301,6 +332,124 @@ def host_denoise(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_n
     return linear, rgba
 
 
+class DenoiseHistory:
+    """The device history of the temporal denoiser (ptamd_denoise_history_*): colour history and length, luminance moments and
+    the geometry records of the last call, 100 bytes per pixel allocated once.  Close it before its context."""
+
+    def __init__(self, ctx: Context, width: int, height: int):
+        self.ctx, self.width, self.height = ctx, width, height
+        h = C.c_void_p()
+        N.check(ctx._lib.ptamd_denoise_history_create(ctx._h, width, height, C.byref(h)))
+        self.handle = h.value
+
+    def reset(self, stream=None) -> None:
+        """The next call starts a new history (a cut)."""
+        N.check(self.ctx._lib.ptamd_denoise_history_reset(self.ctx._h, self.handle, _stream_handle(stream)))
+
+    def read(self) -> dict:
+        """The history as the last call left it, copied to host memory (synchronises the device): valid, frame_nb, camera,
+        color float32[H, W, 4], moments [H, W, 2], normal [H, W, 4], position [H, W, 4]."""
+        import torch
+        v = N.DenoiseHistoryView()
+        N.check(self.ctx._lib.ptamd_denoise_history_view_of(self.handle, C.byref(v)))
+        torch.cuda.synchronize(self.ctx.device)
+        out = {"valid": v.valid, "frame_nb": v.frame_nb, "camera": v.camera}
+        for name, k in (("color", 4), ("moments", 2), ("normal", 4), ("position", 4)):
+            a = np.zeros((self.height, self.width, k), np.float32)
+            N.check(self.ctx._lib.ptamd_device_to_host(self.ctx._h, a.ctypes.data, getattr(v, name), a.nbytes, None))
+            out[name] = a
+        N.check(self.ctx._lib.ptamd_stream_synchronize(self.ctx._h, None))
+        return out
+
+    def close(self) -> None:
+        if self.handle:
+            N.check(self.ctx._lib.ptamd_denoise_history_destroy(self.ctx._h, self.handle))
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class HostDenoiseHistory:
+    """The history of the host mirror (ptamd_host_denoise_temporal) in numpy arrays, the layout DenoiseHistory.read() returns."""
+
+    def __init__(self, width: int, height: int):
+        self.width, self.height = width, height
+        self.color = np.zeros((height, width, 4), np.float32)
+        self.moments = np.zeros((height, width, 2), np.float32)
+        self.normal = np.zeros((height, width, 4), np.float32)
+        self.position = np.zeros((height, width, 4), np.float32)
+        self.view = N.DenoiseHistoryView()
+        self.view.width, self.view.height = width, height
+        for name in ("color", "moments", "normal", "position"):
+            setattr(self.view, name, getattr(self, name).ctypes.data)
+
+    @property
+    def valid(self) -> int:
+        return self.view.valid
+
+    @property
+    def frame_nb(self) -> int:
+        return self.view.frame_nb
+
+    def reset(self) -> None:
+        for a in (self.color, self.moments, self.normal, self.position):
+            a[...] = 0
+        self.view.valid = 0
+        self.view.frame_nb = 0
+        self.view.camera = N.Camera()
+
+
+def host_denoise_temporal(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_nb: int, history: HostDenoiseHistory,
+                          levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_l: float = 0.0,
+                          sigma_x: float = 0.0, alpha_color: float = 0.0, alpha_moments: float = 0.0,
+                          reset_history: bool = False):
+    """Host mirror of Context.denoise_temporal (ptamd_host_denoise_temporal) over `history`, which it updates.
+    Returns (linear float32[H, W, 3], rgba uint8[H, W, 4], history_length float32[H, W]), row 0 = top."""
+    features = np.ascontiguousarray(features, dtype=np.float32)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    h, w = accum.shape[:2]
+    if features.shape != (h, w, 8):
+        raise ValueError(f"features must be float32[{h}, {w}, 8]")
+    d = N.DenoiseTemporalDesc()
+    b = d.base
+    b.frame_nb, b.camera, b.width, b.height = frame_nb, cam, w, h
+    b.post_id, b.levels = post_id, levels
+    b.sigma_n, b.sigma_l, b.sigma_x = sigma_n, sigma_l, sigma_x
+    d.alpha_color, d.alpha_moments = alpha_color, alpha_moments
+    d.reset_history = 1 if reset_history else 0
+    length = np.zeros((h, w), np.float32)
+    d.history_length = length.ctypes.data
+    linear = np.zeros((h, w, 3), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    N.check(N.load().ptamd_host_denoise_temporal(features.ctypes.data, accum.ctypes.data, C.byref(d), C.byref(history.view),
+                                                 linear.ctypes.data, rgba.ctypes.data))
+    return linear, rgba, length
+
+
+def orbit_camera(cam: N.Camera, angle: float, radius: float = 0.0) -> N.Camera:
+    """`cam` turned by `angle` radians about the vertical axis through the point `radius` ahead of it (its focus distance when
+    radius is 0), still looking at that point: one step of the camera path of scripts/render_path.py.  angle 0 is `cam`."""
+    import math
+    r = radius if radius > 0.0 else cam.focus_dist
+    p = np.array([cam.position.x, cam.position.y, cam.position.z], np.float64)
+    d = np.array([cam.dir.x, cam.dir.y, cam.dir.z], np.float64)
+    d /= np.linalg.norm(d)
+    pivot = p + r * d
+    c, s = math.cos(angle), math.sin(angle)
+    rot = lambda v: np.array([c * v[0] + s * v[2], v[1], -s * v[0] + c * v[2]])
+    p2 = pivot + rot(p - pivot)
+    d2 = rot(d)
+    out = N.Camera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(N.Camera))
+    out.position.x, out.position.y, out.position.z = (float(v) for v in p2)
+    out.dir.x, out.dir.y, out.dir.z = (float(v) for v in d2)
+    return out
+
+
 def interleaved_rows(height: int, ranks: int, rank: int, band_rows: int) -> int:
     """Rows the interleaved bands of `rank` hold (ptamd_interleaved_rows)."""
     return N.load().ptamd_interleaved_rows(height, ranks, rank, band_rows)
@@ -344,10 +493,14 @@ class FrameRenderer:
             self.surface = torch.zeros((n_rows, width, 4), dtype=torch.uint8, device=dev)
         self.accum = torch.zeros((n_rows, width, 3), dtype=torch.float32, device=dev)
         self.last_frame_nb = 0   # frame number of the last launch (the divisor denoise() hands on)
+        self._accumulation = 0   # counts the accumulations render() started (denoise_temporal's independence rule)
+        self._fresh = True       # the accumulator is zero: the next render() starts an accumulation
+        self._temporal_last = None   # (history handle, accumulation) of the last denoise_temporal()
 
     def reset(self) -> None:
         self.accum.zero_()
         self.surface.zero_()
+        self._fresh = True
 
     def render(self, spp: int, bounces: int = REFERENCE_BOUNCES, post_id: int = POST_NONE,
                kernel: int = N.KERNEL_AUTO, stream=None, first_frame: int = 1, batched: bool = False,
@@ -356,6 +509,9 @@ class FrameRenderer:
         accumulator and final surface bit for bit, no kernel tails between frames.  `reset=True` starts a new
         accumulation: the first launch treats the accumulator as zero (ptamd_launch.reset_accumulation) — the same
         result as clearing it first."""
+        if reset or self._fresh:
+            self._accumulation += 1
+            self._fresh = False
         if batched and spp > 1:
             l = self.ctx.make_launch(self.surface, self.accum, self.scene_id, self.cubemap_id, self.cam,
                                      self.width, self.height, frame_nb=first_frame, bounces=bounces, post_id=post_id,
@@ -385,3 +541,23 @@ class FrameRenderer:
         self.ctx.denoise(self.surface if surface is None else surface, self.accum, self.scene_id, self.cubemap_id, self.cam,
                          self.width, self.height, self.last_frame_nb, levels=levels, post_id=post_id, sigma_n=sigma_n,
                          sigma_l=sigma_l, sigma_x=sigma_x, linear=linear, stream=stream)
+
+    def denoise_temporal(self, history: DenoiseHistory, levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0,
+                         sigma_l: float = 0.0, sigma_x: float = 0.0, alpha_color: float = 0.0, alpha_moments: float = 0.0,
+                         reset_history: bool = False, history_length=None, linear=None, stream=None, surface=None) -> None:
+        """Temporal + spatial denoise of the last render() into the renderer's surface (or `surface`).  Each call
+        should follow a render(reset=True) (the camera moved): its accumulator is then an independent estimate.  When the
+        accumulator went on converging without a reset since this renderer's last temporal call on `history`, the call resets
+        the history by itself, so that a static view is never counted twice."""
+        if self.rows != (0, self.height) or self.band_local or self.interleave is not None:
+            raise ValueError("denoise_temporal() needs a full-frame renderer (no row band, band-local or interleaved buffers)")
+        if self.last_frame_nb == 0:
+            raise ValueError("denoise_temporal() before any render(): the accumulator holds no frame")
+        key = (history.handle, self._accumulation)
+        continued = self._temporal_last == key
+        self.ctx.denoise_temporal(self.surface if surface is None else surface, self.accum, self.scene_id, self.cubemap_id,
+                                  self.cam, self.width, self.height, self.last_frame_nb, history, levels=levels, post_id=post_id,
+                                  sigma_n=sigma_n, sigma_l=sigma_l, sigma_x=sigma_x, alpha_color=alpha_color,
+                                  alpha_moments=alpha_moments, reset_history=reset_history or continued,
+                                  history_length=history_length, linear=linear, stream=stream)
+        self._temporal_last = key

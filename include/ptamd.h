@@ -458,6 +458,60 @@ int ptamd_render_features(ptamd_context* ctx, uint32_t scene_id, uint32_t cubema
 int ptamd_host_denoise(const float* features, const float* temporal_framebuffer, const ptamd_denoise_desc* desc,
                        float* linear_rgb, uint8_t* rgba8);
 
+/* ---- Temporal reprojection -------------------------------------------------------------------------------
+ * SVGF's other half, opt-in: each call's demodulated colour and luminance moments are blended with what the previous calls on the
+ * same history integrated at the same surface point, found by projecting the pixel's first hit into the previous call's camera.
+ * Contract: each call's accumulator is an independent estimate (a launch sequence that began with reset_accumulation or moved);
+ * an accumulator that went on converging since the last call must not be given again without reset_history.
+ *
+ * A history belongs to one context and one frame size.  It holds, per pixel, the colour history with its length, the luminance
+ * moments and two sets of geometry records (ping-pong): 100 bytes, allocated once by ptamd_denoise_history_create.  Calls that use
+ * one history must be ordered (one stream, or events); two histories on one context are independent, but they share the context's
+ * denoiser workspace like ptamd_denoise. */
+typedef struct ptamd_denoise_history ptamd_denoise_history;
+
+int ptamd_denoise_history_create(ptamd_context* ctx, uint32_t width, uint32_t height, ptamd_denoise_history** out);
+/* Destroy a history before its context: ptamd_destroy does not free the histories of the context. */
+int ptamd_denoise_history_destroy(ptamd_context* ctx, ptamd_denoise_history* history);   /* waits for the device */
+/* The next call starts a new history (as reset_history); the buffers are cleared on `stream`. */
+int ptamd_denoise_history_reset(ptamd_context* ctx, ptamd_denoise_history* history, void* stream);
+
+typedef struct {
+  ptamd_denoise_desc base;             /* as ptamd_denoise; levels 0 filters nothing spatially (below) */
+  ptamd_denoise_history* history;
+  float alpha_color;                   /* blend factor of the colour, (0, 1]; 0: the default 0.2 */
+  float alpha_moments;                 /* ... of the luminance moments, (0, 1]; 0: the default 0.2 */
+  uint32_t reset_history;              /* != 0: ignore what the history holds (a cut); the call then equals ptamd_denoise of base */
+  float* history_length;               /* optional out: width x height floats, row 0 = top: n', 1 where there was no history */
+} ptamd_denoise_temporal_desc;
+
+/* Temporal + spatial denoise of base's accumulator into base.surface_rgba8 (and linear_rgb), asynchronous on base.stream; updates
+ * the history for the next call.  With a fresh or reset history the surface and linear colour equal ptamd_denoise's byte for byte.
+ * levels == 0: pixels without history get the plain resolve's bytes, the others the integrated colour through the output stage.
+ * Errors: those of ptamd_denoise, a null history, a history of another context or frame size, an alpha outside (0, 1]. */
+int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc* desc);
+
+/* The buffers of a history, row 0 = top, width x height entries each.  For a device history (ptamd_denoise_history_view_of) they are
+ * device pointers to the state the last call left; for the host mirror the caller owns them, in host memory. */
+typedef struct {
+  uint32_t width, height;
+  uint32_t valid;                      /* 0: fresh or reset: the next call reads nothing */
+  uint32_t frame_nb;                   /* the last call's base.frame_nb */
+  ptamd_camera camera;                 /* the last call's camera */
+  float* color;                        /* 4 floats: the colour history {rgb, length}: level 0's output, remodulated on mesh pixels */
+  float* moments;                      /* 2 floats: {E[l], E[l^2]} of the demodulated luminance */
+  float* normal;                       /* 4 floats: the geometry record {unit normal, kind << 30 as bits} */
+  float* position;                     /* 4 floats: {X = position + t d, t} */
+} ptamd_denoise_history_view;
+
+int ptamd_denoise_history_view_of(const ptamd_denoise_history* history, ptamd_denoise_history_view* out);
+
+/* Host mirror of ptamd_denoise_temporal over host memory (same binary32 operations): features and accumulator as for
+ * ptamd_host_denoise, desc->base as there, desc->alpha_*, reset_history and history_length (a host pointer, optional) as for the
+ * device; desc->history is ignored: `history` is read and updated instead (buffers allocated by the caller, width and height set). */
+int ptamd_host_denoise_temporal(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* desc,
+                                ptamd_denoise_history_view* history, float* linear_rgb, uint8_t* rgba8);
+
 /* The frame number of the context's last ptamd_raytrace (raytrace.cu:296's `seed`): the divisor of its resolve. */
 int ptamd_get_frame_counter(ptamd_context* ctx, uint32_t* out);
 
