@@ -378,8 +378,10 @@ struct KParams {
   uint32_t surf_row0;
   unsigned long long* stats; // 8 counters or nullptr
   unsigned long long* error_flag; // incremented when a bounded spin of the split kernel times out
-  // persistent variant: 8x8 tiles over the row band, handed out by a ticket counter
-  uint32_t* tile_counter;
+  // persistent variant: 8x8 tiles over the row band, handed out by a ticket counter.  The restart kernel's list form (PT_RS_LIST,
+  // adaptive sampling) reads the adaptive state's device block here instead (pt_adaptive.h: ad_counts, ad_list); the union keeps
+  // the layout of the kernel arguments, and so the code of every other kernel, as it was
+  union { uint32_t* tile_counter; uint32_t* adaptive; };
   // persistent kernel: eight ticket heads, PT_HEAD_STRIDE dwords apart (one per XCD; a single head saturates at ~88
   // dequeues/us, MI355X_MICROARCH.md 'dequeue').  Head h hands out tickets n_static + 8 t + h; the first n_static
   // tickets are taken by the waves without an atomic.

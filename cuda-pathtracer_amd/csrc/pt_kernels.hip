@@ -20,6 +20,7 @@
 //     raytrace.cu:194-199), so its remaining iterations skip the walk — exact.
 #include "pt_device.h"
 #include "pt_launch.h"
+#include "pt_adaptive.h"
 #ifndef PT_FMA_BUILD
 #include "pt_denoise.h"
 #endif
@@ -739,14 +740,15 @@ struct Path {
 };
 
 // kernel() prologue: seed, generateRay, camera_dof (raytrace.cu:227-240)
-PT_DEV void path_begin(const KParams& p, uint32_t x, uint32_t y, Path& st, uint32_t k = 0)
+// frame != 0: the sample's own frame number (the restart kernel's list form: a pixel's samples follow its count), hashed here
+PT_DEV void path_begin(const KParams& p, uint32_t x, uint32_t y, Path& st, uint32_t k = 0, uint32_t frame = 0)
 {
   // raytrace.cu:227-229 with the reference's launch geometry (16x16 blocks, padded grid)
   const uint32_t width = PT_KARG(p, width);
   const uint32_t grid_x = width / 16u + 1u;
   const uint32_t tid = ((x >> 4) + (y >> 4) * grid_x) * 256u + (y & 15u) * 16u + (x & 15u);
   // k > 0 only in batched launches: frame frame_nb0 + k has hash_seed WangHash(frame_nb0 + k) (raytrace.cu:321)
-  const uint32_t hash_seed = k == 0 ? PT_KARG(p, hash_seed) : wang_hash(PT_KARG(p, frame_nb0) + k);
+  const uint32_t hash_seed = frame != 0u ? wang_hash(frame) : (k == 0 ? PT_KARG(p, hash_seed) : wang_hash(PT_KARG(p, frame_nb0) + k));
   xorwow_init(st.rng, hash_seed + tid);
 
   // The 14 camera constants are only needed here, once per tile in the persistent kernels: they are re-read from the
@@ -1981,6 +1983,7 @@ PT_DEV bool region_tile(const KParams& p, uint32_t ticket, uint32_t& col, uint32
 #define PT_RS_WIDE8 4   /* scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one */
 #define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
 #define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
+#define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
 
 template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
@@ -1992,6 +1995,13 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
   // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
   constexpr bool LEAN = LDS_RESIDENT && VARIANT == PT_RS_PLAIN;
+  // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
+  // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
+  // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
+  // the pools of fresh paths live in LDS for a resident scene and in the global slab for the four-wide walk (ptamd_api.cpp).
+  constexpr bool LIST = VARIANT == PT_RS_LIST;
+  // constants of the launch the shipped instantiation and the list form share: static camera, no XCD regions, no interleaved bands
+  constexpr bool FIXED = LEAN || LIST;
   extern __shared__ float4 s_mem[];
   const float4* s_nodes;
   const float4* s_tris;
@@ -2042,11 +2052,18 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   uint32_t tile_row_delta = 0;   // (frame row) - (row of the launch's buffers + row_begin): non-zero for interleaved bands
   uint32_t tile = 0, tile_end = 0;
   // XCD-local regions (KParams::xcd_regions): the waves of XCD x take the tickets = x (mod 8), their first ones without an atomic
-  uint32_t ticket = (!LEAN && PT_KARG(p, xcd_regions)) ? ((blockIdx.x >> 3) * (THREADS / 64u) + (threadIdx.x >> 6)) * 8u + (blockIdx.x & 7u) : gwave;
+  uint32_t ticket = (!FIXED && PT_KARG(p, xcd_regions)) ? ((blockIdx.x >> 3) * (THREADS / 64u) + (threadIdx.x >> 6)) * 8u + (blockIdx.x & 7u) : gwave;
   ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);   // wave-uniform: the tile arithmetic stays scalar
   uint32_t reg_col = 0, reg_row = 0, reg_k = 0;
   uint32_t head = blockIdx.x & 7u, dry = 0;
   bool have_ticket = true, exhausted = false;
+  // list form: entries on the list (written by the select pass ahead of this launch, read once per wave), its chunks, the
+  // first entry of the pool's chunk
+  uint32_t list_n = 0, list_chunks = 0, list_base = 0;
+  if constexpr (LIST) {
+    list_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)*ad_active(p.adaptive, p.width * p.height));
+    list_chunks = (list_n + 63u) >> 6;
+  }
   for (;;) {
     // ---- restart lanes without a path from the pool; an empty pool is refilled with a whole tile, all lanes active
     long long tr0 = 0;
@@ -2057,7 +2074,9 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         if (exhausted) break;
         if (tile >= tile_end) {
           const uint32_t tiles_per_ticket = PT_KARG(p, tiles_per_ticket);
-          const uint32_t total = PT_KARG(p, n_tiles) * PT_KARG(p, sample_count); // (tile, frame) pairs
+          uint32_t total;
+          if constexpr (LIST) total = list_chunks * PT_KARG(p, sample_count);   // (chunk, sample) pairs
+          else total = PT_KARG(p, n_tiles) * PT_KARG(p, sample_count); // (tile, frame) pairs
           // a ticket that names work: the wave's own first one (no atomic), then from this workgroup's XCD head; a head that has run
           // dry sends the wave on to the next one for good
           for (;;) {
@@ -2069,22 +2088,25 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
               ticket = PT_KARG(p, n_static) + t * 8u + head;
             }
             have_ticket = false;
-            if ((!LEAN && PT_KARG(p, xcd_regions)) ? region_tile(p, ticket, reg_col, reg_row, reg_k) : ((unsigned long long)ticket * tiles_per_ticket < total)) break;
+            if ((!FIXED && PT_KARG(p, xcd_regions)) ? region_tile(p, ticket, reg_col, reg_row, reg_k) : ((unsigned long long)ticket * tiles_per_ticket < total)) break;
             head = (head + 1u) & 7u;
             if (++dry == 8u) break;
           }
           if (dry == 8u) { exhausted = true; PT_STAMP(2); break; }
-          if (!LEAN && PT_KARG(p, xcd_regions)) { tile = ticket; tile_end = ticket + 1u; }
+          if (!FIXED && PT_KARG(p, xcd_regions)) { tile = ticket; tile_end = ticket + 1u; }
           else {
             tile = ticket * tiles_per_ticket;
             tile_end = tile + tiles_per_ticket;
             if (tile_end > total) tile_end = total;
           }
         }
-        {
+        if constexpr (LIST) {
+          tile_k = tile / list_chunks;
+          list_base = (tile - tile_k * list_chunks) * 64u;
+        } else {
           const uint32_t n_tiles = PT_KARG(p, n_tiles), tiles_x = PT_KARG(p, tiles_x), row_begin = PT_KARG(p, row_begin);
           uint32_t local_y0;                                      // row inside this launch's share of the frame
-          if (!LEAN && PT_KARG(p, xcd_regions)) {
+          if (!FIXED && PT_KARG(p, xcd_regions)) {
             tile_k = reg_k; tile_x0 = reg_col * PT_TILE_W; local_y0 = reg_row * PT_TILE_H;
           } else {
             tile_k = tile / n_tiles;
@@ -2105,7 +2127,18 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
           tile_row_delta = tile_y0 - (row_begin + local_y0);
         }
         ++tile;
-        {
+        if constexpr (LIST) {
+          const uint32_t i = list_base + lane;
+          if (i < list_n) {
+            const uint32_t n_px = p.width * p.height;
+            const uint32_t px = ad_list(p.adaptive, n_px)[i];
+            Path fresh;
+            path_begin(p, px % p.width, px / p.width, fresh, tile_k, ad_counts(p.adaptive)[px] + 1u + tile_k);
+            if (LDS_RESIDENT) pool_store_lds(lds_pool, lane, fresh);
+            else pool_store(slab, lane, fresh);
+          }
+          if (!LDS_RESIDENT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
           const uint32_t x = tile_x0 + (lane & (PT_TILE_W - 1u)), y = tile_y0 + (lane >> PT_TILE_W_LOG2);
           if (x < p.width && y < p.y_limit) {
             Path fresh;
@@ -2120,7 +2153,21 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
       }
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
       const uint32_t avail = 64u - pool_rd;
-      if (idle && rank < avail) {
+      if constexpr (LIST) {
+        const uint32_t i = list_base + pool_rd + rank;
+        if (idle && rank < avail && i < list_n) {   // entries past the end of the list were never written
+          if (LDS_RESIDENT) pool_load_lds(lds_pool, pool_rd + rank, st);
+          else pool_load(slab, pool_rd + rank, st);
+          st.throughput = mk3(1.0f);
+          st.acc = mk3(0.0f);
+          st.specular_col = 0.0f;
+          // parked at samples_out[k][i]: path_finish_sample addresses (k, row, x) of a full-frame launch, row * width + x = i
+          st.xy = (i % p.width) | ((i / p.width) << 16);
+          st.bk = tile_k << 16;
+          idle = false;
+          walking = false;
+        }
+      } else if (idle && rank < avail) {
         const uint32_t e = pool_rd + rank;
         const uint32_t x = tile_x0 + (e & (PT_TILE_W - 1u)), y = tile_y0 + (e >> PT_TILE_W_LOG2);
         if (x < p.width && y < p.y_limit) {   // entries of pixels outside the frame were never written: skip them
@@ -2175,14 +2222,14 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         // path's random stream is the same, and r1 need not live (in scratch, as it turned out) across the walk
         long long tl0 = 0;
         if (STATS) tl0 = clock64();
-        const float r1 = path_pre<LEAN>(p, st);
+        const float r1 = path_pre<FIXED>(p, st);
         Nearest n;
         n.t = best.t; n.u = best.u; n.v = best.v; n.idx = best.idx;
         n = nearest_lights(p, st.o, st.d, n);
         walking = false;
         long long tl1 = 0;
         if (STATS) { asm volatile("" : "+v"(n.t), "+v"(n.idx)); tl1 = clock64(); if (PT_WAVE_ONE()) cnt.cyc[3] += (unsigned long long)(tl1 - tl0); }   // [3]: r1 + light loop
-        if (path_post<STATS, LEAN>(p, st, r1, n, cnt)) {
+        if (path_post<STATS, FIXED>(p, st, r1, n, cnt)) {
           path_finish_sample(p, st);
           idle = true;
           if (STATS) samples++;
@@ -2945,14 +2992,19 @@ static const void* restart_entry_unused(int variant)
     case PT_RS_WIDE8: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE8>);   // (only ever a non-resident scene)
     case PT_RS_WIDE4Q: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE4Q>);
     case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);   // (only ever a resident scene)
+    case PT_RS_LIST: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_LIST>);
     default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
   }
 }
 
 // variant: instrumented build when counters are wanted, else the far-origin form, else the time-stamp form, else the shipped kernel —
-// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form
-static const void* restart_select(bool lds_resident, bool stats, const KParams* p = nullptr)
+// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form.
+// list: the list form of adaptive sampling (its own instantiations, resident scene or four-wide walk; not in the contracted build).
+static const void* restart_select(bool lds_resident, bool stats, const KParams* p = nullptr, bool list = false)
 {
+#ifndef PT_FMA_BUILD
+  if (list) return lds_resident ? restart_entry<true>(PT_RS_LIST) : restart_entry<false>(PT_RS_LIST);
+#endif
   const bool lean = !p || (p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !p->generic_round);
   const int variant = stats ? PT_RS_STATS : (p && p->brute_walk ? PT_RS_BRUTE : (p && p->timeline ? PT_RS_STAMPS : (p && p->wide8 && !lds_resident ? (p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8) :
                       (lds_resident && !lean ? PT_RS_GENERIC : PT_RS_PLAIN))));
@@ -2966,9 +3018,9 @@ uint32_t restart_threads(bool lds_resident) { return lds_resident ? PT_RS_THREAD
 uint32_t restart_wide_blocks_per_cu() { return (PT_RS4_WAVES_PER_EU * 256u) / PT_RS4_THREADS; }
 
 // lds_bytes: the staged scene when lds_resident, else the stacks of the wide walk
-hipError_t restart_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out)
+hipError_t restart_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out, bool list)
 {
-  const void* fn = restart_select(lds_resident, false);
+  const void* fn = restart_select(lds_resident, false, nullptr, list);
   if (lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
@@ -2977,10 +3029,10 @@ hipError_t restart_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out)
 }
 
 hipError_t launch_megakernel_restart(const KParams& p, bool lds_resident, size_t lds_bytes, bool stats,
-                                     uint32_t n_blocks, hipStream_t stream)
+                                     uint32_t n_blocks, hipStream_t stream, bool list)
 {
   if (p.n_tiles == 0 || n_blocks == 0) return hipSuccess;
-  const void* fn = restart_select(lds_resident, stats, &p);
+  const void* fn = restart_select(lds_resident, stats, &p, list);
   if (lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
@@ -3108,6 +3160,7 @@ hipError_t resolve_kernels()
     split_select(true, false), split_select(false, false), blockwise_select(true, false), blockwise_select(false, false),
     restart_entry<true>(PT_RS_PLAIN), restart_entry<false>(PT_RS_PLAIN), restart_entry<true>(PT_RS_STATS), restart_entry<false>(PT_RS_STATS),
     restart_entry<true>(PT_RS_STAMPS), restart_entry<false>(PT_RS_STAMPS), restart_entry<true>(PT_RS_BRUTE), restart_entry<false>(PT_RS_BRUTE), restart_entry<false>(PT_RS_WIDE8), restart_entry<false>(PT_RS_WIDE4Q), restart_entry<true>(PT_RS_GENERIC),
+    restart_entry<true>(PT_RS_LIST), restart_entry<false>(PT_RS_LIST),
     reinterpret_cast<const void*>(pt_megakernel<1, true, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<1, false, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<2, true, false, PT_TILE_THREADS>),

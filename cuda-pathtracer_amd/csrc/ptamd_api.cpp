@@ -9,6 +9,7 @@
 // computed here once per launch with the same float operations the kernel would do.
 #include "../host/ptamd_internal.h"
 #include "pt_device.h"
+#include "pt_adaptive.h"
 #include "pt_denoise.h"
 #include "pt_denoise_temporal.h"
 #include "pt_launch.h"
@@ -84,7 +85,7 @@ struct ptamd_context {
   int n_cus = 0;
   // resident workgroups per CU of the persistent kernels: depends on the scene's dynamic LDS bytes, so the cache is
   // keyed by them ([0] persistent, [1] blockwise, [2] split, [3] restart)
-  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[5];   // ([4]: the contracted restart kernel)
+  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[6];   // ([4]: the contracted restart kernel, [5]: its list form)
   // parked samples of batched launches, one scratch per stream: launches on one stream are ordered, launches on
   // different streams of one context (frames in flight, ptamd_launch.machine_share) must not share a buffer
   // Four slabs per stream.  [0..2] are used in turn by pipelined launches (megakernel on an internal stream, below): the
@@ -306,9 +307,23 @@ int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
 extern "C" hipError_t ptamd_fma_restart_blocks_per_cu(int lds_resident, size_t lds_bytes, int* out);
 extern "C" hipError_t ptamd_fma_launch_restart(const void* kparams, int lds_resident, size_t lds_bytes, uint32_t n_blocks, hipStream_t stream);
 
+// Box margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins inside the scene's extent
+// (bvh_builder.cpp).  A camera so far outside it that this bound exceeds the margin (e.g. 1e5 units from a
+// unit-sized scene) would need wider boxes (do_launch: such launches test every face instead).
+bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam)
+{
+  const float cam_far = std::fmax(std::fabs(cam.position.x), std::fmax(std::fabs(cam.position.y), std::fabs(cam.position.z))) +
+                        std::fabs(cam.aperture);
+  // (2^-21, not the 2^-22 of a single fma: the centre / half-extent form rounds a slab distance twice — t(centre), then -+ half * |1/d| —
+  // on top of the reciprocal's and -o/d's roundings: worst case about 1.75 (|origin| + |plane|) * 2^-22, bvh_builder.cpp)
+  return !((cam_far + s.extent) * (1.0f / 2097152.0f) <= s.margin_floor) && s.n_faces != 0;   // also true for NaN
+}
+
 // later_chunk: the launch is the second or a later part of a batch the library cut into parts (kMaxFramesPerSlab): it follows
 // its predecessor on the same stream by construction, so it is pipelined behind it whatever the caller's machine_share
-int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool later_chunk = false)
+// ad: the trace step of one round of adaptive sampling (ptamd_render_adaptive): the restart kernel's list form over the state's
+// active list, frame_count = samples per round, whole frame, on the caller's stream; its resolve is the list resolve
+int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool later_chunk = false, const AdaptiveParams* ad = nullptr)
 {
   int rc = validate_launch(ctx, l_in);
   if (rc != PTAMD_OK) return rc;
@@ -373,17 +388,16 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
   p.stats = stats ? ctx->d_stats : nullptr;
   p.error_flag = ctx->d_stats + 15;
 
-  uint32_t which = l->kernel == PTAMD_KERNEL_AUTO ? ctx->default_kernel : l->kernel;
-  // Box margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins inside the scene's extent
-  // (bvh_builder.cpp).  A camera so far outside it that this bound exceeds the margin (e.g. 1e5 units from a
-  // unit-sized scene) would need wider boxes: such launches test every face instead — the reference algorithm, exact
-  // for any origin — inside the restart kernel (KParams::brute_walk: all its launch shapes keep working, interleaved
+  // (the list form has one kernel: PTAMD_KERNEL_AUTO means it whatever default kernel PTAMD_DEFAULT_KERNEL pinned)
+  uint32_t which = l->kernel == PTAMD_KERNEL_AUTO ? (ad ? (uint32_t)PTAMD_KERNEL_BVH_RESTART : ctx->default_kernel) : l->kernel;
+  // A camera beyond the reach of the box margins (far_origin_camera): such launches test every face instead — the reference
+  // algorithm, exact for any origin — inside the restart kernel (KParams::brute_walk: all its launch shapes keep working, interleaved
   // bands and batched frames included) or, for the other kernels, through the exhaustive tile kernel.
-  const float cam_far = std::fmax(std::fabs(cam.position.x), std::fmax(std::fabs(cam.position.y), std::fabs(cam.position.z))) +
-                        std::fabs(cam.aperture);
-  // (2^-21, not the 2^-22 of a single fma: the centre / half-extent form rounds a slab distance twice — t(centre), then -+ half * |1/d| —
-  // on top of the reciprocal's and -o/d's roundings: worst case about 1.75 (|origin| + |plane|) * 2^-22, bvh_builder.cpp)
-  const bool far_origin = !((cam_far + s.extent) * (1.0f / 2097152.0f) <= s.margin_floor) && s.n_faces != 0;   // also true for NaN
+  const bool far_origin = far_origin_camera(s, cam);
+  if (ad && (far_origin || which != PTAMD_KERNEL_BVH_RESTART || l->frame_count > kMaxFramesPerSlab)) {
+    set_error("ptamd_render_adaptive: the list form needs the restart kernel and a camera within reach of the box margins");
+    return PTAMD_ERR_ARG;
+  }
   if (far_origin) {
     if (which == PTAMD_KERNEL_BVH_RESTART) p.brute_walk = 1u;
     else which = PTAMD_KERNEL_BRUTE_FORCE;
@@ -430,7 +444,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
   // side and the tail of one is covered by the bulk of the other, exactly what a host gets from two streams and
   // machine_share = 2.  Not when the caller runs its own pipeline (machine_share > 1), captures a graph or wants counters;
   // a host that waits for every frame gets whole-GPU launches on its own stream as before.
-  bool pipelined = ctx->overlap && which == PTAMD_KERNEL_BVH_RESTART && (l->machine_share <= 1u || later_chunk) && !stats;
+  bool pipelined = ctx->overlap && which == PTAMD_KERNEL_BVH_RESTART && (l->machine_share <= 1u || later_chunk) && !stats && !ad;
   bool capturing = false;
   if (stream != nullptr) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -442,7 +456,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
   // one launch at a time: the persistent kernel writes the surface itself, the restart kernel would add its resolve
   // pass to every launch (1080p, one launch per spp, one at a time: 6.03 vs 5.89 Gsamples/s).
   if (l->kernel == PTAMD_KERNEL_AUTO && which == PTAMD_KERNEL_BVH_RESTART && ctx->default_kernel_is_builtin && l->frame_count <= 1 &&
-      resident && l->interleave_ranks <= 1 && l->machine_share <= 1 && !pipelined && !p.brute_walk)
+      resident && l->interleave_ranks <= 1 && l->machine_share <= 1 && !pipelined && !p.brute_walk && !ad)
     which = PTAMD_KERNEL_BVH_PERSISTENT;
   const bool overlap = pipelined;
   hipError_t e;
@@ -516,9 +530,10 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
       // for 1 / 0 (axis-parallel rays) the inner fma stays finite for coordinates up to kQuantisedMaxExtent; beyond it the float
       // nodes are walked, whose planes overflow one by one (an infinite slab distance is still a correct one)
       const bool quantised_ok = s.extent <= kQuantisedMaxExtent;
-      const bool wide8 = ctx->wide8 && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.n_nodes8 != 0;
+      // (tuning knobs, none of them for the list form of adaptive sampling: it is compiled for the four-wide float nodes)
+      const bool wide8 = ctx->wide8 && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.n_nodes8 != 0 && !ad;
       if (wide8) { p.nodes4 = s.nodes8; p.n_nodes4 = s.n_nodes8; p.wide8 = 1u; }
-      const bool wide4q = !wide8 && ctx->wide4q && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.nodes4q != nullptr;
+      const bool wide4q = !wide8 && ctx->wide4q && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.nodes4q != nullptr && !ad;
       if (wide4q) { p.nodes4 = s.nodes4q; p.wide8 = 2u; }
       const uint32_t node_bytes = wide4q ? 64u : 128u;
       const uint32_t need = (wide8 ? 7u * s.depth8 : 3u * s.depth4) + 1u;   // a visit stacks all hit children but the nearest
@@ -527,7 +542,8 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
       // the top of the tree (breadth-first numbering: nodes 0..340 are its first five levels when full) goes to LDS too:
       // 512 nodes = 64 KB of the one workgroup's 160 KB, then 7 stack entries per lane
       // ... and the waves' pools of fresh paths (PT_POOL_LDS_BYTES each), behind the stacks
-      const uint32_t pools = (ctx->pool_in_lds && ctx->pool_in_lds_wide) ? waves * PT_POOL_LDS_BYTES : 0u;
+      // (the list form keeps them in the global slab: it is compiled for that)
+      const uint32_t pools = (ctx->pool_in_lds && ctx->pool_in_lds_wide && !ad) ? waves * PT_POOL_LDS_BYTES : 0u;
       // (the same LDS bytes hold twice as many 64-byte nodes)
       // chunk-major treelet (pt_kernels.hip: PT_TREELET_SOA): a region of fixed size whatever the number of nodes staged
       const uint32_t region = restart_treelet_region_bytes();
@@ -554,18 +570,20 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
       const uint32_t waves = restart_threads(true) / 64u;
       const size_t with_pools = ((lds + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES;
       const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
-      if (ctx->pool_in_lds && with_pools * blocks_wanted + 1024u <= 160u * 1024u) {
+      // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
+      // there whatever the knob, at one workgroup per CU when two do not fit
+      if (ad || (ctx->pool_in_lds && with_pools * blocks_wanted + 1024u <= 160u * 1024u)) {
         p.pool_lds_offset = (uint32_t)((lds + 15u) & ~(size_t)15u);
         if (p.pool_lds_offset == 0) p.pool_lds_offset = 16u;               // (an empty scene: keep the flag non-zero)
         launch_lds = p.pool_lds_offset + (size_t)waves * PT_POOL_LDS_BYTES;
       }
     }
-    ptamd_context::Occupancy& occ = ctx->occupancy[split ? 2 : (restart ? (fma ? 4 : 3) : 0)];
+    ptamd_context::Occupancy& occ = ctx->occupancy[split ? 2 : (restart ? (fma ? 4 : (ad ? 5 : 3)) : 0)];
     const size_t occ_key = resident ? (restart ? launch_lds : lds) : (restart ? launch_lds + 1u : 0);
     if (occ.blocks_per_cu < 0 || occ.lds != occ_key) {
       int q = -1;
       e = split ? split_blocks_per_cu(resident, lds, &q)
-                : (restart ? (fma ? ptamd_fma_restart_blocks_per_cu(resident ? 1 : 0, launch_lds, &q) : restart_blocks_per_cu(resident, launch_lds, &q)) : persistent_blocks_per_cu(resident, lds, &q));
+                : (restart ? (fma ? ptamd_fma_restart_blocks_per_cu(resident ? 1 : 0, launch_lds, &q) : restart_blocks_per_cu(resident, launch_lds, &q, ad != nullptr)) : persistent_blocks_per_cu(resident, lds, &q));
       if (e != hipSuccess || q < 1) { occ.blocks_per_cu = -1; return hip_fail("occupancy query of the persistent kernel", e); }
       occ.blocks_per_cu = q; occ.lds = occ_key;
     }
@@ -579,7 +597,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     // (measured, batched 1080p: 4 bounces 4.65 vs 4.46 Gsamples/s without/with, 5: 3.90 vs 4.13,
     // 6: 3.44 vs 3.92, 8: 2.89 vs 3.71); below that, whole-wave refill keeps primary rays coherent.
     p.refill_min = ctx->refill_min ? ctx->refill_min : (l->bounces >= 5 ? 16u : 64u);
-    const uint32_t tiles_per_ticket = ctx->tiles_per_ticket;
+    const uint32_t tiles_per_ticket = ad ? 1u : ctx->tiles_per_ticket;   // (the list form: one chunk of 64 entries per ticket)
     const uint32_t share = overlap ? (l->machine_share > 2u ? l->machine_share : 2u) : l->machine_share;
     if (share > 1u) n_blocks = n_blocks / share > 0u ? n_blocks / share : 1u;
     const uint32_t n_tickets = (p.n_tiles * count + tiles_per_ticket - 1u) / tiles_per_ticket;
@@ -587,7 +605,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     if (n_blocks > useful) n_blocks = useful;
     // XCD-local regions (pt_kernels.hip: region_tile): the ticket -> tile map that keeps every XCD on a compact part of the frame.
     // Needs whole groups of eight workgroups (one per XCD) and one tile per ticket.
-    if (restart && tiles_per_ticket == 1u && n_blocks >= 8u && (uint64_t)p.n_tiles * count < (1ull << 28) &&
+    if (restart && !ad && tiles_per_ticket == 1u && n_blocks >= 8u && (uint64_t)p.n_tiles * count < (1ull << 28) &&
         (ctx->xcd_regions == 2u || (ctx->xcd_regions == 1u && !resident))) {
       n_blocks &= ~7u;
       p.xcd_regions = 1u;
@@ -663,6 +681,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     }
     if (capturing && sc) { ctx->slot_pinned[slot] = true; sc->pinned_slots.push_back(slot); sc->captured = true; }
     p.tile_counter = ctx->d_tickets + slot;
+    if (ad) p.adaptive = ad->block;   // (the restart kernel takes no ticket counter: the field names the list form's state instead)
     p.n_static = n_blocks * waves_per_block;
     if (split) PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)p.n_static, 1, stream));
     hipStream_t mega_stream = stream;
@@ -681,14 +700,21 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     }
     if (restart && !fma && ctx->d_timeline && n_blocks * waves_per_block <= ctx->timeline_waves) p.timeline = ctx->d_timeline;
     if (split) { p.tiles_per_ticket = 1; e = launch_megakernel_split(p, resident, lds, stats, n_blocks, stream); }
-    else if (restart) e = fma ? ptamd_fma_launch_restart(&p, resident ? 1 : 0, launch_lds, n_blocks, mega_stream) : launch_megakernel_restart(p, resident, launch_lds, stats, n_blocks, mega_stream);
+    else if (restart) e = fma ? ptamd_fma_launch_restart(&p, resident ? 1 : 0, launch_lds, n_blocks, mega_stream) : launch_megakernel_restart(p, resident, launch_lds, stats, n_blocks, mega_stream, ad != nullptr);
     else e = launch_megakernel_persistent(p, resident, lds, stats, n_blocks, stream);
     if (e == hipSuccess && overlap) {
       PT_HIP(hipEventRecord(sc->mega_done[scratch_slab], mega_stream));
       PT_HIP(hipStreamWaitEvent(stream, sc->mega_done[scratch_slab], 0));
     }
     if (e == hipSuccess && parks) {
-      e = launch_resolve(p, stream);
+      if (ad) {
+        AdaptiveParams a = *ad;
+        a.samples = p.samples_out;
+        a.tile_heads = p.tile_heads;
+        e = launch_adaptive_resolve_list(a, stream);
+      } else {
+        e = launch_resolve(p, stream);
+      }
       if (e == hipSuccess && !split) ctx->heads_clean[slot] = true;
       if (e == hipSuccess && overlap) {
         // whoever writes this slab next (a megakernel on an internal stream) waits for this pass
@@ -1385,6 +1411,15 @@ int ptamd_device_to_host(ptamd_context* ctx, void* dst_host, const void* src_dev
   return PTAMD_OK;
 }
 
+int ptamd_host_to_device(ptamd_context* ctx, void* dst_dev, const void* src_host, size_t bytes, void* stream)
+{
+  if (!ctx || !dst_dev || !src_host) { set_error("ptamd_host_to_device: null argument"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+  PT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  return PTAMD_OK;
+}
+
 int ptamd_stream_synchronize(ptamd_context* ctx, void* stream)
 {
   if (!ctx) { set_error("ptamd_stream_synchronize: null context"); return PTAMD_ERR_ARG; }
@@ -1709,6 +1744,209 @@ int ptamd_host_denoise_temporal(const float* features, const float* temporal_fra
   hv->frame_nb = d->frame_nb;
   hv->valid = 1u;
   std::memcpy(rgba8, surface.data(), n * 4);
+  return PTAMD_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- adaptive sampling (pt_adaptive.h)
+
+struct ptamd_adaptive_state {
+  const ptamd_context* ctx = nullptr;
+  uint32_t width = 0, height = 0, tiles_x = 0, n_tiles = 0;
+  uint32_t* block = nullptr;   // pt_adaptive.h: counts | moments | list | active count | tile masks | tile offsets
+};
+
+namespace {
+
+constexpr uint32_t kAdaptiveMaxPixels = 1u << 28;   // 4 words per pixel stay addressable in 32 bits (pt_adaptive.h)
+constexpr uint32_t kAdaptiveMaxSpp = 65536;
+
+// the checks of select (and of the host mirror): frame, spp rules, threshold, floor, dilate; fills the select's constants
+int adaptive_rules(const char* who, const ptamd_adaptive_desc* d, AdaptiveParams& a)
+{
+  auto fail = [&](const char* what) { set_error(std::string(who) + ": " + what); return PTAMD_ERR_ARG; };
+  if (d->width == 0 || d->height == 0 || d->width > 65536 || d->height > 65536 || (uint64_t)d->width * d->height > kAdaptiveMaxPixels)
+    return fail("bad frame size (1..65536 per side, at most 2^28 pixels)");
+  if (d->samples_per_round < 1 || d->samples_per_round > kMaxFramesPerSlab) return fail("samples_per_round out of range (1..4)");
+  if (d->min_spp < 2 || d->min_spp > d->max_spp || d->max_spp > kAdaptiveMaxSpp) return fail("spp rules: 2 <= min_spp <= max_spp <= 65536");
+  if (d->min_spp % d->samples_per_round || d->max_spp % d->samples_per_round) return fail("spp rules: min_spp and max_spp must be multiples of samples_per_round");
+  if (!(d->threshold >= 0.0f)) return fail("threshold must be >= 0 (not NaN)");
+  if (!(d->err_floor >= 0.0f)) return fail("err_floor must be >= 0 (not NaN)");
+  if (d->dilate > 1) return fail("dilate must be 0 or 1");
+  std::memset(&a, 0, sizeof a);
+  a.width = d->width; a.height = d->height;
+  a.tiles_x = (d->width + PT_TILE_W - 1u) / PT_TILE_W;
+  a.n_tiles = a.tiles_x * ((d->height + PT_TILE_H - 1u) / PT_TILE_H);
+  a.min_spp = d->min_spp; a.max_spp = d->max_spp; a.spr = d->samples_per_round;
+  a.threshold = d->threshold;
+  a.err_floor = d->err_floor == 0.0f ? PT_AD_ERR_FLOOR : d->err_floor;
+  a.dilate = d->dilate;
+  a.active_counts = d->active_counts;
+  return PTAMD_OK;
+}
+
+// the device entry points' checks.  what: 0 select, 1 resolve (+ output buffers), 2 render (+ scene, camera, bounces, kernel, rounds)
+int adaptive_checks(const char* who, const ptamd_context* ctx, const ptamd_adaptive_desc* d, int what, AdaptiveParams& a)
+{
+  auto fail = [&](const char* msg) { set_error(std::string(who) + ": " + msg); return PTAMD_ERR_ARG; };
+  if (!ctx || !d) return fail("null context or desc");
+  if (!d->state) return fail("null state");
+  int rc = adaptive_rules(who, d, a);
+  if (rc != PTAMD_OK) return rc;
+  const ptamd_adaptive_state* st = d->state;
+  if (st->ctx != ctx) return fail("the state belongs to another context");
+  if (st->width != d->width || st->height != d->height) return fail("the state belongs to another frame size");
+  if (what >= 1) {
+    if (!d->surface_rgba8 || !d->temporal_framebuffer) return fail("null output buffer");
+    if (d->post_id > 3) return fail("post_id out of range (0..3)");
+  }
+  if (what >= 2) {
+    if (d->scene_id >= ctx->scenes.size()) return fail("scene_id out of range");
+    if (d->cubemap_id >= ctx->cubemaps.size()) return fail("cubemap_id out of range");
+    if (d->bounces == 0 || d->bounces > 1024) return fail("bounces out of range (1..1024)");
+    if (d->kernel != PTAMD_KERNEL_AUTO && d->kernel != PTAMD_KERNEL_BVH_RESTART) return fail("kernel must be PTAMD_KERNEL_AUTO or PTAMD_KERNEL_BVH_RESTART");
+    if (d->rounds < 1 || d->rounds > 65536) return fail("rounds out of range (1..65536)");
+  }
+  a.block = st->block;
+  a.post_id = d->post_id;
+  a.gamma_table = ctx->d_gamma;
+  a.tfb = d->temporal_framebuffer;
+  a.surface = static_cast<uint32_t*>(d->surface_rgba8);
+  return PTAMD_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptamd_adaptive_create(ptamd_context* ctx, uint32_t width, uint32_t height, ptamd_adaptive_state** out)
+{
+  if (!ctx || !out) { set_error("ptamd_adaptive_create: null argument"); return PTAMD_ERR_ARG; }
+  *out = nullptr;
+  if (width == 0 || height == 0 || width > 65536 || height > 65536 || (uint64_t)width * height > kAdaptiveMaxPixels) {
+    set_error("ptamd_adaptive_create: bad frame size (1..65536 per side, at most 2^28 pixels)");
+    return PTAMD_ERR_ARG;
+  }
+  PT_HIP(hipSetDevice(ctx->device));
+  ptamd_adaptive_state* st = new (std::nothrow) ptamd_adaptive_state;
+  if (!st) { set_error("ptamd_adaptive_create: out of memory"); return PTAMD_ERR_LIMIT; }
+  st->ctx = ctx;
+  st->width = width; st->height = height;
+  st->tiles_x = (width + PT_TILE_W - 1u) / PT_TILE_W;
+  st->n_tiles = st->tiles_x * ((height + PT_TILE_H - 1u) / PT_TILE_H);
+  const size_t bytes = ad_block_bytes(width * height, st->n_tiles);
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->block), bytes);
+  if (e != hipSuccess) { delete st; return hip_fail("hipMalloc (adaptive state)", e); }
+  const hipError_t z = hipMemset(st->block, 0, bytes);
+  if (z != hipSuccess) { (void)hipFree(st->block); delete st; return hip_fail("hipMemset (adaptive state)", z); }
+  *out = st;
+  return PTAMD_OK;
+}
+
+int ptamd_adaptive_destroy(ptamd_context* ctx, ptamd_adaptive_state* st)
+{
+  if (!ctx || !st) { set_error("ptamd_adaptive_destroy: null argument"); return PTAMD_ERR_ARG; }
+  if (st->ctx != ctx) { set_error("ptamd_adaptive_destroy: the state belongs to another context"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  (void)hipFree(st->block);   // (waits for the work in flight that may still use it)
+  delete st;
+  return PTAMD_OK;
+}
+
+int ptamd_adaptive_reset(ptamd_context* ctx, ptamd_adaptive_state* st, void* stream)
+{
+  if (!ctx || !st) { set_error("ptamd_adaptive_reset: null argument"); return PTAMD_ERR_ARG; }
+  if (st->ctx != ctx) { set_error("ptamd_adaptive_reset: the state belongs to another context"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(hipMemsetAsync(ad_counts(st->block), 0, (size_t)st->width * st->height * 4u, static_cast<hipStream_t>(stream)));
+  return PTAMD_OK;
+}
+
+int ptamd_adaptive_view_of(const ptamd_adaptive_state* st, ptamd_adaptive_view* out)
+{
+  if (!st || !out) { set_error("ptamd_adaptive_view_of: null argument"); return PTAMD_ERR_ARG; }
+  const uint32_t n = st->width * st->height;
+  out->width = st->width; out->height = st->height;
+  out->counts = ad_counts(st->block);
+  out->moments = ad_moments(st->block, n);
+  out->list = ad_list(st->block, n);
+  out->active_count = ad_active(st->block, n);
+  return PTAMD_OK;
+}
+
+int ptamd_adaptive_select(ptamd_context* ctx, const ptamd_adaptive_desc* d)
+{
+  AdaptiveParams a;
+  int rc = adaptive_checks("ptamd_adaptive_select", ctx, d, 0, a);
+  if (rc != PTAMD_OK) return rc;
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(launch_adaptive_select(a, static_cast<hipStream_t>(d->stream)));
+  return PTAMD_OK;
+}
+
+int ptamd_adaptive_resolve(ptamd_context* ctx, const ptamd_adaptive_desc* d, float* linear_rgb)
+{
+  AdaptiveParams a;
+  int rc = adaptive_checks("ptamd_adaptive_resolve", ctx, d, 1, a);
+  if (rc != PTAMD_OK) return rc;
+  a.linear = linear_rgb;
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(launch_adaptive_resolve(a, static_cast<hipStream_t>(d->stream)));
+  return PTAMD_OK;
+}
+
+int ptamd_render_adaptive(ptamd_context* ctx, const ptamd_adaptive_desc* d)
+{
+  AdaptiveParams a;
+  int rc = adaptive_checks("ptamd_render_adaptive", ctx, d, 2, a);
+  if (rc != PTAMD_OK) return rc;
+  if (far_origin_camera(ctx->scenes[d->scene_id], d->camera)) {
+    set_error("ptamd_render_adaptive: the camera is beyond the reach of the box margins (launches of it walk every triangle): "
+              "not supported by the list form; render it with ptamd_raytrace_ex");
+    return PTAMD_ERR_ARG;
+  }
+  ptamd_launch l;
+  std::memset(&l, 0, sizeof l);
+  l.surface_rgba8 = d->surface_rgba8;
+  l.temporal_framebuffer = d->temporal_framebuffer;
+  l.stream = d->stream;
+  l.camera = d->camera;
+  l.scene_id = d->scene_id; l.cubemap_id = d->cubemap_id;
+  l.width = d->width; l.height = d->height;
+  l.row_begin = 0; l.row_end = d->height;
+  l.frame_nb = 1;   // (unused: every sample's frame number comes from its pixel's count)
+  l.bounces = d->bounces;
+  l.post_id = d->post_id;
+  l.kernel = d->kernel;
+  l.frame_count = d->samples_per_round;
+  l.no_pipelining = 1;
+  PT_HIP(hipSetDevice(ctx->device));
+  for (uint32_t r = 0; r < d->rounds; ++r) {
+    a.round = r;
+    PT_HIP(launch_adaptive_select(a, static_cast<hipStream_t>(d->stream)));
+    rc = do_launch(ctx, &l, false, false, &a);
+    if (rc != PTAMD_OK) return rc;
+  }
+  return PTAMD_OK;
+}
+
+int ptamd_host_adaptive_select(const ptamd_adaptive_desc* d, const uint32_t* counts, const float* moments, uint32_t* list,
+                               uint32_t* active_count)
+{
+  if (!d || !counts || !moments || !list || !active_count) { set_error("ptamd_host_adaptive_select: null argument"); return PTAMD_ERR_ARG; }
+  AdaptiveParams a;
+  int rc = adaptive_rules("ptamd_host_adaptive_select", d, a);
+  if (rc != PTAMD_OK) return rc;
+  uint32_t n = 0;
+  for (uint32_t tile = 0; tile < a.n_tiles; ++tile) {
+    const uint32_t x0 = (tile % a.tiles_x) * PT_TILE_W, y0 = (tile / a.tiles_x) * PT_TILE_H;
+    for (uint32_t lane = 0; lane < 64u; ++lane) {
+      const uint32_t x = x0 + (lane & (PT_TILE_W - 1u)), y = y0 + (lane >> PT_TILE_W_LOG2);
+      if (x < a.width && y < a.height && ad_pixel_active(a, counts, moments, x, y)) list[n++] = y * a.width + x;
+    }
+  }
+  *active_count = n;
   return PTAMD_OK;
 }
 

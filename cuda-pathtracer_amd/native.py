@@ -113,6 +113,23 @@ class DenoiseHistoryView(C.Structure):    # ptamd_denoise_history_view (include/
 DENOISE_HISTORY_BYTES = 100                           # per pixel of a device history
 
 
+class AdaptiveView(C.Structure):          # ptamd_adaptive_view (include/ptamd.h)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("counts", C.c_void_p), ("moments", C.c_void_p),
+                ("list", C.c_void_p), ("active_count", C.c_void_p)]
+
+
+class AdaptiveDesc(C.Structure):          # ptamd_adaptive_desc (include/ptamd.h)
+    _fields_ = [("surface_rgba8", C.c_void_p), ("temporal_framebuffer", C.c_void_p), ("stream", C.c_void_p),
+                ("camera", Camera), ("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("bounces", C.c_uint32), ("post_id", C.c_uint32), ("kernel", C.c_uint32),
+                ("state", C.c_void_p), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("samples_per_round", C.c_uint32),
+                ("rounds", C.c_uint32), ("threshold", C.c_float), ("err_floor", C.c_float), ("dilate", C.c_uint32),
+                ("active_counts", C.c_void_p)]
+
+
+ADAPTIVE_ERR_FLOOR = 0.01                             # ptamd_adaptive_desc.err_floor 0
+
+
 FEATURE_MISS, FEATURE_MESH, FEATURE_LIGHT = 0, 1, 2   # kind of a feature record (code >> 30)
 FEATURE_BYTES = 32                                    # per pixel: {normal.xyz, t} {albedo.rgb, kind << 30 | index}
 DENOISE_MAX_LEVELS = 8
@@ -192,10 +209,19 @@ SIGNATURES = {
     "ptamd_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(DenoiseTemporalDesc)]),
     "ptamd_host_denoise_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseTemporalDesc), C.POINTER(DenoiseHistoryView),
                                               C.c_void_p, C.c_void_p]),
+    "ptamd_adaptive_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ptamd_adaptive_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ptamd_adaptive_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptamd_adaptive_view_of": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveView)]),
+    "ptamd_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveDesc)]),
+    "ptamd_adaptive_select": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveDesc)]),
+    "ptamd_adaptive_resolve": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveDesc), C.c_void_p]),
+    "ptamd_host_adaptive_select": (C.c_int, [C.POINTER(AdaptiveDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptamd_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "ptamd_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_device_memset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "ptamd_device_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ptamd_host_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ptamd_stream_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 

@@ -165,6 +165,10 @@ class Context:
         d.sigma_n, d.sigma_l, d.sigma_x = sigma_n, sigma_l, sigma_x
         N.check(self._lib.ptamd_denoise(self._h, C.byref(d)))
 
+    def adaptive_state(self, width: int, height: int) -> "AdaptiveState":
+        """Per-pixel sample counts, luminance moments and active list of width x height pixels (ptamd_adaptive_create)."""
+        return AdaptiveState(self, width, height)
+
     def denoise_history(self, width: int, height: int) -> "DenoiseHistory":
         """A temporal history of width x height pixels on this context (ptamd_denoise_history_create)."""
         return DenoiseHistory(self, width, height)
@@ -373,6 +377,92 @@ class DenoiseHistory:
         self.close()
 
 
+class AdaptiveState:
+    """The device state of adaptive sampling (ptamd_adaptive_*): per pixel a sample count, the luminance moments {m1, m2} and the
+    active list of the last select, allocated once.  Close it before its context."""
+
+    def __init__(self, ctx: Context, width: int, height: int):
+        self.ctx, self.width, self.height = ctx, width, height
+        h = C.c_void_p()
+        N.check(ctx._lib.ptamd_adaptive_create(ctx._h, width, height, C.byref(h)))
+        self.handle = h.value
+
+    def view(self) -> N.AdaptiveView:
+        v = N.AdaptiveView()
+        N.check(self.ctx._lib.ptamd_adaptive_view_of(self.handle, C.byref(v)))
+        return v
+
+    def reset(self, stream=None) -> None:
+        """Every count to 0: the next render_adaptive() starts a new accumulation (the accumulator need not be cleared)."""
+        N.check(self.ctx._lib.ptamd_adaptive_reset(self.ctx._h, self.handle, _stream_handle(stream)))
+
+    def read(self) -> dict:
+        """The state copied to host memory (synchronises the device): counts uint32[H, W], moments float32[H, W, 2], and the
+        active list uint32[n] of the last select."""
+        import torch
+        v = self.view()
+        torch.cuda.synchronize(self.ctx.device)
+        n = np.zeros(1, np.uint32)
+        counts = np.zeros((self.height, self.width), np.uint32)
+        moments = np.zeros((self.height, self.width, 2), np.float32)
+        lib, h = self.ctx._lib, self.ctx._h
+        N.check(lib.ptamd_device_to_host(h, n.ctypes.data, v.active_count, 4, None))
+        N.check(lib.ptamd_device_to_host(h, counts.ctypes.data, v.counts, counts.nbytes, None))
+        N.check(lib.ptamd_device_to_host(h, moments.ctypes.data, v.moments, moments.nbytes, None))
+        lst = np.zeros(int(n[0]), np.uint32)
+        if lst.size:
+            N.check(lib.ptamd_device_to_host(h, lst.ctypes.data, v.list, lst.nbytes, None))
+        N.check(lib.ptamd_stream_synchronize(h, None))
+        return {"counts": counts, "moments": moments, "list": lst}
+
+    def write(self, counts: np.ndarray, moments: np.ndarray) -> None:
+        """Counts and moments from host memory (tests, hosts that carry a state over; synchronises the device)."""
+        v = self.view()
+        c = np.ascontiguousarray(counts, np.uint32)
+        m = np.ascontiguousarray(moments, np.float32)
+        if c.shape != (self.height, self.width) or m.shape != (self.height, self.width, 2):
+            raise ValueError("counts must be uint32[H, W] and moments float32[H, W, 2]")
+        lib, h = self.ctx._lib, self.ctx._h
+        N.check(lib.ptamd_host_to_device(h, v.counts, c.ctypes.data, c.nbytes, None))
+        N.check(lib.ptamd_host_to_device(h, v.moments, m.ctypes.data, m.nbytes, None))
+        N.check(lib.ptamd_stream_synchronize(h, None))
+
+    def close(self) -> None:
+        if self.handle:
+            N.check(self.ctx._lib.ptamd_adaptive_destroy(self.ctx._h, self.handle))
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def adaptive_desc(width: int, height: int, min_spp: int, max_spp: int, samples_per_round: int = 4, threshold: float = 0.0,
+                  err_floor: float = 0.0, dilate: bool = False, rounds: int = 1) -> N.AdaptiveDesc:
+    d = N.AdaptiveDesc()
+    d.width, d.height, d.min_spp, d.max_spp, d.samples_per_round = width, height, min_spp, max_spp, samples_per_round
+    d.threshold, d.err_floor, d.dilate, d.rounds = threshold, err_floor, 1 if dilate else 0, rounds
+    return d
+
+
+def host_adaptive_select(counts: np.ndarray, moments: np.ndarray, min_spp: int, max_spp: int, samples_per_round: int = 4,
+                         threshold: float = 0.0, err_floor: float = 0.0, dilate: bool = False) -> np.ndarray:
+    """Host mirror of the select step (ptamd_host_adaptive_select): the active list (pixel indices y * W + x, 8x8 tiles row-major,
+    pixels row-major inside a tile) from counts uint32[H, W] and moments float32[H, W, 2]."""
+    c = np.ascontiguousarray(counts, np.uint32)
+    m = np.ascontiguousarray(moments, np.float32)
+    h, w = c.shape
+    if m.shape != (h, w, 2):
+        raise ValueError("moments must be float32[H, W, 2]")
+    d = adaptive_desc(w, h, min_spp, max_spp, samples_per_round, threshold, err_floor, dilate)
+    lst = np.zeros(max(w * h, 1), np.uint32)
+    n = np.zeros(1, np.uint32)
+    N.check(N.load().ptamd_host_adaptive_select(C.byref(d), c.ctypes.data, m.ctypes.data, lst.ctypes.data, n.ctypes.data))
+    return lst[: int(n[0])].copy()
+
+
 class HostDenoiseHistory:
     """The history of the host mirror (ptamd_host_denoise_temporal) in numpy arrays, the layout DenoiseHistory.read() returns."""
 
@@ -561,3 +651,44 @@ class FrameRenderer:
                                   alpha_moments=alpha_moments, reset_history=reset_history or continued,
                                   history_length=history_length, linear=linear, stream=stream)
         self._temporal_last = key
+
+    # ---- adaptive sampling (ptamd_render_adaptive)
+
+    def _adaptive(self, state: AdaptiveState, min_spp: int, max_spp: int, samples_per_round: int, rounds: int, threshold: float,
+                  err_floor: float, dilate: bool, bounces: int, post_id: int, kernel: int, active_counts, stream) -> N.AdaptiveDesc:
+        if self.rows != (0, self.height) or self.band_local or self.interleave is not None:
+            raise ValueError("adaptive sampling needs a full-frame renderer (no row band, band-local or interleaved buffers)")
+        d = adaptive_desc(self.width, self.height, min_spp, max_spp, samples_per_round, threshold, err_floor, dilate, rounds)
+        d.surface_rgba8, d.temporal_framebuffer = _ptr(self.surface), _ptr(self.accum)
+        d.stream = _stream_handle(stream)
+        d.camera = self.cam
+        d.scene_id, d.cubemap_id, d.bounces, d.post_id, d.kernel = self.scene_id, self.cubemap_id, bounces, post_id, kernel
+        d.state = state.handle
+        d.active_counts = _ptr(active_counts) if active_counts is not None else None
+        return d
+
+    def render_adaptive(self, state: AdaptiveState, min_spp: int, max_spp: int, samples_per_round: int = 4, rounds: int = 1,
+                        threshold: float = 0.0, err_floor: float = 0.0, dilate: bool = False, bounces: int = REFERENCE_BOUNCES,
+                        post_id: int = POST_NONE, kernel: int = N.KERNEL_AUTO, active_counts=None, stream=None) -> None:
+        """`rounds` rounds of adaptive sampling into this renderer's accumulator and surface: each round samples
+        `samples_per_round` more frames of every pixel below min_spp, or below max_spp with a relative error above `threshold`.
+        A pixel with c samples then holds the accumulator and bytes of a c-frame uniform render.  The state's counts decide
+        what the accumulator holds: after a camera move, state.reset() (the accumulator need not be cleared).
+        active_counts: optional uint32/int32 device tensor of `rounds` entries, the list length of each round."""
+        d = self._adaptive(state, min_spp, max_spp, samples_per_round, rounds, threshold, err_floor, dilate, bounces, post_id,
+                           kernel, active_counts, stream)
+        N.check(self.ctx._lib.ptamd_render_adaptive(self.ctx._h, C.byref(d)))
+        self._fresh = False
+
+    def adaptive_select(self, state: AdaptiveState, min_spp: int, max_spp: int, samples_per_round: int = 4, threshold: float = 0.0,
+                        err_floor: float = 0.0, dilate: bool = False, active_counts=None, stream=None) -> None:
+        """The select step alone: the state's active list from its counts and moments (ptamd_adaptive_select)."""
+        d = self._adaptive(state, min_spp, max_spp, samples_per_round, 1, threshold, err_floor, dilate, REFERENCE_BOUNCES,
+                           POST_NONE, N.KERNEL_AUTO, active_counts, stream)
+        N.check(self.ctx._lib.ptamd_adaptive_select(self.ctx._h, C.byref(d)))
+
+    def adaptive_resolve(self, state: AdaptiveState, post_id: int = POST_NONE, linear=None, stream=None) -> None:
+        """Every pixel's bytes from the accumulator divided by its own count (ptamd_adaptive_resolve); linear: optional
+        float32[H, W, 3] device tensor for that colour, row 0 = top."""
+        d = self._adaptive(state, 2, 2, 1, 1, 0.0, 0.0, False, REFERENCE_BOUNCES, post_id, N.KERNEL_AUTO, None, stream)
+        N.check(self.ctx._lib.ptamd_adaptive_resolve(self.ctx._h, C.byref(d), _ptr(linear) if linear is not None else None))

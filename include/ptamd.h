@@ -438,7 +438,8 @@ typedef struct {
   float sigma_x;                       /* plane-distance scale, > 0 (0: 1) */
 } ptamd_denoise_desc;
 
-/* Denoises the accumulator into surface_rgba8 (and linear_rgb): asynchronous on `stream`.  Call it after ptamd_raytrace /
+/* Denoises the accumulator into surface_rgba8 (and linear_rgb): asynchronous on `stream`.  The accumulator must be uniform (every
+ * pixel frame_nb samples): the accumulators of adaptive sampling (ptamd_render_adaptive) are not inputs of the denoiser.  Call it after ptamd_raytrace /
  * ptamd_raytrace_ex on the same stream (stream order makes the accumulator complete).  Errors: PTAMD_ERR_ARG for null pointers,
  * ids or post_id out of range, levels > 8, a sigma out of range, frame_nb 0, frames outside 1..65536 per side.
  * Workspace: the feature records, the geometry records and two ping-pong images (96 bytes per pixel) belong to the context.  They
@@ -512,6 +513,81 @@ int ptamd_denoise_history_view_of(const ptamd_denoise_history* history, ptamd_de
 int ptamd_host_denoise_temporal(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* desc,
                                 ptamd_denoise_history_view* history, float* linear_rgb, uint8_t* rgba8);
 
+/* ---- Adaptive sampling ----------------------------------------------------------------------------------
+ * Per-pixel sample counts: rounds of samples go to the pixels whose luminance error estimate is still above a threshold.  A sample
+ * of pixel (x, y) with frame number n depends only on n and the pixel, so a pixel that has taken c samples holds exactly the
+ * accumulator and surface bytes of the reference's image after c frames.
+ *
+ * A state belongs to one context and one frame size and holds, per pixel (surface row order, row 0 = top, index y * width + x): the
+ * sample count (uint32), the luminance moments {m1, m2} (2 floats), the active list (uint32 pixel indices), and one word with the
+ * list's length.  A pixel with count 0 counts its accumulator as zero (as reset_accumulation does): a new accumulation needs
+ * ptamd_adaptive_reset, not a cleared accumulator.  A camera move means a reset.  Calls that use one state must be ordered (one
+ * stream, or events). */
+typedef struct ptamd_adaptive_state ptamd_adaptive_state;
+
+int ptamd_adaptive_create(ptamd_context* ctx, uint32_t width, uint32_t height, ptamd_adaptive_state** out);   /* counts 0 */
+/* Destroy a state before its context: ptamd_destroy does not free the states of the context. */
+int ptamd_adaptive_destroy(ptamd_context* ctx, ptamd_adaptive_state* state);   /* waits for the device */
+/* Every count to 0, on `stream`. */
+int ptamd_adaptive_reset(ptamd_context* ctx, ptamd_adaptive_state* state, void* stream);
+
+/* The state's device buffers, width x height entries each (moments: 2 floats per pixel). */
+typedef struct {
+  uint32_t width, height;
+  uint32_t* counts;
+  float* moments;                      /* {m1, m2}: sums of the luminance l = (0.2126 r + 0.7152 g) + 0.0722 b of the samples and of l^2 */
+  uint32_t* list;                      /* the active list of the last select: pixel indices, 8x8 tiles row-major, pixels row-major inside */
+  uint32_t* active_count;              /* one word: the list's length */
+} ptamd_adaptive_view;
+
+int ptamd_adaptive_view_of(const ptamd_adaptive_state* state, ptamd_adaptive_view* out);
+
+typedef struct {
+  void* surface_rgba8;                 /* width x height RGBA8, row 0 = top: the bytes of the pixels a round sampled are rewritten */
+  float* temporal_framebuffer;         /* the accumulator, reference layout (row-flipped), full frame */
+  void* stream;                        /* hipStream_t; NULL = default stream */
+  ptamd_camera camera;
+  uint32_t scene_id, cubemap_id;
+  uint32_t width, height;              /* full frames only (the state's size) */
+  uint32_t bounces;                    /* 1..1024 */
+  uint32_t post_id;                    /* 0..3 */
+  uint32_t kernel;                     /* PTAMD_KERNEL_AUTO or PTAMD_KERNEL_BVH_RESTART: both the list form of the restart kernel */
+  ptamd_adaptive_state* state;
+  uint32_t min_spp, max_spp;           /* 2 <= min_spp <= max_spp <= 65536, both multiples of samples_per_round */
+  uint32_t samples_per_round;          /* 1..4 */
+  uint32_t rounds;                     /* 1..65536 */
+  float threshold;                     /* >= 0: a pixel stays active while its relative error is above it */
+  float err_floor;                     /* >= 0 added to the mean in the relative error; 0: the default 0.01 */
+  uint32_t dilate;                     /* 0 or 1: a pixel below max_spp is also active when a pixel of its 3x3 neighbourhood is */
+  uint32_t* active_counts;             /* optional device pointer: rounds words, the list length of each round's select */
+} ptamd_adaptive_desc;
+
+/* Enqueues `rounds` rounds on desc->stream, without host synchronisation between them.  A round: select (the active list from counts
+ * and moments: count < min_spp, or count < max_spp and err > threshold, err = sqrt(var / n) / (mean + err_floor) with
+ * var = max(0, (m2 / n - mean^2) n / (n - 1)), then dilation), trace (samples_per_round samples of every listed pixel; sample k of
+ * pixel p has frame number count_p + 1 + k), resolve (samples added to the accumulator in frame order, moments, counts += samples_per_round,
+ * the listed pixels' bytes from accumulator / count).  Full frames only: no bands, interleave, machine_share or pipelining.  The
+ * first call of a frame size on a stream sizes the stream's sample slab; later calls only enqueue (they can be captured into a graph,
+ * as ptamd_raytrace_ex, ptamd_release_captured included).  The library's tuning knobs (PTAMD_TUNING) do not apply to these calls.  A camera so far from the scene that launches walk every triangle
+ * (ptamd_raytrace_ex's far-origin rule) is refused with PTAMD_ERR_ARG.  Errors: PTAMD_ERR_ARG for null pointers, bad ids, the
+ * rules of the fields above, a NaN threshold or floor, a state of another context or frame size. */
+int ptamd_render_adaptive(ptamd_context* ctx, const ptamd_adaptive_desc* desc);
+
+/* The select step alone (the list and its length in the state; active_counts[0] when given).  Reads width, height, state,
+ * min_spp, max_spp, samples_per_round, threshold, err_floor, dilate, active_counts and stream. */
+int ptamd_adaptive_select(ptamd_context* ctx, const ptamd_adaptive_desc* desc);
+
+/* Every pixel's bytes from accumulator and count (count 0: black) into surface_rgba8, after a change of post_id for instance;
+ * linear_rgb (optional, device, width x height x 3, row 0 = top) receives accumulator / count.  Reads the fields select reads plus
+ * surface_rgba8, temporal_framebuffer and post_id. */
+int ptamd_adaptive_resolve(ptamd_context* ctx, const ptamd_adaptive_desc* desc, float* linear_rgb);
+
+/* Host mirror of select over host buffers (the same binary32 operations): counts and moments of width x height pixels, list (width x
+ * height entries) and its length out.  desc supplies width, height, min_spp, max_spp, samples_per_round, threshold, err_floor and
+ * dilate; the rest is ignored. */
+int ptamd_host_adaptive_select(const ptamd_adaptive_desc* desc, const uint32_t* counts, const float* moments, uint32_t* list,
+                               uint32_t* active_count);
+
 /* The frame number of the context's last ptamd_raytrace (raytrace.cu:296's `seed`): the divisor of its resolve. */
 int ptamd_get_frame_counter(ptamd_context* ctx, uint32_t* out);
 
@@ -520,6 +596,8 @@ int ptamd_device_alloc(ptamd_context* ctx, size_t bytes, void** out);
 int ptamd_device_free(ptamd_context* ctx, void* p);
 int ptamd_device_memset(ptamd_context* ctx, void* p, int value, size_t bytes, void* stream);
 int ptamd_device_to_host(ptamd_context* ctx, void* dst_host, const void* src_dev, size_t bytes, void* stream);
+/* ptamd_device_to_host and ptamd_host_to_device are synchronous: the copy is enqueued on `stream`, which is then synchronised. */
+int ptamd_host_to_device(ptamd_context* ctx, void* dst_dev, const void* src_host, size_t bytes, void* stream);
 int ptamd_stream_synchronize(ptamd_context* ctx, void* stream);
 
 #ifdef __cplusplus
