@@ -54,6 +54,7 @@ struct DeviceScene {
   uint32_t n_nodes4 = 0, depth4 = 0;
   float extent = 0.0f;       // largest finite |coordinate| of the scene (bvh_builder.cpp)
   bool all_finite = true;    // no NaN or infinite vertex coordinate
+  float reach = 0.0f;        // origin reach: largest |coordinate| of an origin the path forms, light spheres included (bvh_builder.cpp)
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
   ptamd_scene_info info{};
 };
@@ -308,15 +309,17 @@ extern "C" hipError_t ptamd_fma_restart_blocks_per_cu(int lds_resident, size_t l
 extern "C" hipError_t ptamd_fma_launch_restart(const void* kparams, int lds_resident, size_t lds_bytes, uint32_t n_blocks, hipStream_t stream);
 
 // Box margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins inside the scene's extent
-// (bvh_builder.cpp).  A camera so far outside it that this bound exceeds the margin (e.g. 1e5 units from a
-// unit-sized scene) would need wider boxes (do_launch: such launches test every face instead).
+// (bvh_builder.cpp).  A camera so far outside it that this bound exceeds the margin (e.g. 1e5 units from a unit-sized scene)
+// would need wider boxes, and so would the surface of a light sphere that far out: paths that hit a light carry on from it,
+// so the scene's origin reach (bvh_builder.cpp: origin_reach; infinite for a NaN or infinite light) is an origin as much as the
+// camera is.  do_launch, feature_scene and ptamd_render_adaptive all take this one rule: such launches test every face.
 bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam)
 {
   const float cam_far = std::fmax(std::fabs(cam.position.x), std::fmax(std::fabs(cam.position.y), std::fabs(cam.position.z))) +
                         std::fabs(cam.aperture);
   // (2^-21, not the 2^-22 of a single fma: the centre / half-extent form rounds a slab distance twice — t(centre), then -+ half * |1/d| —
   // on top of the reciprocal's and -o/d's roundings: worst case about 1.75 (|origin| + |plane|) * 2^-22, bvh_builder.cpp)
-  return !((cam_far + s.extent) * (1.0f / 2097152.0f) <= s.margin_floor) && s.n_faces != 0;   // also true for NaN
+  return !(margins_cover(s.extent, s.margin_floor, cam_far) && margins_cover(s.extent, s.margin_floor, s.reach)) && s.n_faces != 0;   // also true for NaN
 }
 
 // later_chunk: the launch is the second or a later part of a batch the library cut into parts (kMaxFramesPerSlab): it follows
@@ -777,9 +780,7 @@ int feature_scene(const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_
   p.env_uniform = cm.uniform ? 1u : 0u; p.env_r = cm.color[0]; p.env_g = cm.color[1]; p.env_b = cm.color[2];
   p.n_faces = s.n_faces; p.n_lights = s.n_lights; p.n_nodes = s.n_nodes; p.n_bvh_tris = s.n_bvh_tris;
   // the same rule as do_launch: an origin beyond what the boxes' margins cover tests every face
-  const float cam_far = std::fmax(std::fabs(cam.position.x), std::fmax(std::fabs(cam.position.y), std::fabs(cam.position.z)));
-  const bool far_origin = !((cam_far + s.extent) * (1.0f / 2097152.0f) <= s.margin_floor) && s.n_faces != 0;
-  return far_origin ? 1 : 2;
+  return far_origin_camera(s, cam) ? 1 : 2;
 }
 
 // the context's denoiser workspace for n pixels: feature records, geometry records, two images (96 bytes per pixel)
@@ -1023,7 +1024,8 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
 
   Bvh bvh;
   // (the quantised node forms only where their tuning knob is set: nothing else can select them)
-  int rc = build_bvh(sc->faces, sc->n_faces, kBoxMargin, kMaxLeaf, bvh, (ctx->wide8 ? kBvhForm8 : 0u) | (ctx->wide4q ? kBvhForm4q : 0u));
+  int rc = build_bvh(sc->faces, sc->n_faces, kBoxMargin, kMaxLeaf, bvh, (ctx->wide8 ? kBvhForm8 : 0u) | (ctx->wide4q ? kBvhForm4q : 0u),
+                     sc->lights, sc->n_lights);
   if (rc != PTAMD_OK) return rc;
 
   // storage-order {e1,e2,v0,idx} records for the brute-force variant, and the shading records
@@ -1083,7 +1085,7 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
   PT_HIP(hipSetDevice(ctx->device));
   DeviceScene d;
   d.n_faces = sc->n_faces; d.n_lights = sc->n_lights; d.n_nodes = bvh.n_nodes; d.n_bvh_tris = bvh.n_tris;
-  d.extent = bvh.extent; d.all_finite = bvh.all_finite; d.margin_floor = bvh.margin_floor;
+  d.extent = bvh.extent; d.all_finite = bvh.all_finite; d.reach = bvh.reach; d.margin_floor = bvh.margin_floor;
   d.n_nodes4 = bvh.n_nodes4; d.depth4 = bvh.depth4;
   d.n_nodes8 = bvh.n_nodes8; d.depth8 = bvh.depth8;
   d.n_materials = sc->n_materials; d.n_textures = sc->n_textures;

@@ -268,7 +268,27 @@ inline float u2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
 } // namespace
 
-int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms)
+// Light spheres are ray origins as well: a path that hits one adds its emission and carries on from the hit point, stepped
+// 0.03 along its new direction (|direction| <= 1: a mix of unit vectors, not renormalised).  The sphere test's hit point lies
+// off the sphere by a rounding error: the discriminant b^2 - |op|^2 + r^2 cancels, and the direction is unit only to a few
+// ulps, so |hit - centre| <= |r| + about 2^-9.5 |o - centre|.  With |o|, |centre| within the reach that is under 2^-7.7 of the
+// reach, which the factor 1 + 2^-6 on a light's term covers (where the triangles set the reach, a light at most 1 / (1 + 2^-6)
+// of it stays below it).  A NaN or infinite centre or radius makes the reach infinite.
+float origin_reach(const ptamd_light* lights, uint32_t n_lights, float extent)
+{
+  float reach = extent;
+  for (uint32_t i = 0; i < n_lights; ++i) {
+    const ptamd_light& l = lights[i];
+    if (!(std::isfinite(l.vec.x) && std::isfinite(l.vec.y) && std::isfinite(l.vec.z) && std::isfinite(l.radius)))
+      return std::numeric_limits<float>::infinity();
+    const float c = std::max(std::fabs(l.vec.x), std::max(std::fabs(l.vec.y), std::fabs(l.vec.z)));
+    reach = std::max(reach, (c + std::fabs(l.radius) + 0.03f) * (1.0f + 1.0f / 64.0f));   // (+inf when the sum overflows)
+  }
+  return reach;
+}
+
+int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms,
+              const ptamd_light* lights, uint32_t n_lights)
 {
   out = Bvh();
   float split_alpha = 0.0f;   // pre-splitting off unless asked for (tuning knobs)
@@ -363,10 +383,15 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
   // final fma (|o| + |p|) 2^-24 — at most (|o| + |p|) 2^-22 + |o| 2^-24 with an exact reciprocal, about 1.75 (|o| + |p|) 2^-22
   // with a 2-ulp one.  (The box [c - h, c + h] itself contains [lo, hi] exactly: h is rounded up where the record is formed.)
   // Bounce rays start on the scene's surfaces (|o| <= extent), so every box also gets extent * 2^-20 — 2.3x the worst case at
-  // |o| = |p| = extent — and |p| * 1e-6 on top; a camera much farther out than the scene is the launcher's business
-  // (ptamd_api.cpp: far-origin check, (|camera| + extent) * 2^-21 against Bvh::margin_floor).
+  // |o| = |p| = extent — and |p| * 1e-6 on top.  Origins farther out — a camera much farther out than the scene, or a light
+  // sphere far outside the mesh, which paths bounce off (origin_reach) — are the launcher's business (ptamd_api.cpp:
+  // far_origin_camera, margins_cover against Bvh::margin_floor; every face is tested beyond it).  Widening the boxes by
+  // reach * 2^-20 instead would cover the slab test but not Moller-Trumbore's own rounding, which grows with |o - v0| / det:
+  // with origins 1e4 .. 6e4 units out, a random soup still gave 1 to 52 of 200 000 rays whose brute-force hit (a grazing one,
+  // off the triangle by its rounding) lay outside every such box.
   const float origin_margin = extent * (1.0f / 1048576.0f);
   out.extent = extent;
+  out.reach = origin_reach(lights, n_lights, extent);
   out.all_finite = all_finite;
   out.margin_floor = margin + origin_margin;
   uint32_t tri_cursor = 0;
@@ -1215,5 +1240,19 @@ extern "C" int ptamd_host_bvh_trace(const ptamd_face* faces, uint32_t n_faces, c
     std::memcpy(&out[i * 4 + 2], &h.t, 4);
     out[i * 4 + 3] = 0;
   }
+  return PTAMD_OK;
+}
+
+extern "C" int ptamd_host_origin_reach(const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights,
+                                       float* out)
+{
+  if ((n_faces && !faces) || (n_lights && !lights) || !out) { ptamd::set_error("ptamd_host_origin_reach: null argument"); return PTAMD_ERR_ARG; }
+  ptamd::Bvh bvh;
+  int rc = ptamd::build_bvh(faces, n_faces, 1e-3f, 4, bvh, 0u, lights, n_lights);
+  if (rc != PTAMD_OK) return rc;
+  out[0] = bvh.extent;
+  out[1] = n_faces ? bvh.reach : ptamd::origin_reach(lights, n_lights, 0.0f);
+  out[2] = bvh.margin_floor;
+  out[3] = (n_faces == 0 || ptamd::margins_cover(bvh.extent, bvh.margin_floor, out[1])) ? 1.0f : 0.0f;
   return PTAMD_OK;
 }

@@ -100,6 +100,7 @@ struct Bvh {
   uint32_t n_nodes8 = 0, depth8 = 0, max_leaf8 = 0;
   float extent = 0.0f;           // largest finite |coordinate| of the scene
   bool all_finite = true;        // no vertex coordinate is NaN or infinite
+  float reach = 0.0f;            // origin reach: largest |coordinate| of a ray origin the path can form (origin_reach)
   float margin_floor = 0.0f;     // smallest inflation any box face received (absolute margin + extent * 2^-20)
 };
 
@@ -108,7 +109,23 @@ struct Bvh {
 // forms: which of the knob-only node forms to build beside the binary tree and the four-wide float nodes (the eight-wide quantised
 // nodes take a dynamic programme over the whole tree; a production upload builds neither)
 constexpr uint32_t kBvhForm8 = 1u, kBvhForm4q = 2u;
-int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms = kBvhForm8 | kBvhForm4q);
+// lights: the scene's light spheres, whose surfaces are ray origins too (a path that hits one carries on from it): they set
+// Bvh::reach (origin_reach), not the boxes
+int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms = kBvhForm8 | kBvhForm4q,
+              const ptamd_light* lights = nullptr, uint32_t n_lights = 0);
+
+// The origin reach of a scene: the larger of the triangle extent and, over all lights, (max-axis |centre| + |radius| + 0.03)
+// times (1 + 2^-6) — the largest max-axis |coordinate| of any origin the path forms (bvh_builder.cpp).  Infinite when a light's
+// centre or radius is NaN or infinite.
+float origin_reach(const ptamd_light* lights, uint32_t n_lights, float extent);
+
+// The boxes' margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins with max-axis
+// |coordinate| <= origin_far (planes lie within `extent`); false for NaN and infinity.  The launcher's one rule for walking the
+// tree (ptamd_api.cpp: far_origin_camera): beyond it a launch tests every face.
+inline bool margins_cover(float extent, float margin_floor, float origin_far)
+{
+  return (origin_far + extent) * (1.0f / 2097152.0f) <= margin_floor;
+}
 
 // Host traversal with the same structure the kernel uses (tests + stats cross-check).
 struct HostHit { int32_t kind; int32_t index; float t; float u, v; };

@@ -195,6 +195,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "ptamd_host_bvh8_trace": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "ptamd_host_origin_reach": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(Light), C.c_uint32, C.POINTER(C.c_float)]),
     "ptamd_trace_rays_queue": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.POINTER(C.c_uint32)]),
     "ptamd_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseDesc)]),

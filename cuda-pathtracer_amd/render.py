@@ -268,6 +268,15 @@ class Context:
         N.check(self._lib.ptamd_stream_synchronize(self._h, _stream_handle(stream)))
 
 
+def origin_reach(scene: HostScene):
+    """(triangle extent, origin reach, smallest box inflation, whether the boxes' margins cover the reach) of `scene`
+    (ptamd_host_origin_reach): where they do not, its launches test every face."""
+    out = (C.c_float * 4)(0.0, 0.0, 0.0, 0.0)
+    N.check(N.load().ptamd_host_origin_reach(scene.faces.ctypes.data_as(C.POINTER(N.Face)), len(scene.faces),
+                                             scene.lights.ctypes.data_as(C.POINTER(N.Light)), len(scene.lights), out))
+    return out[0], out[1], out[2], bool(out[3])
+
+
 def host_bvh_trace(scene: HostScene, rays: np.ndarray):
     """Host mirror of the device BVH walk (test hook, no GPU): returns (int32[n,4], nodes, tris)."""
     rays = np.ascontiguousarray(rays, dtype=np.float32)

@@ -364,7 +364,11 @@ int ptamd_gamma_table_selftest(ptamd_context* ctx, uint64_t* out_checked, uint64
 /* Nearest-hit query on explicit rays through the device traversal (tests: BVH vs brute
  * force equivalence).  kernel: PTAMD_KERNEL_BRUTE_FORCE, PTAMD_KERNEL_BVH (binary walk) or
  * PTAMD_KERNEL_BVH_RESTART (the four-wide stack walk).  rays: n * {dir.xyz, origin.xyz};
- * out: n * {kind, index, t bits, pad}. */
+ * out: n * {kind, index, t bits, pad}.  Exactness: PTAMD_KERNEL_BRUTE_FORCE returns the reference's record for any origin.
+ * The BVH walks return the same record for origins whose max-axis |coordinate| o satisfies (o + extent) * 2^-21 <=
+ * margin_floor (ptamd_host_origin_reach: out[0], out[2]) — about 2 000 units around a unit-sized scene.  That covers every
+ * origin the path tracer forms when out[3] is 1; the renderer tests every face otherwise, while this call walks the tree as
+ * asked: farther origins are not checked per ray. */
 int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel,
                      const float* rays_host, uint32_t n, int32_t* out_host);
 
@@ -404,6 +408,15 @@ int ptamd_host_bvh4q_trace(const ptamd_face* faces, uint32_t n_faces, const floa
  * [0] += nodes visited, [1] += triangles tested, [2] = depth, [3] / [4] += visits to the first 73 / 585 nodes, [5] = node count. */
 int ptamd_host_bvh8_trace(const ptamd_face* faces, uint32_t n_faces, const float* rays, uint32_t n,
                           int32_t* out, uint64_t* counters);
+
+/* out[0] = the scene's triangle extent (largest finite |vertex coordinate|), out[1] = its ORIGIN REACH: the larger of the
+ * extent and, over the lights, (max-axis |centre| + |radius| + 0.03) * (1 + 2^-6) — a bound on the max-axis |coordinate| of
+ * every origin a path forms (triangle hits, light-sphere hits, the 0.03 step); +inf if a light's centre or radius is NaN or
+ * infinite.  out[2] = the smallest inflation of any box face (1e-3 + extent * 2^-20).  out[3] = 1 if the boxes' margins
+ * cover origins out to the reach, (reach + extent) * 2^-21 <= out[2], else 0: launches of such a scene test every face
+ * (as for a camera beyond that distance).  DESIGN.md §4. */
+int ptamd_host_origin_reach(const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights,
+                            float* out);
 
 /* ---- Edge-aware denoiser -------------------------------------------------------------------------------
  * An opt-in pass behind the accumulator: the spatial half of SVGF over an edge-avoiding a-trous wavelet, guided by a first-hit

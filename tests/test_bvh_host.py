@@ -331,3 +331,123 @@ def test_infinite_and_huge_coordinates(P, O):
         if not np.isfinite(bad) or abs(bad) <= 1.0e8:
             np.testing.assert_array_equal(P.host_bvh4q_trace(hs, rays)[0], want)
             np.testing.assert_array_equal(P.host_bvh8_trace(hs, rays)[0], want)
+
+
+# ---- origins on light spheres far outside the mesh ("origin reach") ----------------------------------------
+
+def sliver_tris():
+    """The thin-in-z scene of test_gpu_parity.py::test_far_camera_keeps_bvh_exact."""
+    rng = np.random.default_rng(5)
+    c = rng.uniform(-1.0, 1.0, size=(200, 1, 3))
+    return (c + rng.normal(scale=0.08, size=(200, 3, 3)) * np.float32([1.0, 1.0, 0.002])).astype(np.float32)
+
+
+def light_bounce_rays(rng, tris, centre, radius, n):
+    """Rays as a path forms them after hitting a light sphere, in binary32: a point on the sphere, a new direction back
+    towards the scene (at a triangle's centroid), and the 0.03 step along it (raytrace.cu, the light branch)."""
+    f32 = np.float32
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    p = np.asarray(centre, f32) + f32(radius) * u.astype(f32)
+    target = tris.mean(axis=1, dtype=f32)[rng.integers(0, len(tris), n)]
+    d = target - p
+    d = d / np.sqrt((d * d).sum(axis=1, dtype=f32))[:, None]
+    return np.concatenate([d, p + d * f32(0.03)], axis=1).astype(f32)
+
+
+def sun(distance, radius):
+    return [((np.float32([0.36, 0.48, 0.8]) * np.float32(distance)).tolist(), (1.0, 0.95, 0.8), 5.0, radius)]
+
+
+def covers(extent, reach, floor):
+    """The launcher's rule for walking the tree (ptamd_internal.h: margins_cover), in binary32."""
+    f32 = np.float32
+    return bool((f32(reach) + f32(extent)) * f32(2.0 ** -21) <= f32(floor))
+
+
+WALKS = ("host_bvh_trace", "host_bvh4_trace", "host_bvh4q_trace", "host_bvh8_trace")
+
+
+@pytest.mark.parametrize("scene", ["sliver", "soup"])
+@pytest.mark.parametrize("distance", [2.0e3, 1.0e4, 3.0e4, 6.0e4])
+@pytest.mark.parametrize("size", ["small", "sun"])
+def test_origins_on_far_lights_are_walked_only_within_the_margins(P, O, scene, distance, size):
+    """A path that hits a light sphere carries on from its surface: with a light far outside the mesh those origins lie far
+    beyond the triangles' extent.  The scene's origin reach bounds them; where the boxes' margins cover it the four walks
+    equal brute force on 200 000 such rays, and where they do not the scene is marked for the every-face route (as a far
+    camera is).  The walks DO miss faces there: up to 163 of these rays per walk at 1e4 .. 6e4 on the sliver scene, and boxes
+    widened by reach * 2^-20 still missed 1 to 52 on the soup (Moller-Trumbore's own rounding: DESIGN.md §4)."""
+    rng = np.random.default_rng(int(distance) + (7 if size == "sun" else 0) + (1 if scene == "soup" else 0))
+    tris = sliver_tris() if scene == "sliver" else random_soup(rng, 400, extent=1.5, size=0.2)
+    radius = 0.3 if size == "small" else 0.1 * distance
+    hs = make_scene(P, tris, lights=sun(distance, radius))
+    extent, reach, floor, covered = P.origin_reach(hs)
+    assert reach >= distance * 0.8 + radius and floor == np.float32(np.float32(1e-3) + np.float32(extent) * np.float32(2.0 ** -20))
+    assert covered == covers(extent, reach, floor) == (distance < 5.0e3)
+    rays = light_bounce_rays(rng, tris, hs.lights[0]["vec"], radius, 200000)
+    assert np.abs(rays[:, 3:]).max() <= reach
+    if not covered:
+        return
+    want = O.intersect(lightless(O, P, hs), rays)
+    assert (want[:, 0] == 1).sum() > 50000
+    for name in WALKS:
+        bad = (getattr(P, name)(hs, rays)[0] != want).any(axis=1)
+        assert not bad.any(), f"{name}: {int(bad.sum())} of {len(rays)} rays differ from brute force"
+
+
+def test_origin_reach_edges(P, O):
+    """Lights that are not finite make the reach infinite (the launcher then tests every face); an empty mesh has nothing to
+    walk whatever its lights; lights whose origins reach 2 000, 2 090 and 2 300 units — about where margins from the
+    triangles stop covering them — are walked exactly where the rule says they are covered."""
+    tris = sliver_tris()
+    for bad in ((np.nan, 0.0, 0.0, 0.3), (0.0, np.inf, 0.0, 0.3), (0.0, 0.0, -np.inf, 0.3), (0.0, 0.0, 50.0, np.nan),
+                (0.0, 0.0, 50.0, np.inf), (3.0e38, 0.0, 0.0, 3.0e38)):
+        hs = make_scene(P, tris, lights=[(bad[:3], (1, 1, 1), 3.0, bad[3])])
+        extent, reach, floor, covered = P.origin_reach(hs)
+        assert np.isinf(reach) and not covered
+    empty = make_scene(P, np.zeros((0, 3, 3), np.float32), lights=sun(6.0e4, 50.0))
+    extent, reach, floor, covered = P.origin_reach(empty)
+    assert reach >= 0.8 * 6.0e4 + 50.0 and covered
+    rays = random_rays(np.random.default_rng(4), 1000)
+    for name in WALKS:
+        assert (getattr(P, name)(empty, rays)[0][:, 0] == 0).all()
+    rng = np.random.default_rng(13)
+    seen = set()
+    for dist in (2.0e3, 2.09e3, 2.3e3):
+        hs = make_scene(P, tris, lights=[((0.0, 0.0, dist - 0.33), (1, 1, 1), 3.0, 0.3)])
+        extent, reach, floor, covered = P.origin_reach(hs)
+        assert covered == covers(extent, reach, floor) and reach >= dist
+        seen.add(covered)
+        rays = light_bounce_rays(rng, tris, hs.lights[0]["vec"], 0.3, 200000)
+        assert np.abs(rays[:, 3:]).max() <= reach
+        if covered:
+            want = O.intersect(lightless(O, P, hs), rays)
+            for name in WALKS:
+                np.testing.assert_array_equal(getattr(P, name)(hs, rays)[0], want, err_msg=f"light origins at {dist:g}, {name}")
+    assert seen == {True, False}
+
+
+# node and triangle visits of the four walks (binary, four-wide, quantised four-wide, eight-wide) on 4 000 fixed rays, as the
+# trees built from the triangles alone gave them: the shipped scenes keep their lights within the triangles' extent, so
+# their reach IS the extent and their trees are unchanged
+SHIPPED_TREE_VISITS = {
+    "indoor": [(38896, 6442), (10611, 7423), (11359, 7037), (6999, 4726)],
+    "crate_land": [(10740, 1313), (4987, 1783), (5017, 1809), (4333, 1351)],
+    "color_sample": [(33524, 6994), (8771, 8009), (9141, 7682), (5839, 5063)],
+    "island": [(84628, 13298), (22451, 15695), (23224, 15912), (12281, 14542)],
+    "sss_crate": [(10760, 1305), (5017, 1793), (5046, 1821), (4330, 1370)],
+    "atrium": [(154588, 9093), (54399, 16640), (55354, 16874), (28364, 10460)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(SHIPPED_TREE_VISITS))
+def test_shipped_scenes_reach_is_their_extent(P, tmp_path, name):
+    from cuda_pathtracer_amd.synthetic import write_atrium
+    hs = P.HostScene.load(write_atrium(str(tmp_path)) if name == "atrium" else os.path.join(ASSETS, name + ".scene"))
+    extent, reach, floor, covered = P.origin_reach(hs)
+    assert reach == extent and covered
+    assert floor == np.float32(np.float32(1e-3) + np.float32(extent) * np.float32(2.0 ** -20))
+    rays = random_rays(np.random.default_rng(11), 4000, extent=4.0)
+    visits = [tuple(int(x) for x in walk(hs, rays)[1:3])
+              for walk in (P.host_bvh_trace, P.host_bvh4_trace, P.host_bvh4q_trace, P.host_bvh8_trace)]
+    assert visits == SHIPPED_TREE_VISITS[name]

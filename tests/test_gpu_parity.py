@@ -1205,3 +1205,167 @@ def test_coincident_triangles_resolve_to_the_lowest_face_index(P, O, gpu_ctx):
         for kernel in KERNELS:
             acc, rgba = gpu_render(P, gpu_ctx, hs, cube, 96, 64, 2, 4, kid(P, kernel))
             assert_same(acc, rgba, *ref, f"coincident triangles x3, {3 * n_base} faces, {kernel}")
+
+
+# ---- origins on light spheres far outside the mesh (origin reach) -------------------------------------------
+
+def _sliver_tris():
+    rng = np.random.default_rng(5)
+    c = rng.uniform(-1.0, 1.0, size=(200, 1, 3))
+    return (c + rng.normal(scale=0.08, size=(200, 3, 3)) * np.float32([1.0, 1.0, 0.002])).astype(np.float32)
+
+
+def _sun(distance, radius, emission=5.0):
+    return [((np.float32([0.36, 0.48, 0.8]) * np.float32(distance)).tolist(), (1.0, 0.95, 0.8), emission, radius)]
+
+
+def _light_bounce_rays(rng, tris, centre, radius, n):
+    """As tests/test_bvh_host.py: a point on the sphere, a direction back at a triangle's centroid, the 0.03 step (binary32)."""
+    f32 = np.float32
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    p = np.asarray(centre, f32) + f32(radius) * u.astype(f32)
+    target = tris.mean(axis=1, dtype=f32)[rng.integers(0, len(tris), n)]
+    d = target - p
+    d = d / np.sqrt((d * d).sum(axis=1, dtype=f32))[:, None]
+    return np.concatenate([d, p + d * f32(0.03)], axis=1).astype(f32)
+
+
+@pytest.mark.parametrize("knob", [None, "PTAMD_WIDE4Q", "PTAMD_WIDE8"])
+def test_trace_rays_on_light_bounce_origins(P, O, monkeypatch, knob):
+    """Rays that start where paths leave a light sphere.  Within the margins' reach (a light 2 000 units out) the binary walk,
+    the four-wide walk (float nodes, or the quantised four- and eight-wide forms under their knobs) and its queue-fed form
+    equal the oracle; farther out (1e4, 6e4: such scenes render through the every-face route) the brute-force query does."""
+    import torch
+    if knob:
+        monkeypatch.setenv("PTAMD_TUNING", "1")
+        monkeypatch.setenv(knob, "1")
+    rng = np.random.default_rng(61)
+    tris = _sliver_tris()
+    with P.Context(0) as ctx:                       # (knobs are read when a context is created)
+        for distance, radius in ((2.0e3, 0.3), (2.0e3, 200.0), (1.0e4, 0.3), (6.0e4, 6.0e3)):
+            hs = make_scene(P, tris, lights=_sun(distance, radius))
+            covered = P.origin_reach(hs)[3]
+            assert covered == (distance < 5.0e3)
+            sid = ctx.upload_scene(hs)
+            rays = _light_bounce_rays(rng, tris, hs.lights[0]["vec"], radius, 200000)
+            want = O.intersect(O.OracleScene.from_host_scene(hs, P.cubemap_from_color()), rays)
+            assert (want[:, 0] == 1).sum() > 40000
+            what = f"light at {distance:g}, radius {radius:g}, {knob}"
+            np.testing.assert_array_equal(ctx.trace_rays(sid, rays, P.KERNEL_BRUTE_FORCE), want, err_msg=what)
+            if not covered:
+                continue
+            for k in (P.KERNEL_BVH, P.KERNEL_BVH_RESTART):
+                np.testing.assert_array_equal(ctx.trace_rays(sid, rays, k), want, err_msg=f"{what}, kernel {k}")
+            if knob is None:
+                out = torch.full((len(rays), 4), -7, dtype=torch.int32, device="cuda")
+                ctx.trace_rays_queue(sid, torch.from_numpy(rays).cuda(), out, 0, 8)
+                torch.cuda.synchronize()
+                np.testing.assert_array_equal(out.cpu().numpy(), want, err_msg=f"{what}, queue")
+
+
+def _sun_scene(P, distance, with_light=True):
+    # the camera looks down -z at the thin geometry, every face wound to face it; the sun stands straight above it, where the
+    # bounces go, and covers a cone of 25 degrees (1 400 units out it stays within the margins' reach)
+    tris = _sliver_tris()
+    e1, e2 = tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
+    down = np.cross(e1, e2)[:, 2] < 0
+    tris[down] = tris[down][:, [0, 2, 1]]
+    sun = [((0.0, 0.0, float(distance)), (1.0, 0.95, 0.8), 5.0, 0.43 * distance)]
+    return make_scene(P, tris, lights=sun if with_light else None,
+                      camera=dict(position=(0.1, 0.2, 2.0), dir=(0.0, 0.0, -1.0), fov_x=0.9, aperture=0.0, focus_dist=2.0))
+
+
+@pytest.mark.parametrize("distance", [1.4e3, 1.0e4, 6.0e4])
+def test_sun_far_outside_the_mesh_renders_exactly(P, O, gpu_ctx, distance):
+    """A sun well outside thin geometry, large enough that many paths hit it and carry on from its surface: every kernel, a
+    batched launch and interleaved bands equal the oracle bit for bit (beyond the margins' reach the launcher tests every face,
+    as for a far camera), and the sun really is hit: the accumulator differs from the sunless scene's."""
+    import torch
+    W, H, spp, B = 64, 48, 2, 4
+    rng = np.random.default_rng(71)
+    cube = synthetic_cubemap(rng, 2)
+    hs = _sun_scene(P, distance)
+    assert P.origin_reach(hs)[3] == (distance < 5.0e3)
+    osc = O.OracleScene.from_host_scene(hs, cube)
+    ref_acc, ref_rgba = O.render(osc, O.camera_from_record(hs.camera), W, H, spp=spp, bounces=B)
+    dark = O.render(O.OracleScene.from_host_scene(_sun_scene(P, distance, False), cube), O.camera_from_record(hs.camera),
+                    W, H, spp=spp, bounces=B)[0]
+    lit = (ref_acc.view(np.uint32) != dark.view(np.uint32)).any(axis=2)
+    assert lit.sum() > 100, int(lit.sum())
+    ids = (gpu_ctx.upload_scene(hs), gpu_ctx.upload_cubemap(cube))
+    for kernel in KERNELS:
+        acc, rgba = gpu_render(P, gpu_ctx, hs, cube, W, H, spp, B, kid(P, kernel), ids=ids)
+        assert_same(acc, rgba, ref_acc, ref_rgba, f"sun at {distance:g}/{kernel}")
+    if batched_ok():
+        fr = P.FrameRenderer(gpu_ctx, *ids, hs.camera_struct(), W, H)
+        fr.render(spp=spp, bounces=B, kernel=P.KERNEL_BVH_RESTART, batched=True)
+        torch.cuda.synchronize()
+        assert_same(fr.accum.cpu().numpy(), fr.surface.cpu().numpy(), ref_acc, ref_rgba, f"sun at {distance:g}/batched")
+    if os.environ.get("PTAMD_DEFAULT_KERNEL", "6") == "6":
+        world, rank_rows = 3, 8
+        rgba = np.zeros_like(ref_rgba)
+        acc = np.zeros_like(ref_acc)
+        for rank in range(world):
+            fr = P.FrameRenderer(gpu_ctx, *ids, hs.camera_struct(), W, H, interleave=(world, rank, rank_rows))
+            fr.render(spp=spp, bounces=B, batched=batched_ok())
+            torch.cuda.synchronize()
+            s, a = fr.surface.cpu().numpy(), fr.accum.cpu().numpy()
+            local = 0
+            for b, e in P.interleaved_bands(H, world, rank, rank_rows):
+                rgba[b:e] = s[local:local + (e - b)]
+                acc[H - e:H - b] = a[s.shape[0] - (local + (e - b)):s.shape[0] - local]
+                local += e - b
+        assert_same(acc, rgba, ref_acc, ref_rgba, f"sun at {distance:g}/interleaved bands")
+
+
+def test_sun_far_outside_the_mesh_adaptive_and_features(P, O, gpu_ctx):
+    """Adaptive sampling's list form walks the tree: on a sun within the margins' reach every pixel equals the oracle at its
+    own sample count; a sun beyond it is refused like a far camera.  The denoiser's feature pass takes the same route rule:
+    with the sun out of the camera's view its first hits equal those of the sunless scene (walked)."""
+    import torch
+    from test_adaptive_gpu import host_error
+    W, H, B = 64, 48, 3
+    f32 = np.float32
+    rng = np.random.default_rng(73)
+    cube = synthetic_cubemap(rng, 2)
+    hs = _sun_scene(P, 1.4e3)
+    assert P.origin_reach(hs)[3]
+    sid, cid = gpu_ctx.upload_scene(hs), gpu_ctx.upload_cubemap(cube)
+    fr = P.FrameRenderer(gpu_ctx, sid, cid, hs.camera_struct(), W, H)
+    with gpu_ctx.adaptive_state(W, H) as st:
+        fr.render_adaptive(st, 2, 8, 2, rounds=1, threshold=0.0, bounces=B)
+        s1 = st.read()
+        e1 = host_error(s1["counts"], s1["moments"])
+        fr.render_adaptive(st, 2, 8, 2, rounds=3, threshold=float(np.median(e1[e1 > 0])), bounces=B)
+        torch.cuda.synchronize()
+        counts = st.read()["counts"]
+        acc, rgba = fr.accum.cpu().numpy(), fr.surface.cpu().numpy()
+    assert len(np.unique(counts)) >= 3, np.unique(counts)
+    osc = O.OracleScene.from_host_scene(hs, cube)
+    cam = O.camera_from_record(hs.camera)
+    tfb = np.zeros((H, W, 3), f32)
+    flip_counts = np.ascontiguousarray(counts[::-1])
+    for k in range(1, int(counts.max()) + 1):
+        _, surf = O.render(osc, cam, W, H, spp=1, bounces=B, first_frame=k, accum=tfb)
+        at = flip_counts == k
+        assert np.array_equal(acc[at].view(np.uint32), tfb[at].view(np.uint32)), k
+        at = counts == k
+        assert np.array_equal(rgba[at], surf[at]), k
+    far = _sun_scene(P, 1.0e4)
+    fsid = gpu_ctx.upload_scene(far)
+    ffr = P.FrameRenderer(gpu_ctx, fsid, cid, far.camera_struct(), W, H)
+    with gpu_ctx.adaptive_state(W, H) as st:
+        with pytest.raises(P.PtamdError):
+            ffr.render_adaptive(st, 2, 8, 2, rounds=1, threshold=0.0, bounces=B)
+    feats = []
+    for scene in (far, _sun_scene(P, 1.0e4, False)):
+        s_id = gpu_ctx.upload_scene(scene)
+        f = torch.zeros((H, W, 8), dtype=torch.float32, device="cuda")
+        rays = torch.zeros((H, W, 6), dtype=torch.float32, device="cuda")
+        gpu_ctx.render_features(s_id, cid, scene.camera_struct(), W, H, f, rays)
+        torch.cuda.synchronize()
+        feats.append((f.cpu().numpy(), rays.cpu().numpy()))
+    assert (feats[0][0] != 0).any()
+    np.testing.assert_array_equal(feats[0][0].view(np.uint32), feats[1][0].view(np.uint32))
+    np.testing.assert_array_equal(feats[0][1].view(np.uint32), feats[1][1].view(np.uint32))
