@@ -89,12 +89,12 @@ struct ptamd_context {
   struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[6];   // ([4]: the contracted restart kernel, [5]: its list form)
   // parked samples of batched launches, one scratch per stream: launches on one stream are ordered, launches on
   // different streams of one context (frames in flight, ptamd_launch.machine_share) must not share a buffer
-  // Four slabs per stream.  [0..2] are used in turn by pipelined launches (megakernel on an internal stream, below): the
+  // Four slabs per stream.  [0..2] are used in turn by pipelined launches (megakernel on a lane, below): the
   // megakernel of launch N+1 writes its samples while the resolve pass of launch N still reads its own, and with three of
-  // them the megakernel of launch N+2 — next on launch N's internal stream — does not have to wait for that resolve pass
+  // them the megakernel of launch N+2 does not have to wait for that resolve pass
   // either (two slabs: a 60 us bubble per launch, two event hops and the pass itself); [3] belongs to launches that stay on
-  // the caller's stream from start to end (one at a time, captured into a graph, instrumented, or part of the caller's own
-  // pipeline): stream order alone protects it, also against replays of a captured launch.
+  // the caller's stream from start to end (one at a time, captured into a graph, instrumented, no_pipelining, the adaptive
+  // list form, the other persistent kinds): stream order alone protects it, also against replays of a captured launch.
   struct SampleScratch {
     void* stream = nullptr;
     float* buf[4] = { nullptr, nullptr, nullptr, nullptr };
@@ -112,11 +112,22 @@ struct ptamd_context {
   };
   std::vector<SampleScratch> sample_scratch;
   // Consecutive launches on ONE caller stream overlap: the megakernel of a launch (which reads scene tables and writes only
-  // the context's scratch) runs on one of two internal streams, its resolve pass (the only part that touches the caller's
+  // the context's scratch) runs on one of the context's lanes, its resolve pass (the only part that touches the caller's
   // accumulator and surface) on the caller's stream behind an event.  The tail of launch N — waves finishing the tiles
   // they hold at falling occupancy once the tickets are gone — is then filled by the first workgroups of launch N+1, for
-  // a host that simply calls raytrace() again without synchronising (gpu_processor.cpp:365-386 does not).
+  // a host that simply calls raytrace() again without synchronising (gpu_processor.cpp:365-386 does not).  Launches with
+  // machine_share > 1 (the caller's own pipeline: frames in flight on several streams) run their megakernels on the lanes too.
+  // A lane is a stream with a hardware queue of its own (add_lane): plain streams share the runtime's few pooled queues, and
+  // two megakernels whose streams land on one queue run one after the other.  Two lanes come with the first
+  // launch that takes one, two more with the first launch with machine_share >= 3; launches take them in turn, context-wide.
+  // A lane is a blocking stream (the runtime creates CU-masked streams no other way): it waits for the null stream and the null
+  // stream waits for it.  So launches on the null stream take the two plain non-blocking streams `internal` instead, and a host
+  // that only uses the null stream never has a lane.
+  static constexpr uint32_t kMaxLanes = 4;
+  hipStream_t lane[kMaxLanes] = { nullptr, nullptr, nullptr, nullptr };
+  uint32_t n_lanes = 0;
   hipStream_t internal[2] = { nullptr, nullptr };
+  uint32_t lane_next = 0;                 // context-wide turn of the lanes (and of the two internal streams)
   bool overlap = true;                    // PTAMD_OVERLAP=0 (tuning): everything on the caller's stream
   bool wide4q = false;                    // PTAMD_WIDE4Q=1 (tuning): big scenes walk the 64-byte quantised four-wide nodes instead of the float ones (ahead by 2.8 % while the walk's LDS accesses went out as FLAT instructions, level since they are LDS instructions: profiles/r03_notes.md)
   bool generic_round = false;             // PTAMD_RS_GENERIC=1 (tuning): resident scenes take the restart kernel's generic instantiation (launch constants read at run time), for A/B and tests
@@ -244,6 +255,35 @@ void free_scratch(ptamd_context::SampleScratch& c)
   }
   if (c.last_done) (void)hipEventDestroy(c.last_done);
   c = ptamd_context::SampleScratch();
+}
+
+// The first operation of a new stream, issued and waited for at once: it brings the stream's queue up (~6 ms on this runtime),
+// which would otherwise land in a frame
+int bring_up(ptamd_context* ctx, hipStream_t s)
+{
+  PT_HIP(hipMemsetAsync(ctx->d_stats + 13, 0, sizeof(unsigned long long), s));   // (word 13: read by no one)
+  PT_HIP(hipStreamSynchronize(s));
+  return PTAMD_OK;
+}
+
+// The context's next launch lane (ptamd_context::lane).  A stream created with a CU mask — here every CU — gets a hardware queue
+// of its own: the HIP runtime hands out its pooled queues (GPU_MAX_HW_QUEUES of them, shared by every plain stream of the
+// process) only to streams without a mask.  profiles/r09_queue_trace_before.txt shows both kinds.  Where the runtime refuses
+// the mask, a plain non-blocking stream stands in.
+int add_lane(ptamd_context* ctx)
+{
+  if (ctx->n_lanes >= ptamd_context::kMaxLanes) return PTAMD_OK;
+  const uint32_t n_cus = ctx->n_cus > 0 ? (uint32_t)ctx->n_cus : 1u;
+  std::vector<uint32_t> mask((n_cus + 31u) / 32u, 0xFFFFFFFFu);
+  if (n_cus % 32u) mask.back() = (1u << (n_cus % 32u)) - 1u;
+  hipStream_t s = nullptr;
+  if (hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+    (void)hipGetLastError();
+    s = nullptr;
+    PT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  }
+  ctx->lane[ctx->n_lanes++] = s;
+  return bring_up(ctx, s);
 }
 
 inline f3 hf3(ptamd_float3 v) { f3 r; r.x = v.x; r.y = v.y; r.z = v.z; return r; }
@@ -442,19 +482,29 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     }
   }
   // Launches of the restart kernel that a host issues back to back on one stream are pipelined by the library
-  // (ptamd_context::internal): when the previous launch of this stream has not finished yet — the host is running ahead —
-  // this one is sized to half the GPU and its megakernel goes to an internal stream, so that the two are resident side by
+  // (ptamd_context::lane): when the previous launch of this stream has not finished yet — the host is running ahead —
+  // this one is sized to half the GPU and its megakernel goes to a lane, so that the two are resident side by
   // side and the tail of one is covered by the bulk of the other, exactly what a host gets from two streams and
-  // machine_share = 2.  Not when the caller runs its own pipeline (machine_share > 1), captures a graph or wants counters;
-  // a host that waits for every frame gets whole-GPU launches on its own stream as before.
-  bool pipelined = ctx->overlap && which == PTAMD_KERNEL_BVH_RESTART && (l->machine_share <= 1u || later_chunk) && !stats && !ad;
+  // machine_share = 2.  A launch with machine_share > 1 (the caller runs its own pipeline) takes a lane whatever the state of its
+  // stream: the frames the caller keeps in flight then share the GPU whatever hardware queues its streams landed on.  Not when
+  // the caller captures a graph, wants counters or sets no_pipelining, and not for the first launch of a stream, which sizes the
+  // stream's own slab as before (what a later graph capture on that stream needs); a host that waits for every frame gets
+  // whole-GPU launches on its own stream as before.  Later parts of a long batch follow the first on a lane.
+  bool pipelined = ctx->overlap && which == PTAMD_KERNEL_BVH_RESTART && !stats && !ad;
   bool capturing = false;
   if (stream != nullptr) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) capturing = true;
   }
   if (capturing || (sc && sc->no_pipeline) || l->no_pipelining) pipelined = false;
-  if (pipelined && !later_chunk) pipelined = sc->last_done != nullptr && hipEventQuery(sc->last_done) == hipErrorNotReady;
+  if (pipelined && !later_chunk)
+    pipelined = sc->last_done != nullptr && (l->machine_share > 1u || hipEventQuery(sc->last_done) == hipErrorNotReady);
+  // lanes 1 and 2 for the first launch from a stream other than the null stream that takes one, 3 and 4 for callers that keep
+  // three or more frames in flight
+  if (pipelined && stream != nullptr) {
+    const uint32_t want = l->machine_share >= 3u ? ptamd_context::kMaxLanes : 2u;
+    while (ctx->n_lanes < want) { rc = add_lane(ctx); if (rc != PTAMD_OK) return rc; }
+  }
   // PTAMD_KERNEL_AUTO, one frame per launch (the reference's interactive loop, ptamd_raytrace) on an LDS-resident scene,
   // one launch at a time: the persistent kernel writes the surface itself, the restart kernel would add its resolve
   // pass to every launch (1080p, one launch per spp, one at a time: 6.03 vs 5.89 Gsamples/s).
@@ -637,6 +687,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
       // that finds its predecessor still running, which costs that launch its overlap and no more.
       auto grow = [&](uint32_t i) -> int {
         PT_HIP(hipStreamSynchronize(stream));
+        for (uint32_t k = 0; k < ctx->n_lanes; ++k) PT_HIP(hipStreamSynchronize(ctx->lane[k]));
         for (hipStream_t is : ctx->internal) if (is) PT_HIP(hipStreamSynchronize(is));
         (void)hipFree(sc->buf[i]);
         sc->buf[i] = nullptr; sc->bytes[i] = 0;
@@ -690,8 +741,11 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
     hipStream_t mega_stream = stream;
     if (overlap) {
       // the megakernel touches nothing of the caller's: it may start before earlier work on the caller's stream has finished,
-      // as soon as the slab's previous reader (the resolve pass three launches back) is done
-      mega_stream = ctx->internal[sc->flip++ & 1u];
+      // as soon as the slab's previous reader (the resolve pass three launches back) is done.  Lanes are taken in turn by every
+      // launch of the context, whichever stream it comes from: consecutive launches do not queue behind each other.  (Null-stream
+      // callers: the two internal streams, ptamd_context::lane)
+      mega_stream = stream != nullptr ? ctx->lane[ctx->lane_next++ % ctx->n_lanes] : ctx->internal[ctx->lane_next++ & 1u];
+      sc->flip++;
       if (sc->resolved_valid[scratch_slab]) PT_HIP(hipStreamWaitEvent(mega_stream, sc->resolved[scratch_slab], 0));
     }
     if (!split) {
@@ -720,7 +774,7 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
       }
       if (e == hipSuccess && !split) ctx->heads_clean[slot] = true;
       if (e == hipSuccess && overlap) {
-        // whoever writes this slab next (a megakernel on an internal stream) waits for this pass
+        // whoever writes this slab next (a megakernel on a lane) waits for this pass
         PT_HIP(hipEventRecord(sc->resolved[scratch_slab], stream));
         sc->resolved_valid[scratch_slab] = true;
       }
@@ -913,18 +967,17 @@ int ptamd_create(int32_t device_ordinal, ptamd_context** out)
     }
   }
   if (const char* e = tuning_env("PTAMD_OVERLAP")) ctx->overlap = std::atoi(e) != 0; // tuning knob
-  if (ctx->overlap) {
-    // the two internal streams of the launch pipeline, with their hardware queues brought up now (a stream's first
-    // operation costs ~6 ms on this runtime: it would otherwise land in the frame where a host starts to run ahead)
-    for (hipStream_t& is : ctx->internal) {
-      PT_HIP(hipStreamCreateWithFlags(&is, hipStreamNonBlocking));
-      PT_HIP(hipMemsetAsync(ctx->d_stats, 0, sizeof(unsigned long long), is));
-      PT_HIP(hipStreamSynchronize(is));
-    }
-  }
   hipDeviceProp_t prop;
   PT_HIP(hipGetDeviceProperties(&prop, device_ordinal));
   ctx->n_cus = prop.multiProcessorCount;
+  if (ctx->overlap) {
+    // the two internal streams of the launch pipeline (null-stream callers), with their queues brought up now
+    for (hipStream_t& is : ctx->internal) {
+      PT_HIP(hipStreamCreateWithFlags(&is, hipStreamNonBlocking));
+      const int brc = bring_up(ctx.get(), is);
+      if (brc != PTAMD_OK) return brc;
+    }
+  }
   if (const char* e = tuning_env("PTAMD_REFILL_MIN")) { // tuning knob
     int v = std::atoi(e);
     ctx->refill_min = (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
@@ -975,8 +1028,8 @@ void ptamd_destroy(ptamd_context* ctx)
 {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  // before anything is freed: megakernels may still be running on the non-blocking internal streams (they read the scene tables
-  // and the ticket heads), resolve passes on the callers' streams
+  // before anything is freed: megakernels may still be running on the lanes and internal streams (they read the scene tables and
+  // the ticket heads), resolve passes on the callers' streams
   (void)hipDeviceSynchronize();
   for (auto& s : ctx->scenes) free_scene(s);
   for (auto& c : ctx->cubemaps) (void)hipFree(c.faces);
@@ -985,6 +1038,7 @@ void ptamd_destroy(ptamd_context* ctx)
   (void)hipFree(ctx->d_tickets);
   (void)hipFree(ctx->d_heads);
   for (auto& c : ctx->sample_scratch) free_scratch(c);
+  for (uint32_t i = 0; i < ctx->n_lanes; ++i) (void)hipStreamDestroy(ctx->lane[i]);
   for (hipStream_t is : ctx->internal) if (is) (void)hipStreamDestroy(is);
   (void)hipFree(ctx->d_timeline);
   (void)hipFree(ctx->d_trace_spill);

@@ -249,6 +249,9 @@ typedef struct {
   uint32_t machine_share;      /* persistent kernels: 0 or 1 = size the grid to the whole GPU; k > 1 = to 1/k of it, so that
                                   k launches in flight (one per stream) co-reside instead of queueing behind each other —
                                   what a multi-GPU host does with its small per-GPU bands (results do not depend on it).
+                                  With the restart kernel the path-tracing kernel of such a launch runs on one of the
+                                  context's lanes (below, "Back-to-back launches"), so the frames in flight co-reside
+                                  whatever hardware queues the caller's streams share.
                                   Launches in flight on different streams may share one context: batched launches park
                                   their samples in a per-stream scratch owned by the context.  Calls on one context must
                                   still come from one host thread at a time (as for the reference's raytrace()) */
@@ -288,11 +291,17 @@ typedef struct {
  *
  * Back-to-back launches.  A host that issues launches of the default kernel on ONE stream without waiting for them (the
  * reference's render loop does not wait: gpu_processor.cpp:365-386) gets them pipelined by the library: when the stream's
- * previous launch has not finished, the new one is sized to half the GPU and its path-tracing kernel runs on an internal stream,
- * its accumulate / tonemap pass on the caller's stream behind an event — two launches are then resident side by side and
- * the tail of one is covered by the bulk of the next.  Stream semantics are unchanged: everything the launch writes that the
- * caller can see (accumulator, surface) is written on the caller's stream, in order.  Not applied when machine_share > 1 (the
- * caller runs its own pipeline), during graph capture, or for ptamd_raytrace_stats. */
+ * previous launch has not finished, the new one is sized to half the GPU and its path-tracing kernel runs on one of the
+ * context's lanes, its accumulate / tonemap pass on the caller's stream behind an event — two launches are then resident side
+ * by side and the tail of one is covered by the bulk of the next.  A launch with machine_share > 1 (the caller runs its own
+ * pipeline) takes a lane too, every launch of its stream but the first, and keeps its 1/machine_share grid.  A lane is a
+ * stream the context owns with a hardware queue of its own; a context makes two at the first launch that takes one, four at
+ * its first launch with machine_share >= 3, and takes them in turn whichever stream a launch comes from.  A lane is a
+ * blocking stream (the runtime makes CU-masked streams no other way), so launches on the null stream take two plain
+ * non-blocking internal streams instead, and a host that uses only the null stream never has a lane.  Stream semantics are unchanged:
+ * everything the launch writes that the caller can see (accumulator, surface) is written on the caller's stream, in order.
+ * Not applied during graph capture, with no_pipelining, for ptamd_raytrace_stats, for the adaptive list form or for the
+ * other persistent kinds: those run wholly on the caller's stream. */
 int ptamd_raytrace_ex(ptamd_context* ctx, const ptamd_launch* launch);
 /* Tells the library that the graphs captured on `stream` are gone (or will not be replayed any more): its sample slab may be
  * reallocated again and its pinned ring slots return to the rotation.  PTAMD_OK also when nothing was pinned. */
