@@ -84,9 +84,10 @@ struct ptamd_context {
   std::vector<bool> heads_clean;   // per ring slot: its ticket heads are known to be zero (creation, or its last user's resolve pass)
   std::vector<bool> slot_pinned;   // per ring slot: baked into a captured graph (skipped by the rotation until ptamd_release_captured)
   int n_cus = 0;
-  // resident workgroups per CU of the persistent kernels: depends on the scene's dynamic LDS bytes, so the cache is
-  // keyed by them ([0] persistent, [1] blockwise, [2] split, [3] restart)
-  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[6];   // ([4]: the contracted restart kernel, [5]: its list form)
+  // resident workgroups per CU of the persistent kernels, one entry per code object, keyed by the launch's dynamic LDS bytes
+  // (blocks_per_cu).  The first four in the order of PTAMD_KERNEL_BVH_PERSISTENT.._RESTART, then the restart kernel's two other forms.
+  enum { kOccPersistent, kOccBlockwise, kOccSplit, kOccRestart, kOccRestartFma, kOccRestartList, kOccEntries };
+  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[kOccEntries];
   // parked samples of batched launches, one scratch per stream: launches on one stream are ordered, launches on
   // different streams of one context (frames in flight, ptamd_launch.machine_share) must not share a buffer
   // Four slabs per stream.  [0..2] are used in turn by pipelined launches (megakernel on a lane, below): the
@@ -139,7 +140,7 @@ struct ptamd_context {
   uint32_t timeline_waves = 0;
   uint32_t default_kernel = PTAMD_KERNEL_BVH_RESTART; // what PTAMD_KERNEL_AUTO means
   bool default_kernel_is_builtin = true;              // false once PTAMD_DEFAULT_KERNEL pinned it
-  uint32_t refill_min = 0; // 0 = choose per launch (see do_launch); PTAMD_REFILL_MIN pins it
+  uint32_t refill_min = 0; // 0 = choose per launch (see size_grid); PTAMD_REFILL_MIN pins it
   // restart kernel: a round of walks ends once fewer than min(round_min, entering lanes / round_div) lanes are unfinished
   // measured (round 2 sweep, 1080p x 4 spp x 4 bounces; re-run with scripts/gpu_ab.sh): round_min 16-32 and walk_min 4-6 are a flat optimum
   uint32_t round_min = 16, round_div = 4; // PTAMD_ROUND_MIN, PTAMD_ROUND_DIV
@@ -174,7 +175,7 @@ float frame_nb_inverse(float c)
   return 1.0f / c;
 }
 constexpr uint32_t kCompactMaxNodes = 896;   // 896 * 32 B = 28 KB of boxes below 0x8000 with 4 KB to spare for static LDS
-constexpr float kQuantisedMaxExtent = 1.0e8f;   // largest |coordinate| of a scene walked over quantised nodes (nodes4q / nodes8): see do_launch
+constexpr float kQuantisedMaxExtent = 1.0e8f;   // largest |coordinate| of a scene walked over quantised nodes (nodes4q / nodes8): see choose_wide_nodes
 constexpr uint32_t kCompactMaxTris = 2047;   // a leaf's link code holds count << 11 | first triangle record in 15 bits (stage_scene)
 constexpr size_t kShadeFloats = 28;   // 7 float4 per face (pt_kernels.hip: resolve_hit).  Round 4 re-measured on the atrium: a 128-byte stride (one line per record) -1.2 %, a 64-byte hot half + 64-byte cold half (one line, 17 MB instead of 30) level, -0.6 % on textured scenes (profiles/r04_notes.md)
 constexpr float kBoxMargin = 1e-3f; // absolute box inflation, DESIGN.md "Conservative boxes"
@@ -362,58 +363,96 @@ bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam)
   return !(margins_cover(s.extent, s.margin_floor, cam_far) && margins_cover(s.extent, s.margin_floor, s.reach)) && s.n_faces != 0;   // also true for NaN
 }
 
-// later_chunk: the launch is the second or a later part of a batch the library cut into parts (kMaxFramesPerSlab): it follows
-// its predecessor on the same stream by construction, so it is pipelined behind it whatever the caller's machine_share
-// ad: the trace step of one round of adaptive sampling (ptamd_render_adaptive): the restart kernel's list form over the state's
-// active list, frame_count = samples per round, whole frame, on the caller's stream; its resolve is the list resolve
-int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool later_chunk = false, const AdaptiveParams* ad = nullptr)
+// Tables, counts and environment of a scene in KParams.  cm: null for the ray queries (ptamd_trace_rays), which never leave the scene
+void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p)
 {
-  int rc = validate_launch(ctx, l_in);
-  if (rc != PTAMD_OK) return rc;
-  // PTAMD_KERNEL_BVH_RESTART_FMA: everything below treats the launch as one of the restart kernel; only the code object differs
-  const bool fma = l_in->kernel == PTAMD_KERNEL_BVH_RESTART_FMA;
-  ptamd_launch l_copy;
-  const ptamd_launch* l = l_in;
-  if (fma) {
-    if (stats) { set_error("ptamd_raytrace_stats: the contracted kernel has no instrumented build"); return PTAMD_ERR_ARG; }
-    l_copy = *l_in; l_copy.kernel = PTAMD_KERNEL_BVH_RESTART; l = &l_copy;
-  }
-  // Batches longer than kMaxFramesPerSlab: consecutive launches of at most that many frames.  frame_count = N is by contract the
-  // same accumulator and final surface as N consecutive calls, so this changes no bit; what it bounds is the sample slab
-  // (rows x width x 12 bytes x 4 frames whatever N: 0.4 GB at 4K instead of 1.6 GB at 16 spp, and four slabs per stream).
-  if (l_in->frame_count > kMaxFramesPerSlab) {
-    for (uint32_t k0 = 0; k0 < l_in->frame_count; k0 += kMaxFramesPerSlab) {
-      ptamd_launch part = *l_in;
-      part.frame_nb = l_in->frame_nb + k0;
-      part.frame_count = l_in->frame_count - k0 < kMaxFramesPerSlab ? l_in->frame_count - k0 : kMaxFramesPerSlab;
-      if (k0 > 0) part.reset_accumulation = 0;
-      rc = do_launch(ctx, &part, stats, k0 > 0);
-      if (rc != PTAMD_OK) return rc;
-    }
-    return PTAMD_OK;
-  }
-  PT_HIP(hipSetDevice(ctx->device));
-  const DeviceScene& s = ctx->scenes[l->scene_id];
-  const DeviceCubemap& cm = ctx->cubemaps[l->cubemap_id];
-
-  KParams p;
-  std::memset(&p, 0, sizeof p);
   p.nodes = s.nodes; p.tris_bvh = s.tris_bvh; p.tris_brute = s.tris_brute; p.shade = s.shade;
   p.materials = s.materials; p.lights = s.lights; p.textures = s.textures; p.texels = s.texels;
-  p.cubemap = cm.faces; p.cubemap_size = cm.size;
-  p.env_uniform = cm.uniform ? 1u : 0u; p.env_r = cm.color[0]; p.env_g = cm.color[1]; p.env_b = cm.color[2];
-  p.gamma_table = ctx->d_gamma;
   p.n_faces = s.n_faces; p.n_lights = s.n_lights; p.n_nodes = s.n_nodes; p.n_bvh_tris = s.n_bvh_tris;
   p.nodes4 = s.nodes4; p.n_nodes4 = s.n_nodes4;
+  if (!cm) return;
+  p.cubemap = cm->faces; p.cubemap_size = cm->size;
+  p.env_uniform = cm->uniform ? 1u : 0u; p.env_r = cm->color[0]; p.env_g = cm->color[1]; p.env_b = cm->color[2];
+}
+
+// The wide walk's nodes: the four-wide float form, or where the caller lets the tuning knobs apply, PTAMD_WIDE8's or PTAMD_WIDE4Q's
+// quantised form.  Those decode a plane as fma(plane, scale / d, fma(origin, 1 / d, -o / d)): with the 1e30 that stands in for 1 / 0
+// (axis-parallel rays) the inner fma stays finite for coordinates up to kQuantisedMaxExtent; beyond it the float nodes are walked,
+// whose planes overflow one by one (an infinite slab distance is still a correct one).  Returns the stack entries the walk needs.
+uint32_t choose_wide_nodes(const ptamd_context* ctx, const DeviceScene& s, bool knobs, KParams& p)
+{
+  const bool quantised_ok = knobs && s.extent <= kQuantisedMaxExtent;
+  if (quantised_ok && ctx->wide8 && s.n_nodes8 != 0) {
+    p.nodes4 = s.nodes8; p.n_nodes4 = s.n_nodes8; p.wide8 = 1u;
+    return 7u * s.depth8 + 1u;   // a visit stacks all hit children but the nearest
+  }
+  if (quantised_ok && ctx->wide4q && s.nodes4q != nullptr) { p.nodes4 = s.nodes4q; p.wide8 = 2u; }
+  return 3u * s.depth4 + 1u;
+}
+
+// What the steps of a launch decided
+struct LaunchPlan {
+  uint32_t which = 0;             // the kernel that runs: PTAMD_KERNEL_AUTO, the contracted kernel and far-origin cameras resolved
+  bool fma = false;               // PTAMD_KERNEL_BVH_RESTART_FMA: the restart kernel's contracted code object
+  bool brute_walk = false;        // the restart kernel tests every face (KParams::brute_walk)
+  bool resident = false;          // the scene's copy (lds bytes) fits in LDS
+  size_t lds = 0, launch_lds = 0; // LDS bytes of the scene's copy, dynamic LDS bytes of the megakernel
+  hipStream_t stream = nullptr;
+  ptamd_context::SampleScratch* sc = nullptr;   // the rest: persistent family only
+  bool capturing = false, pipelined = false;
+  uint32_t waves_per_block = 0, n_blocks = 0, slab = 3, slot = 0;
+};
+
+inline bool persistent_family(uint32_t k) { return k == PTAMD_KERNEL_BVH_PERSISTENT || k == PTAMD_KERNEL_BVH_SPLIT || k == PTAMD_KERNEL_BVH_RESTART; }
+
+// Step 1: the kernel.  ad: the list form, whose caller has already refused other kernels, long rounds and far-origin cameras
+int resolve_kernel(const ptamd_context* ctx, const ptamd_launch* l, bool stats, const AdaptiveParams* ad, LaunchPlan& pl)
+{
+  // PTAMD_KERNEL_BVH_RESTART_FMA: everything below treats the launch as one of the restart kernel; only the code object differs
+  pl.fma = l->kernel == PTAMD_KERNEL_BVH_RESTART_FMA;
+  if (pl.fma && stats) { set_error("ptamd_raytrace_stats: the contracted kernel has no instrumented build"); return PTAMD_ERR_ARG; }
+  pl.which = pl.fma ? (uint32_t)PTAMD_KERNEL_BVH_RESTART : l->kernel;
+  // (the list form has one kernel: PTAMD_KERNEL_AUTO means it whatever default kernel PTAMD_DEFAULT_KERNEL pinned)
+  if (pl.which == PTAMD_KERNEL_AUTO) pl.which = ad ? (uint32_t)PTAMD_KERNEL_BVH_RESTART : ctx->default_kernel;
+  const DeviceScene& s = ctx->scenes[l->scene_id];
+  // A camera beyond the reach of the box margins (far_origin_camera): such launches test every face instead — the reference
+  // algorithm, exact for any origin — inside the restart kernel (KParams::brute_walk: all its launch shapes keep working, interleaved
+  // bands and batched frames included) or, for the other kernels, through the exhaustive tile kernel, one frame per launch.
+  const bool far_origin = far_origin_camera(s, l->camera);
+  if (far_origin) {
+    if (pl.which == PTAMD_KERNEL_BVH_RESTART) pl.brute_walk = true;
+    else pl.which = PTAMD_KERNEL_BRUTE_FORCE;
+  }
+  // only the restart kernel maps its tiles to the rows of interleaved bands; every other kernel would render the whole
+  // frame into the band-local buffers (PTAMD_DEFAULT_KERNEL behind PTAMD_KERNEL_AUTO can ask for one)
+  if (l->interleave_ranks > 1u && pl.which != PTAMD_KERNEL_BVH_RESTART) {
+    set_error("ptamd_raytrace: interleaved bands need the restart kernel (PTAMD_KERNEL_AUTO resolves to another one here)");
+    return PTAMD_ERR_ARG;
+  }
+  if (l->frame_count > 1 && !far_origin && !persistent_family(pl.which)) {
+    set_error("ptamd_raytrace: frame_count > 1 needs a persistent kernel (PTAMD_KERNEL_AUTO, _BVH_PERSISTENT, _BVH_RESTART or _BVH_SPLIT)");
+    return PTAMD_ERR_ARG;
+  }
+  const bool brute = pl.which == PTAMD_KERNEL_BRUTE_FORCE;
+  pl.lds = pl.launch_lds = brute ? s.info.lds_bytes_brute : s.info.lds_bytes_bvh;
+  // the LDS copy of a BVH addresses its boxes with 15 bits (pt_kernels.hip: stage_scene): 32 bytes per node, nodes first
+  pl.resident = pl.lds <= kLdsBudget && (brute || (s.n_nodes <= kCompactMaxNodes && s.n_bvh_tris <= kCompactMaxTris));
+  pl.stream = static_cast<hipStream_t>(l->stream);
+  return PTAMD_OK;
+}
+
+// KParams of a launch before the kernel's own steps
+void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, const LaunchPlan& pl, KParams& p)
+{
+  const DeviceScene& s = ctx->scenes[l->scene_id];
+  std::memset(&p, 0, sizeof p);
+  fill_scene(s, &ctx->cubemaps[l->cubemap_id], p);
+  p.gamma_table = ctx->d_gamma;
   fill_far_table(p.far_table);
   // finite edges of at most 2e8 per axis and unit directions: det = e1 . (dir x e2) is far below 2^125 (or NaN, which
   // both forms of the reciprocal pass on)
   p.small_det = ctx->short_rcp && s.all_finite && s.extent <= 1.0e8f ? 1u : 0u;
-
-  // generateRay's pixel-invariant part (intersection.cuh:79-89)
-  const ptamd_camera& cam = l->camera;
-  camera_terms(cam, l->width, p);
-
+  camera_terms(l->camera, l->width, p);   // generateRay's pixel-invariant part (intersection.cuh:79-89)
   p.width = l->width; p.height = l->height; p.row_begin = l->row_begin; p.row_end = l->row_end;
   p.hash_seed = ptamd_wang_hash(l->frame_nb);
   p.frame_nb_f = (float)(int)l->frame_nb;
@@ -430,363 +469,377 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l_in, bool stats, bool lat
   }
   p.stats = stats ? ctx->d_stats : nullptr;
   p.error_flag = ctx->d_stats + 15;
-
-  // (the list form has one kernel: PTAMD_KERNEL_AUTO means it whatever default kernel PTAMD_DEFAULT_KERNEL pinned)
-  uint32_t which = l->kernel == PTAMD_KERNEL_AUTO ? (ad ? (uint32_t)PTAMD_KERNEL_BVH_RESTART : ctx->default_kernel) : l->kernel;
-  // A camera beyond the reach of the box margins (far_origin_camera): such launches test every face instead — the reference
-  // algorithm, exact for any origin — inside the restart kernel (KParams::brute_walk: all its launch shapes keep working, interleaved
-  // bands and batched frames included) or, for the other kernels, through the exhaustive tile kernel.
-  const bool far_origin = far_origin_camera(s, cam);
-  if (ad && (far_origin || which != PTAMD_KERNEL_BVH_RESTART || l->frame_count > kMaxFramesPerSlab)) {
-    set_error("ptamd_render_adaptive: the list form needs the restart kernel and a camera within reach of the box margins");
-    return PTAMD_ERR_ARG;
-  }
-  if (far_origin) {
-    if (which == PTAMD_KERNEL_BVH_RESTART) p.brute_walk = 1u;
-    else which = PTAMD_KERNEL_BRUTE_FORCE;
-  }
+  p.brute_walk = pl.brute_walk ? 1u : 0u;
   p.generic_round = ctx->generic_round ? 1u : 0u;
-  // only the restart kernel maps its tiles to the rows of interleaved bands; every other kernel would render the whole
-  // frame into the band-local buffers (PTAMD_DEFAULT_KERNEL behind PTAMD_KERNEL_AUTO can ask for one)
-  if (l->interleave_ranks > 1u && which != PTAMD_KERNEL_BVH_RESTART) {
-    set_error("ptamd_raytrace: interleaved bands need the restart kernel (PTAMD_KERNEL_AUTO resolves to another one here)");
-    return PTAMD_ERR_ARG;
-  }
-  const int kind = which == PTAMD_KERNEL_BRUTE_FORCE ? 1 : 2;
-  const size_t lds = kind == 1 ? s.info.lds_bytes_brute : s.info.lds_bytes_bvh;
-  // the LDS copy of a BVH addresses its boxes with 15 bits (pt_kernels.hip: stage_scene): 32 bytes per node, nodes first
-  const bool resident = lds <= kLdsBudget && (kind == 1 || (s.n_nodes <= kCompactMaxNodes && s.n_bvh_tris <= kCompactMaxTris));
-  hipStream_t stream = static_cast<hipStream_t>(l->stream);
-  // Per-stream state of the persistent kernels: sample slabs, events (found or made here, once per launch)
-  ptamd_context::SampleScratch* sc = nullptr;
-  if (which == PTAMD_KERNEL_BVH_PERSISTENT || which == PTAMD_KERNEL_BVH_SPLIT || which == PTAMD_KERNEL_BVH_RESTART) {
-    for (auto& c : ctx->sample_scratch) if (c.stream == l->stream) sc = &c;
-    if (!sc) {
-      if (ctx->sample_scratch.size() >= kMaxScratchStreams) {
-        // a host cycling through short-lived streams: drop every scratch once nothing can be using them — except those a captured
-        // graph has pinned (ptamd_release_captured frees them for this)
-        size_t pinned = 0;
-        for (auto& c : ctx->sample_scratch) pinned += c.captured ? 1u : 0u;
-        if (pinned >= kMaxScratchStreams) {
-          set_error("ptamd_raytrace: all 16 per-stream sample scratches of this context are pinned by captured graphs (ptamd_release_captured)");
-          return PTAMD_ERR_LIMIT;
-        }
-        PT_HIP(hipDeviceSynchronize());
-        std::vector<ptamd_context::SampleScratch> kept;
-        for (auto& c : ctx->sample_scratch) { if (c.captured) kept.push_back(c); else free_scratch(c); }
-        ctx->sample_scratch.swap(kept);
+}
+
+// Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
+// first launch of a stream, which sizes the stream's own slab (what a later capture on that stream needs); AUTO's persistent kernel.
+// later_chunk: a later part of a batch follows its predecessor on the same stream, so it is pipelined whatever machine_share says.
+int plan_stream(ptamd_context* ctx, const ptamd_launch* l, bool stats, bool later_chunk, const AdaptiveParams* ad, LaunchPlan& pl)
+{
+  for (auto& c : ctx->sample_scratch) if (c.stream == l->stream) pl.sc = &c;
+  if (!pl.sc) {
+    if (ctx->sample_scratch.size() >= kMaxScratchStreams) {
+      // a host cycling through short-lived streams: drop every scratch once nothing can be using them — except those a captured
+      // graph has pinned (ptamd_release_captured frees them for this)
+      size_t pinned = 0;
+      for (auto& c : ctx->sample_scratch) pinned += c.captured ? 1u : 0u;
+      if (pinned >= kMaxScratchStreams) {
+        set_error("ptamd_raytrace: all 16 per-stream sample scratches of this context are pinned by captured graphs (ptamd_release_captured)");
+        return PTAMD_ERR_LIMIT;
       }
-      ctx->sample_scratch.emplace_back();
-      sc = &ctx->sample_scratch.back();
-      sc->stream = l->stream;
+      PT_HIP(hipDeviceSynchronize());
+      std::vector<ptamd_context::SampleScratch> kept;
+      for (auto& c : ctx->sample_scratch) { if (c.captured) kept.push_back(c); else free_scratch(c); }
+      ctx->sample_scratch.swap(kept);
     }
+    ctx->sample_scratch.emplace_back();
+    pl.sc = &ctx->sample_scratch.back();
+    pl.sc->stream = l->stream;
   }
-  // Launches of the restart kernel that a host issues back to back on one stream are pipelined by the library
-  // (ptamd_context::lane): when the previous launch of this stream has not finished yet — the host is running ahead —
-  // this one is sized to half the GPU and its megakernel goes to a lane, so that the two are resident side by
-  // side and the tail of one is covered by the bulk of the other, exactly what a host gets from two streams and
-  // machine_share = 2.  A launch with machine_share > 1 (the caller runs its own pipeline) takes a lane whatever the state of its
-  // stream: the frames the caller keeps in flight then share the GPU whatever hardware queues its streams landed on.  Not when
-  // the caller captures a graph, wants counters or sets no_pipelining, and not for the first launch of a stream, which sizes the
-  // stream's own slab as before (what a later graph capture on that stream needs); a host that waits for every frame gets
-  // whole-GPU launches on its own stream as before.  Later parts of a long batch follow the first on a lane.
-  bool pipelined = ctx->overlap && which == PTAMD_KERNEL_BVH_RESTART && !stats && !ad;
-  bool capturing = false;
-  if (stream != nullptr) {
+  pl.pipelined = ctx->overlap && pl.which == PTAMD_KERNEL_BVH_RESTART && !stats && !ad;
+  if (pl.stream != nullptr) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) capturing = true;
+    if (hipStreamIsCapturing(pl.stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) pl.capturing = true;
   }
-  if (capturing || (sc && sc->no_pipeline) || l->no_pipelining) pipelined = false;
-  if (pipelined && !later_chunk)
-    pipelined = sc->last_done != nullptr && (l->machine_share > 1u || hipEventQuery(sc->last_done) == hipErrorNotReady);
-  // lanes 1 and 2 for the first launch from a stream other than the null stream that takes one, 3 and 4 for callers that keep
-  // three or more frames in flight
-  if (pipelined && stream != nullptr) {
+  if (pl.capturing || pl.sc->no_pipeline || l->no_pipelining) pl.pipelined = false;
+  if (pl.pipelined && !later_chunk)
+    pl.pipelined = pl.sc->last_done != nullptr && (l->machine_share > 1u || hipEventQuery(pl.sc->last_done) == hipErrorNotReady);
+  if (pl.pipelined && pl.stream != nullptr) {
     const uint32_t want = l->machine_share >= 3u ? ptamd_context::kMaxLanes : 2u;
-    while (ctx->n_lanes < want) { rc = add_lane(ctx); if (rc != PTAMD_OK) return rc; }
+    while (ctx->n_lanes < want) { int rc = add_lane(ctx); if (rc != PTAMD_OK) return rc; }
   }
   // PTAMD_KERNEL_AUTO, one frame per launch (the reference's interactive loop, ptamd_raytrace) on an LDS-resident scene,
   // one launch at a time: the persistent kernel writes the surface itself, the restart kernel would add its resolve
   // pass to every launch (1080p, one launch per spp, one at a time: 6.03 vs 5.89 Gsamples/s).
-  if (l->kernel == PTAMD_KERNEL_AUTO && which == PTAMD_KERNEL_BVH_RESTART && ctx->default_kernel_is_builtin && l->frame_count <= 1 &&
-      resident && l->interleave_ranks <= 1 && l->machine_share <= 1 && !pipelined && !p.brute_walk && !ad)
-    which = PTAMD_KERNEL_BVH_PERSISTENT;
-  const bool overlap = pipelined;
-  hipError_t e;
-  if (far_origin && !p.brute_walk && l->frame_count > 1) {
-    // batched frames == consecutive launches by contract: issue them that way
-    for (uint32_t k = 0; k < l->frame_count; ++k) {
-      ptamd_launch one = *l;
-      one.frame_nb = l->frame_nb + k; one.frame_count = 1; one.kernel = PTAMD_KERNEL_BRUTE_FORCE;
-      if (k > 0) one.reset_accumulation = 0;
-      rc = do_launch(ctx, &one, stats);
-      if (rc != PTAMD_OK) return rc;
+  if (l->kernel == PTAMD_KERNEL_AUTO && pl.which == PTAMD_KERNEL_BVH_RESTART && ctx->default_kernel_is_builtin && l->frame_count <= 1 &&
+      pl.resident && l->interleave_ranks <= 1 && l->machine_share <= 1 && !pl.pipelined && !pl.brute_walk && !ad)
+    pl.which = PTAMD_KERNEL_BVH_PERSISTENT;
+  return PTAMD_OK;
+}
+
+// Step 5: the restart kernel's dynamic LDS
+void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, const AdaptiveParams* ad, LaunchPlan& pl, KParams& p)
+{
+  if (pl.which != PTAMD_KERNEL_BVH_RESTART) return;
+  if (pl.resident) {
+    // pools of fresh paths in LDS when two workgroups with their scene copies leave room for them (PT_POOL_LDS_BYTES
+    // per wave); else in a global slab (3 KiB per wave, L2-resident)
+    const uint32_t waves = restart_threads(true) / 64u;
+    const size_t with_pools = ((pl.lds + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES;
+    const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
+    // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
+    // there whatever the knob, at one workgroup per CU when two do not fit
+    if (ad || (ctx->pool_in_lds && with_pools * blocks_wanted + 1024u <= 160u * 1024u)) {
+      p.pool_lds_offset = (uint32_t)((pl.lds + 15u) & ~(size_t)15u);
+      if (p.pool_lds_offset == 0) p.pool_lds_offset = 16u;               // (an empty scene: keep the flag non-zero)
+      pl.launch_lds = p.pool_lds_offset + (size_t)waves * PT_POOL_LDS_BYTES;
     }
+    return;
+  }
+  // A scene that does not fit in LDS: the wide walk.  As many of its per-lane stack entries as fit the workgroup's LDS share live in
+  // LDS ([entry][lane], 512 bytes per entry and wave), the rest in a global slab.  The knobs' node forms are not for the instrumented,
+  // time-stamp and far-origin instantiations, nor for the list form, which is compiled for the four-wide float nodes.
+  const uint32_t need = choose_wide_nodes(ctx, s, !stats && !pl.fma && !pl.brute_walk && !ctx->d_timeline && !ad, p);
+  const uint32_t node_bytes = p.wide8 == 2u ? 64u : 128u;
+  const uint32_t waves = restart_threads(false) / 64u;
+  const uint32_t share = 160u * 1024u / restart_wide_blocks_per_cu() - 256u;   // LDS bytes of one resident workgroup
+  // the top of the tree (breadth-first numbering: nodes 0..340 are its first five levels when full) goes to LDS too:
+  // 512 nodes = 64 KB of the one workgroup's 160 KB, then 7 stack entries per lane
+  // ... and the waves' pools of fresh paths (PT_POOL_LDS_BYTES each), behind the stacks
+  // (the list form keeps them in the global slab: it is compiled for that)
+  const uint32_t pools = (ctx->pool_in_lds && ctx->pool_in_lds_wide && !ad) ? waves * PT_POOL_LDS_BYTES : 0u;
+  // (the same LDS bytes hold twice as many 64-byte nodes)
+  // chunk-major treelet (pt_kernels.hip: PT_TREELET_SOA): a region of fixed size whatever the number of nodes staged
+  const uint32_t region = restart_treelet_region_bytes();
+  uint32_t treelet_want = ctx->treelet_nodes * (128u / node_bytes);
+  if (region && treelet_want > region / node_bytes) treelet_want = region / node_bytes;
+  uint32_t treelet = treelet_want < p.n_nodes4 ? treelet_want : p.n_nodes4;
+  if (!region && treelet * node_bytes + waves * 512u * 4u + pools > share) treelet = (share - pools - waves * 512u * 4u) / node_bytes;   // keep >= 4 stack entries
+  const uint32_t treelet_bytes = region ? (treelet ? region : 0u) : treelet * node_bytes;
+  uint32_t fit = (share - pools - treelet_bytes) / (waves * 512u);
+  if (const char* ev = tuning_env("PTAMD_STACK_LDS")) { int v = std::atoi(ev); if (v >= 1 && (uint32_t)v <= fit) fit = (uint32_t)v; }   // tuning knob
+  p.treelet_nodes = treelet;
+  p.stack_lds_entries = need < fit ? need : fit;
+  p.stack_spill_entries = need - p.stack_lds_entries;
+  pl.launch_lds = (size_t)treelet_bytes + (size_t)p.stack_lds_entries * waves * 512u;
+  if (pools) {
+    p.pool_lds_offset = (uint32_t)pl.launch_lds;
+    if (!p.pool_lds_offset) p.pool_lds_offset = 16u;
+    pl.launch_lds = p.pool_lds_offset + pools;
+  }
+}
+
+// Resident workgroups per CU of the launch's kernel, cached per code object (ptamd_context::occupancy) and key: the dynamic LDS
+// bytes for LDS-resident scenes; for the wide walk, the restart kernel's + 1 and 0 for the other kernels
+int blocks_per_cu(ptamd_context* ctx, const LaunchPlan& pl, bool list, int& bpc)
+{
+  const bool restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
+  ptamd_context::Occupancy& occ = ctx->occupancy[pl.which - PTAMD_KERNEL_BVH_PERSISTENT + (pl.fma ? 1 : 0) + (list ? 2 : 0)];
+  const size_t key = pl.resident ? pl.launch_lds : (restart ? pl.launch_lds + 1u : 0);
+  if (occ.blocks_per_cu < 0 || occ.lds != key) {
+    int q = -1;
+    hipError_t e;
+    switch (pl.which) {
+      case PTAMD_KERNEL_BVH_PERSISTENT: e = persistent_blocks_per_cu(pl.resident, pl.lds, &q); break;
+      case PTAMD_KERNEL_BVH_BLOCKWISE: e = blockwise_blocks_per_cu(pl.resident, pl.lds, &q); break;
+      case PTAMD_KERNEL_BVH_SPLIT: e = split_blocks_per_cu(pl.resident, pl.lds, &q); break;
+      default: e = pl.fma ? ptamd_fma_restart_blocks_per_cu(pl.resident ? 1 : 0, pl.launch_lds, &q) : restart_blocks_per_cu(pl.resident, pl.launch_lds, &q, list);
+    }
+    if (e != hipSuccess || q < 1) {
+      occ.blocks_per_cu = -1;
+      return hip_fail(pl.which == PTAMD_KERNEL_BVH_BLOCKWISE ? "occupancy query of the blockwise kernel" : "occupancy query of the persistent kernel", e);
+    }
+    occ.blocks_per_cu = q; occ.lds = key;
+  }
+  bpc = occ.blocks_per_cu;
+  return PTAMD_OK;
+}
+
+// Step 6: the tiles and the grid.  Interleaved bands: the launch's buffers hold the rank's rows; parked samples and the resolve pass
+// address them as the band [0, rows) with band-local buffers, and only the restart kernel's tile -> frame-row map knows the interleaving.
+int size_grid(ptamd_context* ctx, const ptamd_launch* l, const AdaptiveParams* ad, LaunchPlan& pl, KParams& p)
+{
+  const bool restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
+  const uint32_t count = l->frame_count > 1 ? l->frame_count : 1u;
+  uint32_t rows = l->row_end - l->row_begin;
+  if (l->interleave_ranks > 1u) {
+    rows = ptamd_interleaved_rows(l->height, l->interleave_ranks, l->interleave_rank, l->interleave_rows);
+    p.ilv_ranks = l->interleave_ranks; p.ilv_rank = l->interleave_rank; p.ilv_rows = l->interleave_rows;
+    p.row_begin = 0; p.row_end = rows;
+    p.tfb_row0 = l->height - rows;
+    p.surf_row0 = 0;
+  }
+  p.y_limit = l->row_end;
+  p.tiles_x = (l->width + PT_TILE_W - 1u) / PT_TILE_W;
+  p.n_tiles = p.tiles_x * ((rows + PT_TILE_H - 1u) / PT_TILE_H);
+  if (p.n_tiles == 0) return PTAMD_OK;
+  if ((uint64_t)p.n_tiles * count >= (1ull << 31)) {   // (tile, frame) tickets are 32-bit
+    set_error("ptamd_raytrace: rows x width x frame_count too large for one launch (split the batch)");
+    return PTAMD_ERR_LIMIT;
+  }
+  int bpc = 0;
+  const int rc = blocks_per_cu(ctx, pl, ad != nullptr, bpc);
+  if (rc != PTAMD_OK) return rc;
+  // waves that take tile tickets: every wave of a persistent block, the shader waves of a split block
+  pl.waves_per_block = pl.which == PTAMD_KERNEL_BVH_SPLIT ? split_shader_waves() : (restart ? restart_threads(pl.resident) / 64u : kPersistentThreads / 64u);
+  uint32_t n_blocks = (uint32_t)ctx->n_cus * (uint32_t)bpc;
+  p.sample_count = count;
+  p.frame_nb0 = l->frame_nb;
+  // Mid-path lane refill pays once paths are long enough for dead lanes to dominate the box loop
+  // (measured, batched 1080p: 4 bounces 4.65 vs 4.46 Gsamples/s without/with, 5: 3.90 vs 4.13,
+  // 6: 3.44 vs 3.92, 8: 2.89 vs 3.71); below that, whole-wave refill keeps primary rays coherent.
+  p.refill_min = ctx->refill_min ? ctx->refill_min : (l->bounces >= 5 ? 16u : 64u);
+  p.tiles_per_ticket = ad ? 1u : ctx->tiles_per_ticket;   // (the list form: one chunk of 64 entries per ticket)
+  const uint32_t share = pl.pipelined ? (l->machine_share > 2u ? l->machine_share : 2u) : l->machine_share;
+  if (share > 1u) n_blocks = n_blocks / share > 0u ? n_blocks / share : 1u;
+  const uint32_t n_tickets = (p.n_tiles * count + p.tiles_per_ticket - 1u) / p.tiles_per_ticket;
+  const uint32_t useful = (n_tickets + pl.waves_per_block - 1u) / pl.waves_per_block;
+  if (n_blocks > useful) n_blocks = useful;
+  // XCD-local regions (pt_kernels.hip: region_tile): the ticket -> tile map that keeps every XCD on a compact part of the frame.
+  // Needs whole groups of eight workgroups (one per XCD) and one tile per ticket.
+  if (restart && !ad && p.tiles_per_ticket == 1u && n_blocks >= 8u && (uint64_t)p.n_tiles * count < (1ull << 28) &&
+      (ctx->xcd_regions == 2u || (ctx->xcd_regions == 1u && !pl.resident))) {
+    n_blocks &= ~7u;
+    p.xcd_regions = 1u;
+  }
+  pl.n_blocks = n_blocks;
+  // seeds of frames frame_nb+1.. are hashed on the device; the tonemap uses the last frame number
+  if (count > 1) p.frame_nb_f = (float)(int)(l->frame_nb + count - 1u);
+  p.frame_nb_inv = frame_nb_inverse(p.frame_nb_f);
+  return PTAMD_OK;
+}
+
+constexpr int kReplan = -1;   // bind_slab: the pipelining slabs could not be allocated, plan the launch again without pipelining
+
+// Step 7: the slab the launch parks its samples in (ptamd_context::SampleScratch; the restart kernel parks every sample: its resolve
+// pass accumulates and tonemaps).  Growing synchronises (the old buffer may be in use): once per stream and configuration, for the
+// pipelining slabs at the first launch that finds its predecessor still running, which costs that launch its overlap and no more.
+int bind_slab(ptamd_context* ctx, const ptamd_launch* l, LaunchPlan& pl, KParams& p)
+{
+  ptamd_context::SampleScratch* sc = pl.sc;
+  const bool restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
+  if (p.sample_count <= 1 && !restart) return PTAMD_OK;
+  const size_t sample_bytes = ((size_t)p.sample_count * (p.row_end - p.row_begin) * l->width * 3u * sizeof(float) + 255u) & ~(size_t)255u;
+  const size_t pool_bytes = (restart && !p.pool_lds_offset) ? (size_t)pl.n_blocks * pl.waves_per_block * 192u * sizeof(float4) : 0u;
+  const size_t spill_bytes = (size_t)pl.n_blocks * pl.waves_per_block * p.stack_spill_entries * 512u;
+  const size_t need = sample_bytes + pool_bytes + spill_bytes + 16u;
+  auto grow = [&](uint32_t i) -> int {
+    PT_HIP(hipStreamSynchronize(pl.stream));
+    for (uint32_t k = 0; k < ctx->n_lanes; ++k) PT_HIP(hipStreamSynchronize(ctx->lane[k]));
+    for (hipStream_t is : ctx->internal) if (is) PT_HIP(hipStreamSynchronize(is));
+    (void)hipFree(sc->buf[i]);
+    sc->buf[i] = nullptr; sc->bytes[i] = 0;
+    hipError_t me = hipMalloc(reinterpret_cast<void**>(&sc->buf[i]), need);
+    if (me != hipSuccess) { sc->buf[i] = nullptr; (void)hipGetLastError(); return PTAMD_ERR_HIP; }
+    sc->bytes[i] = need;
     return PTAMD_OK;
+  };
+  pl.slab = pl.pipelined ? sc->flip % 3u : 3u;
+  if (pl.pipelined) {
+    for (int i = 0; i < 3; ++i) {
+      if (!sc->mega_done[i]) PT_HIP(hipEventCreateWithFlags(&sc->mega_done[i], hipEventDisableTiming));
+      if (!sc->resolved[i]) PT_HIP(hipEventCreateWithFlags(&sc->resolved[i], hipEventDisableTiming));
+    }
+    bool ok = true;
+    for (uint32_t i = 0; i < 3u && ok; ++i) if (need > sc->bytes[i]) ok = grow(i) == PTAMD_OK;
+    if (!ok) {
+      // no room for the pipelining slabs: this stream renders unpipelined from now on (slab [3] on the caller's stream)
+      for (uint32_t i = 0; i < 3u; ++i) { (void)hipFree(sc->buf[i]); sc->buf[i] = nullptr; sc->bytes[i] = 0; }
+      sc->no_pipeline = true;
+      return kReplan;
+    }
+  } else if (need > sc->bytes[3]) {
+    if (pl.capturing) {
+      set_error("ptamd_raytrace: a launch cannot size its stream's sample slab inside a graph capture: issue this configuration once eagerly first");
+      return PTAMD_ERR_LIMIT;
+    }
+    if (sc->captured) {
+      set_error("ptamd_raytrace: a captured graph pins this stream's sample slab; a larger launch would reallocate it under the graph "
+                "(ptamd_release_captured(ctx, stream) once the graph is gone)");
+      return PTAMD_ERR_LIMIT;
+    }
+    if (grow(3u) != PTAMD_OK) return hip_fail("hipMalloc of the sample slab", hipErrorOutOfMemory);
   }
-  if (l->frame_count > 1 && which != PTAMD_KERNEL_BVH_PERSISTENT && which != PTAMD_KERNEL_BVH_SPLIT && which != PTAMD_KERNEL_BVH_RESTART) {
-    set_error("ptamd_raytrace: frame_count > 1 needs a persistent kernel (PTAMD_KERNEL_AUTO, _BVH_PERSISTENT, _BVH_RESTART or _BVH_SPLIT)");
-    return PTAMD_ERR_ARG;
+  p.samples_out = sc->buf[pl.slab];
+  p.pool = reinterpret_cast<float4*>(reinterpret_cast<char*>(sc->buf[pl.slab]) + sample_bytes);
+  p.stack_spill = reinterpret_cast<uint2*>(reinterpret_cast<char*>(sc->buf[pl.slab]) + sample_bytes + pool_bytes);
+  return PTAMD_OK;
+}
+
+// Step 8: the launch's ring slot of ticket counter and heads.  Slots baked into captured graphs are not handed out again; a launch
+// captured on a stream with a scratch pins its own.  (Blockwise launches have no scratch: their slots are never pinned.)
+int take_slot(ptamd_context* ctx, bool capturing, ptamd_context::SampleScratch* sc, uint32_t& slot)
+{
+  slot = ctx->ticket_next++ % kTicketRing;
+  for (uint32_t tries = 0; ctx->slot_pinned[slot]; ++tries) {
+    if (tries >= kTicketRing) { set_error("ptamd_raytrace: every ring slot of ticket heads is pinned by captured graphs (ptamd_release_captured)"); return PTAMD_ERR_LIMIT; }
+    slot = ctx->ticket_next++ % kTicketRing;
   }
-  if (which == PTAMD_KERNEL_BVH_BLOCKWISE) {
-    // persistent workgroups over 32x16 super-tiles; tickets 0..n_blocks-1 are static
+  if (capturing && sc) { ctx->slot_pinned[slot] = true; sc->pinned_slots.push_back(slot); sc->captured = true; }
+  return PTAMD_OK;
+}
+
+// Step 9: the megakernel, its events and the resolve pass
+int issue(ptamd_context* ctx, bool stats, const AdaptiveParams* ad, const LaunchPlan& pl, KParams& p)
+{
+  const bool split = pl.which == PTAMD_KERNEL_BVH_SPLIT, restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
+  ptamd_context::SampleScratch* sc = pl.sc;
+  p.round_min = ctx->round_min;
+  p.round_div = ctx->round_div;
+  p.round_div_m16 = (65536u + ctx->round_div - 1u) / ctx->round_div;
+  p.walk_min = ctx->walk_min;
+  p.walk_min4 = ctx->walk_min4;
+  p.tile_counter = ctx->d_tickets + pl.slot;
+  if (ad) p.adaptive = ad->block;   // (the restart kernel takes no ticket counter: the field names the list form's state instead)
+  // tickets 0..n_static-1 are taken statically by the waves; the shared counter hands out the rest
+  p.n_static = pl.n_blocks * pl.waves_per_block;
+  if (split) PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)p.n_static, 1, pl.stream));
+  hipStream_t mega_stream = pl.stream;
+  if (pl.pipelined) {
+    // the megakernel touches nothing of the caller's: it waits only for the slab's previous reader (the resolve pass three
+    // launches back).  Lanes (null-stream callers: the internal streams) are taken in turn by every launch of the context.
+    mega_stream = pl.stream != nullptr ? ctx->lane[ctx->lane_next++ % ctx->n_lanes] : ctx->internal[ctx->lane_next++ & 1u];
+    sc->flip++;
+    if (sc->resolved_valid[pl.slab]) PT_HIP(hipStreamWaitEvent(mega_stream, sc->resolved[pl.slab], 0));
+  }
+  if (!split) {
+    p.tile_heads = ctx->d_heads + (size_t)pl.slot * 8u * PT_HEAD_STRIDE;
+    // the whole ring is zeroed at creation and a launch that parks its samples has its resolve pass zero its heads
+    // again (pt_resolve_kernel); only slots whose last user did not get that far are cleared here
+    if (!ctx->heads_clean[pl.slot]) PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_heads), 0, 8u * PT_HEAD_STRIDE, mega_stream));
+    ctx->heads_clean[pl.slot] = false;
+  }
+  if (restart && !pl.fma && ctx->d_timeline && p.n_static <= ctx->timeline_waves) p.timeline = ctx->d_timeline;
+  hipError_t e;
+  if (split) { p.tiles_per_ticket = 1; e = launch_megakernel_split(p, pl.resident, pl.lds, stats, pl.n_blocks, pl.stream); }
+  else if (!restart) e = launch_megakernel_persistent(p, pl.resident, pl.lds, stats, pl.n_blocks, pl.stream);
+  else if (pl.fma) e = ptamd_fma_launch_restart(&p, pl.resident ? 1 : 0, pl.launch_lds, pl.n_blocks, mega_stream);
+  else e = launch_megakernel_restart(p, pl.resident, pl.launch_lds, stats, pl.n_blocks, mega_stream, ad != nullptr);
+  if (e == hipSuccess && pl.pipelined) {
+    PT_HIP(hipEventRecord(sc->mega_done[pl.slab], mega_stream));
+    PT_HIP(hipStreamWaitEvent(pl.stream, sc->mega_done[pl.slab], 0));
+  }
+  if (e == hipSuccess && (p.sample_count > 1 || restart)) {   // the launch parked its samples (bind_slab)
+    if (ad) {
+      AdaptiveParams a = *ad;
+      a.samples = p.samples_out;
+      a.tile_heads = p.tile_heads;
+      e = launch_adaptive_resolve_list(a, pl.stream);
+    } else {
+      e = launch_resolve(p, pl.stream);
+    }
+    if (e == hipSuccess && !split) ctx->heads_clean[pl.slot] = true;
+    if (e == hipSuccess && pl.pipelined) {
+      // whoever writes this slab next (a megakernel on a lane) waits for this pass
+      PT_HIP(hipEventRecord(sc->resolved[pl.slab], pl.stream));
+      sc->resolved_valid[pl.slab] = true;
+    }
+  }
+  if (e == hipSuccess && !pl.capturing && ctx->overlap) {
+    if (!sc->last_done) PT_HIP(hipEventCreateWithFlags(&sc->last_done, hipEventDisableTiming));
+    PT_HIP(hipEventRecord(sc->last_done, pl.stream));
+  }
+  return e == hipSuccess ? PTAMD_OK : hip_fail("megakernel launch", e);
+}
+
+// One launch of at most kMaxFramesPerSlab frames, its kernel resolved (step 1)
+int launch_part(ptamd_context* ctx, const ptamd_launch* l, bool stats, bool later_chunk, const AdaptiveParams* ad, const LaunchPlan& resolved)
+{
+  LaunchPlan pl = resolved;
+  KParams p;
+  int rc;
+  if (persistent_family(pl.which)) {
+    do {   // (a second pass when the pipelining slabs could not be allocated: without pipelining, AUTO may mean another kernel)
+      pl = resolved;
+      fill_launch(ctx, l, stats, pl, p);
+      if ((rc = plan_stream(ctx, l, stats, later_chunk, ad, pl)) != PTAMD_OK) return rc;
+      lay_out_lds(ctx, ctx->scenes[l->scene_id], stats, ad, pl, p);
+      if ((rc = size_grid(ctx, l, ad, pl, p)) != PTAMD_OK || p.n_tiles == 0) return rc;
+      rc = bind_slab(ctx, l, pl, p);
+    } while (rc == kReplan);
+    if (rc != PTAMD_OK || (rc = take_slot(ctx, pl.capturing, pl.sc, pl.slot)) != PTAMD_OK) return rc;
+    return issue(ctx, stats, ad, pl, p);
+  }
+  fill_launch(ctx, l, stats, pl, p);
+  hipError_t e;
+  if (pl.which == PTAMD_KERNEL_BVH_BLOCKWISE) {
+    // persistent workgroups over 32 x (2 * waves) super-tiles; tickets 0..n_blocks-1 are static
     const uint32_t rows = l->row_end - l->row_begin;
-    const uint32_t st_rows = (PT_BW_THREADS / 64u) * 2u; // super-tile = 32 x (2 * waves) pixels
+    const uint32_t st_rows = (PT_BW_THREADS / 64u) * 2u;
     p.tiles_x = (l->width + 31u) / 32u;
     p.n_tiles = p.tiles_x * ((rows + st_rows - 1u) / st_rows);
     if (p.n_tiles == 0) return PTAMD_OK;
-    ptamd_context::Occupancy& occ = ctx->occupancy[1];
-    const size_t occ_key = resident ? lds : 0;
-    if (occ.blocks_per_cu < 0 || occ.lds != occ_key) {
-      int q = -1;
-      e = blockwise_blocks_per_cu(resident, lds, &q);
-      if (e != hipSuccess || q < 1) { occ.blocks_per_cu = -1; return hip_fail("occupancy query of the blockwise kernel", e); }
-      occ.blocks_per_cu = q; occ.lds = occ_key;
-    }
-    const int bpc = occ.blocks_per_cu;
-    uint32_t n_blocks = (uint32_t)ctx->n_cus * (uint32_t)bpc;
-    if (n_blocks > p.n_tiles) n_blocks = p.n_tiles;
-    p.tile_counter = ctx->d_tickets + (ctx->ticket_next++ % kTicketRing);
-    PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)n_blocks, 1, stream));
-    e = launch_megakernel_blockwise(p, resident, lds, stats, n_blocks, stream);
-  } else if (which == PTAMD_KERNEL_BVH_PERSISTENT || which == PTAMD_KERNEL_BVH_SPLIT || which == PTAMD_KERNEL_BVH_RESTART) {
-    const bool split = which == PTAMD_KERNEL_BVH_SPLIT;
-    const bool restart = which == PTAMD_KERNEL_BVH_RESTART;
-    const uint32_t count = l->frame_count > 1 ? l->frame_count : 1u;
-
-    uint32_t rows = l->row_end - l->row_begin;
-    if (l->interleave_ranks > 1u) {
-      if (!restart) { set_error("ptamd_raytrace: interleaved bands need the restart kernel behind PTAMD_KERNEL_AUTO"); return PTAMD_ERR_ARG; }
-      rows = ptamd_interleaved_rows(l->height, l->interleave_ranks, l->interleave_rank, l->interleave_rows);
-      p.ilv_ranks = l->interleave_ranks; p.ilv_rank = l->interleave_rank; p.ilv_rows = l->interleave_rows;
-      // the launch's buffers hold `rows` rows: parked samples and the resolve pass address them as the band [0, rows)
-      // with band-local buffers; only the restart kernel's tile -> frame-row map knows about the interleaving
-      p.row_begin = 0; p.row_end = rows;
-      p.tfb_row0 = l->height - rows;
-      p.surf_row0 = 0;
-    }
-    p.y_limit = l->row_end;
-    p.tiles_x = (l->width + PT_TILE_W - 1u) / PT_TILE_W;
-    p.n_tiles = p.tiles_x * ((rows + PT_TILE_H - 1u) / PT_TILE_H);
-    if (p.n_tiles == 0) return PTAMD_OK;
-    if ((uint64_t)p.n_tiles * count >= (1ull << 31)) {   // (tile, frame) tickets are 32-bit
-      set_error("ptamd_raytrace: rows x width x frame_count too large for one launch (split the batch)");
-      return PTAMD_ERR_LIMIT;
-    }
-    // restart kernel on a scene that does not fit in LDS: the four-wide walk.  Its per-lane stack needs at most
-    // 3 x (depth of the wide tree) entries of 8 bytes; as many as fit the workgroup's LDS share live in LDS
-    // ([entry][lane], 512 bytes per entry and wave), the rest in a global slab.
-    size_t launch_lds = lds;
-    if (restart && !resident) {
-      // the eight-wide quantised form instead of the four-wide one (knob; not for the instrumented / time-stamp / far-origin instantiations)
-      // the quantised node forms decode a plane as fma(plane, scale / d, fma(origin, 1 / d, -o / d)): with the 1e30 that stands in
-      // for 1 / 0 (axis-parallel rays) the inner fma stays finite for coordinates up to kQuantisedMaxExtent; beyond it the float
-      // nodes are walked, whose planes overflow one by one (an infinite slab distance is still a correct one)
-      const bool quantised_ok = s.extent <= kQuantisedMaxExtent;
-      // (tuning knobs, none of them for the list form of adaptive sampling: it is compiled for the four-wide float nodes)
-      const bool wide8 = ctx->wide8 && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.n_nodes8 != 0 && !ad;
-      if (wide8) { p.nodes4 = s.nodes8; p.n_nodes4 = s.n_nodes8; p.wide8 = 1u; }
-      const bool wide4q = !wide8 && ctx->wide4q && quantised_ok && !stats && !fma && !p.brute_walk && !ctx->d_timeline && s.nodes4q != nullptr && !ad;
-      if (wide4q) { p.nodes4 = s.nodes4q; p.wide8 = 2u; }
-      const uint32_t node_bytes = wide4q ? 64u : 128u;
-      const uint32_t need = (wide8 ? 7u * s.depth8 : 3u * s.depth4) + 1u;   // a visit stacks all hit children but the nearest
-      const uint32_t waves = restart_threads(false) / 64u;
-      const uint32_t share = 160u * 1024u / restart_wide_blocks_per_cu() - 256u;   // LDS bytes of one resident workgroup
-      // the top of the tree (breadth-first numbering: nodes 0..340 are its first five levels when full) goes to LDS too:
-      // 512 nodes = 64 KB of the one workgroup's 160 KB, then 7 stack entries per lane
-      // ... and the waves' pools of fresh paths (PT_POOL_LDS_BYTES each), behind the stacks
-      // (the list form keeps them in the global slab: it is compiled for that)
-      const uint32_t pools = (ctx->pool_in_lds && ctx->pool_in_lds_wide && !ad) ? waves * PT_POOL_LDS_BYTES : 0u;
-      // (the same LDS bytes hold twice as many 64-byte nodes)
-      // chunk-major treelet (pt_kernels.hip: PT_TREELET_SOA): a region of fixed size whatever the number of nodes staged
-      const uint32_t region = restart_treelet_region_bytes();
-      uint32_t treelet_want = ctx->treelet_nodes * (128u / node_bytes);
-      if (region && treelet_want > region / node_bytes) treelet_want = region / node_bytes;
-      uint32_t treelet = treelet_want < p.n_nodes4 ? treelet_want : p.n_nodes4;
-      if (!region && treelet * node_bytes + waves * 512u * 4u + pools > share) treelet = (share - pools - waves * 512u * 4u) / node_bytes;   // keep >= 4 stack entries
-      const uint32_t treelet_bytes = region ? (treelet ? region : 0u) : treelet * node_bytes;
-      uint32_t fit = (share - pools - treelet_bytes) / (waves * 512u);
-      if (const char* ev = tuning_env("PTAMD_STACK_LDS")) { int v = std::atoi(ev); if (v >= 1 && (uint32_t)v <= fit) fit = (uint32_t)v; }   // tuning knob
-      p.treelet_nodes = treelet;
-      p.stack_lds_entries = need < fit ? need : fit;
-      p.stack_spill_entries = need - p.stack_lds_entries;
-      launch_lds = (size_t)treelet_bytes + (size_t)p.stack_lds_entries * waves * 512u;
-      if (pools) {
-        p.pool_lds_offset = (uint32_t)launch_lds;
-        if (!p.pool_lds_offset) p.pool_lds_offset = 16u;
-        launch_lds = p.pool_lds_offset + pools;
-      }
-    }
-    if (restart && resident) {
-      // pools of fresh paths in LDS when two workgroups with their scene copies leave room for them (PT_POOL_LDS_BYTES
-      // per wave); else in a global slab (3 KiB per wave, L2-resident)
-      const uint32_t waves = restart_threads(true) / 64u;
-      const size_t with_pools = ((lds + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES;
-      const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
-      // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
-      // there whatever the knob, at one workgroup per CU when two do not fit
-      if (ad || (ctx->pool_in_lds && with_pools * blocks_wanted + 1024u <= 160u * 1024u)) {
-        p.pool_lds_offset = (uint32_t)((lds + 15u) & ~(size_t)15u);
-        if (p.pool_lds_offset == 0) p.pool_lds_offset = 16u;               // (an empty scene: keep the flag non-zero)
-        launch_lds = p.pool_lds_offset + (size_t)waves * PT_POOL_LDS_BYTES;
-      }
-    }
-    ptamd_context::Occupancy& occ = ctx->occupancy[split ? 2 : (restart ? (fma ? 4 : (ad ? 5 : 3)) : 0)];
-    const size_t occ_key = resident ? (restart ? launch_lds : lds) : (restart ? launch_lds + 1u : 0);
-    if (occ.blocks_per_cu < 0 || occ.lds != occ_key) {
-      int q = -1;
-      e = split ? split_blocks_per_cu(resident, lds, &q)
-                : (restart ? (fma ? ptamd_fma_restart_blocks_per_cu(resident ? 1 : 0, launch_lds, &q) : restart_blocks_per_cu(resident, launch_lds, &q, ad != nullptr)) : persistent_blocks_per_cu(resident, lds, &q));
-      if (e != hipSuccess || q < 1) { occ.blocks_per_cu = -1; return hip_fail("occupancy query of the persistent kernel", e); }
-      occ.blocks_per_cu = q; occ.lds = occ_key;
-    }
-    const int bpc = occ.blocks_per_cu;
-    // waves that take tile tickets: every wave of a persistent block, the shader waves of a split block
-    const uint32_t waves_per_block = split ? split_shader_waves() : (restart ? restart_threads(resident) / 64u : kPersistentThreads / 64u);
-    uint32_t n_blocks = (uint32_t)ctx->n_cus * (uint32_t)bpc;
-    p.sample_count = count;
-    p.frame_nb0 = l->frame_nb;
-    // Mid-path lane refill pays once paths are long enough for dead lanes to dominate the box loop
-    // (measured, batched 1080p: 4 bounces 4.65 vs 4.46 Gsamples/s without/with, 5: 3.90 vs 4.13,
-    // 6: 3.44 vs 3.92, 8: 2.89 vs 3.71); below that, whole-wave refill keeps primary rays coherent.
-    p.refill_min = ctx->refill_min ? ctx->refill_min : (l->bounces >= 5 ? 16u : 64u);
-    const uint32_t tiles_per_ticket = ad ? 1u : ctx->tiles_per_ticket;   // (the list form: one chunk of 64 entries per ticket)
-    const uint32_t share = overlap ? (l->machine_share > 2u ? l->machine_share : 2u) : l->machine_share;
-    if (share > 1u) n_blocks = n_blocks / share > 0u ? n_blocks / share : 1u;
-    const uint32_t n_tickets = (p.n_tiles * count + tiles_per_ticket - 1u) / tiles_per_ticket;
-    const uint32_t useful = (n_tickets + waves_per_block - 1u) / waves_per_block;
-    if (n_blocks > useful) n_blocks = useful;
-    // XCD-local regions (pt_kernels.hip: region_tile): the ticket -> tile map that keeps every XCD on a compact part of the frame.
-    // Needs whole groups of eight workgroups (one per XCD) and one tile per ticket.
-    if (restart && !ad && tiles_per_ticket == 1u && n_blocks >= 8u && (uint64_t)p.n_tiles * count < (1ull << 28) &&
-        (ctx->xcd_regions == 2u || (ctx->xcd_regions == 1u && !resident))) {
-      n_blocks &= ~7u;
-      p.xcd_regions = 1u;
-    }
-    // seeds of frames frame_nb+1.. are hashed on the device; the tonemap uses the last frame number
-    if (count > 1) p.frame_nb_f = (float)(int)(l->frame_nb + count - 1u);
-    p.frame_nb_inv = frame_nb_inverse(p.frame_nb_f);
-    // the restart kernel parks every sample (also of a single frame: pt_resolve_kernel accumulates and tonemaps) and
-    // keeps a 3 KiB pool of fresh paths per wave
-    const bool parks = count > 1 || restart;
-    uint32_t scratch_slab = 0;
-    if (parks) {
-      const size_t sample_bytes = ((size_t)count * rows * l->width * 3u * sizeof(float) + 255u) & ~(size_t)255u;
-      const size_t pool_bytes = (restart && !p.pool_lds_offset) ? (size_t)n_blocks * waves_per_block * 192u * sizeof(float4) : 0u;
-      const size_t spill_bytes = (size_t)n_blocks * waves_per_block * p.stack_spill_entries * 512u;
-      const size_t need = sample_bytes + pool_bytes + spill_bytes + 16u;
-      uint32_t& slab = scratch_slab;
-      slab = overlap ? sc->flip % 3u : 3u;
-      for (int i = 0; i < 3 && overlap; ++i) {
-        if (!sc->mega_done[i]) PT_HIP(hipEventCreateWithFlags(&sc->mega_done[i], hipEventDisableTiming));
-        if (!sc->resolved[i]) PT_HIP(hipEventCreateWithFlags(&sc->resolved[i], hipEventDisableTiming));
-      }
-      // Slab [3] belongs to launches that stay on the caller's stream; [0..2] exist only for streams whose launches the library
-      // has actually pipelined (a host that waits for every frame pays for ONE slab, not four).  Growing synchronises
-      // (the old buffer may be in use): it happens once per stream and configuration — for the pipelining slabs at the first launch
-      // that finds its predecessor still running, which costs that launch its overlap and no more.
-      auto grow = [&](uint32_t i) -> int {
-        PT_HIP(hipStreamSynchronize(stream));
-        for (uint32_t k = 0; k < ctx->n_lanes; ++k) PT_HIP(hipStreamSynchronize(ctx->lane[k]));
-        for (hipStream_t is : ctx->internal) if (is) PT_HIP(hipStreamSynchronize(is));
-        (void)hipFree(sc->buf[i]);
-        sc->buf[i] = nullptr; sc->bytes[i] = 0;
-        hipError_t me = hipMalloc(reinterpret_cast<void**>(&sc->buf[i]), need);
-        if (me != hipSuccess) { sc->buf[i] = nullptr; (void)hipGetLastError(); return PTAMD_ERR_HIP; }
-        sc->bytes[i] = need;
-        return PTAMD_OK;
-      };
-      if (overlap) {
-        bool ok = true;
-        for (uint32_t i = 0; i < 3u && ok; ++i) if (need > sc->bytes[i]) ok = grow(i) == PTAMD_OK;
-        if (!ok) {
-          // no room for the pipelining slabs: this stream renders unpipelined from now on (slab [3] on the caller's stream)
-          for (uint32_t i = 0; i < 3u; ++i) { (void)hipFree(sc->buf[i]); sc->buf[i] = nullptr; sc->bytes[i] = 0; }
-          sc->no_pipeline = true;
-          return do_launch(ctx, l_in, stats, later_chunk);
-        }
-      } else if (need > sc->bytes[3]) {
-        if (capturing) {
-          set_error("ptamd_raytrace: a launch cannot size its stream's sample slab inside a graph capture: issue this configuration once eagerly first");
-          return PTAMD_ERR_LIMIT;
-        }
-        if (sc->captured) {
-          set_error("ptamd_raytrace: a captured graph pins this stream's sample slab; a larger launch would reallocate it under the graph "
-                    "(ptamd_release_captured(ctx, stream) once the graph is gone)");
-          return PTAMD_ERR_LIMIT;
-        }
-        if (grow(3u) != PTAMD_OK) return hip_fail("hipMalloc of the sample slab", hipErrorOutOfMemory);
-      }
-      p.samples_out = sc->buf[slab];
-      p.pool = reinterpret_cast<float4*>(reinterpret_cast<char*>(sc->buf[slab]) + sample_bytes);
-      p.stack_spill = reinterpret_cast<uint2*>(reinterpret_cast<char*>(sc->buf[slab]) + sample_bytes + pool_bytes);
-    }
-    p.round_min = ctx->round_min;
-    p.round_div = ctx->round_div;
-    p.round_div_m16 = (65536u + ctx->round_div - 1u) / ctx->round_div;
-    p.walk_min = ctx->walk_min;
-    p.walk_min4 = ctx->walk_min4;
-    p.tiles_per_ticket = tiles_per_ticket;
-    // tickets 0..n_waves-1 are taken statically by the waves; the shared counter hands out the rest
-    uint32_t slot = ctx->ticket_next++ % kTicketRing;
-    for (uint32_t tries = 0; ctx->slot_pinned[slot]; ++tries) {   // slots baked into captured graphs are not handed out again
-      if (tries >= kTicketRing) { set_error("ptamd_raytrace: every ring slot of ticket heads is pinned by captured graphs (ptamd_release_captured)"); return PTAMD_ERR_LIMIT; }
-      slot = ctx->ticket_next++ % kTicketRing;
-    }
-    if (capturing && sc) { ctx->slot_pinned[slot] = true; sc->pinned_slots.push_back(slot); sc->captured = true; }
-    p.tile_counter = ctx->d_tickets + slot;
-    if (ad) p.adaptive = ad->block;   // (the restart kernel takes no ticket counter: the field names the list form's state instead)
-    p.n_static = n_blocks * waves_per_block;
-    if (split) PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)p.n_static, 1, stream));
-    hipStream_t mega_stream = stream;
-    if (overlap) {
-      // the megakernel touches nothing of the caller's: it may start before earlier work on the caller's stream has finished,
-      // as soon as the slab's previous reader (the resolve pass three launches back) is done.  Lanes are taken in turn by every
-      // launch of the context, whichever stream it comes from: consecutive launches do not queue behind each other.  (Null-stream
-      // callers: the two internal streams, ptamd_context::lane)
-      mega_stream = stream != nullptr ? ctx->lane[ctx->lane_next++ % ctx->n_lanes] : ctx->internal[ctx->lane_next++ & 1u];
-      sc->flip++;
-      if (sc->resolved_valid[scratch_slab]) PT_HIP(hipStreamWaitEvent(mega_stream, sc->resolved[scratch_slab], 0));
-    }
-    if (!split) {
-      p.tile_heads = ctx->d_heads + (size_t)slot * 8u * PT_HEAD_STRIDE;
-      // the whole ring is zeroed at creation and a launch that parks its samples has its resolve pass zero its heads
-      // again (pt_resolve_kernel); only slots whose last user did not get that far are cleared here
-      if (!ctx->heads_clean[slot]) PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_heads), 0, 8u * PT_HEAD_STRIDE, mega_stream));
-      ctx->heads_clean[slot] = false;
-    }
-    if (restart && !fma && ctx->d_timeline && n_blocks * waves_per_block <= ctx->timeline_waves) p.timeline = ctx->d_timeline;
-    if (split) { p.tiles_per_ticket = 1; e = launch_megakernel_split(p, resident, lds, stats, n_blocks, stream); }
-    else if (restart) e = fma ? ptamd_fma_launch_restart(&p, resident ? 1 : 0, launch_lds, n_blocks, mega_stream) : launch_megakernel_restart(p, resident, launch_lds, stats, n_blocks, mega_stream, ad != nullptr);
-    else e = launch_megakernel_persistent(p, resident, lds, stats, n_blocks, stream);
-    if (e == hipSuccess && overlap) {
-      PT_HIP(hipEventRecord(sc->mega_done[scratch_slab], mega_stream));
-      PT_HIP(hipStreamWaitEvent(stream, sc->mega_done[scratch_slab], 0));
-    }
-    if (e == hipSuccess && parks) {
-      if (ad) {
-        AdaptiveParams a = *ad;
-        a.samples = p.samples_out;
-        a.tile_heads = p.tile_heads;
-        e = launch_adaptive_resolve_list(a, stream);
-      } else {
-        e = launch_resolve(p, stream);
-      }
-      if (e == hipSuccess && !split) ctx->heads_clean[slot] = true;
-      if (e == hipSuccess && overlap) {
-        // whoever writes this slab next (a megakernel on a lane) waits for this pass
-        PT_HIP(hipEventRecord(sc->resolved[scratch_slab], stream));
-        sc->resolved_valid[scratch_slab] = true;
-      }
-    }
-    if (e == hipSuccess && !capturing && ctx->overlap && sc) {
-      if (!sc->last_done) PT_HIP(hipEventCreateWithFlags(&sc->last_done, hipEventDisableTiming));
-      PT_HIP(hipEventRecord(sc->last_done, stream));
-    }
+    int bpc = 0;
+    if ((rc = blocks_per_cu(ctx, pl, false, bpc)) != PTAMD_OK || (rc = take_slot(ctx, false, nullptr, pl.slot)) != PTAMD_OK) return rc;
+    const uint32_t n_blocks = std::min((uint32_t)ctx->n_cus * (uint32_t)bpc, p.n_tiles);
+    p.tile_counter = ctx->d_tickets + pl.slot;
+    PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)n_blocks, 1, pl.stream));
+    e = launch_megakernel_blockwise(p, pl.resident, pl.lds, stats, n_blocks, pl.stream);
   } else {
-    e = launch_megakernel(p, kind, resident, lds, stats, stream);
+    e = launch_megakernel(p, pl.which == PTAMD_KERNEL_BRUTE_FORCE ? 1 : 2, pl.resident, pl.lds, stats, pl.stream);
   }
-  if (e != hipSuccess) return hip_fail("megakernel launch", e);
+  return e == hipSuccess ? PTAMD_OK : hip_fail("megakernel launch", e);
+}
+
+// ptamd_raytrace, _ex, _stats and each round of ptamd_render_adaptive (ad: its trace step, the list form over the state's active list).
+// frame_count = N is by contract N consecutive launches: far-origin batches of the non-restart kernels go one frame at a time, and
+// parts of kMaxFramesPerSlab frames bound the sample slab (0.4 GB at 4K instead of 1.6 GB at 16 spp, and four slabs per stream).
+int do_launch(ptamd_context* ctx, const ptamd_launch* l, bool stats, const AdaptiveParams* ad = nullptr)
+{
+  int rc = validate_launch(ctx, l);
+  LaunchPlan resolved;
+  if (rc != PTAMD_OK || (rc = resolve_kernel(ctx, l, stats, ad, resolved)) != PTAMD_OK) return rc;
+  PT_HIP(hipSetDevice(ctx->device));
+  const uint32_t part_frames = persistent_family(resolved.which) ? kMaxFramesPerSlab : 1u;
+  for (uint32_t k0 = 0; k0 == 0 || k0 < l->frame_count; k0 += part_frames) {
+    ptamd_launch part = *l;
+    part.frame_nb = l->frame_nb + k0;
+    part.frame_count = std::min(l->frame_count - k0, part_frames);
+    if (k0 > 0) part.reset_accumulation = 0;
+    if ((rc = launch_part(ctx, &part, stats, k0 > 0, ad, resolved)) != PTAMD_OK) return rc;
+  }
   return PTAMD_OK;
 }
 
@@ -827,12 +880,7 @@ int denoise_params(const char* who, const ptamd_denoise_desc* d, DenoiseParams& 
 int feature_scene(const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, const ptamd_camera& cam, KParams& p)
 {
   const DeviceScene& s = ctx->scenes[scene_id];
-  const DeviceCubemap& cm = ctx->cubemaps[cubemap_id];
-  p.nodes = s.nodes; p.tris_bvh = s.tris_bvh; p.tris_brute = s.tris_brute; p.shade = s.shade;
-  p.materials = s.materials; p.lights = s.lights; p.textures = s.textures; p.texels = s.texels;
-  p.cubemap = cm.faces; p.cubemap_size = cm.size;
-  p.env_uniform = cm.uniform ? 1u : 0u; p.env_r = cm.color[0]; p.env_g = cm.color[1]; p.env_b = cm.color[2];
-  p.n_faces = s.n_faces; p.n_lights = s.n_lights; p.n_nodes = s.n_nodes; p.n_bvh_tris = s.n_bvh_tris;
+  fill_scene(s, &ctx->cubemaps[cubemap_id], p);
   // the same rule as do_launch: an origin beyond what the boxes' margins cover tests every face
   return far_origin_camera(s, cam) ? 1 : 2;
 }
@@ -1358,14 +1406,10 @@ int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel, con
   const DeviceScene& s = ctx->scenes[scene_id];
   KParams p;
   std::memset(&p, 0, sizeof p);
-  p.nodes = s.nodes; p.tris_bvh = s.tris_bvh; p.tris_brute = s.tris_brute; p.lights = s.lights;
-  p.n_faces = s.n_faces; p.n_lights = s.n_lights; p.n_nodes = s.n_nodes; p.n_bvh_tris = s.n_bvh_tris;
-  p.nodes4 = s.nodes4; p.n_nodes4 = s.n_nodes4;
+  fill_scene(s, nullptr, p);
   fill_far_table(p.far_table);
   p.small_det = 0u;                           // caller-supplied directions need not be unit vectors
-  p.stack_lds_entries = 3u * s.depth4 + 1u;   // PTAMD_KERNEL_BVH_RESTART: the wide walk, whole stack in LDS
-  if (ctx->wide8 && s.extent <= kQuantisedMaxExtent && s.n_nodes8 != 0) { p.nodes4 = s.nodes8; p.n_nodes4 = s.n_nodes8; p.wide8 = 1u; p.stack_lds_entries = 7u * s.depth8 + 1u; }
-  else if (ctx->wide4q && s.extent <= kQuantisedMaxExtent && s.nodes4q != nullptr) { p.nodes4 = s.nodes4q; p.wide8 = 2u; }
+  p.stack_lds_entries = choose_wide_nodes(ctx, s, true, p);   // PTAMD_KERNEL_BVH_RESTART: the wide walk, whole stack in LDS
   float* d_rays = nullptr;
   int4* d_out = nullptr;
   PT_HIP(hipMalloc(reinterpret_cast<void**>(&d_rays), (size_t)n * 24));
@@ -1981,7 +2025,7 @@ int ptamd_render_adaptive(ptamd_context* ctx, const ptamd_adaptive_desc* d)
   for (uint32_t r = 0; r < d->rounds; ++r) {
     a.round = r;
     PT_HIP(launch_adaptive_select(a, static_cast<hipStream_t>(d->stream)));
-    rc = do_launch(ctx, &l, false, false, &a);
+    rc = do_launch(ctx, &l, false, &a);
     if (rc != PTAMD_OK) return rc;
   }
   return PTAMD_OK;
