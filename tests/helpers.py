@@ -73,3 +73,90 @@ def random_rays(rng, n, extent=3.0):
 
 def synthetic_cubemap(rng, size):
     return rng.uniform(0.0, 1.0, size=(6, size, size, 4)).astype(np.float32)
+
+
+def wide_scene(P, rng, n=None, n_lights=None):
+    """A seeded scene too large for the LDS-resident kernel forms (nodes * 64 + triangles * 48 > 64 KiB) that reaches every
+    shading branch: 1 500 - 5 000 triangles in clustered and spread soups, 4 - 8 materials over ragged RGBA textures (1 x N,
+    N x 1, odd sizes, one of at least 64 x 48) with and without normal maps, a refractive ior and ior 1.0, uvs outside [0, 1],
+    per-vertex normals that differ from the face normal, a few degenerate faces and faces with NaN tangents, 1 - 5 light
+    spheres (the first inside the mesh bounds, one sometimes in front of the camera) and a random lens."""
+    n = int(rng.integers(1500, 5001)) if n is None else n
+    n_clustered = int(n * rng.uniform(0.3, 0.7))
+    centres = rng.uniform(-2.0, 2.0, size=(int(rng.integers(2, 7)), 3))
+    at = centres[rng.integers(0, len(centres), n_clustered)][:, None, :]
+    clustered = at + rng.normal(scale=0.35, size=(n_clustered, 1, 3)) + rng.normal(scale=0.06, size=(n_clustered, 3, 3))
+    spread = random_soup(rng, n - n_clustered, extent=float(rng.uniform(2.0, 3.0)), size=float(rng.uniform(0.05, 0.15)))
+    tris = np.concatenate([clustered.astype(np.float32), spread])[rng.permutation(n)]
+    deg = rng.choice(n, size=6, replace=False)
+    tris[deg[:3], 2] = tris[deg[:3], 0]                                              # two corners in one place
+    tris[deg[3:], 2] = tris[deg[3:], 0] + np.float32(2.0) * (tris[deg[3:], 1] - tris[deg[3:], 0])   # three on a line
+    with np.errstate(all="ignore"):
+        fn = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0])
+        fn = fn / np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-30)
+    vn = fn[:, None, :] + rng.normal(scale=0.4, size=(n, 3, 3))
+    vn = (vn / np.linalg.norm(vn, axis=2, keepdims=True)).astype(np.float32)
+    flat = rng.random(n) < 0.3
+    vn[flat] = np.repeat(fn[flat, None, :], 3, axis=1)                               # some faces keep flat normals
+    uvs = rng.uniform(-1.5, 2.5, size=(n, 3, 2)).astype(np.float32)
+    big = (int(rng.integers(64, 97)), int(rng.integers(48, 72)))                     # (w, h)
+    textures = [rng.uniform(0.05, 0.95, size=(big[1], big[0], 4)),                  # 0: >= 64 x 48 RGBA
+                rng.uniform(0.05, 0.95, size=(1, int(rng.integers(2, 12)), 4)),     # 1: 1 x N
+                rng.uniform(0.05, 0.95, size=(int(rng.integers(2, 12)), 1, 4)),     # 2: N x 1
+                rng.uniform(0.05, 0.95, size=(int(rng.choice([3, 5, 7, 9])), int(rng.choice([3, 5, 7, 11])), 4)),   # 3: odd
+                rng.uniform(0.0, 1.0, size=(int(rng.integers(2, 17)), int(rng.integers(2, 17)), 3)),   # 4: normal map
+                rng.uniform(0.0, 1.0, size=(int(rng.integers(1, 6)), int(rng.integers(1, 6)), 3)),     # 5: normal map
+                np.array([[[0.9, 0.8, 0.7, float(rng.uniform(0, 1))]]])]            # 6: one colour
+    textures = [t.astype(np.float32) for t in textures]
+    materials = [(0, 4, 1.0), (1, 5, 1.0), (2, -1, 1.0), (3, -1, float(rng.uniform(1.1, 1.8)))]
+    extra = [(6, -1, 1.0), (3, 4, 1.0), (0, -1, float(rng.uniform(1.1, 1.8))), (6, 5, 1.0)]
+    materials += extra[:int(rng.integers(0, 5))]
+    mids = rng.integers(0, len(materials), size=n)
+    nan_tan = rng.choice(np.flatnonzero(mids == 0), size=min(8, int((mids == 0).sum())), replace=False)
+    uvs[nan_tan] = uvs[nan_tan, :1]                                                  # one uv on all corners: NaN tangent
+    lo, hi = tris.reshape(-1, 3).min(axis=0), tris.reshape(-1, 3).max(axis=0)
+    lights = [(tuple(rng.uniform(lo * 0.5, hi * 0.5)), tuple(rng.uniform(0.2, 1, 3)), float(rng.uniform(1, 6)),
+               float(rng.uniform(0.1, 0.5)))]
+    n_lights = int(rng.integers(1, 6)) if n_lights is None else n_lights
+    for k in range(1, n_lights):
+        if k == 1 and rng.random() < 0.6:   # in front of the camera: primary rays see a light sphere
+            pos = (float(rng.uniform(-0.6, 0.6)), float(rng.uniform(-0.4, 0.6)), float(rng.uniform(2.4, 3.0)))
+            lights.append((pos, tuple(rng.uniform(0.2, 1, 3)), float(rng.uniform(1, 6)), float(rng.uniform(0.15, 0.35))))
+        else:
+            lights.append((tuple(rng.uniform(-3, 3, 3)), tuple(rng.uniform(0.2, 1, 3)), float(rng.uniform(1, 6)),
+                           float(rng.uniform(0.1, 0.8))))
+    hs = make_scene(P, tris, normals=vn, uvs=uvs, material_ids=mids, materials=materials, textures=textures, lights=lights)
+    hs.camera["aperture"] = np.float32(rng.uniform(0.0, 0.2))
+    hs.camera["focus_dist"] = np.float32(rng.uniform(0.5, 4.0))
+    return hs, synthetic_cubemap(rng, int(rng.choice([1, 2, 4, 8])))
+
+
+WIDE_SEEDS = tuple(range(2000, 2010))
+TESSELLATED = (("crate_land", 4), ("color_sample", 5), ("indoor", 2))
+
+
+def tessellated_scene(P, name, n):
+    """A shipped scene with its materials, every face split into n * n coplanar sub-faces (exact (t, face) ties on the
+    shared edges): crate_land (1024^2 RGBA and normal maps, the bilinear 1024^2 cubemap), color_sample (the refraction
+    material), indoor with the textures its MTL names."""
+    import os
+    from cuda_pathtracer_amd.synthetic import tessellate
+    assets = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
+    hs = P.HostScene.load(os.path.join(assets, name + ".scene"), **({"normalise_backslashes": True} if name == "indoor" else {}))
+    assert hs.unloaded_textures == [], (name, hs.unloaded_textures)
+    cube = P.cubemap_for_scene(hs, asset_folder=assets)
+    return tessellate(hs, n), cube
+
+
+def wide_case(P, key):
+    """(HostScene, cubemap) of a WIDE_SEEDS seed or a TESSELLATED name."""
+    if isinstance(key, str):
+        return tessellated_scene(P, key, dict(TESSELLATED)[key])
+    return wide_scene(P, np.random.default_rng(key))
+
+
+def oracle_threads():
+    """The oracle's worker count from the environment (OMP_NUM_THREADS, else this process's CPU affinity)."""
+    import os
+    n = os.environ.get("OMP_NUM_THREADS", "")
+    return int(n) if n.isdigit() and int(n) > 0 else len(os.sched_getaffinity(0))
