@@ -350,7 +350,8 @@ struct KParams {
   const float4* nodes;      // 4 float4 per BVH node
   const float4* tris_bvh;   // 3 float4 per triangle, leaf-major
   const float4* tris_brute; // 3 float4 per triangle, storage order
-  const float4* shade;      // 7 float4 per face, storage order: n0 n1 n2 | uv0 uv1 uv2 | tangent | material id, ior | diffuse map desc | normal map desc
+  const float4* shade;      // 7 float4 per face, storage order: n0 n1 n2 | uv0 uv1 uv2 | tangent | material id, ior | diffuse map desc | normal map desc;
+                            // a flat scene's compact records follow (4 float4 per face: {n0, diffuse.r} {n1, diffuse.g} {n2, diffuse.b} {specular, 0, 0, 0})
   const int4* materials;    // {diffuse_spec_map, normal_map, bits(ior), 0}
   const float4* lights;     // 2 float4 per light: {color.xyz, vec.x} {vec.y, vec.z, emission, radius^2}
   const TexDesc* textures;
@@ -425,8 +426,13 @@ struct KParams {
   uint32_t xcd_regions;           // restart kernel: != 0: tickets map to tiles through XCD-local regions (pt_kernels.hip: region_tile); needs n_static % 8 == 0 and tiles_per_ticket == 1
   uint32_t brute_walk;            // restart kernel: the launch wants the instantiation that tests every triangle record instead of walking the tree (far origin)
   unsigned long long* timeline;   // restart kernel: != nullptr selects the instantiation that records 4 time stamps per wave (ptamd_set_timeline)
-  uint32_t generic_round;         // restart kernel: != 0 sends a resident scene's launch to the generic instantiation even when the shipped one serves it (PTAMD_RS_GENERIC)
+  // restart kernel, read by the host only (restart_select): where a resident scene's launch goes that the shipped instantiation
+  // serves.  PT_ROUND_GENERIC: to the generic one (PTAMD_RS_GENERIC); PT_ROUND_FLAT: to the flat one (a flat scene under a one-colour
+  // environment, ptamd_api.cpp: scene_is_flat)
+  uint32_t round_form;
 };
+#define PT_ROUND_GENERIC 1u
+#define PT_ROUND_FLAT 2u
 // LDS bytes of one wave's pool of fresh paths (restart kernel: 64 entries x 9 dwords)
 #define PT_POOL_LDS_BYTES 2304u
 

@@ -609,11 +609,42 @@ PT_DEV Nearest trace_nearest(const KParams& p, const float4* s_nodes, const floa
 // Second half of intersection.cuh:161-246 for the winner only: the deferred interpolation of
 // intersectTriangle (:124-131), the light normal (:204-210), texture and normal-map fetches
 // (:216-243).  Returns intersection.dist < MAX_DIST.
-template <bool STATS>
+// FLAT: the scene is flat (ptamd_api.cpp: scene_is_flat): the face's record is the compact one behind the general records
+// (KParams::shade), whose texel is the only one its 1x1 map has, and no material has a normal map or an ior other than 1
+template <bool STATS, bool FLAT = false>
 PT_DEV bool resolve_hit(const KParams& p, f3 d, Nearest n, Hit& hit, Counters& cnt)
 {
   hit.dist = n.t;
   if (n.idx == PT_END) return false; // n.t == MAX_DIST
+  if constexpr (FLAT) {
+    // both cases in registers, each field of `hit` stored once behind them (stores of different fields sunk into one store
+    // through a selected address keep the whole struct in scratch)
+    f3 normal, col;
+    float spec = hit.specular_col, emission = hit.emission, ior = hit.ior;
+    int light = -1;
+    if (n.idx & PT_LIGHT) {
+      const uint32_t l = n.idx & ~PT_LIGHT;
+      const float4 la = p.lights[l * 2 + 0], lb = p.lights[l * 2 + 1];
+      light = (int)l;
+      emission = lb.z;
+      col = mk3(la.x, la.y, la.z);
+      normal = normalize_hot(mk3(la.w, lb.x, lb.y) - (n.t * d)); // intersection.cuh:208: origin ignored
+    } else {
+      // three 16-byte loads and one 4-byte one: 13 registers instead of the general record's 24
+      const float4* sh = p.shade + (size_t)PT_KARG(p, n_faces) * 7 + (size_t)n.idx * 4;
+      const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
+      spec = reinterpret_cast<const float*>(sh + 3)[0];
+      const f3 n0 = mk3(s0.x, s0.y, s0.z), n1 = mk3(s1.x, s1.y, s1.z), n2 = mk3(s2.x, s2.y, s2.z);
+      const float u = n.u, v = n.v;
+      const float w = 1.0f - u - v;
+      normal = w * n0 + u * n1 + v * n2;
+      col = mk3(s0.w, s1.w, s2.w);
+      ior = 1.0f;
+      if (STATS) cnt.mesh_hits++;
+    }
+    hit.normal = normal; hit.diffuse_col = col; hit.specular_col = spec; hit.emission = emission; hit.ior = ior; hit.light = light;
+    return hit.dist < PT_MAX_DIST;
+  }
   if (n.idx & PT_LIGHT) {
     const uint32_t l = n.idx & ~PT_LIGHT;
     const float4 la = p.lights[l * 2 + 0], lb = p.lights[l * 2 + 1];
@@ -676,10 +707,12 @@ PT_DEV bool resolve_hit(const KParams& p, f3 d, Nearest n, Hit& hit, Counters& c
 }
 
 // texCubemap restated (see oracle/pt_oracle.c: or_tex_cubemap for the definition)
+// UNIFORM: the instantiation only ever runs launches whose environment is one colour (PT_RS_FLAT)
+template <bool UNIFORM = false>
 PT_DEV f3 env_lookup(const KParams& p, f3 dir)
 {
   // one-colour environment (flag set by the host, ptamd_upload_cubemap): the face choice below cannot matter
-  if (PT_KARG(p, env_uniform)) return mk3(PT_KARG(p, env_r), PT_KARG(p, env_g), PT_KARG(p, env_b));
+  if (UNIFORM || PT_KARG(p, env_uniform)) return mk3(PT_KARG(p, env_r), PT_KARG(p, env_g), PT_KARG(p, env_b));
   float x = dir.x, y = dir.y, z = -dir.z; // raytrace.cu:60,197
   // (the compiler otherwise computes |dir| where the walk is set up, for both uses, and spills it across the walk)
   asm volatile("" : "+v"(x), "+v"(y), "+v"(z));
@@ -799,7 +832,8 @@ PT_DEV float path_pre(const KParams& p, Path& st)
 }
 
 // Returns true when the path is complete (st.acc is final).
-template <bool STATS, bool STATIC = false>
+// FLAT: a flat scene under a uniform environment (PT_RS_FLAT): the compact record, no lookup, no refraction branch
+template <bool STATS, bool STATIC = false, bool FLAT = false>
 PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Counters& cnt)
 {
   Hit inter;
@@ -807,7 +841,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
   inter.dist = 0.f; inter.specular_col = st.specular_col; inter.ior = 0.f; inter.light = -1; inter.emission = 0.f;
   long long ts0 = 0;
   if (STATS) ts0 = clock64();
-  const bool found = resolve_hit<STATS>(p, st.d, nearest, inter, cnt);
+  const bool found = resolve_hit<STATS, FLAT>(p, st.d, nearest, inter, cnt);
   if (STATS) {   // [8]: the shading record (and texels) of the hit: fetch and decode
     asm volatile("" : "+v"(inter.normal.x), "+v"(inter.diffuse_col.x), "+v"(inter.specular_col));
     const long long ts1 = clock64();
@@ -815,7 +849,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
   }
 
   if (!STATIC && !p.is_static) {
-    st.acc = found ? inter.diffuse_col : env_lookup(p, st.d);
+    st.acc = found ? inter.diffuse_col : env_lookup<FLAT>(p, st.d);
     return true;
   }
 
@@ -825,7 +859,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
     // The reference keeps looping with the unchanged ray (raytrace.cu:194-199): every remaining
     // iteration misses again and adds the same environment sample.  Run them here, without
     // the walk, drawing r1 exactly as the loop does.
-    const f3 env = env_lookup(p, st.d);
+    const f3 env = env_lookup<FLAT>(p, st.d);
     for (;;) {
       st.acc = st.acc + env * st.throughput;
       const float pmax = __builtin_fmaxf(st.throughput.x, __builtin_fmaxf(st.throughput.y, st.throughput.z));
@@ -845,7 +879,7 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
   f3 oriented_normal = inter.normal;
   const f3 spec = normalize_hot(reflect(d, inter.normal));
   const f3 direct_light = inter.diffuse_col / 0.5f; // brdf_lambert / pdf_lambert (brdf.cuh:14-31)
-  if (inter.ior == 1.0f || inter.light >= 0) {
+  if (FLAT || inter.ior == 1.0f || inter.light >= 0) {
     if (inter.light >= 0) {
       // raytrace.cu:86: (light colour * emission) * throughput; resolve_hit has both in registers (no second fetch of the record)
       st.acc = st.acc + (inter.diffuse_col * inter.emission) * st.throughput;
@@ -1984,6 +2018,7 @@ PT_DEV bool region_tile(const KParams& p, uint32_t ticket, uint32_t& col, uint32
 #define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
 #define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
 #define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
+#define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
 
 template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
@@ -1994,7 +2029,10 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // The shipped instantiation (LDS-resident scene, PT_RS_PLAIN) serves only the common launch, which fixes four launch constants:
   // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
   // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
-  constexpr bool LEAN = LDS_RESIDENT && VARIANT == PT_RS_PLAIN;
+  // PT_RS_FLAT is the same launch of a flat scene under a uniform environment (ptamd_api.cpp: scene_is_flat): the shading half
+  // reads the compact record and has no texel fetch, normal map, cubemap lookup or refraction branch
+  constexpr bool FLAT = LDS_RESIDENT && VARIANT == PT_RS_FLAT;
+  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || FLAT);
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
   // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
   // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
@@ -2229,7 +2267,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         walking = false;
         long long tl1 = 0;
         if (STATS) { asm volatile("" : "+v"(n.t), "+v"(n.idx)); tl1 = clock64(); if (PT_WAVE_ONE()) cnt.cyc[3] += (unsigned long long)(tl1 - tl0); }   // [3]: r1 + light loop
-        if (path_post<STATS, FIXED>(p, st, r1, n, cnt)) {
+        if (path_post<STATS, FIXED, FLAT>(p, st, r1, n, cnt)) {
           path_finish_sample(p, st);
           idle = true;
           if (STATS) samples++;
@@ -2993,21 +3031,24 @@ static const void* restart_entry_unused(int variant)
     case PT_RS_WIDE4Q: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE4Q>);
     case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);   // (only ever a resident scene)
     case PT_RS_LIST: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_LIST>);
+    case PT_RS_FLAT: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_FLAT>);   // (only ever a resident scene)
     default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
   }
 }
 
 // variant: instrumented build when counters are wanted, else the far-origin form, else the time-stamp form, else the shipped kernel —
-// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form.
+// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form;
+// in the shipped kernel's place its flat form when the scene is flat and the environment uniform (KParams::round_form).
 // list: the list form of adaptive sampling (its own instantiations, resident scene or four-wide walk; not in the contracted build).
 static const void* restart_select(bool lds_resident, bool stats, const KParams* p = nullptr, bool list = false)
 {
 #ifndef PT_FMA_BUILD
   if (list) return lds_resident ? restart_entry<true>(PT_RS_LIST) : restart_entry<false>(PT_RS_LIST);
 #endif
-  const bool lean = !p || (p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !p->generic_round);
+  const bool lean = !p || (p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC));
+  const bool flat = lean && p && (p->round_form & PT_ROUND_FLAT);   // (the contracted build has no flat form: its restart_entry serves PT_RS_PLAIN)
   const int variant = stats ? PT_RS_STATS : (p && p->brute_walk ? PT_RS_BRUTE : (p && p->timeline ? PT_RS_STAMPS : (p && p->wide8 && !lds_resident ? (p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8) :
-                      (lds_resident && !lean ? PT_RS_GENERIC : PT_RS_PLAIN))));
+                      (lds_resident && !lean ? PT_RS_GENERIC : (lds_resident && flat ? PT_RS_FLAT : PT_RS_PLAIN)))));
   return lds_resident ? restart_entry<true>(variant) : restart_entry<false>(variant);
 }
 
@@ -3160,7 +3201,7 @@ hipError_t resolve_kernels()
     split_select(true, false), split_select(false, false), blockwise_select(true, false), blockwise_select(false, false),
     restart_entry<true>(PT_RS_PLAIN), restart_entry<false>(PT_RS_PLAIN), restart_entry<true>(PT_RS_STATS), restart_entry<false>(PT_RS_STATS),
     restart_entry<true>(PT_RS_STAMPS), restart_entry<false>(PT_RS_STAMPS), restart_entry<true>(PT_RS_BRUTE), restart_entry<false>(PT_RS_BRUTE), restart_entry<false>(PT_RS_WIDE8), restart_entry<false>(PT_RS_WIDE4Q), restart_entry<true>(PT_RS_GENERIC),
-    restart_entry<true>(PT_RS_LIST), restart_entry<false>(PT_RS_LIST),
+    restart_entry<true>(PT_RS_LIST), restart_entry<false>(PT_RS_LIST), restart_entry<true>(PT_RS_FLAT),
     reinterpret_cast<const void*>(pt_megakernel<1, true, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<1, false, false, PT_TILE_THREADS>),
     reinterpret_cast<const void*>(pt_megakernel<2, true, false, PT_TILE_THREADS>),

@@ -45,6 +45,7 @@ struct DeviceScene {
   float4* tris_bvh = nullptr;
   float4* tris_brute = nullptr;
   float4* shade = nullptr;
+  bool flat = false;          // scene_is_flat: `shade` holds the compact records behind the general ones
   int4* materials = nullptr;
   float4* lights = nullptr;
   TexDesc* textures = nullptr;
@@ -132,6 +133,7 @@ struct ptamd_context {
   bool overlap = true;                    // PTAMD_OVERLAP=0 (tuning): everything on the caller's stream
   bool wide4q = false;                    // PTAMD_WIDE4Q=1 (tuning): big scenes walk the 64-byte quantised four-wide nodes instead of the float ones (ahead by 2.8 % while the walk's LDS accesses went out as FLAT instructions, level since they are LDS instructions: profiles/r03_notes.md)
   bool generic_round = false;             // PTAMD_RS_GENERIC=1 (tuning): resident scenes take the restart kernel's generic instantiation (launch constants read at run time), for A/B and tests
+  bool flat_round = true;                 // PTAMD_RS_FLAT=0 (tuning): flat scenes take PT_RS_PLAIN instead of the restart kernel's flat instantiation, for A/B and tests
   bool wide8 = false;                     // PTAMD_WIDE8=1 (tuning): big scenes walk the eight-wide quantised nodes (measured 8 % slower: DESIGN.md §4)
   uint2* d_trace_spill = nullptr;             // ptamd_trace_rays_queue: global continuation of the walk-only kernel's stacks (grown on demand)
   struct { uint32_t config = ~0u; size_t lds = 0; int resident = 0; } trace_queue_cache;   // ... its last configuration: dynamic-LDS attribute set, blocks resident per CU
@@ -363,6 +365,22 @@ bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam)
   return !(margins_cover(s.extent, s.margin_floor, cam_far) && margins_cover(s.extent, s.margin_floor, s.reach)) && s.n_faces != 0;   // also true for NaN
 }
 
+// A flat scene: every face's diffuse+specular map is 1x1 (its record carries the one texel), no material a face uses has a
+// normal map, and each such material's ior is bitwise 1.0f (path_post tests ior == 1.0f: a NaN ior is not flat).  Launches of
+// it under a one-colour environment take the restart kernel's flat form (PT_RS_FLAT), which reads the compact records only.
+// The descriptor's ids are in range (the caller checked them).
+bool scene_is_flat(const ptamd_scene_desc* sc)
+{
+  for (uint32_t i = 0; i < sc->n_faces; ++i) {
+    const ptamd_material& m = sc->materials[sc->faces[i].material_id];
+    const ptamd_texture_desc& dt = sc->textures[m.diffuse_spec_map];
+    uint32_t ior;
+    std::memcpy(&ior, &m.ior, 4);
+    if (dt.w != 1 || dt.h != 1 || m.normal_map >= 0 || ior != 0x3F800000u) return false;
+  }
+  return true;
+}
+
 // Tables, counts and environment of a scene in KParams.  cm: null for the ray queries (ptamd_trace_rays), which never leave the scene
 void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p)
 {
@@ -470,7 +488,8 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   p.stats = stats ? ctx->d_stats : nullptr;
   p.error_flag = ctx->d_stats + 15;
   p.brute_walk = pl.brute_walk ? 1u : 0u;
-  p.generic_round = ctx->generic_round ? 1u : 0u;
+  // the flat form of the restart kernel: a flat scene (its compact records exist) under a one-colour environment
+  p.round_form = (ctx->generic_round ? PT_ROUND_GENERIC : 0u) | (ctx->flat_round && s.flat && ctx->cubemaps[l->cubemap_id].uniform ? PT_ROUND_FLAT : 0u);
 }
 
 // Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
@@ -1049,6 +1068,7 @@ int ptamd_create(int32_t device_ordinal, ptamd_context** out)
   if (const char* e = tuning_env("PTAMD_SHORT_RCP")) ctx->short_rcp = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_WIDE8")) ctx->wide8 = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_RS_GENERIC")) ctx->generic_round = std::atoi(e) != 0; // tuning knob
+  if (const char* e = tuning_env("PTAMD_RS_FLAT")) ctx->flat_round = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_WIDE4Q")) ctx->wide4q = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS")) ctx->pool_in_lds = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS_WIDE")) ctx->pool_in_lds_wide = std::atoi(e) != 0; // tuning knob
@@ -1178,6 +1198,20 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     mats[i * 4 + 1] = sc->materials[i].normal_map;
     std::memcpy(&mats[i * 4 + 2], &sc->materials[i].ior, 4);
   }
+  // flat scenes: behind the general records, the compact record of PT_RS_FLAT (pt_kernels.hip: resolve_hit), 64 bytes per face =
+  // {n0, diffuse.r} {n1, diffuse.g} {n2, diffuse.b} {specular, 0, 0, 0}: three 16-byte loads and one 4-byte load per hit
+  const bool flat = scene_is_flat(sc);
+  if (flat) shade.resize(shade.size() + (size_t)sc->n_faces * 16, 0.0f);
+  for (uint32_t i = 0; flat && i < sc->n_faces; ++i) {
+    const ptamd_face& f = sc->faces[i];
+    const float* texel = sc->texels + sc->textures[sc->materials[f.material_id].diffuse_spec_map].offset;
+    float* r = &shade[(size_t)sc->n_faces * kShadeFloats + (size_t)i * 16];
+    for (int k = 0; k < 3; ++k) {
+      std::memcpy(r + 4 * k, &f.normals[k], 12);
+      r[4 * k + 3] = texel[k];
+    }
+    r[12] = texel[3];
+  }
   std::vector<TexDesc> tex(sc->n_textures);
   for (uint32_t i = 0; i < sc->n_textures; ++i) {
     tex[i].w = sc->textures[i].w; tex[i].h = sc->textures[i].h; tex[i].nb_chan = sc->textures[i].nb_chan;
@@ -1191,6 +1225,7 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
   d.n_nodes4 = bvh.n_nodes4; d.depth4 = bvh.depth4;
   d.n_nodes8 = bvh.n_nodes8; d.depth8 = bvh.depth8;
   d.n_materials = sc->n_materials; d.n_textures = sc->n_textures;
+  d.flat = flat;
   // device copy of the lights: the radius only ever enters as radius * radius (intersection.cuh:147) — the same binary32
   // product whoever forms it — so the table carries the square in its place and every sphere test saves the multiply
   std::vector<ptamd_light> dev_lights(sc->lights, sc->lights + sc->n_lights);
@@ -1390,6 +1425,33 @@ int ptamd_scene_info_get(ptamd_context* ctx, uint32_t scene_id, ptamd_scene_info
 {
   if (!ctx || !out || scene_id >= ctx->scenes.size()) { set_error("ptamd_scene_info_get: bad argument"); return PTAMD_ERR_ARG; }
   *out = ctx->scenes[scene_id].info;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_desc_is_flat(const ptamd_scene_desc* sc, int32_t* out_flat)
+{
+  if (!sc || !out_flat || (sc->n_faces && !sc->faces) || (sc->n_materials && !sc->materials) || (sc->n_textures && !sc->textures)) {
+    set_error("ptamd_scene_desc_is_flat: null argument or table");
+    return PTAMD_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < sc->n_faces; ++i) {
+    const uint32_t m = sc->faces[i].material_id;
+    if (m >= sc->n_materials || sc->materials[m].diffuse_spec_map < 0 || (uint32_t)sc->materials[m].diffuse_spec_map >= sc->n_textures) {
+      set_error("ptamd_scene_desc_is_flat: material or texture id out of range");
+      return PTAMD_ERR_ARG;
+    }
+  }
+  *out_flat = scene_is_flat(sc) ? 1 : 0;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, int32_t* out_flat)
+{
+  if (!ctx || !out_flat || scene_id >= ctx->scenes.size() || cubemap_id >= ctx->cubemaps.size()) {
+    set_error("ptamd_scene_is_flat: bad argument");
+    return PTAMD_ERR_ARG;
+  }
+  *out_flat = ctx->flat_round && ctx->scenes[scene_id].flat && ctx->cubemaps[cubemap_id].uniform ? 1 : 0;
   return PTAMD_OK;
 }
 

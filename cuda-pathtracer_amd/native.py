@@ -180,6 +180,8 @@ SIGNATURES = {
     "ptamd_release_captured": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_raytrace_stats": (C.c_int, [C.c_void_p, C.POINTER(Launch), C.POINTER(TraceStats)]),
     "ptamd_scene_info_get": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SceneInfo)]),
+    "ptamd_scene_desc_is_flat": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_int32)]),
+    "ptamd_scene_is_flat": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
     "ptamd_set_timeline": (C.c_int, [C.c_void_p, C.c_uint32]),
     "ptamd_read_timeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "ptamd_device_error_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -101,6 +101,12 @@ class Context:
         N.check(self._lib.ptamd_scene_info_get(self._h, scene_id, C.byref(info)))
         return {n: getattr(info, n) for n, _ in N.SceneInfo._fields_}
 
+    def scene_is_flat(self, scene_id: int, cubemap_id: int) -> bool:
+        """ptamd_scene_is_flat: launches of the scene under the cubemap take the restart kernel's flat form."""
+        out = C.c_int32()
+        N.check(self._lib.ptamd_scene_is_flat(self._h, scene_id, cubemap_id, C.byref(out)))
+        return out.value != 0
+
     # ---- the hot path
     def raytrace(self, array, scene_id: int, cubemap_id: int, cam: N.Camera, width: int, height: int,
                  stream, temporal_framebuffer, moved: bool, post_id: int) -> None:

@@ -115,6 +115,13 @@ class HostScene:
         d.texels = self.texels.ctypes.data_as(C.POINTER(C.c_float)); d.n_texel_floats = len(self.texels)
         return d
 
+    def is_flat(self) -> bool:
+        """ptamd_scene_desc_is_flat: every face's diffuse+specular map 1x1, no normal map, every ior bitwise 1.0f."""
+        d = self.desc()
+        out = C.c_int32()
+        N.check(N.load().ptamd_scene_desc_is_flat(C.byref(d), C.byref(out)))
+        return out.value != 0
+
     def camera_struct(self) -> N.Camera:
         return N.Camera.from_buffer_copy(self.camera.tobytes())
 

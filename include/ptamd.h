@@ -358,6 +358,15 @@ typedef struct {
 } ptamd_scene_info;
 int ptamd_scene_info_get(ptamd_context* ctx, uint32_t scene_id, ptamd_scene_info* out);
 
+/* Flat scenes.  A scene is flat when every face's diffuse+specular map is 1x1, no material a face uses has a normal map and
+ * every such material's ior is bitwise 1.0f.  Launches of a flat scene under a one-colour environment (a 1x1 cubemap whose six
+ * texels are equal) that the restart kernel's shipped instantiation would serve take its flat form, compiled without texel
+ * fetches, normal maps, cubemap lookups or refraction; the image is the same.  ptamd_scene_desc_is_flat classifies a scene
+ * description on the host (no device needed); ptamd_scene_is_flat says whether launches of an uploaded scene under a cubemap
+ * take the flat form (0 also with PTAMD_TUNING=1 PTAMD_RS_FLAT=0). */
+int ptamd_scene_desc_is_flat(const ptamd_scene_desc* scene, int32_t* out_flat);
+int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, int32_t* out_flat);
+
 /* Synchronises the device and returns how many times a bounded spin of the split kernel's
  * producer/consumer protocol timed out since the context was created (always 0 unless there is a bug;
  * a non-zero count means frames rendered by PTAMD_KERNEL_BVH_SPLIT are incomplete). */
