@@ -13,6 +13,7 @@
 #include "pt_denoise.h"
 #include "pt_denoise_temporal.h"
 #include "pt_launch.h"
+#include "pt_refit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,6 +59,26 @@ struct DeviceScene {
   float reach = 0.0f;        // origin reach: largest |coordinate| of an origin the path forms, light spheres included (bvh_builder.cpp)
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
   ptamd_scene_info info{};
+  // ---- ptamd_scene_update / ptamd_scene_release
+  bool released = false;     // a tombstone: the tables are gone, the id stays taken
+  bool refit_ok = false;     // the tree can be refitted (no pre-split references, no quantised node forms)
+  std::vector<uint32_t> material_ids;   // host copy: an update may not change them
+  std::vector<ptamd_light> host_lights; // host copy: the origin reach follows the new extent
+  float* raw = nullptr;                 // raw boxes, 8 floats per node (pt_refit.h)
+  uint32_t* refit_groups = nullptr;     // the children-first schedule (bvh_builder.cpp: plan_refit) and the wide nodes' children
+  uint32_t* refit_levels = nullptr;
+  uint32_t* refit_sched = nullptr;
+  uint32_t* wide_child = nullptr;
+  uint32_t n_refit_groups = 0, n_refit_levels = 0, n_refit_sched = 0, refit_top_first = 0, refit_top_levels = 0;
+  // staging of an update's faces, allocated at the first update: two pinned host buffers used in turn (the host fills one while
+  // the copy out of the other may still be in flight), one device buffer
+  float* d_faces = nullptr;
+  void* h_stage[2] = { nullptr, nullptr };
+  hipEvent_t staged[2] = { nullptr, nullptr };   // the copy out of h_stage[i] has finished
+  bool staged_valid[2] = { false, false };
+  uint32_t stage_next = 0;
+  hipEvent_t updated = nullptr;                  // the last update's kernels have finished: lanes and other streams wait for it
+  bool updated_valid = false;
 };
 
 struct DeviceCubemap {
@@ -229,8 +250,14 @@ int upload_padded(T*& dst, const void* src, size_t bytes, size_t pad)
 
 void free_scene(DeviceScene& s)
 {
-  void* ptrs[] = { s.nodes, s.nodes4, s.nodes8, s.nodes4q, s.tris_bvh, s.tris_brute, s.shade, s.materials, s.lights, s.textures, s.texels };
+  void* ptrs[] = { s.nodes, s.nodes4, s.nodes8, s.nodes4q, s.tris_bvh, s.tris_brute, s.shade, s.materials, s.lights, s.textures, s.texels,
+                   s.raw, s.refit_groups, s.refit_levels, s.refit_sched, s.wide_child, s.d_faces };
   for (void* q : ptrs) (void)hipFree(q);
+  for (int i = 0; i < 2; ++i) {
+    if (s.h_stage[i]) (void)hipHostFree(s.h_stage[i]);
+    if (s.staged[i]) (void)hipEventDestroy(s.staged[i]);
+  }
+  if (s.updated) (void)hipEventDestroy(s.updated);
   s = DeviceScene();
 }
 
@@ -320,11 +347,17 @@ float camera_terms(const ptamd_camera& cam, uint32_t width, KParams& p)
   return screen_dist;
 }
 
+// the id names an uploaded scene that has not been released (ptamd_scene_release leaves a tombstone)
+inline bool live_scene(const ptamd_context* ctx, uint32_t scene_id)
+{
+  return scene_id < ctx->scenes.size() && !ctx->scenes[scene_id].released;
+}
+
 int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
 {
   if (!ctx || !l) { set_error("ptamd_raytrace: null context or launch"); return PTAMD_ERR_ARG; }
   if (!l->surface_rgba8 || !l->temporal_framebuffer) { set_error("ptamd_raytrace: null output buffer"); return PTAMD_ERR_ARG; }
-  if (l->scene_id >= ctx->scenes.size()) { set_error("ptamd_raytrace: scene_id out of range"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, l->scene_id)) { set_error("ptamd_raytrace: scene_id out of range or released"); return PTAMD_ERR_ARG; }
   if (l->cubemap_id >= ctx->cubemaps.size()) { set_error("ptamd_raytrace: cubemap_id out of range"); return PTAMD_ERR_ARG; }
   if (l->post_id > 3) { set_error("ptamd_raytrace: post_id out of range (0..3)"); return PTAMD_ERR_ARG; }
   if (l->width == 0 || l->height == 0 || l->width > 65536 || l->height > 65536) { set_error("ptamd_raytrace: bad frame size"); return PTAMD_ERR_ARG; }
@@ -740,11 +773,23 @@ int take_slot(ptamd_context* ctx, bool capturing, ptamd_context::SampleScratch* 
   return PTAMD_OK;
 }
 
+// A launch of a scene that ptamd_scene_update has touched waits for the last update's kernels: a no-op on the stream the update
+// was issued on, the order "launches enqueued after the update render the new geometry" on every other one.  Not inside a graph
+// capture (an event recorded outside it cannot be waited for there): a captured launch follows the update by stream order alone.
+int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing)
+{
+  if (!s.updated_valid || capturing) return PTAMD_OK;
+  PT_HIP(hipStreamWaitEvent(stream, s.updated, 0));
+  return PTAMD_OK;
+}
+
 // Step 9: the megakernel, its events and the resolve pass
-int issue(ptamd_context* ctx, bool stats, const AdaptiveParams* ad, const LaunchPlan& pl, KParams& p)
+int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const AdaptiveParams* ad, const LaunchPlan& pl, KParams& p)
 {
   const bool split = pl.which == PTAMD_KERNEL_BVH_SPLIT, restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
   ptamd_context::SampleScratch* sc = pl.sc;
+  int urc = wait_for_update(scene, pl.stream, pl.capturing);
+  if (urc != PTAMD_OK) return urc;
   p.round_min = ctx->round_min;
   p.round_div = ctx->round_div;
   p.round_div_m16 = (65536u + ctx->round_div - 1u) / ctx->round_div;
@@ -762,6 +807,7 @@ int issue(ptamd_context* ctx, bool stats, const AdaptiveParams* ad, const Launch
     mega_stream = pl.stream != nullptr ? ctx->lane[ctx->lane_next++ % ctx->n_lanes] : ctx->internal[ctx->lane_next++ & 1u];
     sc->flip++;
     if (sc->resolved_valid[pl.slab]) PT_HIP(hipStreamWaitEvent(mega_stream, sc->resolved[pl.slab], 0));
+    if ((urc = wait_for_update(scene, mega_stream, false)) != PTAMD_OK) return urc;   // (the lane reads the scene's tables)
   }
   if (!split) {
     p.tile_heads = ctx->d_heads + (size_t)pl.slot * 8u * PT_HEAD_STRIDE;
@@ -819,9 +865,14 @@ int launch_part(ptamd_context* ctx, const ptamd_launch* l, bool stats, bool late
       rc = bind_slab(ctx, l, pl, p);
     } while (rc == kReplan);
     if (rc != PTAMD_OK || (rc = take_slot(ctx, pl.capturing, pl.sc, pl.slot)) != PTAMD_OK) return rc;
-    return issue(ctx, stats, ad, pl, p);
+    return issue(ctx, ctx->scenes[l->scene_id], stats, ad, pl, p);
   }
   fill_launch(ctx, l, stats, pl, p);
+  if (ctx->scenes[l->scene_id].updated_valid) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = pl.stream != nullptr && (hipStreamIsCapturing(pl.stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone);
+    if ((rc = wait_for_update(ctx->scenes[l->scene_id], pl.stream, capturing)) != PTAMD_OK) return rc;
+  }
   hipError_t e;
   if (pl.which == PTAMD_KERNEL_BVH_BLOCKWISE) {
     // persistent workgroups over 32 x (2 * waves) super-tiles; tickets 0..n_blocks-1 are static
@@ -858,6 +909,134 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l, bool stats, const Adapt
     part.frame_count = std::min(l->frame_count - k0, part_frames);
     if (k0 > 0) part.reset_accumulation = 0;
     if ((rc = launch_part(ctx, &part, stats, k0 > 0, ad, resolved)) != PTAMD_OK) return rc;
+  }
+  return PTAMD_OK;
+}
+
+// The part of a face's records that follows its geometry: the storage-order triangle record {e1, e2, v0, index} of the brute-force
+// variant and floats 0..17 of the shading record (normals, texcoords, tangent).  The upload and an update (refit_scene_tables,
+// pt_refit.hip: pt_refit_records) write the same bytes.
+void write_face_geometry(const ptamd_face& f, uint32_t i, float* t, float* s)
+{
+  rf_tri_record(&f.vertices[0].x, i, t);
+  std::memcpy(s, f.normals, 36);
+  std::memcpy(s + 9, f.texcoords, 24);
+  std::memcpy(s + 15, &f.tangent, 12);
+}
+
+// ... and of a flat scene's compact record: the three normals (float 3 of each is the texel, which stays)
+void write_flat_normals(const ptamd_face& f, float* r)
+{
+  for (int k = 0; k < 3; ++k) std::memcpy(r + 4 * k, &f.normals[k], 12);
+}
+
+int validate_scene_desc(const ptamd_scene_desc* sc)
+{
+  if ((sc->n_faces && !sc->faces) || (sc->n_materials && !sc->materials) || (sc->n_lights && !sc->lights) ||
+      (sc->n_textures && !sc->textures) || (sc->n_texel_floats && !sc->texels) || (sc->n_meshes && !sc->mesh_sizes)) {
+    set_error("ptamd_upload_scene: null table with non-zero count");
+    return PTAMD_ERR_ARG;
+  }
+  if (sc->n_texel_floats >= (1ull << 32)) { set_error("ptamd_upload_scene: more than 2^32 texel floats"); return PTAMD_ERR_LIMIT; }
+  uint64_t total = 0;
+  for (uint32_t m = 0; m < sc->n_meshes; ++m) total += sc->mesh_sizes[m];
+  if (total != sc->n_faces) { set_error("ptamd_upload_scene: mesh_sizes do not sum to n_faces"); return PTAMD_ERR_ARG; }
+  for (uint32_t i = 0; i < sc->n_faces; ++i)
+    if (sc->faces[i].material_id >= sc->n_materials) { set_error("ptamd_upload_scene: face material_id out of range"); return PTAMD_ERR_ARG; }
+  for (uint32_t i = 0; i < sc->n_textures; ++i) {
+    const ptamd_texture_desc& t = sc->textures[i];
+    if (t.w < 1 || t.h < 1 || t.nb_chan < 1 || t.offset + (uint64_t)t.w * t.h * t.nb_chan > sc->n_texel_floats) {
+      set_error("ptamd_upload_scene: texture descriptor out of the texel blob");
+      return PTAMD_ERR_ARG;
+    }
+  }
+  for (uint32_t i = 0; i < sc->n_materials; ++i) {
+    const ptamd_material& m = sc->materials[i];
+    if (m.diffuse_spec_map < 0 || (uint32_t)m.diffuse_spec_map >= sc->n_textures || sc->textures[m.diffuse_spec_map].nb_chan != 4 ||
+        (m.normal_map >= 0 && ((uint32_t)m.normal_map >= sc->n_textures || sc->textures[m.normal_map].nb_chan < 3))) {
+      set_error("ptamd_upload_scene: material texture id invalid (diffuse+spec must be 4-channel)");
+      return PTAMD_ERR_ARG;
+    }
+  }
+  return PTAMD_OK;
+}
+
+// The five tables a scene's geometry decides: the tree (binary nodes, leaf-major records, four-wide nodes), the storage-order
+// records and the shading records (flat scenes: the compact records behind them)
+struct SceneTables {
+  Bvh bvh;
+  std::vector<float> brute, shade;
+  bool flat = false;
+};
+
+// sc: validated (validate_scene_desc)
+int make_scene_tables(const ptamd_scene_desc* sc, uint32_t forms, SceneTables& t)
+{
+  const int rc = build_bvh(sc->faces, sc->n_faces, kBoxMargin, kMaxLeaf, t.bvh, forms, sc->lights, sc->n_lights);
+  if (rc != PTAMD_OK) return rc;
+
+  // storage-order {e1,e2,v0,idx} records for the brute-force variant, and the shading records
+  std::vector<float>& brute = t.brute;
+  std::vector<float>& shade = t.shade;
+  brute.assign((size_t)sc->n_faces * 12, 0.0f);
+  shade.assign((size_t)sc->n_faces * kShadeFloats, 0.0f);
+  for (uint32_t i = 0; i < sc->n_faces; ++i) {
+    const ptamd_face& f = sc->faces[i];
+    // self-contained shading record (one parallel burst of loads per hit instead of the dependent
+    // face -> material -> texture descriptor -> texel chain of intersection.cuh:216-243): 28 floats =
+    // n0 n1 n2 | uv0 uv1 uv2 | tangent | material id (sign bit: constant map) | ior | diffuse+spec map {w,h,nb_chan,offset}
+    // or its one RGBA texel | normal map {..} (w = 0: none)
+    float* s = &shade[(size_t)i * kShadeFloats];
+    write_face_geometry(f, i, &brute[(size_t)i * 12], s);
+    std::memcpy(s + 18, &f.material_id, 4);
+    const ptamd_material& m = sc->materials[f.material_id];
+    std::memcpy(s + 19, &m.ior, 4);
+    const ptamd_texture_desc& dt = sc->textures[m.diffuse_spec_map];
+    if (dt.w == 1 && dt.h == 1) {
+      // a 1x1 diffuse+specular map (every material of indoor.obj as the reference loads it on Linux): sampleTexture can
+      // only ever return texel 0 (intersection.cuh:20-26: x = int(uv.x * 0)), so the record carries the texel itself
+      // and the kernel skips the dependent texel load; flagged in the sign bit of the material id word
+      std::memcpy(s + 20, sc->texels + dt.offset, 16);
+      const uint32_t flagged = f.material_id | 0x80000000u;
+      std::memcpy(s + 18, &flagged, 4);
+    } else {
+      const int32_t d4[4] = { dt.w, dt.h, dt.nb_chan, (int32_t)(uint32_t)dt.offset };
+      std::memcpy(s + 20, d4, 16);
+    }
+    if (m.normal_map >= 0) {
+      const ptamd_texture_desc& nt = sc->textures[m.normal_map];
+      const int32_t n4[4] = { nt.w, nt.h, nt.nb_chan, (int32_t)(uint32_t)nt.offset };
+      std::memcpy(s + 24, n4, 16);
+      uint32_t word;
+      std::memcpy(&word, s + 18, 4);
+      word |= 0x40000000u;               // bit 30 of the material id word: the record's 7th float4 (normal map) is in use
+      std::memcpy(s + 18, &word, 4);
+    }
+  }
+  // flat scenes: behind the general records, the compact record of PT_RS_FLAT (pt_kernels.hip: resolve_hit), 64 bytes per face =
+  // {n0, diffuse.r} {n1, diffuse.g} {n2, diffuse.b} {specular, 0, 0, 0}: three 16-byte loads and one 4-byte load per hit
+  const bool flat = t.flat = scene_is_flat(sc);
+  if (flat) shade.resize(shade.size() + (size_t)sc->n_faces * 16, 0.0f);
+  for (uint32_t i = 0; flat && i < sc->n_faces; ++i) {
+    const ptamd_face& f = sc->faces[i];
+    const float* texel = sc->texels + sc->textures[sc->materials[f.material_id].diffuse_spec_map].offset;
+    float* r = &shade[(size_t)sc->n_faces * kShadeFloats + (size_t)i * 16];
+    write_flat_normals(f, r);
+    for (int k = 0; k < 3; ++k) r[4 * k + 3] = texel[k];
+    r[12] = texel[3];
+  }
+  return PTAMD_OK;
+}
+
+// The host definition of ptamd_scene_update: the tables of `t` for new faces, topology and everything that comes from materials
+// and textures kept
+int refit_scene_tables(SceneTables& t, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights)
+{
+  const int rc = refit_bvh(t.bvh, faces, n_faces, lights, n_lights);
+  if (rc != PTAMD_OK) return rc;
+  for (uint32_t i = 0; i < n_faces; ++i) {
+    write_face_geometry(faces[i], i, &t.brute[(size_t)i * 12], &t.shade[(size_t)i * kShadeFloats]);
+    if (t.flat) write_flat_normals(faces[i], &t.shade[(size_t)n_faces * kShadeFloats + (size_t)i * 16]);
   }
   return PTAMD_OK;
 }
@@ -920,7 +1099,7 @@ int denoise_workspace(ptamd_context* ctx, size_t n)
 
 int denoise_ids(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id)
 {
-  if (scene_id >= ctx->scenes.size()) { set_error(std::string(who) + ": scene_id out of range"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error(std::string(who) + ": scene_id out of range or released"); return PTAMD_ERR_ARG; }
   if (cubemap_id >= ctx->cubemaps.size()) { set_error(std::string(who) + ": cubemap_id out of range"); return PTAMD_ERR_ARG; }
   return PTAMD_OK;
 }
@@ -1117,100 +1296,20 @@ void ptamd_destroy(ptamd_context* ctx)
 int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t* out_scene_id)
 {
   if (!ctx || !sc || !out_scene_id) { set_error("ptamd_upload_scene: null argument"); return PTAMD_ERR_ARG; }
-  if ((sc->n_faces && !sc->faces) || (sc->n_materials && !sc->materials) || (sc->n_lights && !sc->lights) ||
-      (sc->n_textures && !sc->textures) || (sc->n_texel_floats && !sc->texels) || (sc->n_meshes && !sc->mesh_sizes)) {
-    set_error("ptamd_upload_scene: null table with non-zero count");
-    return PTAMD_ERR_ARG;
-  }
-  if (sc->n_texel_floats >= (1ull << 32)) { set_error("ptamd_upload_scene: more than 2^32 texel floats"); return PTAMD_ERR_LIMIT; }
-  uint64_t total = 0;
-  for (uint32_t m = 0; m < sc->n_meshes; ++m) total += sc->mesh_sizes[m];
-  if (total != sc->n_faces) { set_error("ptamd_upload_scene: mesh_sizes do not sum to n_faces"); return PTAMD_ERR_ARG; }
-  for (uint32_t i = 0; i < sc->n_faces; ++i)
-    if (sc->faces[i].material_id >= sc->n_materials) { set_error("ptamd_upload_scene: face material_id out of range"); return PTAMD_ERR_ARG; }
-  for (uint32_t i = 0; i < sc->n_textures; ++i) {
-    const ptamd_texture_desc& t = sc->textures[i];
-    if (t.w < 1 || t.h < 1 || t.nb_chan < 1 || t.offset + (uint64_t)t.w * t.h * t.nb_chan > sc->n_texel_floats) {
-      set_error("ptamd_upload_scene: texture descriptor out of the texel blob");
-      return PTAMD_ERR_ARG;
-    }
-  }
-  for (uint32_t i = 0; i < sc->n_materials; ++i) {
-    const ptamd_material& m = sc->materials[i];
-    if (m.diffuse_spec_map < 0 || (uint32_t)m.diffuse_spec_map >= sc->n_textures || sc->textures[m.diffuse_spec_map].nb_chan != 4 ||
-        (m.normal_map >= 0 && ((uint32_t)m.normal_map >= sc->n_textures || sc->textures[m.normal_map].nb_chan < 3))) {
-      set_error("ptamd_upload_scene: material texture id invalid (diffuse+spec must be 4-channel)");
-      return PTAMD_ERR_ARG;
-    }
-  }
-
-  Bvh bvh;
-  // (the quantised node forms only where their tuning knob is set: nothing else can select them)
-  int rc = build_bvh(sc->faces, sc->n_faces, kBoxMargin, kMaxLeaf, bvh, (ctx->wide8 ? kBvhForm8 : 0u) | (ctx->wide4q ? kBvhForm4q : 0u),
-                     sc->lights, sc->n_lights);
+  int rc = validate_scene_desc(sc);
   if (rc != PTAMD_OK) return rc;
-
-  // storage-order {e1,e2,v0,idx} records for the brute-force variant, and the shading records
-  std::vector<float> brute((size_t)sc->n_faces * 12, 0.0f), shade((size_t)sc->n_faces * kShadeFloats, 0.0f);
-  for (uint32_t i = 0; i < sc->n_faces; ++i) {
-    const ptamd_face& f = sc->faces[i];
-    float* t = &brute[(size_t)i * 12];
-    t[0] = f.vertices[1].x - f.vertices[0].x; t[1] = f.vertices[1].y - f.vertices[0].y; t[2] = f.vertices[1].z - f.vertices[0].z;
-    t[3] = f.vertices[2].x - f.vertices[0].x; t[4] = f.vertices[2].y - f.vertices[0].y; t[5] = f.vertices[2].z - f.vertices[0].z;
-    t[6] = f.vertices[0].x; t[7] = f.vertices[0].y; t[8] = f.vertices[0].z;
-    std::memcpy(&t[9], &i, 4);
-    // self-contained shading record (one parallel burst of loads per hit instead of the dependent
-    // face -> material -> texture descriptor -> texel chain of intersection.cuh:216-243): 28 floats =
-    // n0 n1 n2 | uv0 uv1 uv2 | tangent | material id (sign bit: constant map) | ior | diffuse+spec map {w,h,nb_chan,offset}
-    // or its one RGBA texel | normal map {..} (w = 0: none)
-    float* s = &shade[(size_t)i * kShadeFloats];
-    std::memcpy(s, f.normals, 36);
-    std::memcpy(s + 9, f.texcoords, 24);
-    std::memcpy(s + 15, &f.tangent, 12);
-    std::memcpy(s + 18, &f.material_id, 4);
-    const ptamd_material& m = sc->materials[f.material_id];
-    std::memcpy(s + 19, &m.ior, 4);
-    const ptamd_texture_desc& dt = sc->textures[m.diffuse_spec_map];
-    if (dt.w == 1 && dt.h == 1) {
-      // a 1x1 diffuse+specular map (every material of indoor.obj as the reference loads it on Linux): sampleTexture can
-      // only ever return texel 0 (intersection.cuh:20-26: x = int(uv.x * 0)), so the record carries the texel itself
-      // and the kernel skips the dependent texel load; flagged in the sign bit of the material id word
-      std::memcpy(s + 20, sc->texels + dt.offset, 16);
-      const uint32_t flagged = f.material_id | 0x80000000u;
-      std::memcpy(s + 18, &flagged, 4);
-    } else {
-      const int32_t d4[4] = { dt.w, dt.h, dt.nb_chan, (int32_t)(uint32_t)dt.offset };
-      std::memcpy(s + 20, d4, 16);
-    }
-    if (m.normal_map >= 0) {
-      const ptamd_texture_desc& nt = sc->textures[m.normal_map];
-      const int32_t n4[4] = { nt.w, nt.h, nt.nb_chan, (int32_t)(uint32_t)nt.offset };
-      std::memcpy(s + 24, n4, 16);
-      uint32_t word;
-      std::memcpy(&word, s + 18, 4);
-      word |= 0x40000000u;               // bit 30 of the material id word: the record's 7th float4 (normal map) is in use
-      std::memcpy(s + 18, &word, 4);
-    }
-  }
+  SceneTables t;
+  // (the quantised node forms only where their tuning knob is set: nothing else can select them)
+  if ((rc = make_scene_tables(sc, (ctx->wide8 ? kBvhForm8 : 0u) | (ctx->wide4q ? kBvhForm4q : 0u), t)) != PTAMD_OK) return rc;
+  const Bvh& bvh = t.bvh;
+  const std::vector<float>& brute = t.brute;
+  const std::vector<float>& shade = t.shade;
+  const bool flat = t.flat;
   std::vector<int32_t> mats((size_t)sc->n_materials * 4, 0);
   for (uint32_t i = 0; i < sc->n_materials; ++i) {
     mats[i * 4 + 0] = sc->materials[i].diffuse_spec_map;
     mats[i * 4 + 1] = sc->materials[i].normal_map;
     std::memcpy(&mats[i * 4 + 2], &sc->materials[i].ior, 4);
-  }
-  // flat scenes: behind the general records, the compact record of PT_RS_FLAT (pt_kernels.hip: resolve_hit), 64 bytes per face =
-  // {n0, diffuse.r} {n1, diffuse.g} {n2, diffuse.b} {specular, 0, 0, 0}: three 16-byte loads and one 4-byte load per hit
-  const bool flat = scene_is_flat(sc);
-  if (flat) shade.resize(shade.size() + (size_t)sc->n_faces * 16, 0.0f);
-  for (uint32_t i = 0; flat && i < sc->n_faces; ++i) {
-    const ptamd_face& f = sc->faces[i];
-    const float* texel = sc->texels + sc->textures[sc->materials[f.material_id].diffuse_spec_map].offset;
-    float* r = &shade[(size_t)sc->n_faces * kShadeFloats + (size_t)i * 16];
-    for (int k = 0; k < 3; ++k) {
-      std::memcpy(r + 4 * k, &f.normals[k], 12);
-      r[4 * k + 3] = texel[k];
-    }
-    r[12] = texel[3];
   }
   std::vector<TexDesc> tex(sc->n_textures);
   for (uint32_t i = 0; i < sc->n_textures; ++i) {
@@ -1244,6 +1343,25 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     free_scene(d);
     return rc;
   }
+  // what ptamd_scene_update needs: raw boxes, the children-first schedule, the wide nodes' children; host copies of what an
+  // update checks (material ids) and recomputes (the origin reach from the lights)
+  d.refit_ok = !bvh.split && bvh.nodes8.empty() && bvh.nodes4q.empty();
+  if (d.refit_ok) {
+    if ((rc = upload(d.raw, bvh.raw.data(), bvh.raw.size() * 4)) ||
+        (rc = upload(d.refit_groups, bvh.refit_groups.data(), bvh.refit_groups.size() * 4)) ||
+        (rc = upload(d.refit_levels, bvh.refit_levels.data(), bvh.refit_levels.size() * 4)) ||
+        (rc = upload(d.refit_sched, bvh.refit_sched.data(), bvh.refit_sched.size() * 4)) ||
+        (rc = upload(d.wide_child, bvh.wide_child.data(), bvh.wide_child.size() * 4))) {
+      free_scene(d);
+      return rc;
+    }
+    d.n_refit_groups = (uint32_t)bvh.refit_groups.size() / 4u; d.n_refit_levels = (uint32_t)bvh.refit_levels.size();
+    d.n_refit_sched = (uint32_t)bvh.refit_sched.size();
+    d.refit_top_first = bvh.refit_top_first; d.refit_top_levels = bvh.refit_top_levels;
+    d.material_ids.resize(sc->n_faces);
+    for (uint32_t i = 0; i < sc->n_faces; ++i) d.material_ids[i] = sc->faces[i].material_id;
+    d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);
+  }
   d.info.n_faces = sc->n_faces; d.info.n_lights = sc->n_lights; d.info.n_nodes = bvh.n_nodes;
   d.info.n_leaves = bvh.n_leaves; d.info.max_leaf_size = bvh.max_leaf; d.info.depth = bvh.depth;
   d.info.node_bytes = 64; d.info.tri_bytes = 48;
@@ -1252,6 +1370,133 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
   d.info.lds_bytes_brute = sc->n_faces * 48u;
   ctx->scenes.push_back(d);
   *out_scene_id = (uint32_t)ctx->scenes.size() - 1;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
+{
+  if (!ctx || !d) { set_error("ptamd_scene_update: null argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, d->scene_id)) { set_error("ptamd_scene_update: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  DeviceScene& s = ctx->scenes[d->scene_id];
+  if (d->n_faces != s.n_faces) { set_error("ptamd_scene_update: n_faces differs from the uploaded count"); return PTAMD_ERR_ARG; }
+  if (d->n_faces && !d->faces) { set_error("ptamd_scene_update: null faces"); return PTAMD_ERR_ARG; }
+  if (!s.refit_ok) {
+    set_error("ptamd_scene_update: this scene's tree is not refitted (built with PTAMD_WIDE8, PTAMD_WIDE4Q or PTAMD_BVH_SPLIT_ALPHA)");
+    return PTAMD_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < d->n_faces; ++i)
+    if (d->faces[i].material_id != s.material_ids[i]) { set_error("ptamd_scene_update: a face's material_id differs from the uploaded one"); return PTAMD_ERR_ARG; }
+  // a captured launch has baked in the walk-or-every-face choice (far_origin_camera) of the geometry it was captured with
+  for (const auto& c : ctx->sample_scratch)
+    if (c.captured) { set_error("ptamd_scene_update: a captured launch pins this context's scenes (ptamd_release_captured)"); return PTAMD_ERR_LIMIT; }
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  if (stream != nullptr) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      set_error("ptamd_scene_update: an update cannot be captured into a graph");
+      return PTAMD_ERR_LIMIT;
+    }
+  }
+  if (d->n_faces == 0) return PTAMD_OK;
+  PT_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)d->n_faces * sizeof(ptamd_face);
+  // the first update of the scene: the staging buffers
+  if (!s.d_faces) PT_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_faces), bytes));
+  for (int i = 0; i < 2; ++i) {
+    if (!s.h_stage[i]) PT_HIP(hipHostMalloc(&s.h_stage[i], bytes, hipHostMallocDefault));
+    if (!s.staged[i]) PT_HIP(hipEventCreateWithFlags(&s.staged[i], hipEventDisableTiming));
+  }
+  if (!s.updated) PT_HIP(hipEventCreateWithFlags(&s.updated, hipEventDisableTiming));
+  // the host pass: extent / reach / margin floor of the NEW geometry by build_bvh's rule, so that far_origin_camera judges later
+  // launches by it; the faces into the staging buffer whose last copy is two updates back
+  Bvh m;
+  m.margin = kBoxMargin;
+  const float origin_margin = bvh_margins(m, d->faces, d->n_faces, s.host_lights.data(), (uint32_t)s.host_lights.size());
+  const uint32_t slot = s.stage_next++ & 1u;
+  if (s.staged_valid[slot]) PT_HIP(hipEventSynchronize(s.staged[slot]));
+  std::memcpy(s.h_stage[slot], d->faces, bytes);
+  // every launch still reading the scene: megakernels on the lanes and internal streams (mega_done), everything a stream was
+  // given so far (last_done); the previous update, which may have gone to another stream
+  for (const auto& c : ctx->sample_scratch) {
+    for (int i = 0; i < 3; ++i) if (c.mega_done[i]) PT_HIP(hipStreamWaitEvent(stream, c.mega_done[i], 0));
+    if (c.last_done) PT_HIP(hipStreamWaitEvent(stream, c.last_done, 0));
+  }
+  if (s.updated_valid) PT_HIP(hipStreamWaitEvent(stream, s.updated, 0));
+  PT_HIP(hipMemcpyAsync(s.d_faces, s.h_stage[slot], bytes, hipMemcpyHostToDevice, stream));
+  PT_HIP(hipEventRecord(s.staged[slot], stream));
+  s.staged_valid[slot] = true;
+  RefitParams r;
+  std::memset(&r, 0, sizeof r);
+  r.faces = s.d_faces;
+  r.nodes = reinterpret_cast<float*>(s.nodes); r.tris_bvh = reinterpret_cast<float*>(s.tris_bvh);
+  r.nodes4 = reinterpret_cast<float*>(s.nodes4); r.tris_brute = reinterpret_cast<float*>(s.tris_brute);
+  r.shade = reinterpret_cast<float*>(s.shade); r.raw = s.raw;
+  r.groups = s.refit_groups; r.levels = s.refit_levels; r.sched = s.refit_sched; r.wide_child = s.wide_child;
+  r.n_faces = s.n_faces; r.n_tris = s.n_bvh_tris; r.n_nodes = s.n_nodes; r.n_nodes4 = s.n_nodes4;
+  r.n_groups = s.n_refit_groups; r.top_level_first = s.refit_top_first; r.top_levels = s.refit_top_levels;
+  r.flat = s.flat ? 1u : 0u;
+  r.margin = kBoxMargin; r.origin_margin = origin_margin;
+  // shapes: every table the kernels index exists and the schedule's level ranges lie inside it
+  if (!r.nodes || !r.tris_bvh || !r.nodes4 || !r.tris_brute || !r.shade || !r.raw || !r.groups || !r.levels || !r.sched || !r.wide_child ||
+      r.n_tris != r.n_faces || r.n_nodes == 0 || r.n_groups == 0 || r.top_level_first + r.top_levels > s.n_refit_levels ||
+      s.n_refit_sched >= r.n_nodes) {
+    set_error("ptamd_scene_update: the scene's refit tables are inconsistent");
+    return PTAMD_ERR_ARG;
+  }
+  PT_HIP(launch_refit(r, stream));
+  PT_HIP(hipEventRecord(s.updated, stream));
+  s.updated_valid = true;
+  s.extent = m.extent; s.all_finite = m.all_finite; s.reach = m.reach; s.margin_floor = m.margin_floor;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_release(ptamd_context* ctx, uint32_t scene_id)
+{
+  if (!ctx) { set_error("ptamd_scene_release: null context"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_release: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  // megakernels on the lanes and internal streams may still read the tables
+  PT_HIP(hipDeviceSynchronize());
+  free_scene(ctx->scenes[scene_id]);
+  ctx->scenes[scene_id].released = true;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_table_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which, void* out, uint64_t* bytes)
+{
+  if (!ctx || !bytes || which > 4u) { set_error("ptamd_scene_table_read: bad argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_table_read: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  const DeviceScene& s = ctx->scenes[scene_id];
+  const void* src[5] = { s.nodes, s.tris_bvh, s.nodes4, s.tris_brute, s.shade };
+  const uint64_t size[5] = { (uint64_t)s.n_nodes * 64u, (uint64_t)s.n_bvh_tris * 48u, (uint64_t)s.n_nodes4 * 128u, (uint64_t)s.n_faces * 48u,
+                             (uint64_t)s.n_faces * (kShadeFloats * 4u + (s.flat ? 64u : 0u)) };
+  const uint64_t room = *bytes;
+  *bytes = size[which];
+  if (!out) return PTAMD_OK;
+  if (room < size[which]) { set_error("ptamd_scene_table_read: the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(hipDeviceSynchronize());
+  if (size[which]) PT_HIP(hipMemcpy(out, src[which], size[which], hipMemcpyDeviceToHost));
+  return PTAMD_OK;
+}
+
+int ptamd_host_scene_refit(const ptamd_scene_desc* sc, const ptamd_face* faces_b, const ptamd_face* faces_c, uint32_t which, void* out,
+                           uint64_t* bytes)
+{
+  if (!sc || !bytes || which > 5u) { set_error("ptamd_host_scene_refit: bad argument"); return PTAMD_ERR_ARG; }
+  int rc = validate_scene_desc(sc);
+  SceneTables t;
+  if (rc != PTAMD_OK || (rc = make_scene_tables(sc, 0u, t)) != PTAMD_OK) return rc;
+  for (const ptamd_face* f : { faces_b, faces_c })
+    if (f && (rc = refit_scene_tables(t, f, sc->n_faces, sc->lights, sc->n_lights)) != PTAMD_OK) return rc;
+  const float scalars[4] = { t.bvh.extent, t.bvh.reach, t.bvh.margin_floor, t.bvh.all_finite ? 1.0f : 0.0f };
+  const void* src[6] = { t.bvh.nodes.data(), t.bvh.tris.data(), t.bvh.nodes4.data(), t.brute.data(), t.shade.data(), scalars };
+  const uint64_t size[6] = { t.bvh.nodes.size() * 4u, t.bvh.tris.size() * 4u, t.bvh.nodes4.size() * 4u, t.brute.size() * 4u, t.shade.size() * 4u, 16u };
+  const uint64_t room = *bytes;
+  *bytes = size[which];
+  if (!out) return PTAMD_OK;
+  if (room < size[which]) { set_error("ptamd_host_scene_refit: the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
+  if (size[which]) std::memcpy(out, src[which], size[which]);
   return PTAMD_OK;
 }
 
@@ -1280,6 +1525,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   // resolves every kernel entry point in the gfx950 code object (hipFuncGetAttributes loads it on first use), so a
   // missing or mismatched device image fails here, as the reference's cudaMemcpyFromSymbol calls would (raytrace.cu:362-374)
   hipError_t e = resolve_kernels();
+  if (e == hipSuccess) e = resolve_refit_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }
@@ -1423,7 +1669,7 @@ int ptamd_read_timeline(ptamd_context* ctx, uint64_t* out, uint32_t n_waves, uin
 
 int ptamd_scene_info_get(ptamd_context* ctx, uint32_t scene_id, ptamd_scene_info* out)
 {
-  if (!ctx || !out || scene_id >= ctx->scenes.size()) { set_error("ptamd_scene_info_get: bad argument"); return PTAMD_ERR_ARG; }
+  if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_info_get: bad argument"); return PTAMD_ERR_ARG; }
   *out = ctx->scenes[scene_id].info;
   return PTAMD_OK;
 }
@@ -1447,7 +1693,7 @@ int ptamd_scene_desc_is_flat(const ptamd_scene_desc* sc, int32_t* out_flat)
 
 int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, int32_t* out_flat)
 {
-  if (!ctx || !out_flat || scene_id >= ctx->scenes.size() || cubemap_id >= ctx->cubemaps.size()) {
+  if (!ctx || !out_flat || !live_scene(ctx, scene_id) || cubemap_id >= ctx->cubemaps.size()) {
     set_error("ptamd_scene_is_flat: bad argument");
     return PTAMD_ERR_ARG;
   }
@@ -1458,7 +1704,7 @@ int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_
 int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel, const float* rays_host, uint32_t n,
                      int32_t* out_host)
 {
-  if (!ctx || scene_id >= ctx->scenes.size() || (n && (!rays_host || !out_host)) ||
+  if (!ctx || !live_scene(ctx, scene_id) || (n && (!rays_host || !out_host)) ||
       (kernel > PTAMD_KERNEL_BVH && kernel != PTAMD_KERNEL_BVH_RESTART)) {
     set_error("ptamd_trace_rays: bad argument");
     return PTAMD_ERR_ARG;
@@ -1491,7 +1737,7 @@ int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel, con
 int ptamd_trace_rays_queue(ptamd_context* ctx, uint32_t scene_id, const float* rays_dev, uint32_t n, int32_t* out_dev, uint32_t config,
                            uint32_t refill_min, void* stream, uint32_t* out_waves_per_cu)
 {
-  if (!ctx || scene_id >= ctx->scenes.size() || (n && (!rays_dev || !out_dev)) || config > 3u || n >= 0x80000000u) { set_error("ptamd_trace_rays_queue: bad argument"); return PTAMD_ERR_ARG; }
+  if (!ctx || !live_scene(ctx, scene_id) || (n && (!rays_dev || !out_dev)) || config > 3u || n >= 0x80000000u) { set_error("ptamd_trace_rays_queue: bad argument"); return PTAMD_ERR_ARG; }
   if (n == 0) return PTAMD_OK;
   PT_HIP(hipSetDevice(ctx->device));
   const DeviceScene& s = ctx->scenes[scene_id];
@@ -1964,7 +2210,7 @@ int adaptive_checks(const char* who, const ptamd_context* ctx, const ptamd_adapt
     if (d->post_id > 3) return fail("post_id out of range (0..3)");
   }
   if (what >= 2) {
-    if (d->scene_id >= ctx->scenes.size()) return fail("scene_id out of range");
+    if (!live_scene(ctx, d->scene_id)) return fail("scene_id out of range or released");
     if (d->cubemap_id >= ctx->cubemaps.size()) return fail("cubemap_id out of range");
     if (d->bounces == 0 || d->bounces > 1024) return fail("bounces out of range (1..1024)");
     if (d->kernel != PTAMD_KERNEL_AUTO && d->kernel != PTAMD_KERNEL_BVH_RESTART) return fail("kernel must be PTAMD_KERNEL_AUTO or PTAMD_KERNEL_BVH_RESTART");

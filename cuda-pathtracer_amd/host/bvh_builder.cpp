@@ -12,6 +12,7 @@
 // ray walks the tree front-to-back without a stack; triangles re-ordered leaf-major as
 // 48-byte {v0, e1, e2, global index} records.
 #include "ptamd_internal.h"
+#include "../csrc/pt_refit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -266,6 +267,168 @@ void split_references(std::vector<Prim>& prims, const ptamd_face* faces, float a
 inline uint32_t f2u(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 inline float u2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
+// ---- the geometry-dependent part of the tables, shared by build_bvh and refit_bvh (arithmetic: csrc/pt_refit.h) ----
+
+// Extent, reach and margin floor of the tree for the faces it stands for; returns the origin-dependent margin extent * 2^-20.
+// NaN and infinite coordinates would poison every ancestor box (an infinite one gives the quantised nodes an origin of -inf, and
+// every plane of such a node decodes to NaN): they stay out of the bounds and of the extent.  Such a face can never pass
+// Moller-Trumbore either way — an infinite edge makes the determinant +-inf or NaN, and with 1 / det = 0 or NaN the hit distance
+// comes out NaN, which `t > 0` rejects (tests/test_gpu_parity.py: every kernel == the brute-force oracle on them).
+float set_margins(Bvh& out, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights)
+{
+  float extent = 0.0f;   // largest finite |coordinate| of the scene
+  bool all_finite = true;
+  for (uint32_t i = 0; i < n_faces; ++i)
+    for (int k = 0; k < 3; ++k) {
+      const float* v = &faces[i].vertices[k].x;
+      for (int a = 0; a < 3; ++a) {
+        if (std::fabs(v[a]) <= std::numeric_limits<float>::max()) extent = std::max(extent, std::fabs(v[a]));
+        else all_finite = false;
+      }
+    }
+  out.extent = extent;
+  out.all_finite = all_finite;
+  out.reach = origin_reach(lights, n_lights, extent);
+  const float origin_margin = extent * (1.0f / 1048576.0f);
+  out.margin_floor = out.margin + origin_margin;
+  return origin_margin;
+}
+
+// every leaf-major record from the face its index word names
+void write_tri_records(Bvh& out, const ptamd_face* faces)
+{
+  for (uint32_t j = 0; j < out.n_tris; ++j) {
+    float* t = &out.tris[(size_t)j * 12];
+    const uint32_t fi = f2u(t[9]);
+    rf_tri_record(&faces[fi].vertices[0].x, fi, t);
+  }
+}
+
+// raw boxes, children first (pre-order: a node's children have larger indices): a leaf's from its faces, an interior node's from
+// its children's
+void refit_raw_boxes(Bvh& out, const ptamd_face* faces)
+{
+  for (uint32_t k = out.n_nodes; k-- > 0;) {
+    const float* q = &out.nodes[(size_t)k * 16];
+    const uint32_t info = f2u(q[3]), count = info >> 24, first = info & 0xFFFFFFu;
+    RfBox b;
+    if (count) {
+      rf_box_reset(b);
+      for (uint32_t j = 0; j < count; ++j) {
+        RfBox fb;
+        rf_face_box(&faces[f2u(out.tris[(size_t)(first + j) * 12 + 9])].vertices[0].x, fb);
+        rf_box_grow(b, fb);
+      }
+    } else {
+      const float* l = &out.raw[(size_t)(k + 1) * 8];
+      const float* r = &out.raw[(size_t)(f2u(q[7]) & 0x3FFFFFFFu) * 8];
+      for (int a = 0; a < 3; ++a) { b.lo[a] = rf_min(l[a], r[a]); b.hi[a] = rf_max(l[4 + a], r[4 + a]); }
+    }
+    float* w = &out.raw[(size_t)k * 8];
+    for (int a = 0; a < 3; ++a) { w[a] = b.lo[a]; w[4 + a] = b.hi[a]; }
+  }
+}
+
+// The planes of the binary nodes from the raw boxes.  The slab tests of the LDS loop and of the four-wide float walk form an
+// axis' distances from the box's centre and half extent: tc = fma(c, 1/d, -(o/d)), then fma(-+h, |1/d|, tc).  Expressed as a
+// displacement of the plane along the axis the roundings add up to: the reciprocal (v_rcp_f32, 1 ulp) (|o| + |p|) 2^-23, -(o/d)
+// |o| 2^-24, tc (|o| + |c|) 2^-24 and the final fma (|o| + |p|) 2^-24 — at most (|o| + |p|) 2^-22 + |o| 2^-24 with an exact
+// reciprocal, about 1.75 (|o| + |p|) 2^-22 with a 2-ulp one.  (The box [c - h, c + h] itself contains [lo, hi] exactly: h is
+// rounded up where the record is formed.)  Bounce rays start on the scene's surfaces (|o| <= extent), so every box also gets
+// extent * 2^-20 — 2.3x the worst case at |o| = |p| = extent — and |p| * 1e-6 on top.  Origins farther out — a camera much
+// farther out than the scene, or a light sphere far outside the mesh, which paths bounce off (origin_reach) — are the launcher's
+// business (ptamd_api.cpp: far_origin_camera, margins_cover against Bvh::margin_floor; every face is tested beyond it).  Widening
+// the boxes by reach * 2^-20 instead would cover the slab test but not Moller-Trumbore's own rounding, which grows with
+// |o - v0| / det: with origins 1e4 .. 6e4 units out, a random soup still gave 1 to 52 of 200 000 rays whose brute-force hit (a
+// grazing one, off the triangle by its rounding) lay outside every such box.
+void write_node_planes(Bvh& out, float origin_margin)
+{
+  for (uint32_t k = 0; k < out.n_nodes; ++k) {
+    float* q = &out.nodes[(size_t)k * 16];
+    const float* w = &out.raw[(size_t)k * 8];
+    for (int a = 0; a < 3; ++a) {
+      q[a] = rf_plane_lo(w[a], out.margin, origin_margin);
+      q[4 + a] = rf_plane_hi(w[4 + a], out.margin, origin_margin);
+    }
+  }
+}
+
+// child boxes (centre, half extent) and visiting orders of the four-wide nodes from the raw boxes of the binary nodes their
+// children were made from (Bvh::wide_child); the references stay
+void write_wide_nodes(Bvh& out, float origin_margin)
+{
+  for (uint32_t w = 0; w < out.n_nodes4; ++w) {
+    float* q = &out.nodes4[(size_t)w * 32];
+    float ctr[4][3];
+    uint32_t present = 0;
+    for (int c = 0; c < 4; ++c) {
+      const uint32_t ch = out.wide_child[(size_t)w * 4 + c];
+      if (ch >= out.n_nodes) {
+        // empty slot: a point box far beyond MAX_DIST (no ray reaches it: its slab distances are +-huge, never within
+        // [0, best <= 1e5])
+        for (int a = 0; a < 3; ++a) { q[a * 4 + c] = 3.0e38f; q[12 + a * 4 + c] = 0.0f; ctr[c][a] = 0.0f; }   // (centre, half extent)
+        continue;
+      }
+      present |= 1u << c;
+      const float* r = &out.raw[(size_t)ch * 8];
+      for (int a = 0; a < 3; ++a) {
+        rf_wide_axis(r[a], r[4 + a], out.margin, origin_margin, q[a * 4 + c], q[12 + a * 4 + c]);
+        ctr[c][a] = 0.5f * r[a] + 0.5f * r[4 + a];
+      }
+    }
+    uint32_t words[4];
+    rf_wide_order(present, ctr, words);
+    for (int i = 0; i < 4; ++i) q[28 + i] = u2f(words[i]);
+  }
+}
+
+// The device's schedule for forming boxes children first (csrc/pt_refit.hip).  Pre-order makes every subtree a contiguous index
+// range: the tree is cut into subtrees of at most kRefitSubtreeNodes nodes, each one workgroup's, whose interior nodes are listed
+// by ascending height (a level = the nodes of one height: their children are leaves or lie in a lower level); the interior nodes
+// above the subtree roots form one more group, handled by one workgroup after all the others.
+void plan_refit(Bvh& out)
+{
+  const uint32_t n = out.n_nodes;
+  std::vector<uint32_t> size(n), height(n);
+  auto right_of = [&](uint32_t k) { return f2u(out.nodes[(size_t)k * 16 + 7]) & 0x3FFFFFFFu; };
+  auto is_leaf = [&](uint32_t k) { return (f2u(out.nodes[(size_t)k * 16 + 3]) >> 24) != 0u; };
+  for (uint32_t k = n; k-- > 0;) {
+    if (is_leaf(k)) { size[k] = 1; height[k] = 0; continue; }
+    const uint32_t r = right_of(k);
+    size[k] = 1u + size[k + 1] + size[r];
+    height[k] = 1u + std::max(height[k + 1], height[r]);
+  }
+  // appends `ids` (interior nodes) to the schedule, one level per height; returns the first level and the number of levels
+  auto emit = [&](std::vector<uint32_t>& ids, uint32_t& first, uint32_t& count) {
+    std::stable_sort(ids.begin(), ids.end(), [&](uint32_t a, uint32_t b) { return height[a] < height[b]; });
+    first = (uint32_t)out.refit_levels.size();
+    for (size_t i = 0; i < ids.size(); ++i) {
+      out.refit_sched.push_back(ids[i]);
+      if (i + 1 == ids.size() || height[ids[i + 1]] != height[ids[i]]) out.refit_levels.push_back((uint32_t)out.refit_sched.size());
+    }
+    count = (uint32_t)out.refit_levels.size() - first;
+  };
+  std::vector<uint32_t> top, ids, stack;
+  if (n) stack.push_back(0);
+  while (!stack.empty()) {
+    const uint32_t k = stack.back();
+    stack.pop_back();
+    if (size[k] > kRefitSubtreeNodes) {
+      top.push_back(k);
+      stack.push_back(right_of(k));
+      stack.push_back(k + 1);
+      continue;
+    }
+    ids.clear();
+    for (uint32_t i = k; i < k + size[k]; ++i) if (!is_leaf(i)) ids.push_back(i);
+    uint32_t first = 0, count = 0;
+    emit(ids, first, count);
+    const uint32_t g[4] = { k, size[k], first, count };
+    out.refit_groups.insert(out.refit_groups.end(), g, g + 4);
+  }
+  emit(top, out.refit_top_first, out.refit_top_levels);
+}
+
 } // namespace
 
 // Light spheres are ray origins as well: a path that hits one adds its emission and carries on from the hit point, stepped
@@ -307,26 +470,13 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
   Builder b;
   b.max_leaf = max_leaf;
   b.prims.resize(n_faces);
-  float extent = 0.0f;   // largest finite |coordinate| of the scene
-  bool all_finite = true;
   for (uint32_t i = 0; i < n_faces; ++i) {
     Prim& p = b.prims[i];
     p.face = i;
-    p.box.reset();
-    for (int k = 0; k < 3; ++k) {
-      const float* v = &faces[i].vertices[k].x;
-      for (int a = 0; a < 3; ++a) {
-        // NaN and infinite coordinates would poison every ancestor box (an infinite one gives the quantised nodes an origin of
-        // -inf, and every plane of such a node decodes to NaN): keep them out of the bounds.  Such a face can never pass
-        // Moller-Trumbore either way — an infinite edge makes the determinant +-inf or NaN, and with 1 / det = 0 or NaN the hit
-        // distance comes out NaN, which `t > 0` rejects (tests/test_gpu_parity.py: every kernel == the brute-force oracle on them).
-        if (std::fabs(v[a]) <= std::numeric_limits<float>::max()) { p.box.lo[a] = std::min(p.box.lo[a], v[a]); p.box.hi[a] = std::max(p.box.hi[a], v[a]); }
-        if (std::fabs(v[a]) <= std::numeric_limits<float>::max()) extent = std::max(extent, std::fabs(v[a]));
-        else all_finite = false;
-      }
-    }
+    RfBox fb;
+    rf_face_box(&faces[i].vertices[0].x, fb);   // (finite coordinates only: set_margins)
     for (int a = 0; a < 3; ++a) {
-      if (p.box.lo[a] > p.box.hi[a]) { p.box.lo[a] = 0.f; p.box.hi[a] = 0.f; }
+      p.box.lo[a] = fb.lo[a]; p.box.hi[a] = fb.hi[a];
       p.c[a] = 0.5f * p.box.lo[a] + 0.5f * p.box.hi[a];
     }
   }
@@ -377,33 +527,17 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
     }
   }
 
-  // The slab tests of the LDS loop and of the four-wide float walk form an axis' distances from the box's centre and half
-  // extent: tc = fma(c, 1/d, -(o/d)), then fma(-+h, |1/d|, tc).  Expressed as a displacement of the plane along the axis the
-  // roundings add up to: the reciprocal (v_rcp_f32, 1 ulp) (|o| + |p|) 2^-23, -(o/d) |o| 2^-24, tc (|o| + |c|) 2^-24 and the
-  // final fma (|o| + |p|) 2^-24 — at most (|o| + |p|) 2^-22 + |o| 2^-24 with an exact reciprocal, about 1.75 (|o| + |p|) 2^-22
-  // with a 2-ulp one.  (The box [c - h, c + h] itself contains [lo, hi] exactly: h is rounded up where the record is formed.)
-  // Bounce rays start on the scene's surfaces (|o| <= extent), so every box also gets extent * 2^-20 — 2.3x the worst case at
-  // |o| = |p| = extent — and |p| * 1e-6 on top.  Origins farther out — a camera much farther out than the scene, or a light
-  // sphere far outside the mesh, which paths bounce off (origin_reach) — are the launcher's business (ptamd_api.cpp:
-  // far_origin_camera, margins_cover against Bvh::margin_floor; every face is tested beyond it).  Widening the boxes by
-  // reach * 2^-20 instead would cover the slab test but not Moller-Trumbore's own rounding, which grows with |o - v0| / det:
-  // with origins 1e4 .. 6e4 units out, a random soup still gave 1 to 52 of 200 000 rays whose brute-force hit (a grazing one,
-  // off the triangle by its rounding) lay outside every such box.
-  const float origin_margin = extent * (1.0f / 1048576.0f);
-  out.extent = extent;
-  out.reach = origin_reach(lights, n_lights, extent);
-  out.all_finite = all_finite;
-  out.margin_floor = margin + origin_margin;
+  // (the planes' margins: write_node_planes)
+  out.margin = margin;
+  out.split = n_refs != n_faces;
+  const float origin_margin = set_margins(out, faces, n_faces, lights, n_lights);
+  out.raw.assign((size_t)n_nodes * 8, 0.0f);
   uint32_t tri_cursor = 0;
   std::vector<uint32_t> leaf_info(b.nodes.size(), 0u);   // build-node id -> first_tri | count << 24 (leaves only)
   for (uint32_t k = 0; k < n_nodes; ++k) {
     const BuildNode& bn = b.nodes[order[k]];
     float* q = &out.nodes[(size_t)k * 16];
-    for (int a = 0; a < 3; ++a) {
-      float lo = bn.box.lo[a], hi = bn.box.hi[a];
-      q[a] = lo - (margin + origin_margin + std::fabs(lo) * 1e-6f);
-      q[4 + a] = hi + (margin + origin_margin + std::fabs(hi) * 1e-6f);
-    }
+    for (int a = 0; a < 3; ++a) { out.raw[(size_t)k * 8 + a] = bn.box.lo[a]; out.raw[(size_t)k * 8 + 4 + a] = bn.box.hi[a]; }
     uint32_t info = 0, child = 0;
     if (bn.left < 0) {
       out.n_leaves++;
@@ -415,21 +549,7 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
       info = tri_cursor | ((uint32_t)ids.size() << 24);
       leaf_info[order[k]] = info;
       out.max_leaf = std::max(out.max_leaf, (uint32_t)ids.size());
-      for (uint32_t fi : ids) {
-        const ptamd_face& f = faces[fi];
-        float* t = &out.tris[(size_t)tri_cursor * 12];
-        // e1/e2 are the reference's v0v1/v0v2 (intersection.cuh:106-107): same subtraction.  Record order e1, e2, v0,
-        // index: the determinant test needs only the first 24 bytes, v0 and the index come with the second read
-        t[0] = f.vertices[1].x - f.vertices[0].x;
-        t[1] = f.vertices[1].y - f.vertices[0].y;
-        t[2] = f.vertices[1].z - f.vertices[0].z;
-        t[3] = f.vertices[2].x - f.vertices[0].x;
-        t[4] = f.vertices[2].y - f.vertices[0].y;
-        t[5] = f.vertices[2].z - f.vertices[0].z;
-        t[6] = f.vertices[0].x; t[7] = f.vertices[0].y; t[8] = f.vertices[0].z;
-        t[9] = u2f(fi);
-        tri_cursor++;
-      }
+      for (uint32_t fi : ids) out.tris[(size_t)tri_cursor++ * 12 + 9] = u2f(fi);   // (the record itself: write_tri_records)
     } else {
       child = pos[bn.right] | ((uint32_t)bn.axis << 30);
     }
@@ -439,6 +559,9 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
   }
   out.tris.resize((size_t)tri_cursor * 12);
   out.n_tris = tri_cursor;
+  write_tri_records(out, faces);
+  write_node_planes(out, origin_margin);
+  plan_refit(out);
 
   // ---- the same tree, collapsed to four children per node (layout: ptamd_internal.h).  A node's children start as the
   // two children of a binary node; the interior child with the largest box is replaced by its own two children until
@@ -483,64 +606,26 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
     for (size_t w = 0; w < wide_root.size(); ++w) wide_of[(size_t)wide_root[w]] = (int)w;
     out.n_nodes4 = (uint32_t)wide.size();
     out.nodes4.assign((size_t)out.n_nodes4 * 32, 0.0f);
+    out.wide_child.assign((size_t)out.n_nodes4 * 4, 0xFFFFFFFFu);
     for (size_t w = 0; w < wide.size(); ++w) {
       float* q = &out.nodes4[w * 32];
-      float key[4][8];
       for (int c = 0; c < 4; ++c) {
-        if (wide[w].child[c] < 0) {
-          // empty slot: a point box far beyond MAX_DIST (no ray reaches it: its slab distances are +-huge, never within
-          // [0, best <= 1e5]), reference 0xFFFFFFFF
-          for (int a = 0; a < 3; ++a) { q[a * 4 + c] = 3.0e38f; q[12 + a * 4 + c] = 0.0f; }   // (centre, half extent)
-          q[24 + c] = u2f(0xFFFFFFFFu);
-          continue;
-        }
-        const BuildNode& cn = b.nodes[(size_t)wide[w].child[c]];
-        for (int a = 0; a < 3; ++a) {
-          const float lo = cn.box.lo[a], hi = cn.box.hi[a];
-          // stored as centre and half extent (the walk then needs no min / max per axis: t(centre) -+ half * |1/d|); the half extent
-          // is rounded up, so [centre - half, centre + half] contains the inflated box; a box that is not finite becomes "everything"
-          const float blo = lo - (margin + origin_margin + std::fabs(lo) * 1e-6f), bhi = hi + (margin + origin_margin + std::fabs(hi) * 1e-6f);
-          float ctr = 0.5f * blo + 0.5f * bhi;
-          float half = std::max(bhi - ctr, ctr - blo) * 1.00000024f;
-          if (!(std::fabs(blo) <= 3.0e38f && std::fabs(bhi) <= 3.0e38f)) { ctr = 0.0f; half = 3.0e38f; }
-          q[a * 4 + c] = ctr;
-          q[12 + a * 4 + c] = half;
-        }
-        uint32_t ref;
-        if (cn.left < 0) {
-          const uint32_t info = leaf_info[(size_t)wide[w].child[c]];
-          ref = 0x80000000u | ((info >> 24) << 24) | (info & 0xFFFFFFu);   // leaf: count in bits 24..30, first triangle below
-        } else {
-          ref = (uint32_t)wide_of[(size_t)wide[w].child[c]];
+        uint32_t ref = 0xFFFFFFFFu;   // empty slot
+        if (wide[w].child[c] >= 0) {
+          const BuildNode& cn = b.nodes[(size_t)wide[w].child[c]];
+          out.wide_child[w * 4 + (size_t)c] = pos[(size_t)wide[w].child[c]];
+          if (cn.left < 0) {
+            const uint32_t info = leaf_info[(size_t)wide[w].child[c]];
+            ref = 0x80000000u | ((info >> 24) << 24) | (info & 0xFFFFFFu);   // leaf: count in bits 24..30, first triangle below
+          } else {
+            ref = (uint32_t)wide_of[(size_t)wide[w].child[c]];
+          }
         }
         q[24 + c] = u2f(ref);
-        // traversal order of octant o: children sorted by the centre of their box along (+-1, +-1, +-1)
-        for (int o = 0; o < 8; ++o) {
-          float k = 0.0f;
-          for (int a = 0; a < 3; ++a) {
-            const float ctr = 0.5f * cn.box.lo[a] + 0.5f * cn.box.hi[a];
-            k += ((o >> a) & 1) ? -ctr : ctr;
-          }
-          key[c][o] = k;
-        }
       }
-      // halfword o of q[28..31]: nibble c = the children a ray of octant o visits AFTER child c (farther ones)
-      uint32_t words[4] = { 0, 0, 0, 0 };
-      for (int o = 0; o < 8; ++o) {
-        uint32_t half = 0;
-        for (int c = 0; c < 4; ++c) {
-          if (wide[w].child[c] < 0) continue;
-          uint32_t farther = 0;
-          for (int d = 0; d < 4; ++d) {
-            if (d == c || wide[w].child[d] < 0) continue;
-            if (key[d][o] > key[c][o] || (key[d][o] == key[c][o] && d > c)) farther |= 1u << d;
-          }
-          half |= farther << (4 * c);
-        }
-        words[o >> 1] |= half << (16 * (o & 1));
-      }
-      for (int i = 0; i < 4; ++i) q[28 + i] = u2f(words[i]);
     }
+    // child boxes and the traversal order of every octant (children sorted by the centre of their box along (+-1, +-1, +-1))
+    write_wide_nodes(out, origin_margin);
 
     // ---- ... and the same four-wide nodes in 64 bytes (Bvh::nodes4q): child boxes as 8-bit planes on a per-node grid (float
     // origin, one power-of-two scale per axis), rounded outward.  Half the bytes and half the load instructions per visit.
@@ -863,6 +948,31 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
       }
     }
   }
+  return PTAMD_OK;
+}
+
+float bvh_margins(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights)
+{
+  return set_margins(bvh, faces, n_faces, lights, n_lights);
+}
+
+// The host definition of a refit: the tree's topology kept (links, leaf ranges, wide references, the schedule), everything that
+// depends on vertex positions formed again from `faces` with the functions build_bvh forms it with.  Keeps no state: refitting to
+// the faces a tree was built from reproduces the build's tables byte for byte.  The quantised node forms are not refitted.
+int refit_bvh(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights)
+{
+  if (n_faces && !faces) { set_error("refit_bvh: null faces"); return PTAMD_ERR_ARG; }
+  if (bvh.split || !bvh.nodes4q.empty() || !bvh.nodes8.empty()) {
+    set_error("refit_bvh: a tree with pre-split references or quantised node forms is not refitted");
+    return PTAMD_ERR_ARG;
+  }
+  if (n_faces != bvh.n_tris) { set_error("refit_bvh: the face count differs from the tree's"); return PTAMD_ERR_ARG; }
+  if (n_faces == 0) return PTAMD_OK;
+  const float origin_margin = set_margins(bvh, faces, n_faces, lights, n_lights);
+  write_tri_records(bvh, faces);
+  refit_raw_boxes(bvh, faces);
+  write_node_planes(bvh, origin_margin);
+  write_wide_nodes(bvh, origin_margin);
   return PTAMD_OK;
 }
 
@@ -1254,5 +1364,27 @@ extern "C" int ptamd_host_origin_reach(const ptamd_face* faces, uint32_t n_faces
   out[1] = n_faces ? bvh.reach : ptamd::origin_reach(lights, n_lights, 0.0f);
   out[2] = bvh.margin_floor;
   out[3] = (n_faces == 0 || ptamd::margins_cover(bvh.extent, bvh.margin_floor, out[1])) ? 1.0f : 0.0f;
+  return PTAMD_OK;
+}
+
+extern "C" int ptamd_host_bvh_refit_trace(const ptamd_face* faces_a, const ptamd_face* faces_b, uint32_t n_faces, const float* rays, uint32_t n,
+                                          int32_t* out_binary, int32_t* out_wide)
+{
+  if ((n_faces && (!faces_a || !faces_b)) || (n && (!rays || !out_binary || !out_wide))) { ptamd::set_error("ptamd_host_bvh_refit_trace: null argument"); return PTAMD_ERR_ARG; }
+  ptamd::Bvh bvh;
+  int rc = ptamd::build_bvh(faces_a, n_faces, 1e-3f, 4, bvh, 0u);
+  if (rc != PTAMD_OK || (rc = ptamd::refit_bvh(bvh, faces_b, n_faces, nullptr, 0)) != PTAMD_OK) return rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    ptamd::HostHit h[2];
+    ptamd::bvh_trace_host(bvh, faces_b, rays + (size_t)i * 6, rays + (size_t)i * 6 + 3, h[0], nullptr, nullptr);
+    ptamd::bvh4_trace_host(bvh, rays + (size_t)i * 6, rays + (size_t)i * 6 + 3, h[1], nullptr, nullptr);
+    int32_t* outs[2] = { out_binary, out_wide };
+    for (int k = 0; k < 2; ++k) {
+      outs[k][i * 4 + 0] = h[k].kind;
+      outs[k][i * 4 + 1] = h[k].index;
+      std::memcpy(&outs[k][i * 4 + 2], &h[k].t, 4);
+      outs[k][i * 4 + 3] = 0;
+    }
+  }
   return PTAMD_OK;
 }

@@ -102,6 +102,16 @@ struct Bvh {
   bool all_finite = true;        // no vertex coordinate is NaN or infinite
   float reach = 0.0f;            // origin reach: largest |coordinate| of a ray origin the path can form (origin_reach)
   float margin_floor = 0.0f;     // smallest inflation any box face received (absolute margin + extent * 2^-20)
+  // ---- what a refit needs beside the tables (refit_bvh, csrc/pt_refit.hip): nothing of it is read by a walk
+  float margin = 0.0f;           // the absolute margin the tree was built with
+  bool split = false;            // references were pre-split (PTAMD_BVH_SPLIT_ALPHA): leaf boxes are clipped boxes, not refitted
+  std::vector<float> raw;        // the boxes before inflation, 8 floats per node {lo.xyz, 0, hi.xyz, 0}
+  std::vector<uint32_t> wide_child;     // per four-wide node and slot: the binary node the child was made from (0xFFFFFFFF: empty)
+  // the schedule that forms boxes children first (bvh_builder.cpp: plan_refit): groups {root node, nodes, first level, levels} of
+  // subtrees of at most kRefitSubtreeNodes nodes; per level the end of its entries in refit_sched; the interior nodes by
+  // subtree and ascending height; the levels of the interior nodes above the subtree roots
+  std::vector<uint32_t> refit_groups, refit_levels, refit_sched;
+  uint32_t refit_top_first = 0, refit_top_levels = 0;
 };
 
 
@@ -113,6 +123,16 @@ constexpr uint32_t kBvhForm8 = 1u, kBvhForm4q = 2u;
 // Bvh::reach (origin_reach), not the boxes
 int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms = kBvhForm8 | kBvhForm4q,
               const ptamd_light* lights = nullptr, uint32_t n_lights = 0);
+
+// The same topology for new vertex positions: triangle records, raw boxes (a leaf's from its faces, an interior node's from its
+// children's), node planes, four-wide child boxes and visiting orders, extent / reach / margin_floor — all formed by the functions
+// build_bvh forms them with (csrc/pt_refit.h), so the walks stay exact on the new faces whatever the deformation did to the
+// tree's quality.  n_faces must equal the built count.  PTAMD_ERR_ARG for trees with pre-split references or quantised forms.
+int refit_bvh(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights = nullptr, uint32_t n_lights = 0);
+
+// The host pass of an update on its own: extent, all_finite, reach and margin_floor of `bvh` (whose margin is set) for `faces`, by
+// build_bvh's rule (non-finite coordinates stay out of the extent); returns the origin-dependent margin extent * 2^-20.
+float bvh_margins(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights);
 
 // The origin reach of a scene: the larger of the triangle extent and, over all lights, (max-axis |centre| + |radius| + 0.03)
 // times (1 + 2^-6) — the largest max-axis |coordinate| of any origin the path forms (bvh_builder.cpp).  Infinite when a light's

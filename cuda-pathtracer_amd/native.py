@@ -66,6 +66,10 @@ class SceneDesc(C.Structure):
                 ("texels", C.POINTER(C.c_float)), ("n_texel_floats", C.c_uint64)]
 
 
+class SceneUpdateDesc(C.Structure):      # ptamd_scene_update_desc (include/ptamd.h)
+    _fields_ = [("scene_id", C.c_uint32), ("faces", C.POINTER(Face)), ("n_faces", C.c_uint32), ("stream", C.c_void_p)]
+
+
 class Launch(C.Structure):
     _fields_ = [("surface_rgba8", C.c_void_p), ("temporal_framebuffer", C.c_void_p), ("stream", C.c_void_p),
                 ("camera", Camera), ("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32),
@@ -130,6 +134,10 @@ class AdaptiveDesc(C.Structure):          # ptamd_adaptive_desc (include/ptamd.h
 ADAPTIVE_ERR_FLOOR = 0.01                             # ptamd_adaptive_desc.err_floor 0
 
 
+# ptamd_scene_table_read / ptamd_host_scene_refit: which table
+TABLE_NODES, TABLE_TRIS_BVH, TABLE_NODES4, TABLE_TRIS_BRUTE, TABLE_SHADE, TABLE_SCALARS = 0, 1, 2, 3, 4, 5
+TABLE_NAMES = ("nodes", "tris_bvh", "nodes4", "tris_brute", "shade")
+
 FEATURE_MISS, FEATURE_MESH, FEATURE_LIGHT = 0, 1, 2   # kind of a feature record (code >> 30)
 FEATURE_BYTES = 32                                    # per pixel: {normal.xyz, t} {albedo.rgb, kind << 30 | index}
 DENOISE_MAX_LEVELS = 8
@@ -169,6 +177,13 @@ SIGNATURES = {
     "ptamd_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
     "ptamd_destroy": (None, [C.c_void_p]),
     "ptamd_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32)]),
+    "ptamd_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDesc)]),
+    "ptamd_scene_release": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ptamd_scene_table_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_host_scene_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.c_void_p,
+                                         C.POINTER(C.c_uint64)]),
+    "ptamd_host_bvh_refit_trace": (C.c_int, [C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ptamd_upload_cubemap": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]),
     "ptamd_setup_function_tables": (C.c_int, [C.c_void_p]),
     "ptamd_raytrace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.c_uint32,

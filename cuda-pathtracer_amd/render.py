@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import native as N
-from .scene import HostScene
+from .scene import FACE_DTYPE, HostScene
 
 POST_NONE, POST_GRAYSCALE, POST_SEPIA, POST_INVERT = 0, 1, 2, 3
 REFERENCE_BOUNCES = 3  # static_samples = 1 -> max_bounces = 3 (raytrace.cu:243,66)
@@ -82,6 +82,31 @@ class Context:
         sid = C.c_uint32()
         N.check(self._lib.ptamd_upload_scene(self._h, C.byref(d), C.byref(sid)))
         return sid.value
+
+    def update_scene(self, scene_id: int, faces, stream=None) -> None:
+        """ptamd_scene_update: the scene's faces replaced in place (a HostScene or a FACE_DTYPE array in the storage order of the
+        upload, same count, same material ids), its tree refitted on the device; asynchronous on `stream`."""
+        faces = np.ascontiguousarray(faces.faces if isinstance(faces, HostScene) else faces, dtype=FACE_DTYPE)
+        d = N.SceneUpdateDesc()
+        d.scene_id = scene_id
+        d.faces = faces.ctypes.data_as(C.POINTER(N.Face)); d.n_faces = len(faces)
+        d.stream = _stream_handle(stream)
+        N.check(self._lib.ptamd_scene_update(self._h, C.byref(d)))   # (the faces are copied before the call returns)
+
+    def release_scene(self, scene_id: int) -> None:
+        """ptamd_scene_release: frees the scene's device tables (synchronises); the id stays taken."""
+        N.check(self._lib.ptamd_scene_release(self._h, scene_id))
+
+    def read_scene_tables(self, scene_id: int) -> dict:
+        """The scene's five geometry tables as the device holds them (ptamd_scene_table_read; synchronises): name -> bytes."""
+        out = {}
+        for which, name in enumerate(N.TABLE_NAMES):
+            n = C.c_uint64(0)
+            N.check(self._lib.ptamd_scene_table_read(self._h, scene_id, which, None, C.byref(n)))
+            buf = np.zeros(n.value, np.uint8)
+            N.check(self._lib.ptamd_scene_table_read(self._h, scene_id, which, buf.ctypes.data, C.byref(n)))
+            out[name] = buf
+        return out
 
     def upload_cubemap(self, faces: np.ndarray) -> int:
         faces = np.ascontiguousarray(faces, dtype=np.float32)
@@ -281,6 +306,43 @@ def origin_reach(scene: HostScene):
     N.check(N.load().ptamd_host_origin_reach(scene.faces.ctypes.data_as(C.POINTER(N.Face)), len(scene.faces),
                                              scene.lights.ctypes.data_as(C.POINTER(N.Light)), len(scene.lights), out))
     return out[0], out[1], out[2], bool(out[3])
+
+
+def host_scene_tables(scene: HostScene, *steps) -> dict:
+    """The host definition of Context.update_scene (ptamd_host_scene_refit, no GPU): the five tables of `scene` as an upload builds
+    them, refitted to each of `steps` in turn (at most two; HostScene or face arrays): name -> bytes, plus "scalars" = float32
+    {extent, origin reach, margin floor, all coordinates finite}."""
+    if len(steps) > 2:
+        raise ValueError("at most two refit steps")
+    faces = [np.ascontiguousarray(f.faces if isinstance(f, HostScene) else f, dtype=FACE_DTYPE) for f in steps]
+    for f in faces:
+        if len(f) != len(scene.faces):
+            raise ValueError("a refit keeps the face count")
+    ptrs = [f.ctypes.data_as(C.POINTER(N.Face)) for f in faces] + [None, None]
+    d = scene.desc()
+    lib = N.load()
+    out = {}
+    for which, name in enumerate(N.TABLE_NAMES + ("scalars",)):
+        n = C.c_uint64(0)
+        N.check(lib.ptamd_host_scene_refit(C.byref(d), ptrs[0], ptrs[1], which, None, C.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        N.check(lib.ptamd_host_scene_refit(C.byref(d), ptrs[0], ptrs[1], which, buf.ctypes.data, C.byref(n)))
+        out[name] = buf.view(np.float32) if name == "scalars" else buf
+    return out
+
+
+def host_bvh_refit_trace(scene_a: HostScene, scene_b: HostScene, rays: np.ndarray):
+    """Builds on scene_a's faces, refits to scene_b's, traces `rays` through the host mirrors of the binary and the four-wide walk
+    (ptamd_host_bvh_refit_trace, no GPU): (int32[n,4], int32[n,4])."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if len(scene_a.faces) != len(scene_b.faces):
+        raise ValueError("a refit keeps the face count")
+    out = np.zeros((2, len(rays), 4), dtype=np.int32)
+    N.check(N.load().ptamd_host_bvh_refit_trace(scene_a.faces.ctypes.data_as(C.POINTER(N.Face)),
+                                                scene_b.faces.ctypes.data_as(C.POINTER(N.Face)), len(scene_a.faces),
+                                                rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays),
+                                                out[0].ctypes.data_as(C.POINTER(C.c_int32)), out[1].ctypes.data_as(C.POINTER(C.c_int32))))
+    return out[0], out[1]
 
 
 def host_bvh_trace(scene: HostScene, rays: np.ndarray):

@@ -48,6 +48,29 @@ def tessellate(scene: HostScene, n: int) -> HostScene:
                      scene.texels, scene.camera, scene.cubemap)
 
 
+def deform(scene: HostScene, t: float, amplitude: float, frequency: float = None, shading: bool = False) -> HostScene:
+    """Moving geometry for Context.update_scene: every vertex displaced by a smooth function of its own position and the
+    time `t`, p + A sin(k p.yzx + t (1, 1.3, 1.7)) in binary32, so vertices shared between faces stay shared.  amplitude is in
+    scene units; frequency k defaults to 2 pi / (the scene's largest finite |coordinate|).  Face count, storage order,
+    material ids, materials, lights and camera are untouched.  shading=True also perturbs normals, texcoords and tangents
+    (each by a function of its own value and t), so that a stale shading record cannot pass for a fresh one."""
+    f = scene.faces.copy()
+    p = scene.faces["vertices"]
+    finite = np.abs(p[np.isfinite(p)])
+    extent = np.float32(finite.max()) if finite.size else np.float32(1.0)
+    k = np.float32(2.0 * np.pi / max(float(extent), 1e-30) if frequency is None else frequency)
+    phase = np.float32(t) * np.array([1.0, 1.3, 1.7], np.float32)
+    with np.errstate(all="ignore"):
+        f["vertices"] = (p + np.float32(amplitude) * np.sin(k * p[..., [1, 2, 0]] + phase)).astype(np.float32)
+        if shading:
+            a = np.float32(0.25)
+            f["normals"] = (scene.faces["normals"] + a * np.sin(np.float32(3.0) * scene.faces["normals"][..., [1, 2, 0]] + phase)).astype(np.float32)
+            f["texcoords"] = (scene.faces["texcoords"] + a * np.sin(np.float32(5.0) * scene.faces["texcoords"][..., [1, 0]] + phase[:2])).astype(np.float32)
+            f["tangent"] = (scene.faces["tangent"] + a * np.sin(np.float32(2.0) * scene.faces["tangent"][..., [1, 2, 0]] + phase)).astype(np.float32)
+    return HostScene(f, scene.mesh_sizes, scene.materials, scene.lights, scene.textures, scene.texels, scene.camera,
+                     scene.cubemap, scene.unloaded_textures)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # BASELINE.json configs[3]: a "Sponza-class" scene written as OBJ + MTL + .scene so that it goes through the same
 # loader path as the reference's assets (scene.cpp:304-358 -> tinyobj -> flatten; SURVEY §8-d C4).

@@ -192,6 +192,47 @@ int ptamd_upload_cubemap(ptamd_context* ctx, const float* faces, uint32_t size, 
  * (hipFuncGetAttributes) and fails with PTAMD_ERR_HIP when the device image cannot be used. */
 int ptamd_setup_function_tables(ptamd_context* ctx);
 
+/* ---- Moving geometry ---------------------------------------------------------------------------------------
+ * ptamd_scene_update replaces the vertices, normals, texcoords and tangents of every face of an uploaded scene in place: the
+ * tree keeps its topology and its boxes are formed again from the new vertices on the device (a refit), so every kernel stays
+ * bit-identical to the reference on the NEW faces whatever the deformation did to the tree.  material_id of every face must equal
+ * the uploaded one; materials, textures, lights, the face count, ptamd_scene_info, LDS residency, flatness and the kernel form a
+ * launch takes do not change — except the walk-or-every-face decision (a camera or light beyond the reach of the box margins),
+ * which later launches make by the new extent.
+ *
+ * faces is a HOST array of n_faces records (= the uploaded count) in the storage order of the upload; it is copied before the
+ * call returns.  The update is asynchronous on `stream`: launches enqueued before it, on any stream of the context, render the
+ * old geometry (it waits for the megakernels of pipelined and machine_share > 1 launches that still read the scene, and for what
+ * ptamd_raytrace / _ex issued on other streams); launches enqueued after it render the new one (lanes and other streams wait for
+ * it).  Other readers of the tables (ptamd_trace_rays, _render_features, the denoisers, adaptive rounds) are ordered against it
+ * by stream order: issue them on the update's stream or behind an event of your own.  The first update of a scene allocates
+ * its staging buffers; no later one synchronises the host (it waits, at most, for the copy of the update before last).
+ *
+ * Errors, before anything is enqueued: PTAMD_ERR_ARG for a null pointer, a bad or released id, another face count, a changed
+ * material_id, and for scenes of a context built with the knob-only node forms (PTAMD_WIDE8, PTAMD_WIDE4Q) or with reference
+ * pre-splitting (PTAMD_BVH_SPLIT_ALPHA), whose tables are not refitted; PTAMD_ERR_LIMIT while any stream of the context holds a
+ * captured launch (until ptamd_release_captured: the captured launch has baked in the walk-or-every-face choice) and for a
+ * `stream` that is capturing.
+ *
+ * Not tracked: a ptamd_denoise_history knows nothing about moved geometry (there are no motion vectors) and a
+ * ptamd_adaptive_state's moments describe the old image: reset both after an update.
+ *
+ * What a refitted tree costs the renderer (measured on the 264 832-triangle atrium, 1080p x 4 spp x 4 bounces, beside a fresh
+ * upload of the same faces; scripts/gpu_refit.py): 0.5 % / 0.8 % / 19 % of the sample rate at displacements of
+ * 0.1 % / 1 % / 10 % of the scene's extent, for an update of 3 ms against an upload of 0.7 s.  Fall back to
+ * ptamd_scene_release + ptamd_upload_scene when the render time lost until the next rebuild exceeds that upload. */
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_face* faces;   /* HOST array, n_faces records in the storage order of the upload */
+  uint32_t n_faces;          /* must equal the uploaded count */
+  void* stream;              /* the update is asynchronous on this stream */
+} ptamd_scene_update_desc;
+int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* desc);
+
+/* Waits for the device, frees the scene's tables and leaves a tombstone: ids of other scenes stay valid, any later use of this
+ * one is PTAMD_ERR_ARG. */
+int ptamd_scene_release(ptamd_context* ctx, uint32_t scene_id);
+
 /* ---- the hot path ---------------------------------------------------------------------
  * ptamd_raytrace == one reference raytrace() call (raytrace.cu:287-325): 1 sample per
  * pixel, frame counter kept in the context (the reference's function-static `seed`,
@@ -435,6 +476,20 @@ int ptamd_host_bvh8_trace(const ptamd_face* faces, uint32_t n_faces, const float
  * (as for a camera beyond that distance).  DESIGN.md §4. */
 int ptamd_host_origin_reach(const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights,
                             float* out);
+
+/* Test hooks for ptamd_scene_update.  ptamd_scene_table_read copies one table of an uploaded scene back (synchronises the
+ * device): which = 0 binary nodes, 1 leaf-major triangle records, 2 four-wide nodes, 3 storage-order triangle records, 4 shading
+ * records (flat scenes: the compact records behind them).  *bytes: in, the room in `out`; out, the table's size (out == NULL: the
+ * size only).  ptamd_host_scene_refit is the host definition of an update, no device needed: the tables of `scene` as an upload
+ * builds them, refitted to faces_b and then to faces_c where those are not NULL (scene->n_faces records each); which as above,
+ * 5 = four floats {extent, origin reach, margin floor, all coordinates finite}.  ptamd_host_bvh_refit_trace builds on faces_a,
+ * refits to faces_b and traces rays through the host mirrors of the binary and the four-wide walk (records as
+ * ptamd_host_bvh_trace). */
+int ptamd_scene_table_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which, void* out, uint64_t* bytes);
+int ptamd_host_scene_refit(const ptamd_scene_desc* scene, const ptamd_face* faces_b, const ptamd_face* faces_c, uint32_t which,
+                           void* out, uint64_t* bytes);
+int ptamd_host_bvh_refit_trace(const ptamd_face* faces_a, const ptamd_face* faces_b, uint32_t n_faces, const float* rays, uint32_t n,
+                               int32_t* out_binary, int32_t* out_wide);
 
 /* ---- Edge-aware denoiser -------------------------------------------------------------------------------
  * An opt-in pass behind the accumulator: the spatial half of SVGF over an edge-avoiding a-trous wavelet, guided by a first-hit
