@@ -140,7 +140,12 @@ struct RefitParams {
   uint32_t n_faces, n_tris, n_nodes, n_nodes4;
   uint32_t n_groups, top_level_first, top_levels, flat;
   float margin, origin_margin;
+  // ptamd_scene_update_device: the word extent * 2^-20 of the NEW faces, written by pt_refit_device.hip's reduction in the kernels
+  // before these; read in place of origin_margin.  Null for ptamd_scene_update, whose host pass has the value at once.
+  const float* device_margin;
 };
+
+PT_RF_HD float rf_origin_margin(const RefitParams& r) { return r.device_margin ? *r.device_margin : r.origin_margin; }
 
 } // namespace ptamd
 

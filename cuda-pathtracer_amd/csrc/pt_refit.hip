@@ -8,6 +8,8 @@
 //             the staged faces, then interior nodes height by height, raw boxes in LDS; writes raw boxes and node planes
 //   top       one workgroup: the interior nodes above the subtree roots, height by height, raw boxes in global memory
 //   wide      one thread per four-wide node: child boxes from the raw boxes of the binary nodes they were made from, visiting order
+// ptamd_scene_update_device runs the same four behind pt_refit_device.hip's extent reduction: `faces` is then the caller's buffer and
+// the origin margin comes from the word that reduction wrote (RefitParams::device_margin).
 #include "pt_refit.h"
 
 namespace ptamd {
@@ -35,13 +37,11 @@ __device__ __forceinline__ void store_tri_record(float* dst, const float (&v)[9]
 }
 
 // planes of binary node k from its raw box; the w words (leaf word, child word) are kept
-__device__ __forceinline__ void store_node(const RefitParams& r, uint32_t k, const RfBox& b, float info, float child)
+__device__ __forceinline__ void store_node(const RefitParams& r, float om, uint32_t k, const RfBox& b, float info, float child)
 {
   float* q = r.nodes + (size_t)k * 16u;
-  st4(q, make_float4(rf_plane_lo(b.lo[0], r.margin, r.origin_margin), rf_plane_lo(b.lo[1], r.margin, r.origin_margin),
-                     rf_plane_lo(b.lo[2], r.margin, r.origin_margin), info));
-  st4(q + 4, make_float4(rf_plane_hi(b.hi[0], r.margin, r.origin_margin), rf_plane_hi(b.hi[1], r.margin, r.origin_margin),
-                         rf_plane_hi(b.hi[2], r.margin, r.origin_margin), child));
+  st4(q, make_float4(rf_plane_lo(b.lo[0], r.margin, om), rf_plane_lo(b.lo[1], r.margin, om), rf_plane_lo(b.lo[2], r.margin, om), info));
+  st4(q + 4, make_float4(rf_plane_hi(b.hi[0], r.margin, om), rf_plane_hi(b.hi[1], r.margin, om), rf_plane_hi(b.hi[2], r.margin, om), child));
   float* w = r.raw + (size_t)k * 8u;
   st4(w, make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f));
   st4(w + 4, make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f));
@@ -96,6 +96,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_subtrees(const RefitPa
   const uint4 g = reinterpret_cast<const uint4*>(r.groups)[blockIdx.x];
   const uint32_t root = g.x, size = g.y;
   if (size > kRefitSubtreeNodes || root >= r.n_nodes || size > r.n_nodes - root) return;   // (the host checked the schedule: never taken)
+  const float om = rf_origin_margin(r);   // (a device-faces update: the word the reduction before this kernel wrote)
   // leaves: the union of their faces' boxes
   for (uint32_t i = threadIdx.x; i < size; i += kRefitThreads) {
     const uint32_t k = root + i;
@@ -115,7 +116,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_subtrees(const RefitPa
       rf_box_grow(b, fb);
     }
     for (int a = 0; a < 3; ++a) { box[a][i] = b.lo[a]; box[3 + a][i] = b.hi[a]; }
-    store_node(r, k, b, info, child);
+    store_node(r, om, k, b, info, child);
   }
   __syncthreads();
   uint32_t begin = g.z ? r.levels[g.z - 1u] : 0u;
@@ -133,7 +134,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_subtrees(const RefitPa
         b.hi[a] = rf_max(box[3 + a][left], box[3 + a][right]);
       }
       for (int a = 0; a < 3; ++a) { box[a][i] = b.lo[a]; box[3 + a][i] = b.hi[a]; }
-      store_node(r, k, b, info, child);
+      store_node(r, om, k, b, info, child);
     }
     __syncthreads();
     begin = end;
@@ -142,6 +143,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_subtrees(const RefitPa
 
 __global__ void __launch_bounds__(kRefitThreads) pt_refit_top(const RefitParams r)
 {
+  const float om = rf_origin_margin(r);
   uint32_t begin = r.top_level_first ? r.levels[r.top_level_first - 1u] : 0u;
   for (uint32_t l = r.top_level_first; l < r.top_level_first + r.top_levels; ++l) {
     const uint32_t end = r.levels[l];
@@ -158,7 +160,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_top(const RefitParams 
       load_raw(r.raw, left, lb);
       load_raw(r.raw, right, rb);
       for (int a = 0; a < 3; ++a) { b.lo[a] = rf_min(lb.lo[a], rb.lo[a]); b.hi[a] = rf_max(lb.hi[a], rb.hi[a]); }
-      store_node(r, k, b, info, child);
+      store_node(r, om, k, b, info, child);
     }
     __syncthreads();
     begin = end;
@@ -169,6 +171,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_wide(const RefitParams
 {
   const uint32_t w = blockIdx.x * kRefitThreads + threadIdx.x;
   if (w >= r.n_nodes4) return;
+  const float om = rf_origin_margin(r);
   const uint4 ch = reinterpret_cast<const uint4*>(r.wide_child)[w];
   const uint32_t child[4] = { ch.x, ch.y, ch.z, ch.w };
   float c[3][4], h[3][4], ctr[4][3];
@@ -186,7 +189,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_refit_wide(const RefitParams
     load_raw(r.raw, child[s], b);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      rf_wide_axis(b.lo[a], b.hi[a], r.margin, r.origin_margin, c[a][s], h[a][s]);
+      rf_wide_axis(b.lo[a], b.hi[a], r.margin, om, c[a][s], h[a][s]);
       ctr[s][a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
     }
   }

@@ -14,6 +14,7 @@
 #include "pt_denoise_temporal.h"
 #include "pt_launch.h"
 #include "pt_refit.h"
+#include "pt_refit_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -79,6 +80,18 @@ struct DeviceScene {
   uint32_t stage_next = 0;
   hipEvent_t updated = nullptr;                  // the last update's kernels have finished: lanes and other streams wait for it
   bool updated_valid = false;
+  // ptamd_scene_update_device: the new faces' extent is formed on the device (pt_refit_device.hip) and copied back behind the
+  // update's kernels; until a reader of extent / all_finite / reach / margin_floor has waited for it (settle_margins) those four
+  // are stale.  Two pinned slots used in turn, so a copy that lands late never overwrites the words of a newer update.
+  float* d_margin = nullptr;                     // kMarginWords floats, behind them the reduction's partials
+  float* h_margin = nullptr;                     // pinned: two slots of kMarginWords floats
+  hipEvent_t margin_ready[2] = { nullptr, nullptr };   // the copy into slot i has finished
+  bool margin_ready_valid[2] = { false, false };
+  uint32_t margin_next = 0, margin_slot = 0;
+  bool margins_pending = false;
+  // ptamd_scene_quality
+  double quality_built = 0.0;                    // the cost of the tree as uploaded (tree_quality)
+  double* d_quality = nullptr;                   // quality_groups(n_nodes) + 1 partial sums, allocated at the first query
 };
 
 struct DeviceCubemap {
@@ -251,12 +264,14 @@ int upload_padded(T*& dst, const void* src, size_t bytes, size_t pad)
 void free_scene(DeviceScene& s)
 {
   void* ptrs[] = { s.nodes, s.nodes4, s.nodes8, s.nodes4q, s.tris_bvh, s.tris_brute, s.shade, s.materials, s.lights, s.textures, s.texels,
-                   s.raw, s.refit_groups, s.refit_levels, s.refit_sched, s.wide_child, s.d_faces };
+                   s.raw, s.refit_groups, s.refit_levels, s.refit_sched, s.wide_child, s.d_faces, s.d_margin, s.d_quality };
   for (void* q : ptrs) (void)hipFree(q);
   for (int i = 0; i < 2; ++i) {
     if (s.h_stage[i]) (void)hipHostFree(s.h_stage[i]);
     if (s.staged[i]) (void)hipEventDestroy(s.staged[i]);
+    if (s.margin_ready[i]) (void)hipEventDestroy(s.margin_ready[i]);
   }
+  if (s.h_margin) (void)hipHostFree(s.h_margin);
   if (s.updated) (void)hipEventDestroy(s.updated);
   s = DeviceScene();
 }
@@ -396,6 +411,45 @@ bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam)
   // (2^-21, not the 2^-22 of a single fma: the centre / half-extent form rounds a slab distance twice — t(centre), then -+ half * |1/d| —
   // on top of the reciprocal's and -o/d's roundings: worst case about 1.75 (|origin| + |plane|) * 2^-22, bvh_builder.cpp)
   return !(margins_cover(s.extent, s.margin_floor, cam_far) && margins_cover(s.extent, s.margin_floor, s.reach)) && s.n_faces != 0;   // also true for NaN
+}
+
+bool stream_is_capturing(hipStream_t stream)
+{
+  if (stream == nullptr) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
+// Every reader of a scene's extent / all_finite / reach / margin_floor calls this first.  After ptamd_scene_update_device the
+// extent of the new faces is on its way back from the device: wait for that copy (it sits behind the update's own kernels and
+// nothing else), then reach and margin_floor by the rule of the upload and of the host update (bvh_margins_of_extent).  `stream`:
+// where the caller is about to enqueue.  A capturing one cannot wait on the host; the call is refused instead.
+int settle_margins(DeviceScene& s, hipStream_t stream, const char* who)
+{
+  if (!s.margins_pending) return PTAMD_OK;
+  if (stream_is_capturing(stream)) {
+    set_error(std::string(who) + ": the scene's margins are pending behind ptamd_scene_update_device and a capture cannot wait for "
+              "them: render the scene once, or call ptamd_scene_quality, outside the capture");
+    return PTAMD_ERR_LIMIT;
+  }
+  PT_HIP(hipEventSynchronize(s.margin_ready[s.margin_slot]));
+  const float* h = s.h_margin + (size_t)s.margin_slot * kMarginWords;
+  Bvh m;
+  m.margin = kBoxMargin;
+  bvh_margins_of_extent(m, h[0], h[1] == 0.0f, s.host_lights.data(), (uint32_t)s.host_lights.size());
+  s.extent = m.extent; s.all_finite = m.all_finite; s.reach = m.reach; s.margin_floor = m.margin_floor;
+  s.margins_pending = false;
+  return PTAMD_OK;
+}
+
+// The surface-area-heuristic cost of a binary tree over the planes the walk tests (ptamd.h: ptamd_scene_quality), terms added in
+// node order
+double tree_quality(const float* nodes, uint32_t n_nodes, uint32_t n_faces)
+{
+  if (n_nodes == 0 || n_faces == 0) return 0.0;
+  double sum = 0.0;
+  for (uint32_t k = 0; k < n_nodes; ++k) sum += rf_quality_term(nodes + (size_t)k * 16u);
+  return sum / rf_node_area(nodes);
 }
 
 // A flat scene: every face's diffuse+specular map is 1x1 (its record carries the one texel), no material a face uses has a
@@ -900,7 +954,8 @@ int do_launch(ptamd_context* ctx, const ptamd_launch* l, bool stats, const Adapt
 {
   int rc = validate_launch(ctx, l);
   LaunchPlan resolved;
-  if (rc != PTAMD_OK || (rc = resolve_kernel(ctx, l, stats, ad, resolved)) != PTAMD_OK) return rc;
+  if (rc != PTAMD_OK || (rc = settle_margins(ctx->scenes[l->scene_id], static_cast<hipStream_t>(l->stream), "ptamd_raytrace")) != PTAMD_OK ||
+      (rc = resolve_kernel(ctx, l, stats, ad, resolved)) != PTAMD_OK) return rc;
   PT_HIP(hipSetDevice(ctx->device));
   const uint32_t part_frames = persistent_family(resolved.which) ? kMaxFramesPerSlab : 1u;
   for (uint32_t k0 = 0; k0 == 0 || k0 < l->frame_count; k0 += part_frames) {
@@ -1097,11 +1152,12 @@ int denoise_workspace(ptamd_context* ctx, size_t n)
   return PTAMD_OK;
 }
 
-int denoise_ids(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id)
+// ... and the scene's margins settled for feature_scene's walk-or-every-face decision
+int denoise_ids(const char* who, ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_id, void* stream)
 {
   if (!live_scene(ctx, scene_id)) { set_error(std::string(who) + ": scene_id out of range or released"); return PTAMD_ERR_ARG; }
   if (cubemap_id >= ctx->cubemaps.size()) { set_error(std::string(who) + ": cubemap_id out of range"); return PTAMD_ERR_ARG; }
-  return PTAMD_OK;
+  return settle_margins(ctx->scenes[scene_id], static_cast<hipStream_t>(stream), who);
 }
 
 // ---------------------------------------------------------------- temporal half of the denoiser (pt_denoise_temporal.h)
@@ -1130,6 +1186,64 @@ void temporal_camera(const ptamd_camera& cam, uint32_t width, TemporalParams& t)
   t.prev_fwd = p.cam_p0 - p.cam_pos;
   t.prev_u = p.cam_u;
   t.prev_v = p.cam_v;
+}
+
+// What the two update calls refuse alike, in two steps (ptamd_scene_update checks the material ids between them)
+int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces)
+{
+  const std::string w(who);
+  if (!live_scene(ctx, scene_id)) { set_error(w + ": scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  const DeviceScene& s = ctx->scenes[scene_id];
+  if (n_faces != s.n_faces) { set_error(w + ": n_faces differs from the uploaded count"); return PTAMD_ERR_ARG; }
+  if (n_faces && !faces) { set_error(w + ": null faces"); return PTAMD_ERR_ARG; }
+  if (!s.refit_ok) {
+    set_error(w + ": this scene's tree is not refitted (built with PTAMD_WIDE8, PTAMD_WIDE4Q or PTAMD_BVH_SPLIT_ALPHA)");
+    return PTAMD_ERR_ARG;
+  }
+  return PTAMD_OK;
+}
+
+int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t stream)
+{
+  // a captured launch has baked in the walk-or-every-face choice (far_origin_camera) of the geometry it was captured with
+  for (const auto& c : ctx->sample_scratch)
+    if (c.captured) { set_error(std::string(who) + ": a captured launch pins this context's scenes (ptamd_release_captured)"); return PTAMD_ERR_LIMIT; }
+  if (stream_is_capturing(stream)) { set_error(std::string(who) + ": an update cannot be captured into a graph"); return PTAMD_ERR_LIMIT; }
+  return PTAMD_OK;
+}
+
+// RefitParams of the scene, everything but the faces and the origin margin; the shapes checked: every table the kernels index
+// exists and the schedule's level ranges lie inside it
+int refit_params(const char* who, const DeviceScene& s, RefitParams& r)
+{
+  std::memset(&r, 0, sizeof r);
+  r.nodes = reinterpret_cast<float*>(s.nodes); r.tris_bvh = reinterpret_cast<float*>(s.tris_bvh);
+  r.nodes4 = reinterpret_cast<float*>(s.nodes4); r.tris_brute = reinterpret_cast<float*>(s.tris_brute);
+  r.shade = reinterpret_cast<float*>(s.shade); r.raw = s.raw;
+  r.groups = s.refit_groups; r.levels = s.refit_levels; r.sched = s.refit_sched; r.wide_child = s.wide_child;
+  r.n_faces = s.n_faces; r.n_tris = s.n_bvh_tris; r.n_nodes = s.n_nodes; r.n_nodes4 = s.n_nodes4;
+  r.n_groups = s.n_refit_groups; r.top_level_first = s.refit_top_first; r.top_levels = s.refit_top_levels;
+  r.flat = s.flat ? 1u : 0u;
+  r.margin = kBoxMargin;
+  if (!r.nodes || !r.tris_bvh || !r.nodes4 || !r.tris_brute || !r.shade || !r.raw || !r.groups || !r.levels || !r.sched || !r.wide_child ||
+      r.n_tris != r.n_faces || r.n_nodes == 0 || r.n_groups == 0 || r.top_level_first + r.top_levels > s.n_refit_levels ||
+      s.n_refit_sched >= r.n_nodes) {
+    set_error(std::string(who) + ": the scene's refit tables are inconsistent");
+    return PTAMD_ERR_ARG;
+  }
+  return PTAMD_OK;
+}
+
+// An update waits on `stream` for every launch still reading the scene: megakernels on the lanes and internal streams (mega_done),
+// everything a stream was given so far (last_done); the previous update, which may have gone to another stream
+int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream)
+{
+  for (const auto& c : ctx->sample_scratch) {
+    for (int i = 0; i < 3; ++i) if (c.mega_done[i]) PT_HIP(hipStreamWaitEvent(stream, c.mega_done[i], 0));
+    if (c.last_done) PT_HIP(hipStreamWaitEvent(stream, c.last_done, 0));
+  }
+  if (s.updated_valid) PT_HIP(hipStreamWaitEvent(stream, s.updated, 0));
+  return PTAMD_OK;
 }
 
 } // namespace
@@ -1362,6 +1476,7 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     for (uint32_t i = 0; i < sc->n_faces; ++i) d.material_ids[i] = sc->faces[i].material_id;
     d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);
   }
+  d.quality_built = tree_quality(bvh.nodes.data(), bvh.n_nodes, sc->n_faces);
   d.info.n_faces = sc->n_faces; d.info.n_lights = sc->n_lights; d.info.n_nodes = bvh.n_nodes;
   d.info.n_leaves = bvh.n_leaves; d.info.max_leaf_size = bvh.max_leaf; d.info.depth = bvh.depth;
   d.info.node_bytes = 64; d.info.tri_bytes = 48;
@@ -1376,29 +1491,17 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
 int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
 {
   if (!ctx || !d) { set_error("ptamd_scene_update: null argument"); return PTAMD_ERR_ARG; }
-  if (!live_scene(ctx, d->scene_id)) { set_error("ptamd_scene_update: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  int rc = update_scene_checks("ptamd_scene_update", ctx, d->scene_id, d->n_faces, d->faces);
+  if (rc != PTAMD_OK) return rc;
   DeviceScene& s = ctx->scenes[d->scene_id];
-  if (d->n_faces != s.n_faces) { set_error("ptamd_scene_update: n_faces differs from the uploaded count"); return PTAMD_ERR_ARG; }
-  if (d->n_faces && !d->faces) { set_error("ptamd_scene_update: null faces"); return PTAMD_ERR_ARG; }
-  if (!s.refit_ok) {
-    set_error("ptamd_scene_update: this scene's tree is not refitted (built with PTAMD_WIDE8, PTAMD_WIDE4Q or PTAMD_BVH_SPLIT_ALPHA)");
-    return PTAMD_ERR_ARG;
-  }
   for (uint32_t i = 0; i < d->n_faces; ++i)
     if (d->faces[i].material_id != s.material_ids[i]) { set_error("ptamd_scene_update: a face's material_id differs from the uploaded one"); return PTAMD_ERR_ARG; }
-  // a captured launch has baked in the walk-or-every-face choice (far_origin_camera) of the geometry it was captured with
-  for (const auto& c : ctx->sample_scratch)
-    if (c.captured) { set_error("ptamd_scene_update: a captured launch pins this context's scenes (ptamd_release_captured)"); return PTAMD_ERR_LIMIT; }
   hipStream_t stream = static_cast<hipStream_t>(d->stream);
-  if (stream != nullptr) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-      set_error("ptamd_scene_update: an update cannot be captured into a graph");
-      return PTAMD_ERR_LIMIT;
-    }
-  }
+  if ((rc = update_capture_checks("ptamd_scene_update", ctx, stream)) != PTAMD_OK) return rc;
   if (d->n_faces == 0) return PTAMD_OK;
   PT_HIP(hipSetDevice(ctx->device));
+  RefitParams r;
+  if ((rc = refit_params("ptamd_scene_update", s, r)) != PTAMD_OK) return rc;
   const size_t bytes = (size_t)d->n_faces * sizeof(ptamd_face);
   // the first update of the scene: the staging buffers
   if (!s.d_faces) PT_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_faces), bytes));
@@ -1411,42 +1514,131 @@ int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
   // launches by it; the faces into the staging buffer whose last copy is two updates back
   Bvh m;
   m.margin = kBoxMargin;
-  const float origin_margin = bvh_margins(m, d->faces, d->n_faces, s.host_lights.data(), (uint32_t)s.host_lights.size());
+  r.origin_margin = bvh_margins(m, d->faces, d->n_faces, s.host_lights.data(), (uint32_t)s.host_lights.size());
   const uint32_t slot = s.stage_next++ & 1u;
   if (s.staged_valid[slot]) PT_HIP(hipEventSynchronize(s.staged[slot]));
   std::memcpy(s.h_stage[slot], d->faces, bytes);
-  // every launch still reading the scene: megakernels on the lanes and internal streams (mega_done), everything a stream was
-  // given so far (last_done); the previous update, which may have gone to another stream
-  for (const auto& c : ctx->sample_scratch) {
-    for (int i = 0; i < 3; ++i) if (c.mega_done[i]) PT_HIP(hipStreamWaitEvent(stream, c.mega_done[i], 0));
-    if (c.last_done) PT_HIP(hipStreamWaitEvent(stream, c.last_done, 0));
-  }
-  if (s.updated_valid) PT_HIP(hipStreamWaitEvent(stream, s.updated, 0));
+  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
   PT_HIP(hipMemcpyAsync(s.d_faces, s.h_stage[slot], bytes, hipMemcpyHostToDevice, stream));
   PT_HIP(hipEventRecord(s.staged[slot], stream));
   s.staged_valid[slot] = true;
-  RefitParams r;
-  std::memset(&r, 0, sizeof r);
   r.faces = s.d_faces;
-  r.nodes = reinterpret_cast<float*>(s.nodes); r.tris_bvh = reinterpret_cast<float*>(s.tris_bvh);
-  r.nodes4 = reinterpret_cast<float*>(s.nodes4); r.tris_brute = reinterpret_cast<float*>(s.tris_brute);
-  r.shade = reinterpret_cast<float*>(s.shade); r.raw = s.raw;
-  r.groups = s.refit_groups; r.levels = s.refit_levels; r.sched = s.refit_sched; r.wide_child = s.wide_child;
-  r.n_faces = s.n_faces; r.n_tris = s.n_bvh_tris; r.n_nodes = s.n_nodes; r.n_nodes4 = s.n_nodes4;
-  r.n_groups = s.n_refit_groups; r.top_level_first = s.refit_top_first; r.top_levels = s.refit_top_levels;
-  r.flat = s.flat ? 1u : 0u;
-  r.margin = kBoxMargin; r.origin_margin = origin_margin;
-  // shapes: every table the kernels index exists and the schedule's level ranges lie inside it
-  if (!r.nodes || !r.tris_bvh || !r.nodes4 || !r.tris_brute || !r.shade || !r.raw || !r.groups || !r.levels || !r.sched || !r.wide_child ||
-      r.n_tris != r.n_faces || r.n_nodes == 0 || r.n_groups == 0 || r.top_level_first + r.top_levels > s.n_refit_levels ||
-      s.n_refit_sched >= r.n_nodes) {
-    set_error("ptamd_scene_update: the scene's refit tables are inconsistent");
-    return PTAMD_ERR_ARG;
-  }
   PT_HIP(launch_refit(r, stream));
   PT_HIP(hipEventRecord(s.updated, stream));
   s.updated_valid = true;
+  // (the values are here at once: whatever ptamd_scene_update_device left pending is superseded)
   s.extent = m.extent; s.all_finite = m.all_finite; s.reach = m.reach; s.margin_floor = m.margin_floor;
+  s.margins_pending = false;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_device_desc* d)
+{
+  const char* who = "ptamd_scene_update_device";
+  if (!ctx || !d) { set_error("ptamd_scene_update_device: null argument"); return PTAMD_ERR_ARG; }
+  int rc = update_scene_checks(who, ctx, d->scene_id, d->n_faces, d->faces);
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
+  DeviceScene& s = ctx->scenes[d->scene_id];
+  if (d->n_faces == 0) return PTAMD_OK;
+  const size_t bytes = (size_t)d->n_faces * sizeof(ptamd_face);
+  if ((reinterpret_cast<uintptr_t>(d->faces) & 15u) != 0u) {
+    set_error("ptamd_scene_update_device: faces is not aligned to 16 bytes (the kernels use 16-byte loads)");
+    return PTAMD_ERR_ARG;
+  }
+  PT_HIP(hipSetDevice(ctx->device));
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  if (hipPointerGetAttributes(&attr, d->faces) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+    (void)hipGetLastError();   // (an unregistered host pointer is reported as an error: not a sticky one)
+    set_error("ptamd_scene_update_device: faces is not device memory of the context's device (host arrays go to ptamd_scene_update)");
+    return PTAMD_ERR_ARG;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t room = 0;
+  if (hipMemGetAddressRange(&base, &room, const_cast<ptamd_face*>(d->faces)) == hipSuccess) {
+    const size_t offset = (size_t)(reinterpret_cast<const char*>(d->faces) - static_cast<const char*>(base));
+    if (offset > room || room - offset < bytes) {
+      set_error("ptamd_scene_update_device: the allocation behind faces is smaller than n_faces records");
+      return PTAMD_ERR_ARG;
+    }
+  } else {
+    (void)hipGetLastError();
+  }
+  RefitParams r;
+  if ((rc = refit_params(who, s, r)) != PTAMD_OK) return rc;
+  // the first update of this kind: the reduction's words and partials, the two pinned slots they are copied back to
+  if (!s.d_margin) PT_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_margin), (kMarginWords + 2u * kExtentMaxGroups) * sizeof(float)));
+  if (!s.h_margin) PT_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_margin), 2u * kMarginWords * sizeof(float), hipHostMallocDefault));
+  for (int i = 0; i < 2; ++i)
+    if (!s.margin_ready[i]) PT_HIP(hipEventCreateWithFlags(&s.margin_ready[i], hipEventDisableTiming));
+  if (!s.updated) PT_HIP(hipEventCreateWithFlags(&s.updated, hipEventDisableTiming));
+  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
+  // (the copies of earlier updates read d_margin behind their `updated`, possibly on another stream)
+  for (int i = 0; i < 2; ++i)
+    if (s.margin_ready_valid[i]) PT_HIP(hipStreamWaitEvent(stream, s.margin_ready[i], 0));
+  const float* faces = reinterpret_cast<const float*>(d->faces);
+  PT_HIP(launch_extent(faces, d->n_faces, s.d_margin + kMarginWords, s.d_margin, stream));
+  r.faces = faces;
+  r.device_margin = s.d_margin + 2;
+  PT_HIP(launch_refit(r, stream));
+  PT_HIP(hipEventRecord(s.updated, stream));
+  s.updated_valid = true;
+  // extent and finiteness back to the host, behind the kernels: launches wait for `updated`, not for this copy
+  const uint32_t slot = s.margin_next++ & 1u;
+  PT_HIP(hipMemcpyAsync(s.h_margin + (size_t)slot * kMarginWords, s.d_margin, kMarginWords * sizeof(float), hipMemcpyDeviceToHost, stream));
+  PT_HIP(hipEventRecord(s.margin_ready[slot], stream));
+  s.margin_ready_valid[slot] = true;
+  s.margin_slot = slot;
+  s.margins_pending = true;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_margins(ptamd_context* ctx, uint32_t scene_id, float out[4])
+{
+  if (!ctx || !out) { set_error("ptamd_scene_margins: null argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_margins: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  DeviceScene& s = ctx->scenes[scene_id];
+  const int rc = settle_margins(s, nullptr, "ptamd_scene_margins");
+  if (rc != PTAMD_OK) return rc;
+  out[0] = s.extent; out[1] = s.reach; out[2] = s.margin_floor; out[3] = s.all_finite ? 1.0f : 0.0f;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_quality(ptamd_context* ctx, uint32_t scene_id, void* stream, ptamd_scene_quality_info* out)
+{
+  if (!ctx || !out) { set_error("ptamd_scene_quality: null argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_quality: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (stream_is_capturing(st)) { set_error("ptamd_scene_quality: the call waits for its result and cannot be captured into a graph"); return PTAMD_ERR_LIMIT; }
+  DeviceScene& s = ctx->scenes[scene_id];
+  int rc = settle_margins(s, st, "ptamd_scene_quality");
+  if (rc != PTAMD_OK) return rc;
+  out->built = s.quality_built;
+  out->now = 0.0;
+  if (s.n_nodes == 0 || s.n_faces == 0) return PTAMD_OK;
+  PT_HIP(hipSetDevice(ctx->device));
+  const uint32_t groups = quality_groups(s.n_nodes);
+  if (!s.d_quality) PT_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_quality), (size_t)(groups + 1u) * sizeof(double)));
+  if ((rc = wait_for_update(s, st, false)) != PTAMD_OK) return rc;
+  PT_HIP(launch_quality(reinterpret_cast<const float*>(s.nodes), s.n_nodes, s.d_quality, st));
+  std::vector<double> part(groups + 1u);
+  PT_HIP(hipMemcpyAsync(part.data(), s.d_quality, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  double sum = 0.0;
+  for (uint32_t g = 0; g < groups; ++g) sum += part[g];   // index order: the same bits for the same tables
+  out->now = sum / part[groups];
+  return PTAMD_OK;
+}
+
+int ptamd_host_scene_quality(const ptamd_scene_desc* sc, const ptamd_face* faces_b, double* out)
+{
+  if (!sc || !out) { set_error("ptamd_host_scene_quality: null argument"); return PTAMD_ERR_ARG; }
+  int rc = validate_scene_desc(sc);
+  SceneTables t;
+  if (rc != PTAMD_OK || (rc = make_scene_tables(sc, 0u, t)) != PTAMD_OK) return rc;
+  if (faces_b && (rc = refit_scene_tables(t, faces_b, sc->n_faces, sc->lights, sc->n_lights)) != PTAMD_OK) return rc;
+  *out = tree_quality(t.bvh.nodes.data(), t.bvh.n_nodes, sc->n_faces);
   return PTAMD_OK;
 }
 
@@ -1526,6 +1718,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   // missing or mismatched device image fails here, as the reference's cudaMemcpyFromSymbol calls would (raytrace.cu:362-374)
   hipError_t e = resolve_kernels();
   if (e == hipSuccess) e = resolve_refit_kernels();
+  if (e == hipSuccess) e = resolve_refit_device_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }
@@ -1711,7 +1904,9 @@ int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel, con
   }
   if (n == 0) return PTAMD_OK;
   PT_HIP(hipSetDevice(ctx->device));
-  const DeviceScene& s = ctx->scenes[scene_id];
+  DeviceScene& s = ctx->scenes[scene_id];
+  int src = settle_margins(s, nullptr, "ptamd_trace_rays");   // (choose_wide_nodes reads the extent)
+  if (src != PTAMD_OK) return src;
   KParams p;
   std::memset(&p, 0, sizeof p);
   fill_scene(s, nullptr, p);
@@ -1848,7 +2043,7 @@ int ptamd_render_features(ptamd_context* ctx, uint32_t scene_id, uint32_t cubema
 {
   if (!ctx || !camera || !features_dev) { set_error("ptamd_render_features: null argument"); return PTAMD_ERR_ARG; }
   if (width == 0 || height == 0 || width > 65536 || height > 65536) { set_error("ptamd_render_features: bad frame size (1..65536 per side)"); return PTAMD_ERR_ARG; }
-  int rc = denoise_ids("ptamd_render_features", ctx, scene_id, cubemap_id);
+  int rc = denoise_ids("ptamd_render_features", ctx, scene_id, cubemap_id, stream);
   if (rc != PTAMD_OK) return rc;
   PT_HIP(hipSetDevice(ctx->device));
   KParams p;
@@ -1864,7 +2059,7 @@ int ptamd_denoise(ptamd_context* ctx, const ptamd_denoise_desc* d)
 {
   if (!ctx || !d) { set_error("ptamd_denoise: null argument"); return PTAMD_ERR_ARG; }
   if (!d->temporal_framebuffer || !d->surface_rgba8) { set_error("ptamd_denoise: null accumulator or surface"); return PTAMD_ERR_ARG; }
-  int rc = denoise_ids("ptamd_denoise", ctx, d->scene_id, d->cubemap_id);
+  int rc = denoise_ids("ptamd_denoise", ctx, d->scene_id, d->cubemap_id, d->stream);
   if (rc != PTAMD_OK) return rc;
   DenoiseParams q;
   KParams p;
@@ -2018,7 +2213,7 @@ int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc
   ptamd_denoise_history* hist = td->history;
   if (!d->temporal_framebuffer || !d->surface_rgba8) { set_error("ptamd_denoise_temporal: null accumulator or surface"); return PTAMD_ERR_ARG; }
   if (hist->ctx != ctx) { set_error("ptamd_denoise_temporal: the history belongs to another context"); return PTAMD_ERR_ARG; }
-  int rc = denoise_ids(who, ctx, d->scene_id, d->cubemap_id);
+  int rc = denoise_ids(who, ctx, d->scene_id, d->cubemap_id, d->stream);
   if (rc != PTAMD_OK) return rc;
   DenoiseParams q;
   KParams p;
@@ -2308,7 +2503,7 @@ int ptamd_render_adaptive(ptamd_context* ctx, const ptamd_adaptive_desc* d)
 {
   AdaptiveParams a;
   int rc = adaptive_checks("ptamd_render_adaptive", ctx, d, 2, a);
-  if (rc != PTAMD_OK) return rc;
+  if (rc != PTAMD_OK || (rc = settle_margins(ctx->scenes[d->scene_id], static_cast<hipStream_t>(d->stream), "ptamd_render_adaptive")) != PTAMD_OK) return rc;
   if (far_origin_camera(ctx->scenes[d->scene_id], d->camera)) {
     set_error("ptamd_render_adaptive: the camera is beyond the reach of the box margins (launches of it walk every triangle): "
               "not supported by the list form; render it with ptamd_raytrace_ex");

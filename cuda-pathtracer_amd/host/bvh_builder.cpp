@@ -12,7 +12,7 @@
 // ray walks the tree front-to-back without a stack; triangles re-ordered leaf-major as
 // 48-byte {v0, e1, e2, global index} records.
 #include "ptamd_internal.h"
-#include "../csrc/pt_refit.h"
+#include "../csrc/pt_refit_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -286,12 +286,7 @@ float set_margins(Bvh& out, const ptamd_face* faces, uint32_t n_faces, const pta
         else all_finite = false;
       }
     }
-  out.extent = extent;
-  out.all_finite = all_finite;
-  out.reach = origin_reach(lights, n_lights, extent);
-  const float origin_margin = extent * (1.0f / 1048576.0f);
-  out.margin_floor = out.margin + origin_margin;
-  return origin_margin;
+  return bvh_margins_of_extent(out, extent, all_finite, lights, n_lights);
 }
 
 // every leaf-major record from the face its index word names
@@ -949,6 +944,16 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
     }
   }
   return PTAMD_OK;
+}
+
+float bvh_margins_of_extent(Bvh& bvh, float extent, bool all_finite, const ptamd_light* lights, uint32_t n_lights)
+{
+  bvh.extent = extent;
+  bvh.all_finite = all_finite;
+  bvh.reach = origin_reach(lights, n_lights, extent);
+  const float origin_margin = rf_extent_margin(extent);
+  bvh.margin_floor = bvh.margin + origin_margin;
+  return origin_margin;
 }
 
 float bvh_margins(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights)

@@ -134,6 +134,10 @@ int refit_bvh(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_l
 // build_bvh's rule (non-finite coordinates stay out of the extent); returns the origin-dependent margin extent * 2^-20.
 float bvh_margins(Bvh& bvh, const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights);
 
+// ... and its tail, for an extent and a finiteness formed elsewhere (ptamd_scene_update_device reduces them on the device): reach
+// and margin_floor by the same rule; returns extent * 2^-20.
+float bvh_margins_of_extent(Bvh& bvh, float extent, bool all_finite, const ptamd_light* lights, uint32_t n_lights);
+
 // The origin reach of a scene: the larger of the triangle extent and, over all lights, (max-axis |centre| + |radius| + 0.03)
 // times (1 + 2^-6) — the largest max-axis |coordinate| of any origin the path forms (bvh_builder.cpp).  Infinite when a light's
 // centre or radius is NaN or infinite.

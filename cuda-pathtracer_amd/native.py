@@ -70,6 +70,14 @@ class SceneUpdateDesc(C.Structure):      # ptamd_scene_update_desc (include/ptam
     _fields_ = [("scene_id", C.c_uint32), ("faces", C.POINTER(Face)), ("n_faces", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class SceneUpdateDeviceDesc(C.Structure):   # ptamd_scene_update_device_desc (include/ptamd.h): faces is a DEVICE address
+    _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p)]
+
+
+class SceneQualityInfo(C.Structure):        # ptamd_scene_quality_info (include/ptamd.h)
+    _fields_ = [("built", C.c_double), ("now", C.c_double)]
+
+
 class Launch(C.Structure):
     _fields_ = [("surface_rgba8", C.c_void_p), ("temporal_framebuffer", C.c_void_p), ("stream", C.c_void_p),
                 ("camera", Camera), ("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32),
@@ -178,6 +186,10 @@ SIGNATURES = {
     "ptamd_destroy": (None, [C.c_void_p]),
     "ptamd_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32)]),
     "ptamd_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDesc)]),
+    "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
+    "ptamd_scene_quality": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SceneQualityInfo)]),
+    "ptamd_host_scene_quality": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(C.c_double)]),
+    "ptamd_scene_margins": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
     "ptamd_scene_release": (C.c_int, [C.c_void_p, C.c_uint32]),
     "ptamd_scene_table_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_host_scene_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.c_void_p,

@@ -93,6 +93,43 @@ class Context:
         d.stream = _stream_handle(stream)
         N.check(self._lib.ptamd_scene_update(self._h, C.byref(d)))   # (the faces are copied before the call returns)
 
+    def update_scene_device(self, scene_id: int, faces, stream=None) -> None:
+        """ptamd_scene_update_device: the same update from faces that already live on the device, read in place.  `faces` is a
+        CUDA tensor on the context's device, float32 of shape (n, 28) or uint8 of shape (n, 112), contiguous, in the storage
+        order of the upload; material ids are not read.  Whatever fills the tensor must be ordered before the call on `stream`,
+        and the tensor stays alive and unmodified until the update's kernels have run (work enqueued on `stream` after the
+        call is behind them).  CPU arrays belong to update_scene."""
+        import torch
+        if not isinstance(faces, torch.Tensor):
+            raise ValueError("update_scene_device takes a torch tensor in device memory (host arrays: update_scene)")
+        if not faces.is_cuda:
+            raise ValueError("update_scene_device takes a tensor in device memory (CPU tensors: update_scene)")
+        if faces.device.index != self.device:
+            raise ValueError(f"the faces live on {faces.device}, the context on device {self.device}")
+        if not ((faces.dtype == torch.float32 and faces.dim() == 2 and faces.shape[1] == 28) or
+                (faces.dtype == torch.uint8 and faces.dim() == 2 and faces.shape[1] == 112)):
+            raise ValueError("faces must be float32 of shape (n, 28) or uint8 of shape (n, 112)")
+        if not faces.is_contiguous():
+            raise ValueError("faces must be contiguous")
+        d = N.SceneUpdateDeviceDesc()
+        d.scene_id = scene_id
+        d.faces = faces.data_ptr(); d.n_faces = faces.shape[0]
+        d.stream = _stream_handle(stream)
+        N.check(self._lib.ptamd_scene_update_device(self._h, C.byref(d)))
+
+    def scene_quality(self, scene_id: int, stream=None):
+        """ptamd_scene_quality: (built, now), the surface-area-heuristic cost of the scene's binary tree at upload and as the
+        device's tables stand (synchronises `stream`)."""
+        q = N.SceneQualityInfo()
+        N.check(self._lib.ptamd_scene_quality(self._h, scene_id, _stream_handle(stream), C.byref(q)))
+        return q.built, q.now
+
+    def scene_margins(self, scene_id: int) -> np.ndarray:
+        """ptamd_scene_margins: float32 {extent, origin reach, margin floor, all coordinates finite} as the context holds them."""
+        out = (C.c_float * 4)()
+        N.check(self._lib.ptamd_scene_margins(self._h, scene_id, out))
+        return np.array(out[:], dtype=np.float32)
+
     def release_scene(self, scene_id: int) -> None:
         """ptamd_scene_release: frees the scene's device tables (synchronises); the id stays taken."""
         N.check(self._lib.ptamd_scene_release(self._h, scene_id))
@@ -329,6 +366,21 @@ def host_scene_tables(scene: HostScene, *steps) -> dict:
         N.check(lib.ptamd_host_scene_refit(C.byref(d), ptrs[0], ptrs[1], which, buf.ctypes.data, C.byref(n)))
         out[name] = buf.view(np.float32) if name == "scalars" else buf
     return out
+
+
+def host_scene_quality(scene: HostScene, faces_b=None) -> float:
+    """ptamd_host_scene_quality (no GPU): the surface-area-heuristic cost of `scene`'s binary tree as an upload builds it, or
+    refitted to `faces_b` (HostScene or face array)."""
+    ptr = None
+    if faces_b is not None:
+        fb = np.ascontiguousarray(faces_b.faces if isinstance(faces_b, HostScene) else faces_b, dtype=FACE_DTYPE)
+        if len(fb) != len(scene.faces):
+            raise ValueError("a refit keeps the face count")
+        ptr = fb.ctypes.data_as(C.POINTER(N.Face))
+    d = scene.desc()
+    out = C.c_double(0.0)
+    N.check(N.load().ptamd_host_scene_quality(C.byref(d), ptr, C.byref(out)))
+    return out.value
 
 
 def host_bvh_refit_trace(scene_a: HostScene, scene_b: HostScene, rays: np.ndarray):

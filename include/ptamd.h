@@ -220,7 +220,9 @@ int ptamd_setup_function_tables(ptamd_context* ctx);
  * What a refitted tree costs the renderer (measured on the 264 832-triangle atrium, 1080p x 4 spp x 4 bounces, beside a fresh
  * upload of the same faces; scripts/gpu_refit.py): 0.5 % / 0.8 % / 19 % of the sample rate at displacements of
  * 0.1 % / 1 % / 10 % of the scene's extent, for an update of 3 ms against an upload of 0.7 s.  Fall back to
- * ptamd_scene_release + ptamd_upload_scene when the render time lost until the next rebuild exceeds that upload. */
+ * ptamd_scene_release + ptamd_upload_scene when the render time lost until the next rebuild exceeds that upload;
+ * ptamd_scene_quality (below) is the number to decide by.  A host whose faces already live on the device calls
+ * ptamd_scene_update_device (below) instead: the same result without the copy. */
 typedef struct {
   uint32_t scene_id;
   const ptamd_face* faces;   /* HOST array, n_faces records in the storage order of the upload */
@@ -228,6 +230,59 @@ typedef struct {
   void* stream;              /* the update is asynchronous on this stream */
 } ptamd_scene_update_desc;
 int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* desc);
+
+/* ptamd_scene_update from faces that already live on the device (a mesh skinned or simulated in device memory).  The scene's
+ * five tables, and every later render, are byte for byte what ptamd_scene_update produces from the same records.
+ *
+ * faces is a DEVICE array on the context's device, n_faces records (= the uploaded count) in the storage order of the upload,
+ * aligned to 16 bytes.  The kernels read it in place: nothing is copied or staged, and a scene that is only ever updated this way
+ * allocates no face buffer.  Whatever produced the faces must be ordered before the call on `stream`.  The caller keeps the buffer
+ * alive and unmodified until the update's kernels have run; work enqueued on `stream` after the call is ordered behind them by the
+ * stream itself.  Ordering against launches is ptamd_scene_update's.
+ *
+ * material_id of the supplied records is NOT READ: the refit keeps the uploaded material words of every shading record, so there
+ * is nothing to validate on the device.  This is the one place where the contract differs from ptamd_scene_update, which refuses
+ * a changed id.
+ *
+ * Margins.  The walk-or-every-face decision needs the extent of the NEW faces.  A reduction kernel, first in the update, forms it
+ * (the largest finite |coordinate|; the same bits as the host's, a maximum does not depend on order), the refit kernels take their
+ * origin margin from that word, and it is copied back behind them.  Until then the scene's margins are pending: the next launch,
+ * ptamd_render_features, denoiser call, adaptive render, ptamd_trace_rays, ptamd_scene_quality or ptamd_scene_margins first waits
+ * on the host for that copy, which sits behind the update's own kernels and nothing else.  A launch that is being CAPTURED while
+ * margins are pending is refused with PTAMD_ERR_LIMIT (no host wait inside a capture): render the scene once, or call
+ * ptamd_scene_quality, outside the capture.  A later update of either kind supersedes pending margins.
+ *
+ * Errors, before anything is enqueued: everything ptamd_scene_update refuses except a changed material_id, and PTAMD_ERR_ARG for
+ * a pointer that is not device memory of the context's device or not aligned to 16 bytes. */
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_face* faces;   /* DEVICE array on the context's device, n_faces records, storage order of the upload */
+  uint32_t n_faces;          /* must equal the uploaded count */
+  void* stream;              /* asynchronous on this stream; the faces are read in stream order, never copied */
+} ptamd_scene_update_device_desc;
+int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_device_desc* desc);
+
+/* Tree quality: the number behind "refit or rebuild".  One definition: the surface-area-heuristic cost of the BINARY tree over
+ * the planes the walk tests (table 0 of ptamd_scene_table_read, margins included; a 64-byte record is {lo.xyz, first | count << 24}
+ * {hi.xyz, child word} and eight miss links; count == 0 marks an interior node).  With A(k) = dx dy + dy dz + dz dx of node k's
+ * stored lo / hi, evaluated in binary64:
+ *     cost = ( sum over interior nodes A(k)  +  sum over leaves A(k) * count(k) ) / A(root).
+ * `built` is the value at upload, computed on the host and kept with the scene; `now` is the value of the device's tables as
+ * they stand, after waiting for the last update (per-workgroup partial sums on the device, added on the host in index order: the
+ * same tables give the same bits).  The call is synchronous on `stream`, settles pending margins and cannot be captured.  A scene
+ * whose planes overflow (coordinates near 3.4e38) yields a value that is not finite; it is returned as it is.  An empty scene
+ * yields 0 for both.  ptamd_host_scene_quality is the same arithmetic over the host tables, no device needed: of `scene` as
+ * uploaded, or (faces_b != NULL) refitted to faces_b.
+ *
+ * What the number is worth as a predictor has been measured once, not modelled, and no threshold is fixed here.  On the
+ * 264 832-triangle atrium (1080p x 4 spp x 4 bounces; scripts/gpu_refit.py, profiles/r13_refit_device.json), at
+ * displacements of 0.1 % / 1 % / 10 % of the extent: now / built = 1.005 / 1.056 / 1.568, now over the value of a fresh build on
+ * the same faces = 1.001 / 1.007 / 1.171, and the refitted tree rendered at 0.996 / 0.993 / 0.817 of the fresh build's rate.  The
+ * deformation itself raises the cost of any tree over those faces (a fresh build's value grows too): now / built overstates what
+ * a rebuild would win back. */
+typedef struct { double built; double now; } ptamd_scene_quality_info;
+int ptamd_scene_quality(ptamd_context* ctx, uint32_t scene_id, void* stream, ptamd_scene_quality_info* out);
+int ptamd_host_scene_quality(const ptamd_scene_desc* scene, const ptamd_face* faces_b, double* out);
 
 /* Waits for the device, frees the scene's tables and leaves a tombstone: ids of other scenes stay valid, any later use of this
  * one is PTAMD_ERR_ARG. */
@@ -486,6 +541,9 @@ int ptamd_host_origin_reach(const ptamd_face* faces, uint32_t n_faces, const pta
  * refits to faces_b and traces rays through the host mirrors of the binary and the four-wide walk (records as
  * ptamd_host_bvh_trace). */
 int ptamd_scene_table_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which, void* out, uint64_t* bytes);
+/* ... and the four floats of which = 5 as the context holds them for `scene_id`; settles margins left pending by
+ * ptamd_scene_update_device. */
+int ptamd_scene_margins(ptamd_context* ctx, uint32_t scene_id, float out[4]);
 int ptamd_host_scene_refit(const ptamd_scene_desc* scene, const ptamd_face* faces_b, const ptamd_face* faces_c, uint32_t which,
                            void* out, uint64_t* bytes);
 int ptamd_host_bvh_refit_trace(const ptamd_face* faces_a, const ptamd_face* faces_b, uint32_t n_faces, const float* rays, uint32_t n,

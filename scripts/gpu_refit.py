@@ -6,9 +6,14 @@ Writes one JSON object (stdout, and --out when given).  Per scene:
   - update_device_ms: device time of one update (events around everything it enqueues: the copy of the faces and the four
     kernels), update_host_ms: wall time of the call (the host pass over the vertices, the copy into the staging buffer, the
     enqueues) — medians of --reps warmed calls, the deformation's time parameter advancing every call;
+  - launch_after_update_ms: wall time of the first launch call issued straight after an update (with --device-faces it first waits
+    for the extent to come back from the device: the settle wait), median of --reps;
   - upload_ms: wall time of ptamd_upload_scene of the deformed scene (host SAH build + copies; the previous one released);
   - render (atrium): Msamples/s at --width x --height, --spp spp, --bounces bounces after an update to deform(t, amplitude) for three
-    amplitudes (fractions of the scene's extent), each beside a fresh upload of the same faces, runs alternating.
+    amplitudes (fractions of the scene's extent), each beside a fresh upload of the same faces, runs alternating; with them the
+    tree-quality pair of ptamd_scene_quality (built, now) and the fresh build's own value.
+--device-faces: the updates are ptamd_scene_update_device calls; every frame's faces are uploaded once as a tensor outside the
+timed region, as a host that animates on the device holds them.
 --trace-only: nothing but warmed updates of each scene, for `rocprofv3 --kernel-trace --stats -- python scripts/gpu_refit.py
 --trace-only` in a run of its own (the per-kernel split: pt_refit_records, _subtrees, _top, _wide).
 """
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--upload-reps", type=int, default=3)
     ap.add_argument("--amplitudes", default="0.001,0.01,0.1", help="fractions of the scene's extent")
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--device-faces", action="store_true", help="update from device tensors (ptamd_scene_update_device)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -47,7 +53,8 @@ def main():
         raise SystemExit("gpu_refit.py needs a GPU: nothing here is measured on a CPU")
     W, H, B, SPP = args.width, args.height, args.bounces, args.spp
     tmp = tempfile.TemporaryDirectory(prefix="ptamd_atrium_")
-    result = {"width": W, "height": H, "spp": SPP, "bounces": B, "reps": args.reps, "scenes": {}}
+    result = {"width": W, "height": H, "spp": SPP, "bounces": B, "reps": args.reps, "device_faces": args.device_faces,
+              "build_id": P.native.load().ptamd_build_id().decode(), "scenes": {}}
     med = statistics.median
 
     for name in args.scenes.split(","):
@@ -62,12 +69,18 @@ def main():
             info = ctx.scene_info(sid)
             st = torch.cuda.Stream()
             dev_ms, host_ms = [], []
+            if args.device_faces:
+                tensors = [torch.from_numpy(f.faces.view(np.uint8).reshape(len(f.faces), 112)).cuda() for f in frames]
+                torch.cuda.synchronize()
+                update = lambda k, stream=None: ctx.update_scene_device(sid, tensors[k], stream=stream)
+            else:
+                update = lambda k, stream=None: ctx.update_scene(sid, frames[k], stream=stream)
             with torch.cuda.stream(st):
-                for k, f in enumerate(frames):
+                for k in range(len(frames)):
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record(st)
                     t0 = time.perf_counter()
-                    ctx.update_scene(sid, f, stream=st)
+                    update(k, st)
                     t1 = time.perf_counter()
                     b.record(st)
                     b.synchronize()
@@ -78,6 +91,21 @@ def main():
                    "face_bytes": hs.faces.nbytes,
                    "table_bytes": info["n_nodes"] * 64 + len(hs.faces) * (48 + 48 + 112) + info["n_nodes4"] * 128,
                    "update_device_ms": med(dev_ms), "update_device_ms_min_max": [min(dev_ms), max(dev_ms)], "update_host_ms": med(host_ms)}
+            # the first launch call behind an update
+            small = P.FrameRenderer(ctx, sid, cid, hs.camera_struct(), 256, 144)
+            after_ms = []
+            with torch.cuda.stream(st):
+                for k in range(len(frames)):
+                    small.render(spp=1, bounces=B, reset=True, stream=st)
+                    st.synchronize()
+                    update(k, st)
+                    t0 = time.perf_counter()
+                    small.render(spp=1, bounces=B, reset=True, stream=st)
+                    t1 = time.perf_counter()
+                    st.synchronize()
+                    if k >= args.warmup:
+                        after_ms.append((t1 - t0) * 1e3)
+            rec["launch_after_update_ms"] = med(after_ms)
             if args.trace_only:
                 result["scenes"][name] = rec
                 continue
@@ -105,8 +133,13 @@ def main():
                 rec["render"] = []
                 for amp in [float(x) for x in args.amplitudes.split(",")]:
                     moved = P.deform(hs, 0.7, amp * extent)
-                    ctx.update_scene(sid, moved)
+                    if args.device_faces:
+                        ctx.update_scene_device(sid, torch.from_numpy(moved.faces.view(np.uint8).reshape(len(moved.faces), 112)).cuda())
+                    else:
+                        ctx.update_scene(sid, moved)
                     fid = ctx.upload_scene(moved)
+                    q_built, q_now = ctx.scene_quality(sid)
+                    q_fresh = ctx.scene_quality(fid)[0]
                     for _ in range(args.warmup):
                         timed(sid), timed(fid)
                     ts = {"refit": [], "fresh": []}
@@ -116,7 +149,9 @@ def main():
                     rate = lambda ms: W * H * SPP / (ms * 1e-3) / 1e6
                     rec["render"].append({"amplitude_of_extent": amp, "refit_ms": med(ts["refit"]), "fresh_ms": med(ts["fresh"]),
                                           "refit_msamples_s": rate(med(ts["refit"])), "fresh_msamples_s": rate(med(ts["fresh"])),
-                                          "refit_over_fresh": med(ts["fresh"]) / med(ts["refit"])})
+                                          "refit_over_fresh": med(ts["fresh"]) / med(ts["refit"]),
+                                          "quality_built": q_built, "quality_now": q_now, "quality_fresh": q_fresh,
+                                          "quality_now_over_built": q_now / q_built, "quality_now_over_fresh": q_now / q_fresh})
                     ctx.release_scene(fid)
             assert ctx.device_error_count() == 0
             result["scenes"][name] = rec
