@@ -151,7 +151,7 @@ inline bool margins_cover(float extent, float margin_floor, float origin_far)
   return (origin_far + extent) * (1.0f / 2097152.0f) <= margin_floor;
 }
 
-// Host traversal with the same structure the kernel uses (tests + stats cross-check).
+// Host traversals with the same structure the kernels use (tests + stats cross-check; bvh_walks.cpp).
 struct HostHit { int32_t kind; int32_t index; float t; float u, v; };
 void bvh_trace_host(const Bvh& bvh, const ptamd_face* faces, const float dir[3], const float origin[3],
                     HostHit& out, uint64_t* nodes_visited, uint64_t* tris_tested);

@@ -9,6 +9,14 @@
 // 2. `iterations` damaged copies of every input file class (bit flips, truncation, doubled chunks, hostile numbers in the text
 //    formats): the loaders may refuse a file, they may not read or write out of bounds, leak, or overflow.
 // Exit code 0: no finding (ASan / UBSan abort the process otherwise).
+//
+//   host_san dump <faces> <leaf sizes> <forms> <lights | -> <refit faces | -> <rays | ->
+//
+// The table pin (tests/test_bvh_tables.py): builds the tree of a file of raw ptamd_face records for every listed leaf size and
+// forms word (comma-separated) and prints one line per build with a digest of every vector of Bvh and the value of every scalar;
+// the same again after a refit_bvh to the second face file, where the tree allows one; with a file of rays (6 floats each), one
+// line per host walk entry point with a digest of its output and of its counters.  This mode honours the PTAMD_BVH_* knobs the
+// way the library does (behind PTAMD_TUNING=1).
 #include "ptamd.h"
 #include "ptamd_internal.h"
 
@@ -27,7 +35,14 @@ namespace ptamd {
 // the two services the host sources take from csrc/ptamd_api.cpp
 static std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
-const char* tuning_env(const char*) { return nullptr; }
+static bool g_knobs_from_env = false;   // the dump mode only: the sanitizer run stays deaf to the environment
+const char* tuning_env(const char* name)
+{
+  if (!g_knobs_from_env) return nullptr;
+  const char* gate = std::getenv("PTAMD_TUNING");   // (the library's rule: csrc/ptamd_api.cpp)
+  if (!gate || std::atoi(gate) != 1) return nullptr;
+  return std::getenv(name);
+}
 } // namespace ptamd
 extern "C" const char* ptamd_get_last_error(void) { return ptamd::g_err.c_str(); }
 
@@ -181,8 +196,94 @@ static void damage_text(std::vector<uint8_t>& b, std::mt19937& rng)
   b.assign(s.begin(), s.end());
 }
 
+// ---- the table pin
+static uint64_t fnv(const void* p, size_t n, uint64_t h = 0xcbf29ce484222325ull)
+{
+  const uint8_t* b = static_cast<const uint8_t*>(p);
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001b3ull; }
+  return h;
+}
+template <class T> static void put_vec(const char* name, const std::vector<T>& v)
+{
+  const uint64_t n = v.size();
+  std::printf(" %s=%016llx", name, (unsigned long long)fnv(v.data(), v.size() * sizeof(T), fnv(&n, 8)));
+}
+static void put_float(const char* name, float f)
+{
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  std::printf(" %s=f%08x", name, u);
+}
+static void put_tables(const char* stage, uint32_t leaf, uint32_t forms, int rc, const ptamd::Bvh& b)
+{
+  std::printf("tables leaf=%u forms=%u stage=%s rc=%d", leaf, forms, stage, rc);
+  put_vec("nodes", b.nodes); put_vec("tris", b.tris); put_vec("raw", b.raw); put_vec("nodes4", b.nodes4);
+  put_vec("nodes4q", b.nodes4q); put_vec("nodes8", b.nodes8); put_vec("wide_child", b.wide_child);
+  put_vec("refit_groups", b.refit_groups); put_vec("refit_levels", b.refit_levels); put_vec("refit_sched", b.refit_sched);
+  std::printf(" n_nodes=%u n_leaves=%u depth=%u max_leaf=%u n_tris=%u n_nodes4=%u depth4=%u n_nodes8=%u depth8=%u max_leaf8=%u split=%d",
+              b.n_nodes, b.n_leaves, b.depth, b.max_leaf, b.n_tris, b.n_nodes4, b.depth4, b.n_nodes8, b.depth8, b.max_leaf8, (int)b.split);
+  put_float("extent", b.extent); put_float("reach", b.reach); put_float("margin_floor", b.margin_floor);
+  std::printf(" all_finite=%d refit_top_first=%u refit_top_levels=%u\n", (int)b.all_finite, b.refit_top_first, b.refit_top_levels);
+}
+template <class T> static std::vector<T> records(const char* path)
+{
+  std::vector<T> v;
+  if (std::strcmp(path, "-") == 0) return v;
+  const std::vector<uint8_t> b = slurp(path);
+  v.resize(b.size() / sizeof(T));
+  if (!v.empty()) std::memcpy(v.data(), b.data(), v.size() * sizeof(T));
+  return v;
+}
+static std::vector<uint32_t> numbers(const char* csv)
+{
+  std::vector<uint32_t> v;
+  std::stringstream ss(csv);
+  for (std::string tok; std::getline(ss, tok, ',');) v.push_back((uint32_t)std::strtoul(tok.c_str(), nullptr, 10));
+  return v;
+}
+static int dump(int argc, char** argv)
+{
+  if (argc < 8) { std::fprintf(stderr, "usage: host_san dump <faces> <leaf sizes> <forms> <lights|-> <refit faces|-> <rays|->\n"); return 2; }
+  ptamd::g_knobs_from_env = true;
+  const std::vector<ptamd_face> faces = records<ptamd_face>(argv[2]), faces_b = records<ptamd_face>(argv[6]);
+  const std::vector<ptamd_light> lights = records<ptamd_light>(argv[5]);
+  const std::vector<float> rays = records<float>(argv[7]);
+  const uint32_t n = (uint32_t)faces.size(), n_lights = (uint32_t)lights.size();
+  for (uint32_t leaf : numbers(argv[3]))
+    for (uint32_t forms : numbers(argv[4])) {
+      ptamd::Bvh b;
+      int rc = ptamd::build_bvh(faces.data(), n, 1e-3f, leaf, b, forms, lights.data(), n_lights);
+      put_tables("build", leaf, forms, rc, b);
+      if (rc != PTAMD_OK || faces_b.size() != faces.size() || b.split || !b.nodes4q.empty() || !b.nodes8.empty()) continue;
+      rc = ptamd::refit_bvh(b, faces_b.data(), n, lights.data(), n_lights);
+      put_tables("refit", leaf, forms, rc, b);
+    }
+  const uint32_t nr = (uint32_t)(rays.size() / 6);
+  if (!nr) return 0;
+  typedef int (*walk_fn)(const ptamd_face*, uint32_t, const float*, uint32_t, int32_t*, uint64_t*);
+  const struct { const char* name; walk_fn fn; } walks[] = { { "bvh", ptamd_host_bvh_trace }, { "bvh4", ptamd_host_bvh4_trace },
+                                                             { "bvh4q", ptamd_host_bvh4q_trace }, { "bvh8", ptamd_host_bvh8_trace } };
+  for (const auto& w : walks) {
+    std::vector<int32_t> out((size_t)nr * 4, 0);
+    std::vector<uint64_t> counters(6, 0);
+    const int rc = w.fn(faces.data(), n, rays.data(), nr, out.data(), counters.data());
+    std::printf("walk name=%s rc=%d", w.name, rc);
+    put_vec("out", out); put_vec("counters", counters);
+    std::printf("\n");
+  }
+  if (faces_b.size() == faces.size()) {
+    std::vector<int32_t> binary((size_t)nr * 4, 0), wide((size_t)nr * 4, 0);
+    const int rc = ptamd_host_bvh_refit_trace(faces.data(), faces_b.data(), n, rays.data(), nr, binary.data(), wide.data());
+    std::printf("walk name=refit rc=%d", rc);
+    put_vec("binary", binary); put_vec("wide", wide);
+    std::printf("\n");
+  }
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
+  if (argc > 1 && std::strcmp(argv[1], "dump") == 0) return dump(argc, argv);
   if (argc < 5) { std::fprintf(stderr, "usage: host_san <assets> <scratch> <iterations> <seed>\n"); return 2; }
   const std::string assets = argv[1], scratch = argv[2];
   const int iterations = std::atoi(argv[3]);
