@@ -324,7 +324,7 @@ PT_DEV void xorwow_init(Xorwow& st, uint32_t seed)
   st.d = 6615241u + t1 + t0;
 }
 
-PT_DEV float xorwow_uniform(Xorwow& st)
+PT_HD float xorwow_uniform(Xorwow& st)
 {
   uint32_t t = st.v0 ^ (st.v0 >> 2);
   st.v0 = st.v1; st.v1 = st.v2; st.v2 = st.v3; st.v3 = st.v4;
@@ -332,6 +332,56 @@ PT_DEV float xorwow_uniform(Xorwow& st)
   st.d += 362437u;
   uint32_t x = st.v4 + st.d;
   return (float)x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+}
+
+// ---------------------------------------------------------------- the misses' loop (raytrace.cu:194-199), one lane's arithmetic
+// After a miss the reference keeps iterating with the unchanged ray: every remaining iteration misses again and adds the same
+// environment sample.  path_post (pt_kernels.hip) runs those iterations without the walk; the flat form of the restart kernel
+// finishes them in closed form.  Both forms are stated here for one lane, shared with the host harness that compares them bit
+// for bit (tests/san/miss_tail_host.cpp).
+
+PT_HD float max3(f3 v) { return __builtin_fmaxf(v.x, __builtin_fmaxf(v.y, v.z)); }
+
+// One iteration as the reference runs it.  bk: bounce index in the low 16 bits (Path::bk); rcp(x): 1.0f / x correctly rounded
+// (rcp_hot on the device).  Returns true when the path ends here.
+template <class Rcp>
+PT_HD bool miss_tail_iteration(f3 env, int max_bounces, f3& acc, f3& thr, uint32_t& bk, float& r1, Xorwow& rng, Rcp rcp)
+{
+  acc = acc + env * thr;
+  const float pmax = max3(thr);
+  if (r1 > pmax && (bk & 0xffffu) > 1u) return true;
+  thr = thr * rcp(pmax);
+  ++bk;
+  if ((int)(bk & 0xffffu) >= max_bounces) return true;
+  r1 = xorwow_uniform(rng);
+  return false;
+}
+
+// The closed form.  With max3(thr) == 1.0f exactly, an iteration changes nothing but acc and the bounce index: 1.0f / 1.0f is 1,
+// so thr (NaN and -0 components included) and its maximum stay what they are; r1 > 1.0f is false for every r1 that
+// xorwow_uniform returns (at most 1.0f), so the roulette never ends the path; and the path ends inside the loop, so the variates it
+// would still draw are read by nothing.  What is left is acc += env * thr, miss_tail_count times, one add after the other
+// (n * e would round differently).  NaN, infinite and zero maxima fail the test and stay on miss_tail_iteration; any other
+// maximum x becomes x * RN(1 / x) after one iteration, which is usually exactly 1.
+PT_HD bool miss_tail_is_closed(f3 thr) { return max3(thr) == 1.0f; }
+// adds left for a path at bounce index b: the loop adds before it tests, so b >= max_bounces still adds once
+PT_HD uint32_t miss_tail_count(uint32_t b, int max_bounces) { const int n = max_bounces - (int)b; return n > 1 ? (uint32_t)n : 1u; }
+// The whole tail of a lane that missed: literal iterations until the maximum is exactly 1 (or the path ends in one of them), then
+// the adds.  Both loops are per lane; in a wave they run to the longest lane's count with the other lanes masked off, and the
+// second one holds no reciprocal, no draw and no roulette test.  Leaves acc final; thr, bk, r1 and rng are dead afterwards.
+// Returns the number of futile intersect() calls the reference issues on the way (statistics builds count them as rays).
+template <class Rcp>
+PT_HD uint32_t miss_tail_finish(f3 env, int max_bounces, f3& acc, f3& thr, uint32_t& bk, float& r1, Xorwow& rng, Rcp rcp)
+{
+  uint32_t futile = 0;
+  while (!miss_tail_is_closed(thr)) {
+    if (miss_tail_iteration(env, max_bounces, acc, thr, bk, r1, rng, rcp)) return futile;
+    ++futile;
+  }
+  const f3 e = env * thr;
+  const uint32_t n = miss_tail_count(bk & 0xffffu, max_bounces);
+  for (uint32_t i = 0; i < n; ++i) acc = acc + e;
+  return futile + n - 1u;
 }
 
 // ---------------------------------------------------------------- kernel parameters

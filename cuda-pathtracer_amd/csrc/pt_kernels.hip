@@ -860,6 +860,16 @@ PT_DEV bool path_post(const KParams& p, Path& st, float r1, Nearest nearest, Cou
     // iteration misses again and adds the same environment sample.  Run them here, without
     // the walk, drawing r1 exactly as the loop does.
     const f3 env = env_lookup<FLAT>(p, st.d);
+    if constexpr (FLAT) {
+      // The same iterations in closed form (pt_device.h: miss_tail_*): a lane whose throughput has a maximum of exactly 1 — every
+      // primary miss, and nearly every later one after one renormalisation — has nothing left to do but add env * throughput
+      // once per remaining bounce.  The wave runs the literal iteration only while some missing lane is not there yet, then the
+      // adds up to its longest lane's count: no reciprocal, no draw and no roulette test per bounce.
+      const uint32_t futile = miss_tail_finish(env, max_bounces, st.acc, st.throughput, st.bk, r1, st.rng, [](float x) { return rcp_hot(x); });
+      if (STATS) cnt.rays += futile;
+      return true;
+    }
+    // (the other forms keep the loop as it was written before miss_tail_iteration restated it: their code is pinned byte for byte)
     for (;;) {
       st.acc = st.acc + env * st.throughput;
       const float pmax = __builtin_fmaxf(st.throughput.x, __builtin_fmaxf(st.throughput.y, st.throughput.z));
