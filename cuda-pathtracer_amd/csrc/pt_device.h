@@ -483,6 +483,38 @@ struct KParams {
 };
 #define PT_ROUND_GENERIC 1u
 #define PT_ROUND_FLAT 2u
+
+// The restart kernel's forms: the VARIANT argument of pt_megakernel_restart<LDS_RESIDENT, VARIANT> (pt_kernels.hip)
+#define PT_RS_PLAIN 0
+#define PT_RS_STATS 1
+#define PT_RS_STAMPS 2
+#define PT_RS_BRUTE 3
+#define PT_RS_WIDE8 4   /* scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one */
+#define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
+#define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
+#define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
+#define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
+#define PT_RS_FORMS 9
+
+// Which instantiation of the restart kernel serves a launch: the first rule that applies.  Host code.  p: the launch, or nullptr for
+// the occupancy query, which asks for the family's plain form.  contracted: the choice of pt_kernels_fma.hip, which compiles PLAIN,
+// BRUTE and GENERIC only: it has no list form, and a rule that names another form sends the launch to PLAIN there.
+struct RestartForm { int variant; bool lds_resident; };
+inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool contracted, const KParams* p)
+{
+  const auto full = [contracted](int variant) { return contracted ? PT_RS_PLAIN : variant; };
+  if (list && !contracted) return { PT_RS_LIST, lds_resident };                // adaptive sampling's active list: instantiations of its own
+  if (stats) return { full(PT_RS_STATS), lds_resident };                      // counters are wanted: the instrumented build
+  if (p && p->brute_walk) return { PT_RS_BRUTE, lds_resident };                // a far origin: every triangle record instead of the tree
+  if (p && p->timeline) return { full(PT_RS_STAMPS), lds_resident };           // ptamd_set_timeline: four time stamps per wave
+  if (!lds_resident && p && p->wide8) return { full(p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8), false };   // the knobs' quantised node forms
+  if (!lds_resident) return { PT_RS_PLAIN, false };                            // the four-wide walk from L2
+  // the shipped instantiation of a resident scene is compiled for four launch constants (pt_megakernel_restart: LEAN): a static
+  // camera, pools in LDS, no XCD regions, no interleaved bands; any other launch, or PTAMD_RS_GENERIC, reads them at run time
+  if (p && !(p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC))) return { PT_RS_GENERIC, true };
+  if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment
+  return { PT_RS_PLAIN, true };
+}
 // LDS bytes of one wave's pool of fresh paths (restart kernel: 64 entries x 9 dwords)
 #define PT_POOL_LDS_BYTES 2304u
 

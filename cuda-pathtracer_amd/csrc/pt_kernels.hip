@@ -2018,17 +2018,7 @@ PT_DEV bool region_tile(const KParams& p, uint32_t ticket, uint32_t& col, uint32
         tl_[(size_t)(blockIdx.x * (THREADS / 64u) + (threadIdx.x >> 6)) * 4u + (slot)] = wall_clock64();                 \
     }                                                                                                                    \
   } while (0)
-// instantiations of the restart kernel: the shipped one, the instrumented one (counters), the one that records per-wave time
-// stamps, and the one that tests every triangle instead of walking the tree (far-origin launches, ptamd_api.cpp)
-#define PT_RS_PLAIN 0
-#define PT_RS_STATS 1
-#define PT_RS_STAMPS 2
-#define PT_RS_BRUTE 3
-#define PT_RS_WIDE8 4   /* scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one */
-#define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
-#define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
-#define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
-#define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
+// (its instantiations, PT_RS_*, and which launch takes which: pt_device.h, restart_select)
 
 template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
@@ -2945,121 +2935,49 @@ hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t str
 
 // ---------------------------------------------------------------- launchers
 
+// A form is one compiled instantiation of a megakernel with its workgroup size, its dynamic LDS and the number of its waves that take
+// tile tickets (pt_launch.h: KernelForm).  The tables below map template arguments to entry points, one per family; megakernel_form
+// describes a launch's form, form_blocks_per_cu and launch_form serve every one of them, resolve_kernels walks the tables.
+#define PT_FN(...) reinterpret_cast<const void*>(__VA_ARGS__)
 #ifndef PT_FMA_BUILD   /* (the contracted instantiation, pt_kernels_fma.hip, only carries the restart kernel) */
-template <int KIND, bool LDS_RES, bool STATS>
-static hipError_t launch_variant(const KParams& p, dim3 grid, size_t lds_bytes, hipStream_t stream)
-{
-  auto kern = pt_megakernel<KIND, LDS_RES, STATS, PT_TILE_THREADS>;
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(PT_TILE_THREADS), lds_bytes, stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_megakernel(const KParams& p, int kind, bool lds_resident, size_t lds_bytes, bool stats,
-                             hipStream_t stream)
-{
-  const uint32_t rows = p.row_end - p.row_begin;
-  if (rows == 0 || p.width == 0) return hipSuccess;
-  const uint32_t block_rows = PT_TILE_THREADS / 16u;
-  dim3 grid((p.width + 15u) / 16u, (rows + block_rows - 1u) / block_rows);
-  if (!lds_resident) lds_bytes = 0;
-#define PT_DISPATCH(K, L, S) return launch_variant<K, L, S>(p, grid, lds_bytes, stream)
-  if (kind == 1) {
-    if (lds_resident) { if (stats) PT_DISPATCH(1, true, true); else PT_DISPATCH(1, true, false); }
-    else { if (stats) PT_DISPATCH(1, false, true); else PT_DISPATCH(1, false, false); }
-  } else {
-    if (lds_resident) { if (stats) PT_DISPATCH(2, true, true); else PT_DISPATCH(2, true, false); }
-    else { if (stats) PT_DISPATCH(2, false, true); else PT_DISPATCH(2, false, false); }
-  }
-#undef PT_DISPATCH
-}
-
-template <bool LDS_RES, bool STATS>
-static const void* persistent_entry()
-{
-  return reinterpret_cast<const void*>(pt_megakernel_persistent<2, LDS_RES, STATS>);
-}
-
-static const void* persistent_select(bool lds_resident, bool stats)
-{
-  if (lds_resident) return stats ? persistent_entry<true, true>() : persistent_entry<true, false>();
-  return stats ? persistent_entry<false, true>() : persistent_entry<false, false>();
-}
-
-// Resident workgroups per CU of the persistent variant (sizes its grid).
-hipError_t persistent_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out)
-{
-  if (!lds_resident) lds_bytes = 0;
-  const void* fn = persistent_select(lds_resident, false);
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fn, PT_PERSISTENT_THREADS, lds_bytes);
-}
-
-hipError_t launch_megakernel_persistent(const KParams& p, bool lds_resident, size_t lds_bytes, bool stats,
-                                        uint32_t n_blocks, hipStream_t stream)
-{
-  if (p.n_tiles == 0 || n_blocks == 0) return hipSuccess;
-  if (!lds_resident) lds_bytes = 0;
-  const void* fn = persistent_select(lds_resident, stats);
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  KParams pc = p;
-  void* args[] = { &pc };
-  return hipLaunchKernel(fn, dim3(n_blocks), dim3(PT_PERSISTENT_THREADS), args, lds_bytes, stream);
-}
-
+static const void* const kTileEntries[2][2][2] = {   // [kind: every face, BVH][lds_resident][stats]
+  { { PT_FN(pt_megakernel<1, false, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<1, false, true, PT_TILE_THREADS>) },
+    { PT_FN(pt_megakernel<1, true, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<1, true, true, PT_TILE_THREADS>) } },
+  { { PT_FN(pt_megakernel<2, false, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<2, false, true, PT_TILE_THREADS>) },
+    { PT_FN(pt_megakernel<2, true, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<2, true, true, PT_TILE_THREADS>) } } };
+static const void* const kPersistentEntries[2][2] = {   // [lds_resident][stats], as the next two
+  { PT_FN(pt_megakernel_persistent<2, false, false>), PT_FN(pt_megakernel_persistent<2, false, true>) },
+  { PT_FN(pt_megakernel_persistent<2, true, false>), PT_FN(pt_megakernel_persistent<2, true, true>) } };
+static const void* const kSplitEntries[2][2] = {
+  { PT_FN(pt_megakernel_split<false, false>), PT_FN(pt_megakernel_split<false, true>) },
+  { PT_FN(pt_megakernel_split<true, false>), PT_FN(pt_megakernel_split<true, true>) } };
+static const void* const kBlockwiseEntries[2][2] = {
+  { PT_FN(pt_megakernel_blockwise<false, false>), PT_FN(pt_megakernel_blockwise<false, true>) },
+  { PT_FN(pt_megakernel_blockwise<true, false>), PT_FN(pt_megakernel_blockwise<true, true>) } };
+constexpr bool kContracted = false;
+#else
+constexpr bool kContracted = true;
 #endif
 
-template <bool LDS_RES>
-static const void* restart_entry(int variant)
+// The restart kernel: (form, LDS_RESIDENT) -> its instantiation, nullptr where none is compiled: WIDE8 and WIDE4Q only ever serve a
+// scene walked from L2, GENERIC and FLAT only a resident one, and the contracted build carries the first five alone (restart_select).
+static const void* restart_entry(int variant, bool lds_resident)
 {
-  switch (variant) {
-#ifdef PT_FMA_BUILD
-    case PT_RS_BRUTE: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_BRUTE>);
-    case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);
-    default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
-  }
-}
-template <bool LDS_RES>
-static const void* restart_entry_unused(int variant)
-{
-  switch (variant) {
-#endif
-    case PT_RS_STATS: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_STATS>);
-    case PT_RS_STAMPS: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_STAMPS>);
-    case PT_RS_BRUTE: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_BRUTE>);
-    case PT_RS_WIDE8: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE8>);   // (only ever a non-resident scene)
-    case PT_RS_WIDE4Q: return reinterpret_cast<const void*>(pt_megakernel_restart<false, PT_RS_WIDE4Q>);
-    case PT_RS_GENERIC: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_GENERIC>);   // (only ever a resident scene)
-    case PT_RS_LIST: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_LIST>);
-    case PT_RS_FLAT: return reinterpret_cast<const void*>(pt_megakernel_restart<true, PT_RS_FLAT>);   // (only ever a resident scene)
-    default: return reinterpret_cast<const void*>(pt_megakernel_restart<LDS_RES, PT_RS_PLAIN>);
-  }
-}
-
-// variant: instrumented build when counters are wanted, else the far-origin form, else the time-stamp form, else the shipped kernel —
-// for a resident scene only when the launch has the constants it is compiled for (pt_megakernel_restart: LEAN), else its generic form;
-// in the shipped kernel's place its flat form when the scene is flat and the environment uniform (KParams::round_form).
-// list: the list form of adaptive sampling (its own instantiations, resident scene or four-wide walk; not in the contracted build).
-static const void* restart_select(bool lds_resident, bool stats, const KParams* p = nullptr, bool list = false)
-{
+#define PT_RS_ENTRY(V, R) case (V) * 2 + ((R) ? 1 : 0): return PT_FN(pt_megakernel_restart<R, V>)
+  switch (variant * 2 + (lds_resident ? 1 : 0)) {
+    PT_RS_ENTRY(PT_RS_PLAIN, false); PT_RS_ENTRY(PT_RS_PLAIN, true);
+    PT_RS_ENTRY(PT_RS_BRUTE, false); PT_RS_ENTRY(PT_RS_BRUTE, true);
+    PT_RS_ENTRY(PT_RS_GENERIC, true);
 #ifndef PT_FMA_BUILD
-  if (list) return lds_resident ? restart_entry<true>(PT_RS_LIST) : restart_entry<false>(PT_RS_LIST);
+    PT_RS_ENTRY(PT_RS_STATS, false); PT_RS_ENTRY(PT_RS_STATS, true);
+    PT_RS_ENTRY(PT_RS_STAMPS, false); PT_RS_ENTRY(PT_RS_STAMPS, true);
+    PT_RS_ENTRY(PT_RS_WIDE8, false); PT_RS_ENTRY(PT_RS_WIDE4Q, false);
+    PT_RS_ENTRY(PT_RS_LIST, false); PT_RS_ENTRY(PT_RS_LIST, true);
+    PT_RS_ENTRY(PT_RS_FLAT, true);
 #endif
-  const bool lean = !p || (p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC));
-  const bool flat = lean && p && (p->round_form & PT_ROUND_FLAT);   // (the contracted build has no flat form: its restart_entry serves PT_RS_PLAIN)
-  const int variant = stats ? PT_RS_STATS : (p && p->brute_walk ? PT_RS_BRUTE : (p && p->timeline ? PT_RS_STAMPS : (p && p->wide8 && !lds_resident ? (p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8) :
-                      (lds_resident && !lean ? PT_RS_GENERIC : (lds_resident && flat ? PT_RS_FLAT : PT_RS_PLAIN)))));
-  return lds_resident ? restart_entry<true>(variant) : restart_entry<false>(variant);
+    default: return nullptr;
+  }
+#undef PT_RS_ENTRY
 }
 
 // chunk-major treelet (PT_TREELET_SOA): bytes of its LDS region and the most 128-byte nodes it can hold (0: node-major, sized by the node count)
@@ -3068,114 +2986,72 @@ uint32_t restart_threads(bool lds_resident) { return lds_resident ? PT_RS_THREAD
 // wide walk: resident workgroups per CU the launch bounds aim for (their LDS share holds the treelet and the waves' stacks)
 uint32_t restart_wide_blocks_per_cu() { return (PT_RS4_WAVES_PER_EU * 256u) / PT_RS4_THREADS; }
 
-// lds_bytes: the staged scene when lds_resident, else the stacks of the wide walk
-hipError_t restart_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out, bool list)
+// lds_bytes: the staged scene (and the pools behind it) when lds_resident, else the treelet and stacks of the wide walk.  Occupancy is
+// asked of the family's plain form (no launch: restart_select's p == nullptr), whatever form the launch takes.
+static KernelForm restart_form(bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)
 {
-  const void* fn = restart_select(lds_resident, false, nullptr, list);
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fn, (int)restart_threads(lds_resident), lds_bytes);
-}
-
-hipError_t launch_megakernel_restart(const KParams& p, bool lds_resident, size_t lds_bytes, bool stats,
-                                     uint32_t n_blocks, hipStream_t stream, bool list)
-{
-  if (p.n_tiles == 0 || n_blocks == 0) return hipSuccess;
-  const void* fn = restart_select(lds_resident, stats, &p, list);
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  KParams pc = p;
-  void* args[] = { &pc };
-  return hipLaunchKernel(fn, dim3(n_blocks), dim3(restart_threads(lds_resident)), args, lds_bytes, stream);
+  const RestartForm launched = restart_select(lds_resident, stats, list, kContracted, p);
+  const RestartForm queried = restart_select(lds_resident, false, list, kContracted, nullptr);
+  const uint32_t threads = restart_threads(lds_resident);
+  KernelForm f = { restart_entry(launched.variant, launched.lds_resident), restart_entry(queried.variant, queried.lds_resident), threads,
+                   threads / 64u, lds_bytes, kFormSlotRestart, "restart" };
+  if (kContracted) { f.cache_slot = kFormSlotRestartContracted; f.name = "contracted restart"; }
+  else if (list) { f.cache_slot = kFormSlotRestartList; f.name = "restart (list form)"; }
+  return f;
 }
 
 #ifndef PT_FMA_BUILD
-static const void* split_select(bool lds_resident, bool stats)
+KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)
 {
-  if (lds_resident)
-    return stats ? reinterpret_cast<const void*>(pt_megakernel_split<true, true>)
-                 : reinterpret_cast<const void*>(pt_megakernel_split<true, false>);
-  return stats ? reinterpret_cast<const void*>(pt_megakernel_split<false, true>)
-               : reinterpret_cast<const void*>(pt_megakernel_split<false, false>);
-}
-
-// LDS of the split variant = staged scene (when resident) + ray batches of the shader waves + control words
-size_t split_lds_bytes(bool lds_resident, size_t scene_lds_bytes)
-{
-  return (lds_resident ? scene_lds_bytes : 0) + (size_t)PT_SP_SHADERS * 64u * 32u + (2u * PT_SP_SHADERS + 4u) * 4u;
-}
-
-uint32_t split_shader_waves() { return PT_SP_SHADERS; }
-
-hipError_t split_blocks_per_cu(bool lds_resident, size_t scene_lds_bytes, int* out)
-{
-  const size_t lds = split_lds_bytes(lds_resident, scene_lds_bytes);
-  const void* fn = split_select(lds_resident, false);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+  const int r = lds_resident ? 1 : 0, s = stats ? 1 : 0;
+  const size_t scene = lds_resident ? lds_bytes : 0;   // every family but the restart kernel's: the scene's copy, staged when it fits
+  switch (kernel) {
+    case PTAMD_KERNEL_BRUTE_FORCE:
+    case PTAMD_KERNEL_BVH: {   // one thread per pixel, no tickets
+      const void* fn = kTileEntries[kernel == PTAMD_KERNEL_BVH ? 1 : 0][r][s];
+      return { fn, fn, PT_TILE_THREADS, 0u, scene, kFormSlotTile, "tile" };
+    }
+    case PTAMD_KERNEL_BVH_PERSISTENT:
+      return { kPersistentEntries[r][s], kPersistentEntries[r][0], PT_PERSISTENT_THREADS, PT_PERSISTENT_THREADS / 64u, scene, kFormSlotPersistent, "persistent" };
+    case PTAMD_KERNEL_BVH_BLOCKWISE:   // + exchange area + count table + ticket, which the workgroup takes as one
+      return { kBlockwiseEntries[r][s], kBlockwiseEntries[r][0], PT_BW_THREADS, 1u, scene + (size_t)PT_BW_THREADS * 32u + 128u * 4u + 16u, kFormSlotBlockwise, "blockwise" };
+    case PTAMD_KERNEL_BVH_SPLIT:   // + ray batches of the shader waves, which take the tickets, + control words
+      return { kSplitEntries[r][s], kSplitEntries[r][0], PT_SP_THREADS, PT_SP_SHADERS, scene + (size_t)PT_SP_SHADERS * 64u * 32u + (2u * PT_SP_SHADERS + 4u) * 4u, kFormSlotSplit, "split" };
+    case PTAMD_KERNEL_BVH_RESTART_FMA: {
+      KernelForm f;
+      ptamd_fma_restart_form(r, lds_bytes, p, &f);
+      return f;
+    }
+    default: return restart_form(lds_resident, stats, list, lds_bytes, p);
   }
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fn, PT_SP_THREADS, lds);
 }
 
-hipError_t launch_megakernel_split(const KParams& p, bool lds_resident, size_t scene_lds_bytes, bool stats,
-                                   uint32_t n_blocks, hipStream_t stream)
+static hipError_t allow_lds(const void* fn, size_t lds_bytes)
 {
-  if (p.n_tiles == 0 || n_blocks == 0) return hipSuccess;
-  const size_t lds = split_lds_bytes(lds_resident, scene_lds_bytes);
-  const void* fn = split_select(lds_resident, stats);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  return lds_bytes > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) : hipSuccess;
+}
+
+// Resident workgroups per CU of a form's family (sizes its grid).
+hipError_t form_blocks_per_cu(const KernelForm& f, int* out)
+{
+  const hipError_t e = allow_lds(f.occupancy_fn, f.lds_bytes);
+  return e != hipSuccess ? e : hipOccupancyMaxActiveBlocksPerMultiprocessor(out, f.occupancy_fn, (int)f.threads, f.lds_bytes);
+}
+
+hipError_t launch_form(const KernelForm& f, const KParams& p, uint32_t n_blocks, hipStream_t stream)
+{
+  if (!f.fn) return hipErrorInvalidDeviceFunction;
+  dim3 grid(n_blocks);
+  if (f.ticket_waves == 0u) {   // the tile kernels: workgroups of 16 x (threads / 16) pixels over the row band
+    const uint32_t rows = p.row_end - p.row_begin, block_rows = f.threads / 16u;
+    grid = dim3((p.width + 15u) / 16u, (rows + block_rows - 1u) / block_rows);
+  } else if (p.n_tiles == 0) return hipSuccess;
+  if (grid.x == 0 || grid.y == 0) return hipSuccess;
+  const hipError_t e = allow_lds(f.fn, f.lds_bytes);
+  if (e != hipSuccess) return e;
   KParams pc = p;
   void* args[] = { &pc };
-  return hipLaunchKernel(fn, dim3(n_blocks), dim3(PT_SP_THREADS), args, lds, stream);
-}
-
-static const void* blockwise_select(bool lds_resident, bool stats)
-{
-  if (lds_resident)
-    return stats ? reinterpret_cast<const void*>(pt_megakernel_blockwise<true, true>)
-                 : reinterpret_cast<const void*>(pt_megakernel_blockwise<true, false>);
-  return stats ? reinterpret_cast<const void*>(pt_megakernel_blockwise<false, true>)
-               : reinterpret_cast<const void*>(pt_megakernel_blockwise<false, false>);
-}
-
-// LDS of the blockwise variant = staged scene (when resident) + exchange area + count table + ticket
-size_t blockwise_lds_bytes(bool lds_resident, size_t scene_lds_bytes)
-{
-  return (lds_resident ? scene_lds_bytes : 0) + (size_t)PT_BW_THREADS * 32u + 128u * 4u + 16u;
-}
-
-hipError_t blockwise_blocks_per_cu(bool lds_resident, size_t scene_lds_bytes, int* out)
-{
-  const size_t lds = blockwise_lds_bytes(lds_resident, scene_lds_bytes);
-  const void* fn = blockwise_select(lds_resident, false);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fn, PT_BW_THREADS, lds);
-}
-
-hipError_t launch_megakernel_blockwise(const KParams& p, bool lds_resident, size_t scene_lds_bytes, bool stats,
-                                       uint32_t n_blocks, hipStream_t stream)
-{
-  if (p.n_tiles == 0 || n_blocks == 0) return hipSuccess;
-  const size_t lds = blockwise_lds_bytes(lds_resident, scene_lds_bytes);
-  const void* fn = blockwise_select(lds_resident, stats);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  KParams pc = p;
-  void* args[] = { &pc };
-  return hipLaunchKernel(fn, dim3(n_blocks), dim3(PT_BW_THREADS), args, lds, stream);
+  return hipLaunchKernel(f.fn, grid, dim3(f.threads), args, f.lds_bytes, stream);
 }
 
 hipError_t launch_resolve(const KParams& p, hipStream_t stream)
@@ -3206,30 +3082,25 @@ hipError_t launch_gamma_selftest(const float* table_dev, uint32_t first, uint32_
 
 hipError_t resolve_kernels()
 {
-  const void* fns[] = {
-    persistent_select(true, false), persistent_select(false, false), persistent_select(true, true), persistent_select(false, true),
-    split_select(true, false), split_select(false, false), blockwise_select(true, false), blockwise_select(false, false),
-    restart_entry<true>(PT_RS_PLAIN), restart_entry<false>(PT_RS_PLAIN), restart_entry<true>(PT_RS_STATS), restart_entry<false>(PT_RS_STATS),
-    restart_entry<true>(PT_RS_STAMPS), restart_entry<false>(PT_RS_STAMPS), restart_entry<true>(PT_RS_BRUTE), restart_entry<false>(PT_RS_BRUTE), restart_entry<false>(PT_RS_WIDE8), restart_entry<false>(PT_RS_WIDE4Q), restart_entry<true>(PT_RS_GENERIC),
-    restart_entry<true>(PT_RS_LIST), restart_entry<false>(PT_RS_LIST), restart_entry<true>(PT_RS_FLAT),
-    reinterpret_cast<const void*>(pt_megakernel<1, true, false, PT_TILE_THREADS>),
-    reinterpret_cast<const void*>(pt_megakernel<1, false, false, PT_TILE_THREADS>),
-    reinterpret_cast<const void*>(pt_megakernel<2, true, false, PT_TILE_THREADS>),
-    reinterpret_cast<const void*>(pt_megakernel<2, false, false, PT_TILE_THREADS>),
-    reinterpret_cast<const void*>(pt_resolve_kernel), reinterpret_cast<const void*>(pt_resolve_kernel4),
-    reinterpret_cast<const void*>(pt_trace_rays_kernel<1>), reinterpret_cast<const void*>(pt_trace_rays_kernel<2>),
-    reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<0>), reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<1>),
-    reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<2>),
-    reinterpret_cast<const void*>(pt_features_kernel<1>), reinterpret_cast<const void*>(pt_features_kernel<2>),
-    reinterpret_cast<const void*>(pt_denoise_kernel<0>), reinterpret_cast<const void*>(pt_denoise_kernel<1>),
-    reinterpret_cast<const void*>(pt_denoise_kernel<2>), reinterpret_cast<const void*>(pt_denoise_kernel<3>),
-  };
-  for (const void* fn : fns) {
+  hipError_t e = hipSuccess;
+  const auto resolve = [&e](const void* const* fns, size_t n) {
     hipFuncAttributes attr;
-    hipError_t e = hipFuncGetAttributes(&attr, fn);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    for (size_t i = 0; i < n && e == hipSuccess; ++i) e = hipFuncGetAttributes(&attr, fns[i]);
+  };
+  resolve(&kTileEntries[0][0][0], 8);
+  resolve(&kPersistentEntries[0][0], 4);
+  resolve(&kSplitEntries[0][0], 4);
+  resolve(&kBlockwiseEntries[0][0], 4);
+  for (int variant = 0; variant < PT_RS_FORMS; ++variant)
+    for (int r = 0; r < 2; ++r) if (const void* fn = restart_entry(variant, r != 0)) resolve(&fn, 1);
+  const void* const others[] = {
+    PT_FN(pt_resolve_kernel), PT_FN(pt_resolve_kernel4), PT_FN(pt_trace_rays_kernel<1>), PT_FN(pt_trace_rays_kernel<2>),
+    PT_FN(pt_trace_rays_wide_kernel<0>), PT_FN(pt_trace_rays_wide_kernel<1>), PT_FN(pt_trace_rays_wide_kernel<2>),
+    PT_FN(pt_features_kernel<1>), PT_FN(pt_features_kernel<2>),
+    PT_FN(pt_denoise_kernel<0>), PT_FN(pt_denoise_kernel<1>), PT_FN(pt_denoise_kernel<2>), PT_FN(pt_denoise_kernel<3>),
+  };
+  resolve(others, sizeof others / sizeof others[0]);
+  return e;
 }
 
 // config: 0 = 16 waves x 1 workgroup per CU (4 waves per SIMD) with a 512-node treelet, 1 = 10 x 2 (5) with 256 nodes each,
@@ -3273,16 +3144,12 @@ hipError_t launch_trace_rays(const KParams& p, int kind, const float* rays_dev, 
   if (n == 0) return hipSuccess;
   if (kind == 3) {   // four-wide walk; p.stack_lds_entries covers the whole stack (3 x depth of the wide tree)
     const size_t lds = (size_t)p.stack_lds_entries * 64u * sizeof(uint2);
-    if (lds > 64 * 1024) {
-      const void* fn = p.wide8 == 1u ? reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<1>)
-                     : (p.wide8 == 2u ? reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<2>) : reinterpret_cast<const void*>(pt_trace_rays_wide_kernel<0>));
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    if (p.wide8 == 1u) hipLaunchKernelGGL(pt_trace_rays_wide_kernel<1>, dim3((n + 63u) / 64u), dim3(64), lds, stream, p, rays_dev, n, out_dev);
-    else if (p.wide8 == 2u) hipLaunchKernelGGL(pt_trace_rays_wide_kernel<2>, dim3((n + 63u) / 64u), dim3(64), lds, stream, p, rays_dev, n, out_dev);
-    else hipLaunchKernelGGL(pt_trace_rays_wide_kernel<0>, dim3((n + 63u) / 64u), dim3(64), lds, stream, p, rays_dev, n, out_dev);
-    return hipGetLastError();
+    const void* fn = p.wide8 == 1u ? PT_FN(pt_trace_rays_wide_kernel<1>) : (p.wide8 == 2u ? PT_FN(pt_trace_rays_wide_kernel<2>) : PT_FN(pt_trace_rays_wide_kernel<0>));
+    const hipError_t e = allow_lds(fn, lds);
+    if (e != hipSuccess) return e;
+    KParams pc = p;
+    void* args[] = { &pc, &rays_dev, &n, &out_dev };
+    return hipLaunchKernel(fn, dim3((n + 63u) / 64u), dim3(64), args, lds, stream);
   }
   dim3 grid((n + 255u) / 256u);
   if (kind == 1) hipLaunchKernelGGL(pt_trace_rays_kernel<1>, grid, dim3(256), 0, stream, p, rays_dev, n, out_dev);
@@ -3292,14 +3159,10 @@ hipError_t launch_trace_rays(const KParams& p, int kind, const float* rays_dev, 
 
 #else
 } // namespace (ptamd_fma in this translation unit)
-// C entry points of the contracted instantiation (pt_kernels_fma.hip): ptamd_api.cpp calls these for PTAMD_KERNEL_BVH_RESTART_FMA
-extern "C" hipError_t ptamd_fma_restart_blocks_per_cu(int lds_resident, size_t lds_bytes, int* out)
+// The one C entry point of the contracted instantiation (pt_kernels_fma.hip): its form of a launch, for megakernel_form
+extern "C" void ptamd_fma_restart_form(int lds_resident, size_t lds_bytes, const ptamd_fma::KParams* p, ptamd_fma::KernelForm* out)
 {
-  return ptamd::restart_blocks_per_cu(lds_resident != 0, lds_bytes, out);
-}
-extern "C" hipError_t ptamd_fma_launch_restart(const void* kparams, int lds_resident, size_t lds_bytes, uint32_t n_blocks, hipStream_t stream)
-{
-  return ptamd::launch_megakernel_restart(*reinterpret_cast<const ptamd::KParams*>(kparams), lds_resident != 0, lds_bytes, false, n_blocks, stream);
+  *out = ptamd::restart_form(lds_resident != 0, false, false, lds_bytes, p);
 }
 namespace ptamd {
 #endif

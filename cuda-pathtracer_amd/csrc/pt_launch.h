@@ -4,32 +4,36 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ptamd.h"
+
 namespace ptamd {
 
 struct KParams;
 struct DenoiseParams;
 struct TemporalParams;
 
-// kind: 1 brute force, 2 BVH.  lds_bytes: dynamic LDS needed when lds_resident.
-hipError_t launch_megakernel(const KParams& p, int kind, bool lds_resident, size_t lds_bytes, bool stats,
-                             hipStream_t stream);
-hipError_t persistent_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out);
-hipError_t launch_megakernel_persistent(const KParams& p, bool lds_resident, size_t lds_bytes, bool stats,
-                                        uint32_t n_blocks, hipStream_t stream);
-hipError_t blockwise_blocks_per_cu(bool lds_resident, size_t scene_lds_bytes, int* out);
-hipError_t launch_megakernel_blockwise(const KParams& p, bool lds_resident, size_t scene_lds_bytes, bool stats,
-                                       uint32_t n_blocks, hipStream_t stream);
-uint32_t split_shader_waves();
-hipError_t split_blocks_per_cu(bool lds_resident, size_t scene_lds_bytes, int* out);
-hipError_t launch_megakernel_split(const KParams& p, bool lds_resident, size_t scene_lds_bytes, bool stats,
-                                   uint32_t n_blocks, hipStream_t stream);
+// One form of a megakernel: a compiled instantiation and what a launch has to know about it (pt_kernels.hip: launchers)
+struct KernelForm {
+  const void* fn;            // what is launched
+  const void* occupancy_fn;  // whose residency sizes the grid: the plain instantiation of the form's family
+  uint32_t threads;          // workgroup size
+  uint32_t ticket_waves;     // waves per workgroup that take tile tickets; 0: the tile kernels' 2-D grid of one thread per pixel
+  size_t lds_bytes;          // dynamic LDS of the launch
+  uint32_t cache_slot;       // index into ptamd_context::occupancy (kFormSlot*)
+  const char* name;          // the family, for error text
+};
+enum : uint32_t { kFormSlotTile, kFormSlotPersistent, kFormSlotBlockwise, kFormSlotSplit, kFormSlotRestart, kFormSlotRestartContracted, kFormSlotRestartList, kFormSlots };
+// kernel: PTAMD_KERNEL_* with AUTO resolved.  lds_bytes: of the scene's copy; for the restart kernel the launch's dynamic LDS
+// (ptamd_api.cpp: lay_out_lds).  list: the list form of adaptive sampling (pt_adaptive.h; KParams::adaptive names the state's device
+// block).  p: the launch, whose fields choose among the restart kernel's forms (pt_device.h: restart_select), or nullptr before it is
+// known: everything but `fn` is then already final.
+KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p);
+hipError_t form_blocks_per_cu(const KernelForm& f, int* out);
+// n_blocks: the grid of every form that takes tickets (the tile kernels' follows from the launch's rows).  Nothing to do: hipSuccess
+hipError_t launch_form(const KernelForm& f, const KParams& p, uint32_t n_blocks, hipStream_t stream);
 uint32_t restart_threads(bool lds_resident);
 uint32_t restart_treelet_region_bytes();   // != 0: the wide walk's LDS treelet is chunk-major in a region of this size (pt_kernels.hip: PT_TREELET_SOA)
 uint32_t restart_wide_blocks_per_cu();
-// list: the list form of adaptive sampling (pt_adaptive.h; KParams::adaptive names the state's device block)
-hipError_t restart_blocks_per_cu(bool lds_resident, size_t lds_bytes, int* out, bool list = false);
-hipError_t launch_megakernel_restart(const KParams& p, bool lds_resident, size_t lds_bytes, bool stats,
-                                     uint32_t n_blocks, hipStream_t stream, bool list = false);
 hipError_t launch_resolve(const KParams& p, hipStream_t stream);
 // gamma step of the tonemap as a table (pt_kernels.hip: gamma_byte): 258 floats, and its exhaustive check
 hipError_t build_gamma_table(float* table_dev, hipStream_t stream);
@@ -55,3 +59,6 @@ hipError_t launch_adaptive_resolve(const AdaptiveParams& a, hipStream_t stream);
 hipError_t launch_temporal_pass(const DenoiseParams& q, const TemporalParams& t, int pass, hipStream_t stream);
 
 } // namespace ptamd
+
+// the contracted instantiation of the restart kernel (pt_kernels_fma.hip) exports its form of a launch; megakernel_form asks it
+extern "C" void ptamd_fma_restart_form(int lds_resident, size_t lds_bytes, const ptamd::KParams* p, ptamd::KernelForm* out);

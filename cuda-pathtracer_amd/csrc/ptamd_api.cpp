@@ -119,10 +119,9 @@ struct ptamd_context {
   std::vector<bool> heads_clean;   // per ring slot: its ticket heads are known to be zero (creation, or its last user's resolve pass)
   std::vector<bool> slot_pinned;   // per ring slot: baked into a captured graph (skipped by the rotation until ptamd_release_captured)
   int n_cus = 0;
-  // resident workgroups per CU of the persistent kernels, one entry per code object, keyed by the launch's dynamic LDS bytes
-  // (blocks_per_cu).  The first four in the order of PTAMD_KERNEL_BVH_PERSISTENT.._RESTART, then the restart kernel's two other forms.
-  enum { kOccPersistent, kOccBlockwise, kOccSplit, kOccRestart, kOccRestartFma, kOccRestartList, kOccEntries };
-  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[kOccEntries];
+  // resident workgroups per CU of the persistent kernels, one entry per KernelForm::cache_slot, keyed by the launch's dynamic LDS
+  // bytes (blocks_per_cu)
+  struct Occupancy { size_t lds = ~(size_t)0; int blocks_per_cu = -1; } occupancy[ptamd::kFormSlots];
   // parked samples of batched launches, one scratch per stream: launches on one stream are ordered, launches on
   // different streams of one context (frames in flight, ptamd_launch.machine_share) must not share a buffer
   // Four slabs per stream.  [0..2] are used in turn by pipelined launches (megakernel on a lane, below): the
@@ -219,13 +218,6 @@ constexpr uint32_t kMaxLeaf = 2;   // 2 / 3 / 4 = 10902 / 10839 / 10160 Msamples
 constexpr uint32_t kTicketRing = 1024;
 constexpr size_t kMaxScratchStreams = 16;   // sample scratches kept per context (one per stream that batches frames)
 constexpr uint32_t kMaxFramesPerSlab = 4;   // a batched launch parks at most this many frames at a time: longer batches are issued as consecutive launches of <= 4 frames (the same bits by the contract of frame_count), so a stream's slab bytes do not depend on frame_count
-#ifndef PT_PERSISTENT_THREADS
-#define PT_PERSISTENT_THREADS 512
-#endif
-#ifndef PT_BW_THREADS
-#define PT_BW_THREADS 512
-#endif
-constexpr uint32_t kPersistentThreads = PT_PERSISTENT_THREADS; // same macro as pt_kernels.hip
 
 int hip_fail(const char* what, hipError_t e)
 {
@@ -394,10 +386,6 @@ int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
   }
   return PTAMD_OK;
 }
-
-// the contracted instantiation of the restart kernel (pt_kernels_fma.hip)
-extern "C" hipError_t ptamd_fma_restart_blocks_per_cu(int lds_resident, size_t lds_bytes, int* out);
-extern "C" hipError_t ptamd_fma_launch_restart(const void* kparams, int lds_resident, size_t lds_bytes, uint32_t n_blocks, hipStream_t stream);
 
 // Box margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins inside the scene's extent
 // (bvh_builder.cpp).  A camera so far outside it that this bound exceeds the margin (e.g. 1e5 units from a unit-sized scene)
@@ -677,25 +665,25 @@ void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, con
   }
 }
 
-// Resident workgroups per CU of the launch's kernel, cached per code object (ptamd_context::occupancy) and key: the dynamic LDS
-// bytes for LDS-resident scenes; for the wide walk, the restart kernel's + 1 and 0 for the other kernels
-int blocks_per_cu(ptamd_context* ctx, const LaunchPlan& pl, bool list, int& bpc)
+// The form of the launch's kernel (pt_launch.h).  p: the launch once its fields are final (issue), else nullptr: all but KernelForm::fn.
+// (launch_lds is the scene copy's bytes for every kernel but the restart kernel: only lay_out_lds moves it)
+KernelForm form_of(const LaunchPlan& pl, bool stats, bool list, const KParams* p)
 {
-  const bool restart = pl.which == PTAMD_KERNEL_BVH_RESTART;
-  ptamd_context::Occupancy& occ = ctx->occupancy[pl.which - PTAMD_KERNEL_BVH_PERSISTENT + (pl.fma ? 1 : 0) + (list ? 2 : 0)];
-  const size_t key = pl.resident ? pl.launch_lds : (restart ? pl.launch_lds + 1u : 0);
+  return megakernel_form(pl.fma ? (uint32_t)PTAMD_KERNEL_BVH_RESTART_FMA : pl.which, pl.resident, stats, list, pl.launch_lds, p);
+}
+
+// Resident workgroups per CU of the launch's kernel, cached per form slot (ptamd_context::occupancy) and key: the dynamic LDS
+// bytes for LDS-resident scenes; for the wide walk, the restart kernel's + 1 and 0 for the other kernels
+int blocks_per_cu(ptamd_context* ctx, const LaunchPlan& pl, const KernelForm& form, int& bpc)
+{
+  ptamd_context::Occupancy& occ = ctx->occupancy[form.cache_slot];
+  const size_t key = pl.resident ? pl.launch_lds : (pl.which == PTAMD_KERNEL_BVH_RESTART ? pl.launch_lds + 1u : 0);
   if (occ.blocks_per_cu < 0 || occ.lds != key) {
     int q = -1;
-    hipError_t e;
-    switch (pl.which) {
-      case PTAMD_KERNEL_BVH_PERSISTENT: e = persistent_blocks_per_cu(pl.resident, pl.lds, &q); break;
-      case PTAMD_KERNEL_BVH_BLOCKWISE: e = blockwise_blocks_per_cu(pl.resident, pl.lds, &q); break;
-      case PTAMD_KERNEL_BVH_SPLIT: e = split_blocks_per_cu(pl.resident, pl.lds, &q); break;
-      default: e = pl.fma ? ptamd_fma_restart_blocks_per_cu(pl.resident ? 1 : 0, pl.launch_lds, &q) : restart_blocks_per_cu(pl.resident, pl.launch_lds, &q, list);
-    }
+    const hipError_t e = form_blocks_per_cu(form, &q);
     if (e != hipSuccess || q < 1) {
       occ.blocks_per_cu = -1;
-      return hip_fail(pl.which == PTAMD_KERNEL_BVH_BLOCKWISE ? "occupancy query of the blockwise kernel" : "occupancy query of the persistent kernel", e);
+      return hip_fail((std::string("occupancy query of the ") + form.name + " kernel").c_str(), e);
     }
     occ.blocks_per_cu = q; occ.lds = key;
   }
@@ -726,10 +714,10 @@ int size_grid(ptamd_context* ctx, const ptamd_launch* l, const AdaptiveParams* a
     return PTAMD_ERR_LIMIT;
   }
   int bpc = 0;
-  const int rc = blocks_per_cu(ctx, pl, ad != nullptr, bpc);
+  const KernelForm form = form_of(pl, false, ad != nullptr, nullptr);
+  const int rc = blocks_per_cu(ctx, pl, form, bpc);
   if (rc != PTAMD_OK) return rc;
-  // waves that take tile tickets: every wave of a persistent block, the shader waves of a split block
-  pl.waves_per_block = pl.which == PTAMD_KERNEL_BVH_SPLIT ? split_shader_waves() : (restart ? restart_threads(pl.resident) / 64u : kPersistentThreads / 64u);
+  pl.waves_per_block = form.ticket_waves;   // every wave of a persistent block, the shader waves of a split block
   uint32_t n_blocks = (uint32_t)ctx->n_cus * (uint32_t)bpc;
   p.sample_count = count;
   p.frame_nb0 = l->frame_nb;
@@ -871,11 +859,8 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
     ctx->heads_clean[pl.slot] = false;
   }
   if (restart && !pl.fma && ctx->d_timeline && p.n_static <= ctx->timeline_waves) p.timeline = ctx->d_timeline;
-  hipError_t e;
-  if (split) { p.tiles_per_ticket = 1; e = launch_megakernel_split(p, pl.resident, pl.lds, stats, pl.n_blocks, pl.stream); }
-  else if (!restart) e = launch_megakernel_persistent(p, pl.resident, pl.lds, stats, pl.n_blocks, pl.stream);
-  else if (pl.fma) e = ptamd_fma_launch_restart(&p, pl.resident ? 1 : 0, pl.launch_lds, pl.n_blocks, mega_stream);
-  else e = launch_megakernel_restart(p, pl.resident, pl.launch_lds, stats, pl.n_blocks, mega_stream, ad != nullptr);
+  if (split) p.tiles_per_ticket = 1;
+  hipError_t e = launch_form(form_of(pl, stats, ad != nullptr, &p), p, pl.n_blocks, restart ? mega_stream : pl.stream);
   if (e == hipSuccess && pl.pipelined) {
     PT_HIP(hipEventRecord(sc->mega_done[pl.slab], mega_stream));
     PT_HIP(hipStreamWaitEvent(pl.stream, sc->mega_done[pl.slab], 0));
@@ -927,23 +912,22 @@ int launch_part(ptamd_context* ctx, const ptamd_launch* l, bool stats, bool late
     const bool capturing = pl.stream != nullptr && (hipStreamIsCapturing(pl.stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone);
     if ((rc = wait_for_update(ctx->scenes[l->scene_id], pl.stream, capturing)) != PTAMD_OK) return rc;
   }
-  hipError_t e;
+  const KernelForm form = form_of(pl, stats, false, &p);
+  uint32_t n_blocks = 0;   // (the tile kernels' grid follows from the rows)
   if (pl.which == PTAMD_KERNEL_BVH_BLOCKWISE) {
     // persistent workgroups over 32 x (2 * waves) super-tiles; tickets 0..n_blocks-1 are static
     const uint32_t rows = l->row_end - l->row_begin;
-    const uint32_t st_rows = (PT_BW_THREADS / 64u) * 2u;
+    const uint32_t st_rows = (form.threads / 64u) * 2u;
     p.tiles_x = (l->width + 31u) / 32u;
     p.n_tiles = p.tiles_x * ((rows + st_rows - 1u) / st_rows);
     if (p.n_tiles == 0) return PTAMD_OK;
     int bpc = 0;
-    if ((rc = blocks_per_cu(ctx, pl, false, bpc)) != PTAMD_OK || (rc = take_slot(ctx, false, nullptr, pl.slot)) != PTAMD_OK) return rc;
-    const uint32_t n_blocks = std::min((uint32_t)ctx->n_cus * (uint32_t)bpc, p.n_tiles);
+    if ((rc = blocks_per_cu(ctx, pl, form, bpc)) != PTAMD_OK || (rc = take_slot(ctx, false, nullptr, pl.slot)) != PTAMD_OK) return rc;
+    n_blocks = std::min((uint32_t)ctx->n_cus * (uint32_t)bpc, p.n_tiles);
     p.tile_counter = ctx->d_tickets + pl.slot;
     PT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.tile_counter), (int)n_blocks, 1, pl.stream));
-    e = launch_megakernel_blockwise(p, pl.resident, pl.lds, stats, n_blocks, pl.stream);
-  } else {
-    e = launch_megakernel(p, pl.which == PTAMD_KERNEL_BRUTE_FORCE ? 1 : 2, pl.resident, pl.lds, stats, pl.stream);
   }
+  const hipError_t e = launch_form(form, p, n_blocks, pl.stream);
   return e == hipSuccess ? PTAMD_OK : hip_fail("megakernel launch", e);
 }
 

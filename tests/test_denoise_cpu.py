@@ -246,9 +246,11 @@ def digests():
 
 
 def test_existing_kernels_compile_to_the_same_code(digests):
-    """tests/golden/kernel_isa_digests.json: the digest of every kernel and device function of the parent build (the commit
-    before the denoiser).  The denoiser moved the resolve's output stage into pt_device.h as host-and-device functions; the
-    device code of everything that existed must not have moved by one byte."""
+    """tests/golden/kernel_isa_digests.json: the digest of every kernel and device function of both units, 54 + 10, recorded on
+    the commit before the launchers became one table of kernel forms (bd82564; the 55 entries recorded earlier, on the commit
+    before the denoiser, came out identical there).  Host-side changes such as that one, or the denoiser's move of the
+    resolve's output stage into pt_device.h as host-and-device functions, must not move the device code of anything that
+    existed by one byte."""
     with open(os.path.join(ROOT, "tests", "golden", "kernel_isa_digests.json")) as fh:
         golden = json.load(fh)
     ver = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
