@@ -478,11 +478,15 @@ struct KParams {
   unsigned long long* timeline;   // restart kernel: != nullptr selects the instantiation that records 4 time stamps per wave (ptamd_set_timeline)
   // restart kernel, read by the host only (restart_select): where a resident scene's launch goes that the shipped instantiation
   // serves.  PT_ROUND_GENERIC: to the generic one (PTAMD_RS_GENERIC); PT_ROUND_FLAT: to the flat one (a flat scene under a one-colour
-  // environment, ptamd_api.cpp: scene_is_flat)
+  // environment, ptamd_api.cpp: scene_is_flat); PT_ROUND_SKIP: to the skip form of the plain or the flat one (the scene has a
+  // relinked link table behind its nodes, host/skip_links.cpp, and the launch's LDS holds the entry nodes in front of the scene)
   uint32_t round_form;
 };
 #define PT_ROUND_GENERIC 1u
 #define PT_ROUND_FLAT 2u
+#define PT_ROUND_SKIP 4u
+// LDS bytes in front of the scene's copy in the skip forms: the node a walk starts at, one word per ray octant
+#define PT_SKIP_ENTRY_BYTES 32u
 
 // The restart kernel's forms: the VARIANT argument of pt_megakernel_restart<LDS_RESIDENT, VARIANT> (pt_kernels.hip)
 #define PT_RS_PLAIN 0
@@ -494,7 +498,9 @@ struct KParams {
 #define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
 #define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
 #define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
-#define PT_RS_FORMS 9
+#define PT_RS_FLAT_SKIP 9   /* PT_RS_FLAT over the relinked links: the box tests of the scene's skip set are left out (KParams::round_form) */
+#define PT_RS_PLAIN_SKIP 10 /* ... and PT_RS_PLAIN */
+#define PT_RS_FORMS 11
 
 // Which instantiation of the restart kernel serves a launch: the first rule that applies.  Host code.  p: the launch, or nullptr for
 // the occupancy query, which asks for the family's plain form.  contracted: the choice of pt_kernels_fma.hip, which compiles PLAIN,
@@ -512,6 +518,7 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
   // the shipped instantiation of a resident scene is compiled for four launch constants (pt_megakernel_restart: LEAN): a static
   // camera, pools in LDS, no XCD regions, no interleaved bands; any other launch, or PTAMD_RS_GENERIC, reads them at run time
   if (p && !(p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC))) return { PT_RS_GENERIC, true };
+  if (p && (p->round_form & PT_ROUND_SKIP) && !contracted) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP : PT_RS_PLAIN_SKIP, true };   // the same two launches of a scene with a skip set
   if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment
   return { PT_RS_PLAIN, true };
 }

@@ -1043,9 +1043,13 @@ PT_DEV void flush_counters(const KParams& p, const Counters& cnt, uint32_t sampl
 // Box addresses must stay below 0x8000: 32 bytes per node, nodes first in LDS, so up to ~900 nodes — more than an
 // LDS-resident scene can have (64 bytes of links + boxes and >= 48 bytes of triangles per node pair in 64 KB); the
 // host checks it (ptamd_api.cpp: kCompactMaxNodes) and walks bigger trees from global memory.
-template <int KIND, bool LDS_RESIDENT, bool COMPACT = false>
-PT_DEV void stage_scene(const KParams& p, float4* s_mem, const float4*& s_nodes, const float4*& s_tris)
+// SKIP (the restart kernel's skip forms, COMPACT only): the link words come from the scene's relinked table behind p.nodes
+// (host/skip_links.cpp: the same codes with node indices for addresses, the targets that are skipped nodes already replaced), and
+// the scene's copy starts PT_SKIP_ENTRY_BYTES into s_mem, behind the eight nodes a walk starts at (node index, PT_END for no tree).
+template <int KIND, bool LDS_RESIDENT, bool COMPACT = false, bool SKIP = false>
+PT_DEV void stage_scene(const KParams& p, float4* s_mem_, const float4*& s_nodes, const float4*& s_tris)
 {
+  float4* const s_mem = SKIP ? s_mem_ + PT_SKIP_ENTRY_BYTES / 16u : s_mem_;
   if (LDS_RESIDENT) {
     if (KIND == 1) {
       stage_to_lds(s_mem, p.tris_brute, p.n_faces * 3);
@@ -1054,6 +1058,11 @@ PT_DEV void stage_scene(const KParams& p, float4* s_mem, const float4*& s_nodes,
     } else {
       if (COMPACT) {
         const uint32_t base = (uint32_t)(uintptr_t)s_mem;
+        const uint32_t* relinked = reinterpret_cast<const uint32_t*>(p.nodes + p.n_nodes * 4);
+        if (SKIP && threadIdx.x < 8u) {
+          const uint32_t e = relinked[p.n_nodes * 8u + threadIdx.x];
+          reinterpret_cast<uint32_t*>(s_mem_)[threadIdx.x] = e == 0xFFFFu ? PT_END : e;
+        }
         // box addresses are 15-bit codes: the host only launches this layout for <= kCompactMaxNodes nodes and the
         // kernels keep no static LDS in front of s_mem; should either ever change, stop here rather than walk garbage
         // ... and a leaf's hit code holds its triangle range: count (<= 15) << 11 | first record (the host launches this layout
@@ -1072,6 +1081,10 @@ PT_DEV void stage_scene(const KParams& p, float4* s_mem, const float4*& s_nodes,
             const uint32_t ha = leaf ? (0x8000u | ((f_as_u(q0.w) >> 24) << 11) | (f_as_u(q0.w) & 0x7FFu)) : base + down * 32u;
             const uint32_t ma = miss[o] == PT_END ? 0xFFFFu : base + miss[o] * 32u;
             word[o] = ha | (ma << 16);
+            if (SKIP) {
+              const uint32_t w = relinked[i * 8u + o], hc = w & 0xFFFFu, mc = w >> 16;
+              word[o] = (hc < 0x8000u ? base + hc * 32u : hc) | ((mc < 0x8000u ? base + mc * 32u : mc) << 16);
+            }
           }
           float4* links = s_mem + p.n_nodes * 2u;
           // the box as centre and half extent (the loop then needs no min / max per axis: walk_to_leaf_lds_state).  The half
@@ -2031,8 +2044,11 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
   // PT_RS_FLAT is the same launch of a flat scene under a uniform environment (ptamd_api.cpp: scene_is_flat): the shading half
   // reads the compact record and has no texel fetch, normal map, cubemap lookup or refraction branch
-  constexpr bool FLAT = LDS_RESIDENT && VARIANT == PT_RS_FLAT;
-  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || FLAT);
+  // PT_RS_FLAT_SKIP and PT_RS_PLAIN_SKIP are those two over the scene's relinked links (stage_scene: SKIP): box tests nearly every
+  // ray passes are left out, and a walk starts at the entry node of its ray's octant instead of the root
+  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && (VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_PLAIN_SKIP);
+  constexpr bool FLAT = LDS_RESIDENT && (VARIANT == PT_RS_FLAT || VARIANT == PT_RS_FLAT_SKIP);
+  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || VARIANT == PT_RS_PLAIN_SKIP || FLAT);
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
   // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
   // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
@@ -2044,7 +2060,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   const float4* s_nodes;
   const float4* s_tris;
   PT_STAMP(0);
-  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK>(p, s_mem, s_nodes, s_tris);
+  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK, SKIP>(p, s_mem, s_nodes, s_tris);
   // scenes that do not fit in LDS are walked in the four-wide form; LDS then holds the waves' stacks
   constexpr bool WIDE = !LDS_RESIDENT;
 
@@ -2233,7 +2249,8 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
     if (!idle) {
       if (!walking) {
         best.t = PT_MAX_DIST; best.u = 0.f; best.v = 0.f; best.idx = PT_END;
-        node = p.n_nodes ? 0u : PT_END;
+        if (SKIP) node = reinterpret_cast<const uint32_t*>(s_mem)[(st.d.x < 0.f ? 1u : 0u) | (st.d.y < 0.f ? 2u : 0u) | (st.d.z < 0.f ? 4u : 0u)];   // (walk_init's octant)
+        else node = p.n_nodes ? 0u : PT_END;
         cur = p.n_nodes4 ? 0u : PT_NONE;
         sp = 0u;
         walking = true;
@@ -2960,7 +2977,8 @@ constexpr bool kContracted = true;
 #endif
 
 // The restart kernel: (form, LDS_RESIDENT) -> its instantiation, nullptr where none is compiled: WIDE8 and WIDE4Q only ever serve a
-// scene walked from L2, GENERIC and FLAT only a resident one, and the contracted build carries the first five alone (restart_select).
+// scene walked from L2, GENERIC, FLAT and the two skip forms only a resident one, and the contracted build carries the first five alone
+// (restart_select).
 static const void* restart_entry(int variant, bool lds_resident)
 {
 #define PT_RS_ENTRY(V, R) case (V) * 2 + ((R) ? 1 : 0): return PT_FN(pt_megakernel_restart<R, V>)
@@ -2974,6 +2992,7 @@ static const void* restart_entry(int variant, bool lds_resident)
     PT_RS_ENTRY(PT_RS_WIDE8, false); PT_RS_ENTRY(PT_RS_WIDE4Q, false);
     PT_RS_ENTRY(PT_RS_LIST, false); PT_RS_ENTRY(PT_RS_LIST, true);
     PT_RS_ENTRY(PT_RS_FLAT, true);
+    PT_RS_ENTRY(PT_RS_FLAT_SKIP, true); PT_RS_ENTRY(PT_RS_PLAIN_SKIP, true);
 #endif
     default: return nullptr;
   }

@@ -57,6 +57,7 @@ struct DeviceScene {
   uint32_t n_nodes4 = 0, depth4 = 0;
   float extent = 0.0f;       // largest finite |coordinate| of the scene (bvh_builder.cpp)
   bool all_finite = true;    // no NaN or infinite vertex coordinate
+  uint32_t n_skipped = 0;    // nodes whose box test the restart kernel's skip forms leave out; their link table lies behind `nodes` (host/skip_links.cpp)
   float reach = 0.0f;        // origin reach: largest |coordinate| of an origin the path forms, light spheres included (bvh_builder.cpp)
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
   ptamd_scene_info info{};
@@ -167,6 +168,8 @@ struct ptamd_context {
   bool wide4q = false;                    // PTAMD_WIDE4Q=1 (tuning): big scenes walk the 64-byte quantised four-wide nodes instead of the float ones (ahead by 2.8 % while the walk's LDS accesses went out as FLAT instructions, level since they are LDS instructions: profiles/r03_notes.md)
   bool generic_round = false;             // PTAMD_RS_GENERIC=1 (tuning): resident scenes take the restart kernel's generic instantiation (launch constants read at run time), for A/B and tests
   bool flat_round = true;                 // PTAMD_RS_FLAT=0 (tuning): flat scenes take PT_RS_PLAIN instead of the restart kernel's flat instantiation, for A/B and tests
+  uint32_t skip_mode = PTAMD_SKIP_DEFAULT; // PTAMD_SKIP (tuning): 0 no node is skipped (PTAMD_SKIP_SET with no set: the old forms are launched), root, all
+  float skip_threshold = 0.0f;            // PTAMD_SKIP_THRESHOLD (tuning): the selection's pass rate (0: kSkipThreshold)
   bool wide8 = false;                     // PTAMD_WIDE8=1 (tuning): big scenes walk the eight-wide quantised nodes (measured 8 % slower: DESIGN.md §4)
   uint2* d_trace_spill = nullptr;             // ptamd_trace_rays_queue: global continuation of the walk-only kernel's stacks (grown on demand)
   struct { uint32_t config = ~0u; size_t lds = 0; int resident = 0; } trace_queue_cache;   // ... its last configuration: dynamic-LDS attribute set, blocks resident per CU
@@ -565,6 +568,8 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   p.brute_walk = pl.brute_walk ? 1u : 0u;
   // the flat form of the restart kernel: a flat scene (its compact records exist) under a one-colour environment
   p.round_form = (ctx->generic_round ? PT_ROUND_GENERIC : 0u) | (ctx->flat_round && s.flat && ctx->cubemaps[l->cubemap_id].uniform ? PT_ROUND_FLAT : 0u);
+  // the skip forms: the scene has a relinked link table behind its nodes (lay_out_lds takes the bit back where their LDS does not fit)
+  if (s.n_skipped && pl.resident) p.round_form |= PT_ROUND_SKIP;
 }
 
 // Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
@@ -621,12 +626,15 @@ void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, con
     // pools of fresh paths in LDS when two workgroups with their scene copies leave room for them (PT_POOL_LDS_BYTES
     // per wave); else in a global slab (3 KiB per wave, L2-resident)
     const uint32_t waves = restart_threads(true) / 64u;
-    const size_t with_pools = ((pl.lds + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES;
     const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
+    const auto fits = [&](size_t scene) { return (((scene + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES) * blocks_wanted + 1024u <= 160u * 1024u; };
+    // the skip forms keep their eight entry nodes in front of the scene's copy (pt_kernels.hip: stage_scene)
+    if ((p.round_form & PT_ROUND_SKIP) && !(ctx->pool_in_lds && fits(pl.lds + PT_SKIP_ENTRY_BYTES))) p.round_form &= ~PT_ROUND_SKIP;
+    const size_t scene_lds = pl.lds + ((p.round_form & PT_ROUND_SKIP) ? PT_SKIP_ENTRY_BYTES : 0u);
     // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
     // there whatever the knob, at one workgroup per CU when two do not fit
-    if (ad || (ctx->pool_in_lds && with_pools * blocks_wanted + 1024u <= 160u * 1024u)) {
-      p.pool_lds_offset = (uint32_t)((pl.lds + 15u) & ~(size_t)15u);
+    if (ad || (ctx->pool_in_lds && fits(scene_lds))) {
+      p.pool_lds_offset = (uint32_t)((scene_lds + 15u) & ~(size_t)15u);
       if (p.pool_lds_offset == 0) p.pool_lds_offset = 16u;               // (an empty scene: keep the flag non-zero)
       pl.launch_lds = p.pool_lds_offset + (size_t)waves * PT_POOL_LDS_BYTES;
     }
@@ -1346,6 +1354,10 @@ int ptamd_create(int32_t device_ordinal, ptamd_context** out)
   if (const char* e = tuning_env("PTAMD_WIDE8")) ctx->wide8 = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_RS_GENERIC")) ctx->generic_round = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_RS_FLAT")) ctx->flat_round = std::atoi(e) != 0; // tuning knob
+  if (const char* e = tuning_env("PTAMD_SKIP")) { // tuning knob
+    ctx->skip_mode = !std::strcmp(e, "root") ? PTAMD_SKIP_ROOT : (!std::strcmp(e, "all") ? PTAMD_SKIP_ALL : (!std::strcmp(e, "0") ? PTAMD_SKIP_SET : PTAMD_SKIP_DEFAULT));
+  }
+  if (const char* e = tuning_env("PTAMD_SKIP_THRESHOLD")) { const float v = (float)std::atof(e); if (v > 0.0f && v < 1.0f) ctx->skip_threshold = v; } // tuning knob
   if (const char* e = tuning_env("PTAMD_WIDE4Q")) ctx->wide4q = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS")) ctx->pool_in_lds = std::atoi(e) != 0; // tuning knob
   if (const char* e = tuning_env("PTAMD_POOL_LDS_WIDE")) ctx->pool_in_lds_wide = std::atoi(e) != 0; // tuning knob
@@ -1427,7 +1439,21 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
   // product whoever forms it — so the table carries the square in its place and every sphere test saves the multiply
   std::vector<ptamd_light> dev_lights(sc->lights, sc->lights + sc->n_lights);
   for (ptamd_light& dl : dev_lights) dl.radius = dl.radius * dl.radius;
-  if ((rc = upload(d.nodes, bvh.nodes.data(), bvh.nodes.size() * 4)) ||
+  // scenes that take the compact LDS layout: the box tests the walk leaves out, and the relinked link table behind the node table
+  // (8 words per node, then the eight entry nodes) for the restart kernel's skip forms
+  std::vector<float> nodes_and_links(bvh.nodes);
+  if (bvh.n_nodes * 64u + bvh.n_tris * 48u <= kLdsBudget && bvh.n_nodes <= kCompactMaxNodes && bvh.n_tris <= kCompactMaxTris && skip_links_fit(bvh)) {
+    std::vector<uint8_t> skip;
+    std::vector<uint32_t> words;
+    skip_set_of(bvh, ctx->skip_mode, ctx->skip_threshold, nullptr, skip);
+    for (uint8_t k : skip) d.n_skipped += k;
+    if (d.n_skipped) {
+      skip_link_table(bvh, skip, words);
+      nodes_and_links.resize(bvh.nodes.size() + words.size());
+      std::memcpy(nodes_and_links.data() + bvh.nodes.size(), words.data(), words.size() * 4);
+    }
+  }
+  if ((rc = upload(d.nodes, nodes_and_links.data(), nodes_and_links.size() * 4)) ||
       (rc = upload(d.nodes4, bvh.nodes4.data(), bvh.nodes4.size() * 4)) ||
       (bvh.nodes8.empty() ? 0 : (rc = upload(d.nodes8, bvh.nodes8.data(), bvh.nodes8.size() * 4))) ||
       (bvh.nodes4q.empty() ? 0 : (rc = upload(d.nodes4q, bvh.nodes4q.data(), bvh.nodes4q.size() * 4))) ||
@@ -1875,6 +1901,13 @@ int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_
     return PTAMD_ERR_ARG;
   }
   *out_flat = ctx->flat_round && ctx->scenes[scene_id].flat && ctx->cubemaps[cubemap_id].uniform ? 1 : 0;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
+{
+  if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_skip_count: bad argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->scenes[scene_id].n_skipped;
   return PTAMD_OK;
 }
 

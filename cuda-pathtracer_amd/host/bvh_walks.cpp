@@ -269,6 +269,62 @@ void bvh_trace_host(const Bvh& bvh, const ptamd_face*, const float dir[3], const
   best.write(out);
 }
 
+// Mirror of the walk of the restart kernel's skip forms (PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP): the box test of bvh_trace_host, the
+// links of a skip set's table (ptamd_internal.h).  A walk starts at its octant's entry node; a hit code with bit 15 set is a leaf's.
+// MIRROR false (the selection's training rays, which only count): the slab distances by a multiply and an add and the minima by
+// compares, several times cheaper on a host than eighteen library calls per box; a pass rate does not turn on the last bit.
+namespace {
+template <bool MIRROR>
+void skip_walk(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], HostHit& out,
+               uint64_t* nodes_visited, uint64_t* tris_tested, uint32_t* node_visits, uint32_t* node_passes)
+{
+  const Ray ray(dir, origin);
+  const uint32_t oct = ray.octant();
+  Best best;
+  uint32_t node = words[(size_t)bvh.n_nodes * 8 + oct];
+  while (node != 0xFFFFu) {
+    const float* q = &bvh.nodes[(size_t)node * 16];
+    if (nodes_visited) ++*nodes_visited;
+    float tnear = -std::numeric_limits<float>::infinity(), tfar = std::numeric_limits<float>::infinity();
+    for (int a = 0; a < 3; ++a) {
+      if (MIRROR) {
+        float t0 = std::fma(q[a], ray.inv[a], ray.noi[a]);
+        float t1 = std::fma(q[4 + a], ray.inv[a], ray.noi[a]);
+        tnear = std::fmax(tnear, std::fmin(t0, t1));
+        tfar = std::fmin(tfar, std::fmax(t0, t1));
+      } else {
+        const float t0 = q[a] * ray.inv[a] + ray.noi[a], t1 = q[4 + a] * ray.inv[a] + ray.noi[a];
+        const float lo = t0 < t1 ? t0 : t1, hi = t0 < t1 ? t1 : t0;
+        tnear = lo > tnear ? lo : tnear;
+        tfar = hi < tfar ? hi : tfar;
+      }
+    }
+    const bool hit = tnear <= tfar && tfar >= 0.0f && tnear <= best.t;
+    if (node_visits) { ++node_visits[node]; node_passes[node] += hit ? 1u : 0u; }
+    const uint32_t word = words[(size_t)node * 8 + oct];
+    uint32_t code = hit ? (word & 0xFFFFu) : (word >> 16);
+    if (code >= 0x8000u && code != 0xFFFFu) {   // parked at a leaf: its records, then on along its miss code
+      test_leaf(bvh, code & 0x7FFu, (code >> 11) & 0xFu, ray, best, tris_tested);
+      code = word >> 16;
+    }
+    node = code;
+  }
+  best.write(out);
+}
+} // namespace
+
+void skip_trace_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], HostHit& out,
+                     uint64_t* nodes_visited, uint64_t* tris_tested, uint32_t* node_visits, uint32_t* node_passes)
+{
+  skip_walk<true>(bvh, words, dir, origin, out, nodes_visited, tris_tested, node_visits, node_passes);
+}
+
+void skip_count_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], uint32_t* node_visits, uint32_t* node_passes)
+{
+  HostHit h;
+  skip_walk<false>(bvh, words, dir, origin, h, nullptr, nullptr, node_visits, node_passes);
+}
+
 } // namespace ptamd
 
 namespace {
@@ -348,5 +404,39 @@ extern "C" int ptamd_host_bvh_refit_trace(const ptamd_face* faces_a, const ptamd
   if (rc != PTAMD_OK || (rc = ptamd::refit_bvh(bvh, faces_b, n_faces, nullptr, 0)) != PTAMD_OK) return rc;
   trace_rays(bvh, binary_walk, rays, n, out_binary, nullptr);
   trace_rays(bvh, ptamd::bvh4_trace_host, rays, n, out_wide, nullptr);
+  return PTAMD_OK;
+}
+
+extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
+                                     const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
+                                     uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out)
+{
+  if ((n_faces && !faces) || (n && (!rays || !out)) || !n_nodes || mode > PTAMD_SKIP_ALL) { ptamd::set_error("ptamd_host_skip_trace: bad argument"); return PTAMD_ERR_ARG; }
+  ptamd::Bvh bvh;
+  int rc = ptamd::build_bvh(faces, n_faces, 1e-3f, 2, bvh, 0u);   // leaves of at most two, as an upload builds them
+  if (rc != PTAMD_OK) return rc;
+  if (!ptamd::skip_links_fit(bvh)) { ptamd::set_error("ptamd_host_skip_trace: the tree is outside the compact layout's code space"); return PTAMD_ERR_LIMIT; }
+  const uint32_t room = *n_nodes;
+  *n_nodes = bvh.n_nodes;
+  if ((skip_out || words_out) && room < bvh.n_nodes) { ptamd::set_error("ptamd_host_skip_trace: room for fewer nodes than the tree has"); return PTAMD_ERR_ARG; }
+  std::vector<uint8_t> skip;
+  std::vector<uint32_t> words;
+  ptamd::skip_set_of(bvh, mode, threshold, skip_in, skip);
+  ptamd::skip_link_table(bvh, skip, words);
+  // the set and the links do not depend on the boxes: a refit keeps both
+  if (faces_refit && (rc = ptamd::refit_bvh(bvh, faces_refit, n_faces, nullptr, 0)) != PTAMD_OK) return rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    ptamd::HostHit h;
+    uint64_t visits = 0;
+    ptamd::skip_trace_host(bvh, words.data(), rays + (size_t)i * 6, rays + (size_t)i * 6 + 3, h, &visits, counters ? &counters[1] : nullptr);
+    if (counters) counters[0] += visits;
+    out[i * 4 + 0] = h.kind;
+    out[i * 4 + 1] = h.index;
+    std::memcpy(&out[i * 4 + 2], &h.t, 4);
+    out[i * 4 + 3] = (int32_t)visits;
+  }
+  if (counters) { counters[2] = 0; for (uint8_t s : skip) counters[2] += s; }
+  if (skip_out && bvh.n_nodes) std::memcpy(skip_out, skip.data(), bvh.n_nodes);
+  if (words_out) std::memcpy(words_out, words.data(), words.size() * 4);
   return PTAMD_OK;
 }

@@ -162,4 +162,34 @@ void bvh8_trace_host(const Bvh& bvh, const float dir[3], const float origin[3], 
 void bvh4q_trace_host(const Bvh& bvh, const float dir[3], const float origin[3], HostHit& out, uint64_t* nodes_visited,
                       uint64_t* tris_tested);
 
+// ---- skipped box tests of the LDS-resident walk (skip_links.cpp) -------------------------------------------
+//
+// In the threaded walk a box test only prunes: going from an interior node straight to the child its ray's octant visits first
+// cannot change the (t, face index) minimum, the leaves below are still box-tested.  A scene's SKIP SET is the interior nodes
+// whose test is left out; its LINK TABLE is what the compact LDS layout's links become with them gone, in node-index form:
+//   words[n * 8 + o] = hit code | miss code << 16 for node n and ray octant o, the codes of pt_kernels.hip: stage_scene with a
+//                      node index where that has an LDS address: < 0x8000 the node to test next, 0xFFFF the end of the walk,
+//                      0x8000 | count << 11 | first record a leaf's hit code.  A target that is a skipped node is replaced by
+//                      the end of its down-chain for o (the first node down the near children that is not skipped).
+//   words[n_nodes * 8 + o] = the node a walk of octant o starts at: the end of the root's down-chain; 0xFFFF for an empty tree.
+// Only for trees within the compact layout's code space (<= 896 nodes, <= 2047 records, leaves of <= 15).
+constexpr float kSkipThreshold = 0.6f;     // a node is skipped when more than this share of the training rays that test it pass
+// training rays: two per node of the tree, which keeps the selection cheaper than the tree's build
+constexpr uint32_t kSkipRaysPerNode = 2u, kSkipMinVisits = 16u;
+bool skip_links_fit(const Bvh& bvh);
+void skip_link_table(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words);
+// The set a mode asks for (ptamd.h: PTAMD_SKIP_*): `given` (one byte per node, null: none; leaves never count), the default
+// selection at `threshold` (0: kSkipThreshold), the root alone, every interior node
+void skip_set_of(const Bvh& bvh, uint32_t mode, float threshold, const uint8_t* given, std::vector<uint8_t>& skip);
+// The default set: training rays leave the scene's own surfaces (area-weighted origins pushed 0.03 along a cosine-weighted
+// direction about the front normal, from a fixed-seed generator that uses +, *, / and sqrt only: the same set on every host);
+// nodes visited at least kSkipMinVisits times whose pass rate exceeds `threshold` join the set, the rays are walked again with
+// those skipped, until nothing is added.
+void select_skip_nodes(const Bvh& bvh, float threshold, std::vector<uint8_t>& skip);
+// Mirror of the relinked walk over `words`; node_visits / node_passes (or null): per node, box tests and those that passed
+void skip_trace_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], HostHit& out,
+                     uint64_t* nodes_visited, uint64_t* tris_tested, uint32_t* node_visits = nullptr, uint32_t* node_passes = nullptr);
+// ... for the selection: the same walk with a cheaper slab test (a multiply and an add, compares), counting only
+void skip_count_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], uint32_t* node_visits, uint32_t* node_passes);
+
 } // namespace ptamd

@@ -253,6 +253,10 @@ SIGNATURES = {
     "ptamd_device_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ptamd_host_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ptamd_stream_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ptamd_scene_skip_count": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ptamd_host_skip_trace": (C.c_int, [C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
+                                        C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

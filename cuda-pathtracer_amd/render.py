@@ -163,6 +163,13 @@ class Context:
         N.check(self._lib.ptamd_scene_info_get(self._h, scene_id, C.byref(info)))
         return {n: getattr(info, n) for n, _ in N.SceneInfo._fields_}
 
+    def scene_skip_count(self, scene_id: int) -> int:
+        """ptamd_scene_skip_count: nodes of the scene whose box test the restart kernel's skip forms leave out (0: its launches
+        take the plain or the flat form)."""
+        out = C.c_uint32(0)
+        N.check(self._lib.ptamd_scene_skip_count(self._h, scene_id, C.byref(out)))
+        return out.value
+
     def scene_is_flat(self, scene_id: int, cubemap_id: int) -> bool:
         """ptamd_scene_is_flat: launches of the scene under the cubemap take the restart kernel's flat form."""
         out = C.c_int32()
@@ -406,6 +413,40 @@ def host_bvh_trace(scene: HostScene, rays: np.ndarray):
                                           rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays),
                                           out.ctypes.data_as(C.POINTER(C.c_int32)), counters))
     return out, counters[0], counters[1]
+
+
+SKIP_MODES = {"set": 0, "default": 1, "root": 2, "all": 3}
+
+
+def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=None, threshold: float = 0.0, refit_to=None) -> dict:
+    """Host mirror of the relinked walk of the restart kernel's skip forms (ptamd_host_skip_trace, no GPU).  mode: "default"
+    (the selection an upload makes, at `threshold` when given), "root", "all", or "set" with `skip` (one byte per node; None: no
+    node).  refit_to (HostScene or face array): the tree is refitted to those faces, set and links kept, before the rays are
+    walked.  Returns records int32[n,4] ({kind, index, t bits, box tests of the ray}), nodes, tris (visits and triangle tests), skip uint8[n_nodes] and words
+    uint32[n_nodes + 1, 8] (per node and octant hit | miss << 16 in node-index form; the last row holds the entry nodes)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    lib = N.load()
+    faces = scene.faces.ctypes.data_as(C.POINTER(N.Face))
+    fb = None
+    if refit_to is not None:
+        fb = np.ascontiguousarray(refit_to.faces if isinstance(refit_to, HostScene) else refit_to, dtype=FACE_DTYPE)
+        if len(fb) != len(scene.faces):
+            raise ValueError("a refit keeps the face count")
+    fb_ptr = fb.ctypes.data_as(C.POINTER(N.Face)) if fb is not None else None
+    given = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+    n_nodes = C.c_uint32(0)
+    N.check(lib.ptamd_host_skip_trace(faces, None, len(scene.faces), 0, 0.0, None, None, 0, None, None, C.byref(n_nodes), None, None))
+    if given is not None and len(given) != n_nodes.value:
+        raise ValueError("skip holds one byte per node")
+    out = np.zeros((len(rays), 4), dtype=np.int32)
+    skip_out = np.zeros(n_nodes.value, dtype=np.uint8)
+    words = np.zeros((n_nodes.value + 1, 8), dtype=np.uint32)
+    counters = (C.c_uint64 * 3)(0, 0, 0)
+    N.check(lib.ptamd_host_skip_trace(faces, fb_ptr, len(scene.faces), SKIP_MODES[mode], threshold,
+                                      given.ctypes.data if given is not None else None,
+                                      rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), out.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      counters, C.byref(n_nodes), skip_out.ctypes.data, words.ctypes.data))
+    return {"records": out, "nodes": counters[0], "tris": counters[1], "skip": skip_out, "words": words}
 
 
 def host_bvh4_trace(scene: HostScene, rays: np.ndarray):

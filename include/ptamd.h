@@ -744,6 +744,35 @@ int ptamd_device_to_host(ptamd_context* ctx, void* dst_host, const void* src_dev
 int ptamd_host_to_device(ptamd_context* ctx, void* dst_dev, const void* src_host, size_t bytes, void* stream);
 int ptamd_stream_synchronize(ptamd_context* ctx, void* stream);
 
+/* ---- Skipped box tests of the LDS-resident walk -----------------------------------------------------------
+ * In the stackless threaded walk a box test only prunes, so an interior node's test may be left out and the walk sent straight to
+ * the child its ray's octant visits first: the leaves below are still box-tested, the triangle test still decides, the result is
+ * the same record.  It pays at nodes nearly every ray passes.  An upload of a scene that takes the compact LDS layout chooses such a
+ * SKIP SET from training rays that leave the scene's own surfaces (the same set on every host) and writes the relinked link table
+ * behind the node table; launches the restart kernel's plain and flat forms would serve then take their skip forms.  A scene
+ * update keeps the set.  With PTAMD_TUNING=1: PTAMD_SKIP=0 none (the old forms are launched), PTAMD_SKIP=root the root alone,
+ * PTAMD_SKIP=all every interior node, PTAMD_SKIP_THRESHOLD=<pass rate> for the selection.
+ *
+ * ptamd_scene_skip_count: how many nodes of an uploaded scene are skipped (0: its launches take the old forms).
+ *
+ * ptamd_host_skip_trace: host mirror of the relinked walk, no device needed.  The tree of `faces` as an upload builds it, the skip
+ * set `mode` asks for (PTAMD_SKIP_SET: skip_in, one byte per node, NULL = none, leaves never count; PTAMD_SKIP_DEFAULT: the
+ * selection at `threshold`, 0 = the default), then, where faces_refit is not NULL, the tree refitted to those faces with set and
+ * links kept, then every ray through the walk.  rays as ptamd_host_bvh_trace; out: n * {kind, index, t bits, box tests of this
+ * ray}; counters (optional, 3 words): [0] += node
+ * visits, [1] += triangle tests, [2] = skipped nodes.  *n_nodes: in, the room of skip_out and words_out in nodes; out, the tree's
+ * node count.  skip_out (optional): the set, one byte per node.  words_out (optional): (n_nodes + 1) * 8 words, per node and ray
+ * octant `hit code | miss code << 16` in node-index form (a node index, 0xFFFF the end of the walk, 0x8000 | count << 11 | first
+ * record a leaf's hit code), then the eight entry nodes, one per octant.  PTAMD_ERR_LIMIT for trees outside the compact layout. */
+#define PTAMD_SKIP_SET 0u
+#define PTAMD_SKIP_DEFAULT 1u
+#define PTAMD_SKIP_ROOT 2u
+#define PTAMD_SKIP_ALL 3u
+int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
+int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
+                          const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
+                          uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ assembler-comment markers at the region boundaries and counts VALU / SALU / LDS 
 them in the ISA listing (block placement follows the source closely enough for this to be a useful map; the markers are
 scheduling barriers, so the listing differs slightly from the shipped code).   python3 scripts/isa_regions.py [--dump REGION]
 VARIANT=6 counts the generic instantiation of a resident scene (PT_RS_GENERIC) instead of the shipped one (0), VARIANT=8 the flat
-one (PT_RS_FLAT: flat scenes under a uniform environment)."""
+one (PT_RS_FLAT: flat scenes under a uniform environment), VARIANT=9 / 10 the skip forms of the flat and the shipped one
+(PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP)."""
 import os, re, subprocess, sys, tempfile, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")
