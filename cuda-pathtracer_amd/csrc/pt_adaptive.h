@@ -1,5 +1,5 @@
 // pt_adaptive.h — the arithmetic of adaptive sampling (ptamd_render_adaptive), written once for the device kernels (pt_adaptive.hip,
-// and the list form of the restart kernel in pt_kernels.hip) and the host mirror (ptamd_api.cpp: ptamd_host_adaptive_select).
+// and the list form of the restart kernel in pt_kernels.hip) and the host mirror (ptamd_adaptive.cpp: ptamd_host_adaptive_select).
 //
 // Both sides are compiled with -ffp-contract=off and call the functions below, so they execute the same binary32 operations in the
 // same order (division and square root correctly rounded on both): the device's active list equals the host mirror's entry for

@@ -1,5 +1,5 @@
 // pt_denoise.h — the arithmetic of the edge-aware denoiser (ptamd_denoise), written once for the device kernels
-// (pt_kernels.hip: pt_denoise_*_kernel) and the host mirror (ptamd_api.cpp: ptamd_host_denoise).
+// (pt_kernels.hip: pt_denoise_*_kernel) and the host mirror (ptamd_denoise.cpp: ptamd_host_denoise).
 //
 // Both sides are compiled with -ffp-contract=off and call the functions below, so they execute the same binary32 operations in
 // the same order: the device output equals the host mirror's bit for bit.  Transcendentals are the build's own (pt_expf here,

@@ -1,5 +1,5 @@
 // pt_denoise_temporal.h — the arithmetic of the temporal half of the denoiser (ptamd_denoise_temporal), written once for the
-// device kernels (pt_denoise_temporal.hip: pt_temporal_kernel) and the host mirror (ptamd_api.cpp: ptamd_host_denoise_temporal).
+// device kernels (pt_denoise_temporal.hip: pt_temporal_kernel) and the host mirror (ptamd_denoise.cpp: ptamd_host_denoise_temporal).
 //
 // As in pt_denoise.h, both sides are compiled with -ffp-contract=off and call the functions below, so they execute the same binary32
 // operations in the same order; there is no transcendental.  DESIGN.md §11 states the definition.  The passes this file adds to

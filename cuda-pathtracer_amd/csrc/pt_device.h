@@ -478,7 +478,7 @@ struct KParams {
   unsigned long long* timeline;   // restart kernel: != nullptr selects the instantiation that records 4 time stamps per wave (ptamd_set_timeline)
   // restart kernel, read by the host only (restart_select): where a resident scene's launch goes that the shipped instantiation
   // serves.  PT_ROUND_GENERIC: to the generic one (PTAMD_RS_GENERIC); PT_ROUND_FLAT: to the flat one (a flat scene under a one-colour
-  // environment, ptamd_api.cpp: scene_is_flat); PT_ROUND_SKIP: to the skip form of the plain or the flat one (the scene has a
+  // environment, ptamd_scene.cpp: scene_is_flat); PT_ROUND_SKIP: to the skip form of the plain or the flat one (the scene has a
   // relinked link table behind its nodes, host/skip_links.cpp, and the launch's LDS holds the entry nodes in front of the scene)
   uint32_t round_form;
 };

@@ -571,7 +571,7 @@ PT_DEV T karg_load(uint32_t byte_offset)
 
 PT_DEV Nearest nearest_lights(const KParams& p, f3 o, f3 d, Nearest n)
 {
-  const ConstF lights = as_constant(p.lights);     // 8 floats per light: color.xyz, vec.xyz, emission, radius^2 (ptamd_api.cpp)
+  const ConstF lights = as_constant(p.lights);     // 8 floats per light: color.xyz, vec.xyz, emission, radius^2 (ptamd_scene.cpp)
   for (uint32_t l = 0; l < p.n_lights; ++l) {
     const ConstF L = lights + l * 8u;
     // the discriminant of intersect_sphere, same operations: when it is negative for every lane of the wave (the usual
@@ -609,7 +609,7 @@ PT_DEV Nearest trace_nearest(const KParams& p, const float4* s_nodes, const floa
 // Second half of intersection.cuh:161-246 for the winner only: the deferred interpolation of
 // intersectTriangle (:124-131), the light normal (:204-210), texture and normal-map fetches
 // (:216-243).  Returns intersection.dist < MAX_DIST.
-// FLAT: the scene is flat (ptamd_api.cpp: scene_is_flat): the face's record is the compact one behind the general records
+// FLAT: the scene is flat (ptamd_scene.cpp: scene_is_flat): the face's record is the compact one behind the general records
 // (KParams::shade), whose texel is the only one its 1x1 map has, and no material has a normal map or an ior other than 1
 template <bool STATS, bool FLAT = false>
 PT_DEV bool resolve_hit(const KParams& p, f3 d, Nearest n, Hit& hit, Counters& cnt)
@@ -675,7 +675,7 @@ PT_DEV bool resolve_hit(const KParams& p, f3 d, Nearest n, Hit& hit, Counters& c
   hit.light = -1;
   hit.ior = s4.w;
   if (f_as_u(s4.z) & 0x80000000u) {
-    // 1x1 diffuse+specular map: the record carries its only texel (ptamd_api.cpp) — no dependent load
+    // 1x1 diffuse+specular map: the record carries its only texel (ptamd_scene.cpp) — no dependent load
     hit.diffuse_col = mk3(s5.x, s5.y, s5.z);
     hit.specular_col = s5.w;
   } else {
@@ -1042,7 +1042,7 @@ PT_DEV void flush_counters(const KParams& p, const Counters& cnt, uint32_t sampl
 // the split axis; miss: the old link), 0xFFFF ends the walk, and a leaf's hit code is 0x8000 | count << 11 | first triangle record.
 // Box addresses must stay below 0x8000: 32 bytes per node, nodes first in LDS, so up to ~900 nodes — more than an
 // LDS-resident scene can have (64 bytes of links + boxes and >= 48 bytes of triangles per node pair in 64 KB); the
-// host checks it (ptamd_api.cpp: kCompactMaxNodes) and walks bigger trees from global memory.
+// host checks it (ptamd_host.h: kCompactMaxNodes) and walks bigger trees from global memory.
 // SKIP (the restart kernel's skip forms, COMPACT only): the link words come from the scene's relinked table behind p.nodes
 // (host/skip_links.cpp: the same codes with node indices for addresses, the targets that are skipped nodes already replaced), and
 // the scene's copy starts PT_SKIP_ENTRY_BYTES into s_mem, behind the eight nodes a walk starts at (node index, PT_END for no tree).
@@ -2042,7 +2042,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // The shipped instantiation (LDS-resident scene, PT_RS_PLAIN) serves only the common launch, which fixes four launch constants:
   // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
   // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
-  // PT_RS_FLAT is the same launch of a flat scene under a uniform environment (ptamd_api.cpp: scene_is_flat): the shading half
+  // PT_RS_FLAT is the same launch of a flat scene under a uniform environment (ptamd_scene.cpp: scene_is_flat): the shading half
   // reads the compact record and has no texel fetch, normal map, cubemap lookup or refraction branch
   // PT_RS_FLAT_SKIP and PT_RS_PLAIN_SKIP are those two over the scene's relinked links (stage_scene: SKIP): box tests nearly every
   // ray passes are left out, and a walk starts at the entry node of its ray's octant instead of the root
@@ -2052,7 +2052,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
   // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
   // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
-  // the pools of fresh paths live in LDS for a resident scene and in the global slab for the four-wide walk (ptamd_api.cpp).
+  // the pools of fresh paths live in LDS for a resident scene and in the global slab for the four-wide walk (ptamd_launch.cpp).
   constexpr bool LIST = VARIANT == PT_RS_LIST;
   // constants of the launch the shipped instantiation and the list form share: static camera, no XCD regions, no interleaved bands
   constexpr bool FIXED = LEAN || LIST;
@@ -2257,7 +2257,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         if (STATS) cnt.rays++;
       }
       if (VARIANT == PT_RS_BRUTE) {
-        // a camera too far outside the scene for the boxes' margins (ptamd_api.cpp: far_origin): every triangle record, as
+        // a camera too far outside the scene for the boxes' margins (ptamd_scene.cpp: far_origin_camera): every triangle record, as
         // the reference does — the (t, face index) minimum does not depend on the order they are tested in
         for (uint32_t i = 0; i < p.n_bvh_tris; ++i) mt_test<false>(s_tris[i * 3u], s_tris[i * 3u + 1u], s_tris[i * 3u + 2u], st.o, st.d, best, false);
         if (STATS) cnt.tris += p.n_bvh_tris;

@@ -24,7 +24,7 @@ struct KernelForm {
 };
 enum : uint32_t { kFormSlotTile, kFormSlotPersistent, kFormSlotBlockwise, kFormSlotSplit, kFormSlotRestart, kFormSlotRestartContracted, kFormSlotRestartList, kFormSlots };
 // kernel: PTAMD_KERNEL_* with AUTO resolved.  lds_bytes: of the scene's copy; for the restart kernel the launch's dynamic LDS
-// (ptamd_api.cpp: lay_out_lds).  list: the list form of adaptive sampling (pt_adaptive.h; KParams::adaptive names the state's device
+// (ptamd_launch.cpp: lay_out_lds).  list: the list form of adaptive sampling (pt_adaptive.h; KParams::adaptive names the state's device
 // block).  p: the launch, whose fields choose among the restart kernel's forms (pt_device.h: restart_select), or nullptr before it is
 // known: everything but `fn` is then already final.
 KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p);

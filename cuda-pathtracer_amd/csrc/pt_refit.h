@@ -1,5 +1,5 @@
 // pt_refit.h — the arithmetic of a BVH refit (ptamd_scene_update), written once for the host builder (host/bvh_builder.cpp:
-// build_bvh and refit_bvh), the scene upload (ptamd_api.cpp) and the device kernels (pt_refit.hip).
+// build_bvh and refit_bvh), the scene upload (ptamd_scene.cpp) and the device kernels (pt_refit.hip).
 //
 // Every side is compiled with -ffp-contract=off and calls the functions below, so they execute the same binary32 operations in
 // the same order: a tree refitted on the device equals refit_bvh's byte for byte, and build_bvh forms its own records with the
@@ -153,7 +153,7 @@ PT_RF_HD float rf_origin_margin(const RefitParams& r) { return r.device_margin ?
 #include <hip/hip_runtime.h>
 namespace ptamd {
 // The kernels of one update, in stream order: records, subtrees (one workgroup each), the top of the tree (one workgroup),
-// four-wide nodes.  Shapes are checked by the caller (ptamd_api.cpp: ptamd_scene_update).
+// four-wide nodes.  Shapes are checked by the caller (ptamd_scene.cpp: ptamd_scene_update).
 hipError_t launch_refit(const RefitParams& r, hipStream_t stream);
 hipError_t resolve_refit_kernels();
 }

@@ -1,6 +1,6 @@
 // pt_refit_device.h — what ptamd_scene_update_device and ptamd_scene_quality add to a refit: the extent of faces
 // that live on the device, and the surface-area-heuristic cost of the binary tree.  The arithmetic is written once for the host
-// (ptamd_api.cpp: ptamd_host_scene_quality, the value kept at upload) and the kernels (pt_refit_device.hip); like pt_refit.h the
+// (ptamd_scene.cpp: ptamd_host_scene_quality, the value kept at upload) and the kernels (pt_refit_device.hip); like pt_refit.h the
 // header includes nothing of HIP.
 #pragma once
 

@@ -377,7 +377,7 @@ void refit_raw_boxes(Bvh& out, const ptamd_face* faces)
 // rounded up where the record is formed.)  Bounce rays start on the scene's surfaces (|o| <= extent), so every box also gets
 // extent * 2^-20 — 2.3x the worst case at |o| = |p| = extent — and |p| * 1e-6 on top.  Origins farther out — a camera much
 // farther out than the scene, or a light sphere far outside the mesh, which paths bounce off (origin_reach) — are the launcher's
-// business (ptamd_api.cpp: far_origin_camera, margins_cover against Bvh::margin_floor; every face is tested beyond it).  Widening
+// business (ptamd_scene.cpp: far_origin_camera, margins_cover against Bvh::margin_floor; every face is tested beyond it).  Widening
 // the boxes by reach * 2^-20 instead would cover the slab test but not Moller-Trumbore's own rounding, which grows with
 // |o - v0| / det: with origins 1e4 .. 6e4 units out, a random soup still gave 1 to 52 of 200 000 rays whose brute-force hit (a
 // grazing one, off the triangle by its rounding) lay outside every such box.

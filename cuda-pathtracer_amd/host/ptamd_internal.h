@@ -145,7 +145,7 @@ float origin_reach(const ptamd_light* lights, uint32_t n_lights, float extent);
 
 // The boxes' margins cover the slab test's rounding, at most 1.75 (|origin| + |plane|) * 2^-22, for origins with max-axis
 // |coordinate| <= origin_far (planes lie within `extent`); false for NaN and infinity.  The launcher's one rule for walking the
-// tree (ptamd_api.cpp: far_origin_camera): beyond it a launch tests every face.
+// tree (ptamd_scene.cpp: far_origin_camera): beyond it a launch tests every face.
 inline bool margins_cover(float extent, float margin_floor, float origin_far)
 {
   return (origin_far + extent) * (1.0f / 2097152.0f) <= margin_floor;

@@ -32,14 +32,14 @@
 #include <vector>
 
 namespace ptamd {
-// the two services the host sources take from csrc/ptamd_api.cpp
+// the two services the host sources take from csrc/ptamd_context.cpp (set_error) and csrc/ptamd_tuning.cpp (tuning_env)
 static std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 static bool g_knobs_from_env = false;   // the dump mode only: the sanitizer run stays deaf to the environment
 const char* tuning_env(const char* name)
 {
   if (!g_knobs_from_env) return nullptr;
-  const char* gate = std::getenv("PTAMD_TUNING");   // (the library's rule: csrc/ptamd_api.cpp)
+  const char* gate = std::getenv("PTAMD_TUNING");   // (the library's rule: csrc/ptamd_tuning.cpp)
   if (!gate || std::atoi(gate) != 1) return nullptr;
   return std::getenv(name);
 }

@@ -466,7 +466,7 @@ def test_quantised_four_wide_walk_on_the_device(P, O, monkeypatch, quantised):
 
 def test_scene_that_fills_the_lds_share_keeps_its_pools_in_global_memory(P, O, gpu_ctx):
     """An LDS-resident scene of 53-64 KB leaves no room for the restart kernel's path pools next to two scene copies: they
-    go to the global slab instead (ptamd_api.cpp); same pixels either way."""
+    go to the global slab instead (ptamd_launch.cpp); same pixels either way."""
     rng = np.random.default_rng(77)
     soup = random_soup(rng, 400, extent=2.0, size=0.35)
     for n in range(280, 400, 10):                       # the first size whose nodes + triangles land in the window
@@ -869,7 +869,7 @@ def test_one_texel_cubemaps(P, O, gpu_ctx):
 
 def test_scenes_outside_the_short_reciprocal_range(P, O, gpu_ctx):
     """The restart kernel divides by the Moller-Trumbore determinant with a 7-instruction exact reciprocal only where the
-    launcher can bound the determinant (all vertices finite and <= 1e8, ptamd_api.cpp: small_det).  One far vertex (3e9), an
+    launcher can bound the determinant (all vertices finite and <= 1e8, ptamd_launch.cpp: small_det).  One far vertex (3e9), an
     infinite one (either sign: infinite coordinates stay out of the boxes, a face with one can never be hit), a NaN one and one
     near the end of the float range switch it off: every variant still renders the oracle's pixels."""
     rng = np.random.default_rng(77)

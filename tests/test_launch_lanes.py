@@ -1,4 +1,4 @@
-"""Launch lanes (ptamd_api.cpp: ptamd_context::lane): megakernels of launches with machine_share > 1 and of a
+"""Launch lanes (ptamd_host.h: ptamd_context::lane): megakernels of launches with machine_share > 1 and of a
 host running ahead on one stream go to streams the context owns, each with a hardware queue of its own; resolve passes stay
 on the caller's stream.  Every case holds frames rendered that way to the same frames rendered on one stream, one frame per
 launch, with the host waiting for each: accumulators and surfaces bit for bit."""

@@ -15,7 +15,7 @@ from helpers import make_scene, random_rays, random_soup
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(ROOT, "assets")
 SHIPPED = ("indoor", "crate_land", "color_sample", "island", "sss_crate")
-COMPACT_MAX_NODES, COMPACT_MAX_TRIS = 896, 2047   # ptamd_api.cpp: kCompactMaxNodes, kCompactMaxTris
+COMPACT_MAX_NODES, COMPACT_MAX_TRIS = 896, 2047   # ptamd_host.h: kCompactMaxNodes, kCompactMaxTris
 
 
 def surface_rays(hs, seed=7, n=30000):
