@@ -115,6 +115,8 @@ int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
   if (l->frame_nb == 0) { set_error("ptamd_raytrace: frame_nb must be >= 1"); return PTAMD_ERR_ARG; }
   if (l->bounces == 0 || l->bounces > 1024) { set_error("ptamd_raytrace: bounces out of range (1..1024)"); return PTAMD_ERR_ARG; }
   if (l->frame_count > 4096) { set_error("ptamd_raytrace: frame_count out of range (<= 4096)"); return PTAMD_ERR_ARG; }
+  // (a batch whose last frame number does not fit 32 bits would wrap to frame 0, which a single launch refuses)
+  if (l->frame_count > 1 && l->frame_nb > 0xFFFFFFFFu - (l->frame_count - 1u)) { set_error("ptamd_raytrace: frame_nb + frame_count - 1 exceeds 2^32 - 1 (the batch would wrap to frame 0)"); return PTAMD_ERR_ARG; }
   if (l->frame_count > 1 && l->moved) { set_error("ptamd_raytrace: batched frames must be static (moved = 0)"); return PTAMD_ERR_ARG; }
   if (l->kernel > PTAMD_KERNEL_BVH_RESTART_FMA) { set_error("ptamd_raytrace: unknown kernel kind"); return PTAMD_ERR_ARG; }
   if (l->machine_share > 64) { set_error("ptamd_raytrace: machine_share out of range (<= 64)"); return PTAMD_ERR_ARG; }

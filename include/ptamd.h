@@ -341,7 +341,9 @@ typedef struct {
   uint32_t band_local_buffers; /* 0: buffers are full-frame; 1: they hold only the row band */
   uint32_t frame_count;        /* 0 or 1: one frame.  N > 1 (static frames, persistent kernels only): frames
                                   frame_nb .. frame_nb+N-1 in ONE launch — same accumulator and final surface
-                                  as N consecutive calls, bit for bit; intermediate surfaces are not produced */
+                                  as N consecutive calls, bit for bit; intermediate surfaces are not produced.
+                                  N <= 4096, and frame_nb + N - 1 <= 2^32 - 1: a batch that would wrap to frame 0,
+                                  which no single launch may render, is refused with PTAMD_ERR_ARG */
   uint32_t machine_share;      /* persistent kernels: 0 or 1 = size the grid to the whole GPU; k > 1 = to 1/k of it, so that
                                   k launches in flight (one per stream) co-reside instead of queueing behind each other —
                                   what a multi-GPU host does with its small per-GPU bands (results do not depend on it).
@@ -577,9 +579,11 @@ typedef struct {
   void* stream;                        /* hipStream_t; NULL = default stream */
   uint32_t post_id;                    /* 0..3, as ptamd_raytrace */
   uint32_t levels;                     /* a-trous levels, 0..8; 0: the plain resolve's bytes (no filtering) */
-  float sigma_n;                       /* normal exponent, a power of two 1..65536 (0: 128) */
+  float sigma_n;                       /* normal exponent, a power of two 1..256 (0: 128).  Larger exponents are refused: raising the
+                                          binary32 cosine to sigma_n multiplies each of its roundings by sigma_n, and beyond 256 the
+                                          filter leaves the 1e-5 it is held to against its float64 definition (512: 2e-5, 65536: 1.5e-3) */
   float sigma_l;                       /* luminance scale, > 0 (0: 2) */
-  float sigma_x;                       /* plane-distance scale, > 0 (0: 1) */
+  float sigma_x;                       /* plane-distance scale, > 0 (0: 1).  A sigma of -0.0, NaN or infinity is refused */
 } ptamd_denoise_desc;
 
 /* Denoises the accumulator into surface_rgba8 (and linear_rgb): asynchronous on `stream`.  The accumulator must be uniform (every

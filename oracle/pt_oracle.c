@@ -714,7 +714,7 @@ typedef struct {
   int32_t frame_nb, moved, bounces;
   float* tfb;
   uint8_t* rgba;
-  atomic_uint* next_row; /* shared row counter: rows differ a lot in cost, so threads pull them */
+  atomic_uint* next_row; /* shared counter of row pieces: they differ a lot in cost, so threads pull them */
   or_stats stats;
 } or_job;
 
@@ -750,13 +750,21 @@ static void render_pixel(or_job* j, int x, int y)
   memcpy(j->rgba + ((size_t)y * width + (unsigned)x) * 4, &px, 4);
 }
 
+#define OR_PIECE 256u /* pixels of a row a thread pulls at a time: a frame of one very wide row still spreads over the threads */
+
+static uint32_t row_pieces(uint32_t width) { return (width + OR_PIECE - 1u) / OR_PIECE; }
+
 static void* render_band(void* arg)
 {
   or_job* j = (or_job*)arg;
+  const uint32_t per_row = row_pieces(j->width);
+  const uint64_t n = (uint64_t)(j->y1 - j->y0) * per_row;
   for (;;) {
-    uint32_t y = j->y0 + atomic_fetch_add(j->next_row, 1u);
-    if (y >= j->y1) break;
-    for (uint32_t x = 0; x < j->width; ++x)
+    uint32_t k = atomic_fetch_add(j->next_row, 1u);
+    if (k >= n) break;
+    uint32_t y = j->y0 + k / per_row, x0 = (k % per_row) * OR_PIECE;
+    uint32_t x1 = x0 + OR_PIECE < j->width ? x0 + OR_PIECE : j->width;
+    for (uint32_t x = x0; x < x1; ++x)
       render_pixel(j, (int)x, (int)y);
   }
   return NULL;
@@ -772,14 +780,15 @@ void or_last_stats(uint64_t out[3])
 }
 
 int or_render(const or_scene* sc, const or_camera* cam, uint32_t width, uint32_t height,
-              uint32_t y0, uint32_t y1, uint32_t hash_seed, int32_t frame_nb, int32_t moved,
+              uint32_t y0, uint32_t y1, uint32_t hash_seed, uint32_t frame_nb, int32_t moved,
               uint32_t post_id, int32_t bounces, float* tfb, uint8_t* rgba, int32_t nthreads)
 {
-  if (!sc || !cam || !tfb || !rgba || y1 > height || y0 > y1 || bounces < 1 || frame_nb < 1 || post_id > 3)
+  if (!sc || !cam || !tfb || !rgba || y1 > height || y0 > y1 || bounces < 1 || frame_nb == 0 || post_id > 3)
     return 1;
   if (nthreads < 1) nthreads = 1;
-  uint32_t rows = y1 - y0;
-  if ((uint32_t)nthreads > rows) nthreads = rows ? (int32_t)rows : 1;
+  uint64_t pieces = (uint64_t)(y1 - y0) * row_pieces(width);
+  if (pieces >= 0xffffffffu) return 1; /* (the piece counter is 32 bits wide) */
+  if ((uint64_t)nthreads > pieces) nthreads = pieces ? (int32_t)pieces : 1;
   or_job* jobs = (or_job*)calloc((size_t)nthreads, sizeof(or_job));
   pthread_t* th = (pthread_t*)calloc((size_t)nthreads, sizeof(pthread_t));
   if (!jobs || !th) { free(jobs); free(th); return 2; }
@@ -789,7 +798,8 @@ int or_render(const or_scene* sc, const or_camera* cam, uint32_t width, uint32_t
     or_job* j = &jobs[t];
     j->sc = sc; j->cam = *cam; j->width = width; j->height = height;
     j->y0 = y0; j->y1 = y1; j->next_row = &next_row;
-    j->hash_seed = hash_seed; j->post_id = post_id; j->frame_nb = frame_nb;
+    j->hash_seed = hash_seed; j->post_id = post_id;
+    j->frame_nb = (int32_t)frame_nb; /* RT:321 hands the unsigned `seed` to the kernel's `int frame_nb` (RT:215) */
     j->moved = moved; j->bounces = bounces; j->tfb = tfb; j->rgba = rgba;
   }
   if (nthreads == 1) {

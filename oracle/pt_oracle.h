@@ -118,13 +118,16 @@ void     or_post_process(uint32_t post_id, const float in[3], float out[3]); /* 
 /*
  * One reference raytrace()+kernel() launch (raytrace.cu:212-325) restricted to surface rows
  * [y0, y1).  hash_seed = WangHash(frame_nb) is computed by the caller exactly as
- * raytrace.cu:321 does.  `bounces` = iterations of the raytrace.cu:67 loop when static
+ * raytrace.cu:321 does.  frame_nb is the reference's unsigned `seed` (raytrace.cu:296), any value
+ * but 0: the kernel receives it as `int` (raytrace.cu:215) and divides by (float) of that
+ * (raytrace.cu:258), so values above 2^31 - 1 divide by a negative number, as there.
+ * `bounces` = iterations of the raytrace.cu:67 loop when static
  * (reference default 3 == static_samples 1).  tfb is the FULL frame accumulator
  * (float3[W*H], reference row-flipped index raytrace.cu:252); rgba is the full W*H*4
  * surface (row 0 = top).  Returns 0 on success.
  */
 int or_render(const or_scene* sc, const or_camera* cam, uint32_t width, uint32_t height,
-              uint32_t y0, uint32_t y1, uint32_t hash_seed, int32_t frame_nb, int32_t moved,
+              uint32_t y0, uint32_t y1, uint32_t hash_seed, uint32_t frame_nb, int32_t moved,
               uint32_t post_id, int32_t bounces, float* tfb, uint8_t* rgba, int32_t nthreads);
 
 /* trace statistics of the last or_render call on this thread group (brute force):

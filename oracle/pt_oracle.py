@@ -114,7 +114,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.or_post_process.argtypes = [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.or_render.restype = C.c_int
     lib.or_render.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                              C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
                               C.c_int32]
     lib.or_last_stats.argtypes = [C.POINTER(C.c_uint64)]
     return lib
