@@ -2,6 +2,7 @@
 // tables, and the few helpers that cross files.  One subsystem per file:
 //   ptamd_context.cpp   last error, ptamd_create / ptamd_destroy, device utilities, counters, self-test, time stamps
 //   ptamd_scene.cpp     scene tables: upload, updates, margins, quality, release, reads, their host mirrors; cubemaps
+//   ptamd_pose.cpp      the scene rig: a scene posed from per-group transforms on the device
 //   ptamd_launch.cpp    the launch pipeline (camera_terms ... do_launch), ptamd_raytrace*, ray queries
 //   ptamd_denoise.cpp   the spatial and temporal denoiser, the history, their host mirrors
 //   ptamd_adaptive.cpp  adaptive sampling
@@ -12,6 +13,7 @@
 #include "../host/ptamd_internal.h"
 #include "pt_device.h"
 #include "pt_launch.h"
+#include "pt_refit.h"
 #include "ptamd_owners.h"
 #include "ptamd_tuning.h"
 
@@ -48,7 +50,7 @@ struct DeviceScene {
   bool released = false;     // a tombstone: the tables are gone, the id stays taken
   bool refit_ok = false;     // the tree can be refitted (no pre-split references, no quantised node forms)
   std::vector<uint32_t> material_ids;   // host copy: an update may not change them
-  std::vector<ptamd_light> host_lights; // host copy: the origin reach follows the new extent
+  std::vector<ptamd_light> host_lights; // host copy, of every scene: the origin reach follows the new extent and the new lights
   DeviceBuffer<float> raw;                 // raw boxes, 8 floats per node (pt_refit.h)
   DeviceBuffer<uint32_t> refit_groups;     // the children-first schedule (bvh_builder.cpp: plan_refit) and the wide nodes' children
   DeviceBuffer<uint32_t> refit_levels;
@@ -73,6 +75,11 @@ struct DeviceScene {
   bool margin_ready_valid[2] = { false, false };
   uint32_t margin_next = 0, margin_slot = 0;
   bool margins_pending = false;
+  // ptamd_scene_update_lights: the new table goes through two pinned slots used in turn, allocated at the first such update
+  PinnedBuffer<ptamd_light> h_lights[2];
+  Event lights_staged[2];                        // the copy out of h_lights[i] has finished
+  bool lights_staged_valid[2] = { false, false };
+  uint32_t lights_next = 0;
   // ptamd_scene_quality
   double quality_built = 0.0;                    // the cost of the tree as uploaded (tree_quality)
   DeviceBuffer<double> d_quality;                // quality_groups(n_nodes) + 1 partial sums, allocated at the first query
@@ -193,6 +200,12 @@ bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam);
 int settle_margins(DeviceScene& s, hipStream_t stream, const char* who);
 void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p);
 int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing);
+// what the update calls share (ptamd_scene_update, _update_device, _update_lights, ptamd_scene_rig_pose)
+int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces);
+int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t stream);
+int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream);
+int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r);
+int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream);
 
 // ---- ptamd_launch.cpp
 float frame_nb_inverse(float c);

@@ -246,7 +246,9 @@ int refit_scene_tables(SceneTables& t, const ptamd_face* faces, uint32_t n_faces
   return PTAMD_OK;
 }
 
-// What the two update calls refuse alike, in two steps (ptamd_scene_update checks the material ids between them)
+} // namespace
+
+// What the update calls refuse alike, in two steps (ptamd_scene_update checks the material ids between them)
 int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces)
 {
   const std::string w(who);
@@ -270,6 +272,8 @@ int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t
   return PTAMD_OK;
 }
 
+namespace {
+
 // RefitParams of the scene, everything but the faces and the origin margin; the shapes checked: every table the kernels index
 // exists and the schedule's level ranges lie inside it
 int refit_params(const char* who, const DeviceScene& s, RefitParams& r)
@@ -292,6 +296,8 @@ int refit_params(const char* who, const DeviceScene& s, RefitParams& r)
   return PTAMD_OK;
 }
 
+} // namespace
+
 // An update waits on `stream` for every launch still reading the scene: megakernels on the lanes and internal streams (mega_done),
 // everything a stream was given so far (last_done); the previous update, which may have gone to another stream
 int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream)
@@ -304,7 +310,42 @@ int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t
   return PTAMD_OK;
 }
 
-} // namespace
+// What an update from device faces needs before anything is enqueued: the refit's parameters, and at the first update of this kind
+// the reduction's words and partials, the two pinned slots they are copied back to, the events
+int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r)
+{
+  const int rc = refit_params(who, s, r);
+  if (rc != PTAMD_OK) return rc;
+  if (!s.d_margin) PT_HIP(s.d_margin.alloc((kMarginWords + 2u * kExtentMaxGroups) * sizeof(float)));
+  if (!s.h_margin) PT_HIP(s.h_margin.alloc(2u * kMarginWords * sizeof(float)));
+  for (int i = 0; i < 2; ++i) PT_HIP(s.margin_ready[i].ensure());
+  PT_HIP(s.updated.ensure());
+  return PTAMD_OK;
+}
+
+// ... and what it enqueues behind wait_for_readers, for ptamd_scene_update_device (the caller's buffer) and ptamd_scene_rig_pose (the
+// rig's posed records) alike: extent reduction, the four refit kernels, `updated`, the margin copy; margins pending
+int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream)
+{
+  // (the copies of earlier updates read d_margin behind their `updated`, possibly on another stream)
+  for (int i = 0; i < 2; ++i)
+    if (s.margin_ready_valid[i]) PT_HIP(hipStreamWaitEvent(stream, s.margin_ready[i].get(), 0));
+  PT_HIP(launch_extent(faces, s.n_faces, s.d_margin.get() + kMarginWords, s.d_margin.get(), stream));
+  r.faces = faces;
+  r.device_margin = s.d_margin.get() + 2;
+  PT_HIP(launch_refit(r, stream));
+  PT_HIP(hipEventRecord(s.updated.get(), stream));
+  s.updated_valid = true;
+  // extent and finiteness back to the host, behind the kernels: launches wait for `updated`, not for this copy
+  const uint32_t slot = s.margin_next++ & 1u;
+  PT_HIP(hipMemcpyAsync(s.h_margin.get() + (size_t)slot * kMarginWords, s.d_margin.get(), kMarginWords * sizeof(float), hipMemcpyDeviceToHost, stream));
+  PT_HIP(hipEventRecord(s.margin_ready[slot].get(), stream));
+  s.margin_ready_valid[slot] = true;
+  s.margin_slot = slot;
+  s.margins_pending = true;
+  return PTAMD_OK;
+}
+
 } // namespace ptamd
 
 using namespace ptamd;
@@ -388,8 +429,8 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     d.refit_top_first = bvh.refit_top_first; d.refit_top_levels = bvh.refit_top_levels;
     d.material_ids.resize(sc->n_faces);
     for (uint32_t i = 0; i < sc->n_faces; ++i) d.material_ids[i] = sc->faces[i].material_id;
-    d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);
   }
+  d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);   // (every scene: ptamd_scene_update_lights recomputes the reach from them)
   d.quality_built = tree_quality(bvh.nodes.data(), bvh.n_nodes, sc->n_faces);
   d.info.n_faces = sc->n_faces; d.info.n_lights = sc->n_lights; d.info.n_nodes = bvh.n_nodes;
   d.info.n_leaves = bvh.n_leaves; d.info.max_leaf_size = bvh.max_leaf; d.info.depth = bvh.depth;
@@ -480,30 +521,53 @@ int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_devic
     (void)hipGetLastError();
   }
   RefitParams r;
-  if ((rc = refit_params(who, s, r)) != PTAMD_OK) return rc;
-  // the first update of this kind: the reduction's words and partials, the two pinned slots they are copied back to
-  if (!s.d_margin) PT_HIP(s.d_margin.alloc((kMarginWords + 2u * kExtentMaxGroups) * sizeof(float)));
-  if (!s.h_margin) PT_HIP(s.h_margin.alloc(2u * kMarginWords * sizeof(float)));
-  for (int i = 0; i < 2; ++i) PT_HIP(s.margin_ready[i].ensure());
+  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
+  return enqueue_device_refit(s, r, reinterpret_cast<const float*>(d->faces), stream);
+}
+
+int ptamd_scene_update_lights(ptamd_context* ctx, const ptamd_scene_lights_desc* d)
+{
+  const char* who = "ptamd_scene_update_lights";
+  if (!ctx || !d) { set_error("ptamd_scene_update_lights: null argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, d->scene_id)) { set_error("ptamd_scene_update_lights: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  DeviceScene& s = ctx->scenes[d->scene_id];
+  if (d->n_lights != s.n_lights) { set_error("ptamd_scene_update_lights: n_lights differs from the uploaded count"); return PTAMD_ERR_ARG; }
+  if (d->n_lights && !d->lights) { set_error("ptamd_scene_update_lights: null lights"); return PTAMD_ERR_ARG; }
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  int rc = update_capture_checks(who, ctx, stream);
+  if (rc != PTAMD_OK) return rc;
+  if (d->n_lights == 0) return PTAMD_OK;
+  PT_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)d->n_lights * sizeof(ptamd_light);
+  // the first update of the lights: two pinned slots used in turn, as h_stage is
+  for (int i = 0; i < 2; ++i) {
+    if (!s.h_lights[i]) PT_HIP(s.h_lights[i].alloc(bytes));
+    PT_HIP(s.lights_staged[i].ensure());
+  }
   PT_HIP(s.updated.ensure());
+  const uint32_t slot = s.lights_next++ & 1u;
+  if (s.lights_staged_valid[slot]) PT_HIP(hipEventSynchronize(s.lights_staged[slot].get()));
+  // the device's table carries radius * radius in the radius slot, as the upload stores it
+  ptamd_light* staged = s.h_lights[slot].get();
+  for (uint32_t i = 0; i < d->n_lights; ++i) {
+    staged[i] = d->lights[i];
+    staged[i].radius = d->lights[i].radius * d->lights[i].radius;
+  }
   if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
-  // (the copies of earlier updates read d_margin behind their `updated`, possibly on another stream)
-  for (int i = 0; i < 2; ++i)
-    if (s.margin_ready_valid[i]) PT_HIP(hipStreamWaitEvent(stream, s.margin_ready[i].get(), 0));
-  const float* faces = reinterpret_cast<const float*>(d->faces);
-  PT_HIP(launch_extent(faces, d->n_faces, s.d_margin.get() + kMarginWords, s.d_margin.get(), stream));
-  r.faces = faces;
-  r.device_margin = s.d_margin.get() + 2;
-  PT_HIP(launch_refit(r, stream));
+  PT_HIP(hipMemcpyAsync(s.lights.get(), staged, bytes, hipMemcpyHostToDevice, stream));
+  PT_HIP(hipEventRecord(s.lights_staged[slot].get(), stream));
+  s.lights_staged_valid[slot] = true;
   PT_HIP(hipEventRecord(s.updated.get(), stream));
   s.updated_valid = true;
-  // extent and finiteness back to the host, behind the kernels: launches wait for `updated`, not for this copy
-  const uint32_t slot = s.margin_next++ & 1u;
-  PT_HIP(hipMemcpyAsync(s.h_margin.get() + (size_t)slot * kMarginWords, s.d_margin.get(), kMarginWords * sizeof(float), hipMemcpyDeviceToHost, stream));
-  PT_HIP(hipEventRecord(s.margin_ready[slot].get(), stream));
-  s.margin_ready_valid[slot] = true;
-  s.margin_slot = slot;
-  s.margins_pending = true;
+  // no box changes (the origin margin follows the extent alone); the origin reach does, and with it the walk-or-every-face
+  // decision of later launches.  Pending margins: settle_margins forms it from host_lights when the extent arrives.
+  s.host_lights.assign(d->lights, d->lights + d->n_lights);
+  if (!s.margins_pending) {
+    Bvh m;
+    m.margin = kBoxMargin;
+    bvh_margins_of_extent(m, s.extent, s.all_finite, s.host_lights.data(), (uint32_t)s.host_lights.size());
+    s.reach = m.reach; s.margin_floor = m.margin_floor;
+  }
   return PTAMD_OK;
 }
 

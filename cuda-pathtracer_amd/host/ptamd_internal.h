@@ -151,6 +151,9 @@ inline bool margins_cover(float extent, float margin_floor, float origin_far)
   return (origin_far + extent) * (1.0f / 2097152.0f) <= margin_floor;
 }
 
+// ---- posing (pose.cpp): group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]); true when the sizes sum to n_faces
+bool pose_groups_cover(const uint32_t* group_sizes, uint32_t n_groups, uint32_t n_faces);
+
 // Host traversals with the same structure the kernels use (tests + stats cross-check; bvh_walks.cpp).
 struct HostHit { int32_t kind; int32_t index; float t; float u, v; };
 void bvh_trace_host(const Bvh& bvh, const ptamd_face* faces, const float dir[3], const float origin[3],

@@ -74,6 +74,15 @@ class SceneUpdateDeviceDesc(C.Structure):   # ptamd_scene_update_device_desc (in
     _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class SceneRigPoseDesc(C.Structure):        # ptamd_scene_rig_pose_desc (include/ptamd.h): transforms and normal matrices are HOST arrays
+    _fields_ = [("rig", C.c_void_p), ("transforms", C.POINTER(C.c_float)), ("normal_matrices", C.POINTER(C.c_float)),
+                ("n_groups", C.c_uint32), ("stream", C.c_void_p)]
+
+
+class SceneLightsDesc(C.Structure):         # ptamd_scene_lights_desc (include/ptamd.h)
+    _fields_ = [("scene_id", C.c_uint32), ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("stream", C.c_void_p)]
+
+
 class SceneQualityInfo(C.Structure):        # ptamd_scene_quality_info (include/ptamd.h)
     _fields_ = [("built", C.c_double), ("now", C.c_double)]
 
@@ -187,6 +196,14 @@ SIGNATURES = {
     "ptamd_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32)]),
     "ptamd_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDesc)]),
     "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
+    "ptamd_scene_rig_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                         C.POINTER(C.c_void_p)]),
+    "ptamd_scene_rig_pose": (C.c_int, [C.c_void_p, C.POINTER(SceneRigPoseDesc)]),
+    "ptamd_scene_rig_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ptamd_scene_rig_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ptamd_host_pose_faces": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float), C.POINTER(Face)]),
+    "ptamd_scene_update_lights": (C.c_int, [C.c_void_p, C.POINTER(SceneLightsDesc)]),
     "ptamd_scene_quality": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SceneQualityInfo)]),
     "ptamd_host_scene_quality": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(C.c_double)]),
     "ptamd_scene_margins": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import native as N
-from .scene import FACE_DTYPE, HostScene
+from .scene import FACE_DTYPE, LIGHT_DTYPE, HostScene
 
 POST_NONE, POST_GRAYSCALE, POST_SEPIA, POST_INVERT = 0, 1, 2, 3
 REFERENCE_BOUNCES = 3  # static_samples = 1 -> max_bounces = 3 (raytrace.cu:243,66)
@@ -116,6 +116,21 @@ class Context:
         d.faces = faces.data_ptr(); d.n_faces = faces.shape[0]
         d.stream = _stream_handle(stream)
         N.check(self._lib.ptamd_scene_update_device(self._h, C.byref(d)))
+
+    def scene_rig(self, scene_id: int, host_scene, group_sizes=None) -> "SceneRig":
+        """ptamd_scene_rig_create: a rig of the uploaded scene with `host_scene` (a HostScene or a FACE_DTYPE array) as its rest
+        pose, cut into groups of consecutive faces; group_sizes defaults to the HostScene's mesh_sizes."""
+        return SceneRig(self, scene_id, host_scene, group_sizes)
+
+    def update_lights(self, scene_id: int, lights, stream=None) -> None:
+        """ptamd_scene_update_lights: the scene's light table replaced (a HostScene or a LIGHT_DTYPE array of the uploaded count);
+        asynchronous on `stream`."""
+        lights = np.ascontiguousarray(lights.lights if isinstance(lights, HostScene) else lights, dtype=LIGHT_DTYPE)
+        d = N.SceneLightsDesc()
+        d.scene_id = scene_id
+        d.lights = lights.ctypes.data_as(C.POINTER(N.Light)); d.n_lights = len(lights)
+        d.stream = _stream_handle(stream)
+        N.check(self._lib.ptamd_scene_update_lights(self._h, C.byref(d)))   # (the lights are copied before the call returns)
 
     def scene_quality(self, scene_id: int, stream=None):
         """ptamd_scene_quality: (built, now), the surface-area-heuristic cost of the scene's binary tree at upload and as the
@@ -375,6 +390,31 @@ def host_scene_tables(scene: HostScene, *steps) -> dict:
     return out
 
 
+def _pose_arrays(n_groups: int, transforms, normal_matrices):
+    t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1)
+    if t.size != n_groups * 12:
+        raise ValueError(f"transforms must hold {n_groups} x 12 floats (row-major 3x4 each)")
+    m = None
+    if normal_matrices is not None:
+        m = np.ascontiguousarray(normal_matrices, dtype=np.float32).reshape(-1)
+        if m.size != n_groups * 9:
+            raise ValueError(f"normal_matrices must hold {n_groups} x 9 floats (row-major 3x3 each)")
+    return t, m
+
+
+def host_pose_faces(hs: HostScene, transforms, normal_matrices=None, group_sizes=None) -> HostScene:
+    """ptamd_host_pose_faces (no GPU): `hs` with every face under the transform of its group (float32[n_groups, 3, 4]; normal
+    matrices float32[n_groups, 3, 3] or None for the transforms' linear parts); group_sizes defaults to hs.mesh_sizes."""
+    sizes = np.ascontiguousarray(hs.mesh_sizes if group_sizes is None else group_sizes, dtype=np.uint32)
+    t, m = _pose_arrays(len(sizes), transforms, normal_matrices)
+    out = np.zeros(len(hs.faces), dtype=FACE_DTYPE)
+    fp = C.POINTER(C.c_float)
+    N.check(N.load().ptamd_host_pose_faces(hs.faces.ctypes.data_as(C.POINTER(N.Face)), len(hs.faces),
+                                           sizes.ctypes.data_as(C.POINTER(C.c_uint32)), len(sizes), t.ctypes.data_as(fp),
+                                           m.ctypes.data_as(fp) if m is not None else None, out.ctypes.data_as(C.POINTER(N.Face))))
+    return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
+
+
 def host_scene_quality(scene: HostScene, faces_b=None) -> float:
     """ptamd_host_scene_quality (no GPU): the surface-area-heuristic cost of `scene`'s binary tree as an upload builds it, or
     refitted to `faces_b` (HostScene or face array)."""
@@ -504,6 +544,60 @@ def host_denoise(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_n
     rgba = np.zeros((h, w, 4), np.uint8)
     N.check(N.load().ptamd_host_denoise(features.ctypes.data, accum.ctypes.data, C.byref(d), linear.ctypes.data, rgba.ctypes.data))
     return linear, rgba
+
+
+class SceneRig:
+    """A scene posed from per-group transforms on the device (ptamd_scene_rig_*): the rest pose, the posed records and one record
+    per group, allocated once.  Close it before its context."""
+
+    def __init__(self, ctx: Context, scene_id: int, host_scene, group_sizes=None):
+        faces = np.ascontiguousarray(host_scene.faces if isinstance(host_scene, HostScene) else host_scene, dtype=FACE_DTYPE)
+        if group_sizes is None:
+            if not isinstance(host_scene, HostScene):
+                raise ValueError("group_sizes is needed with a bare face array")
+            group_sizes = host_scene.mesh_sizes
+        sizes = np.ascontiguousarray(group_sizes, dtype=np.uint32)
+        self.ctx, self.scene_id, self.n_faces, self.n_groups = ctx, scene_id, len(faces), len(sizes)
+        h = C.c_void_p()
+        N.check(ctx._lib.ptamd_scene_rig_create(ctx._h, scene_id, faces.ctypes.data_as(C.POINTER(N.Face)), len(faces),
+                                                sizes.ctypes.data_as(C.POINTER(C.c_uint32)), len(sizes), C.byref(h)))
+        self.handle = h.value
+
+    def pose(self, transforms, normal_matrices=None, stream=None) -> None:
+        """ptamd_scene_rig_pose: the scene's geometry = the rest pose under `transforms` (float32[n_groups, 3, 4]; normal matrices
+        float32[n_groups, 3, 3] or None), its tree refitted; asynchronous on `stream`."""
+        n = np.asarray(transforms).size // 12    # (a count that is not the rig's is the library's to refuse)
+        t, m = _pose_arrays(n, transforms, normal_matrices)
+        d = N.SceneRigPoseDesc()
+        d.rig = self.handle
+        fp = C.POINTER(C.c_float)
+        d.transforms = t.ctypes.data_as(fp)
+        d.normal_matrices = m.ctypes.data_as(fp) if m is not None else None
+        d.n_groups = n
+        d.stream = _stream_handle(stream)
+        N.check(self.ctx._lib.ptamd_scene_rig_pose(self.ctx._h, C.byref(d)))   # (the records are staged before the call returns)
+
+    def faces(self) -> np.ndarray:
+        """The posed records the last pose left, copied to host memory (synchronises the device): FACE_DTYPE[n_faces]."""
+        p = C.c_void_p()
+        N.check(self.ctx._lib.ptamd_scene_rig_faces(self.handle, C.byref(p)))
+        out = np.zeros(self.n_faces, dtype=FACE_DTYPE)
+        import torch
+        torch.cuda.synchronize(self.ctx.device)
+        if out.nbytes:
+            N.check(self.ctx._lib.ptamd_device_to_host(self.ctx._h, out.ctypes.data, p.value, out.nbytes, None))
+        return out
+
+    def close(self) -> None:
+        if self.handle:
+            N.check(self.ctx._lib.ptamd_scene_rig_destroy(self.ctx._h, self.handle))
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class DenoiseHistory:

@@ -262,6 +262,75 @@ typedef struct {
 } ptamd_scene_update_device_desc;
 int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_device_desc* desc);
 
+/* ---- Posing a scene from per-group transforms; moving its lights --------------------------------------------
+ * The common animation is rigid: each mesh moves as a whole.  A ptamd_scene_rig keeps a scene's REST POSE on the device, cut into
+ * groups of consecutive faces (group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]) in storage order; empty groups are
+ * allowed, the sizes sum to n_faces; ptamd_scene_desc.mesh_sizes is such a cut).  ptamd_scene_rig_pose takes one transform per group
+ * from the HOST (48 bytes a group instead of 112 a face), applies it on the device and refits the scene from the result.
+ *
+ * The arithmetic (csrc/pt_pose.h, shared by the kernel and by ptamd_host_pose_faces).  A transform is 12 floats, row-major 3x4
+ * {a00 a01 a02 t0, a10 ...}; a normal matrix 9 floats, row-major 3x3.  All operations are binary32, unfused, in this order:
+ *     a vertex                  x' = ((a00 * x + a01 * y) + a02 * z) + t0           rows 1 and 2 alike
+ *     a normal, the tangent     x' = (n00 * x + n01 * y) + n02 * z
+ * n is the group's normal matrix when normal_matrices is given, else the linear part a.. of its transform: right for rotations
+ * and mirrors; under a scale it scales the normals, and nothing is renormalised or derived (the reference never renormalises a
+ * mesh normal), so a host that scales passes the matrix it wants.  Texcoords and material_id are copied from the rest pose.  The
+ * identity maps every value to itself, except that -0.0 becomes +0.0: always in a vertex, in a normal or tangent unless both of
+ * its other components are negative or -0.0.
+ *
+ * Contract: the posed records, the scene's five tables, its margins and every later render are byte for byte what
+ * ptamd_scene_update produces from ptamd_host_pose_faces of the same inputs, wherever the mirror's value is not a NaN.  Where it
+ * is a NaN (inf * 0, inf - inf) the device's value is a NaN too, of any payload: x86 forms 0xffc00000 there, the GPU a positive
+ * quiet NaN.  The refit keeps non-finite coordinates out of every box either way.
+ *
+ * ptamd_scene_rig_create copies rest_faces (a HOST array, n_faces = the uploaded count, the uploaded material ids) and allocates
+ * everything a pose needs; it synchronises (a set-up call).  Memory per rig: 2 x 112 bytes per face (rest and posed records), a
+ * 4-byte group index per face, 96 bytes per group on the device and twice that in pinned host memory.  Errors: what
+ * ptamd_scene_update refuses (a changed material_id included) and sizes that do not sum to n_faces are PTAMD_ERR_ARG; n_groups
+ * outside 1..65536 is PTAMD_ERR_LIMIT.
+ *
+ * ptamd_scene_rig_pose is asynchronous on `stream`: it stages the group records, waits on the stream for the scene's readers and
+ * its previous update, copies the records, runs the pose kernel into the rig's posed buffer and then enqueues exactly what
+ * ptamd_scene_update_device enqueues for that buffer.  Ordering against launches, the refusals (n_groups must be the rig's; a rig
+ * of another context or of a released scene is PTAMD_ERR_ARG), capture rules and "margins pending" are ptamd_scene_update_device's.
+ * The transforms are read before the call returns.  No pose after the first synchronises the host; at most it waits for the
+ * staging copy of the pose before last.  ptamd_scene_update and _update_device on a rigged scene stay legal: the rig keeps its rest
+ * pose and the next pose replaces the geometry.
+ *
+ * ptamd_scene_rig_faces: the DEVICE address of the posed records the last pose left (the rest pose before the first), valid until
+ * the rig is destroyed; reads are ordered by the pose's stream.  ptamd_scene_rig_destroy waits for the device; destroy a rig
+ * before its context. */
+typedef struct ptamd_scene_rig ptamd_scene_rig;
+int ptamd_scene_rig_create(ptamd_context* ctx, uint32_t scene_id, const ptamd_face* rest_faces, uint32_t n_faces,
+                           const uint32_t* group_sizes, uint32_t n_groups, ptamd_scene_rig** out);
+typedef struct {
+  ptamd_scene_rig* rig;
+  const float* transforms;        /* HOST array, n_groups x 12 */
+  const float* normal_matrices;   /* HOST array, n_groups x 9, or NULL: the linear part of each transform */
+  uint32_t n_groups;              /* must equal the rig's */
+  void* stream;                   /* the pose is asynchronous on this stream */
+} ptamd_scene_rig_pose_desc;
+int ptamd_scene_rig_pose(ptamd_context* ctx, const ptamd_scene_rig_pose_desc* desc);
+int ptamd_scene_rig_faces(const ptamd_scene_rig* rig, const ptamd_face** out_device);
+int ptamd_scene_rig_destroy(ptamd_context* ctx, ptamd_scene_rig* rig);
+/* The host definition of a pose, no device needed: out[i] = rest[i] under its group's transform.  out may be rest.  PTAMD_ERR_ARG
+ * for a null pointer and for sizes that do not sum to n_faces. */
+int ptamd_host_pose_faces(const ptamd_face* rest, uint32_t n_faces, const uint32_t* group_sizes, uint32_t n_groups,
+                          const float* transforms, const float* normal_matrices, ptamd_face* out);
+
+/* ptamd_scene_update_lights replaces the light table of an uploaded scene: lights is a HOST array of n_lights records, which must
+ * equal the uploaded count (the LDS layout and ptamd_scene_info do not change); it is copied before the call returns.  Asynchronous
+ * on `stream` and ordered against launches as ptamd_scene_update is.  No box changes (the boxes' origin margin follows the extent
+ * alone); the origin reach is formed again from the new lights, so only the walk-or-every-face decision of later launches can
+ * flip.  Errors: ptamd_scene_update's, except that scenes of the knob-only node forms are accepted (no tree is touched). */
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_light* lights;   /* HOST array, n_lights records */
+  uint32_t n_lights;           /* must equal the uploaded count */
+  void* stream;
+} ptamd_scene_lights_desc;
+int ptamd_scene_update_lights(ptamd_context* ctx, const ptamd_scene_lights_desc* desc);
+
 /* Tree quality: the number behind "refit or rebuild".  One definition: the surface-area-heuristic cost of the BINARY tree over
  * the planes the walk tests (table 0 of ptamd_scene_table_read, margins included; a 64-byte record is {lo.xyz, first | count << 24}
  * {hi.xyz, child word} and eight miss links; count == 0 marks an interior node).  With A(k) = dx dy + dy dz + dz dx of node k's
