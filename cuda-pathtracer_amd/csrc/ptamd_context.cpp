@@ -3,7 +3,7 @@
 #include "ptamd_host.h"
 #include "pt_refit.h"
 #include "pt_refit_device.h"
-#include "pt_pose.h"
+#include "pt_skin.h"
 
 #include <cstring>
 #include <memory>
@@ -135,6 +135,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_refit_kernels();
   if (e == hipSuccess) e = resolve_refit_device_kernels();
   if (e == hipSuccess) e = resolve_pose_kernels();
+  if (e == hipSuccess) e = resolve_skin_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

@@ -272,6 +272,37 @@ int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t
   return PTAMD_OK;
 }
 
+// `p` is device memory of the context's device with `bytes` bytes behind it (and aligned to 16 bytes when asked): what
+// ptamd_scene_update_device asks of its faces and ptamd_scene_rig_skin of its device transforms.  Makes the device current.
+int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16)
+{
+  const std::string w = std::string(who) + ": ", name(what);
+  if (aligned16 && (reinterpret_cast<uintptr_t>(p) & 15u) != 0u) {
+    set_error(w + name + " is not aligned to 16 bytes (the kernels use 16-byte loads)");
+    return PTAMD_ERR_ARG;
+  }
+  PT_HIP(hipSetDevice(ctx->device));
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+    (void)hipGetLastError();   // (an unregistered host pointer is reported as an error: not a sticky one)
+    set_error(w + name + " is not device memory of the context's device (host arrays go to the call that takes them)");
+    return PTAMD_ERR_ARG;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t room = 0;
+  if (hipMemGetAddressRange(&base, &room, const_cast<void*>(p)) == hipSuccess) {
+    const size_t offset = (size_t)(static_cast<const char*>(p) - static_cast<const char*>(base));
+    if (offset > room || room - offset < bytes) {
+      set_error(w + "the allocation behind " + name + " is smaller than the call reads");
+      return PTAMD_ERR_ARG;
+    }
+  } else {
+    (void)hipGetLastError();
+  }
+  return PTAMD_OK;
+}
+
 namespace {
 
 // RefitParams of the scene, everything but the faces and the origin margin; the shapes checked: every table the kernels index
@@ -496,30 +527,7 @@ int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_devic
   if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
   DeviceScene& s = ctx->scenes[d->scene_id];
   if (d->n_faces == 0) return PTAMD_OK;
-  const size_t bytes = (size_t)d->n_faces * sizeof(ptamd_face);
-  if ((reinterpret_cast<uintptr_t>(d->faces) & 15u) != 0u) {
-    set_error("ptamd_scene_update_device: faces is not aligned to 16 bytes (the kernels use 16-byte loads)");
-    return PTAMD_ERR_ARG;
-  }
-  PT_HIP(hipSetDevice(ctx->device));
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof attr);
-  if (hipPointerGetAttributes(&attr, d->faces) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-    (void)hipGetLastError();   // (an unregistered host pointer is reported as an error: not a sticky one)
-    set_error("ptamd_scene_update_device: faces is not device memory of the context's device (host arrays go to ptamd_scene_update)");
-    return PTAMD_ERR_ARG;
-  }
-  hipDeviceptr_t base = nullptr;
-  size_t room = 0;
-  if (hipMemGetAddressRange(&base, &room, const_cast<ptamd_face*>(d->faces)) == hipSuccess) {
-    const size_t offset = (size_t)(reinterpret_cast<const char*>(d->faces) - static_cast<const char*>(base));
-    if (offset > room || room - offset < bytes) {
-      set_error("ptamd_scene_update_device: the allocation behind faces is smaller than n_faces records");
-      return PTAMD_ERR_ARG;
-    }
-  } else {
-    (void)hipGetLastError();
-  }
+  if ((rc = device_array_checks(who, "faces", ctx, d->faces, (size_t)d->n_faces * sizeof(ptamd_face), true)) != PTAMD_OK) return rc;
   RefitParams r;
   if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
   return enqueue_device_refit(s, r, reinterpret_cast<const float*>(d->faces), stream);

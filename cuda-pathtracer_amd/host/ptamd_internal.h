@@ -153,6 +153,8 @@ inline bool margins_cover(float extent, float margin_floor, float origin_far)
 
 // ---- posing (pose.cpp): group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]); true when the sizes sum to n_faces
 bool pose_groups_cover(const uint32_t* group_sizes, uint32_t n_groups, uint32_t n_faces);
+// ---- skinning (skin.cpp): true when every one of a skin's n_faces x 12 bone indices is below n_bones
+bool skin_indices_valid(const uint16_t* bone_indices, uint32_t n_faces, uint32_t n_bones);
 
 // Host traversals with the same structure the kernels use (tests + stats cross-check; bvh_walks.cpp).
 struct HostHit { int32_t kind; int32_t index; float t; float u, v; };

@@ -19,6 +19,7 @@
 // checks this parser against the real tinyobj 1.0.8 compiled from /root/reference (oracle/_ref) on the
 // shipped assets and on fuzzed OBJ/MTL text; the outputs must be bit-identical.
 #include "ptamd_internal.h"
+#include "../csrc/pt_skin.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -36,7 +37,6 @@ namespace {
 constexpr double kPi = 3.14159265358979323846; // M_PI of <math.h> (scene.cpp:10-11,76,101)
 
 inline ptamd_float3 f3(float x, float y, float z) { return ptamd_float3{ x, y, z }; }
-inline ptamd_float3 sub3(ptamd_float3 a, ptamd_float3 b) { return f3(a.x - b.x, a.y - b.y, a.z - b.z); }
 inline ptamd_float3 cross3(ptamd_float3 a, ptamd_float3 b)
 {
   return f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
@@ -566,14 +566,13 @@ static bool build_faces(const ObjData& obj, HostScene& hs, std::string& err)
         return false;
       }
       face.material_id = (uint32_t)t.material;
-      ptamd_float3 e1 = sub3(face.vertices[1], face.vertices[0]);
-      ptamd_float3 e2 = sub3(face.vertices[2], face.vertices[0]);
-      float du1 = face.texcoords[1].x - face.texcoords[0].x, dv1 = face.texcoords[1].y - face.texcoords[0].y;
-      float du2 = face.texcoords[2].x - face.texcoords[0].x, dv2 = face.texcoords[2].y - face.texcoords[0].y;
-      float f = 1.0f / (du1 * dv2 - du2 * dv1);
-      face.tangent.x = f * (dv2 * e1.x - dv1 * e2.x);
-      face.tangent.y = f * (dv2 * e1.y - dv1 * e2.y);
-      face.tangent.z = f * (dv2 * e1.z - dv1 * e2.z);
+      // the tangent: csrc/pt_skin.h's sk_tangent, the one statement of the reference's formula (scene.cpp:251-261), which a skin
+      // (ptamd_scene_rig_skin) evaluates again from the skinned vertices
+      float v[9], uv[6], tangent[3];
+      std::memcpy(v, face.vertices, sizeof v);
+      std::memcpy(uv, face.texcoords, sizeof uv);
+      sk_tangent(v, uv, tangent);
+      face.tangent = f3(tangent[0], tangent[1], tangent[2]);
       hs.faces.push_back(face);
     }
   }

@@ -79,6 +79,14 @@ class SceneRigPoseDesc(C.Structure):        # ptamd_scene_rig_pose_desc (include
                 ("n_groups", C.c_uint32), ("stream", C.c_void_p)]
 
 
+SKIN_DEVICE_TRANSFORMS = 1
+
+
+class SceneRigSkinDesc(C.Structure):        # ptamd_scene_rig_skin_desc: host arrays, device addresses with SKIN_DEVICE_TRANSFORMS
+    _fields_ = [("rig", C.c_void_p), ("transforms", C.c_void_p), ("normal_matrices", C.c_void_p), ("n_bones", C.c_uint32),
+                ("flags", C.c_uint32), ("stream", C.c_void_p)]
+
+
 class SceneLightsDesc(C.Structure):         # ptamd_scene_lights_desc (include/ptamd.h)
     _fields_ = [("scene_id", C.c_uint32), ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("stream", C.c_void_p)]
 
@@ -203,6 +211,10 @@ SIGNATURES = {
     "ptamd_scene_rig_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_host_pose_faces": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.POINTER(Face)]),
+    "ptamd_scene_rig_attach_skin": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_float), C.c_uint32]),
+    "ptamd_scene_rig_skin": (C.c_int, [C.c_void_p, C.POINTER(SceneRigSkinDesc)]),
+    "ptamd_host_skin_faces": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint16), C.POINTER(C.c_float), C.c_uint32,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Face)]),
     "ptamd_scene_update_lights": (C.c_int, [C.c_void_p, C.POINTER(SceneLightsDesc)]),
     "ptamd_scene_quality": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SceneQualityInfo)]),
     "ptamd_host_scene_quality": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(C.c_double)]),

@@ -415,6 +415,32 @@ def host_pose_faces(hs: HostScene, transforms, normal_matrices=None, group_sizes
     return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
 
 
+def _skin_arrays(n_faces: int, indices, weights):
+    idx = np.asarray(indices)
+    if idx.size and (idx.min() < 0 or idx.max() > 65535):
+        raise ValueError("a bone index does not fit 16 bits")
+    idx = np.ascontiguousarray(idx, dtype=np.uint16).reshape(-1)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if idx.size != n_faces * 12 or w.size != n_faces * 12:
+        raise ValueError(f"indices and weights must hold {n_faces} x 3 x 4 values (four influences per corner)")
+    return idx, w
+
+
+def host_skin_faces(hs: HostScene, indices, weights, transforms, normal_matrices=None) -> HostScene:
+    """ptamd_host_skin_faces (no GPU): `hs` skinned from per-corner influences (indices uint16[n_faces, 3, 4], weights
+    float32[n_faces, 3, 4]) under one transform per bone (float32[n_bones, 3, 4]; normal matrices float32[n_bones, 3, 3] or None
+    for the transforms' linear parts).  The tangents are derived from the skinned vertices."""
+    idx, w = _skin_arrays(len(hs.faces), indices, weights)
+    n_bones = np.asarray(transforms).size // 12
+    t, m = _pose_arrays(n_bones, transforms, normal_matrices)
+    out = np.zeros(len(hs.faces), dtype=FACE_DTYPE)
+    fp = C.POINTER(C.c_float)
+    N.check(N.load().ptamd_host_skin_faces(hs.faces.ctypes.data_as(C.POINTER(N.Face)), len(hs.faces), idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                           w.ctypes.data_as(fp), n_bones, t.ctypes.data_as(fp), m.ctypes.data_as(fp) if m is not None else None,
+                                           out.ctypes.data_as(C.POINTER(N.Face))))
+    return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
+
+
 def host_scene_quality(scene: HostScene, faces_b=None) -> float:
     """ptamd_host_scene_quality (no GPU): the surface-area-heuristic cost of `scene`'s binary tree as an upload builds it, or
     refitted to `faces_b` (HostScene or face array)."""
@@ -576,6 +602,50 @@ class SceneRig:
         d.n_groups = n
         d.stream = _stream_handle(stream)
         N.check(self.ctx._lib.ptamd_scene_rig_pose(self.ctx._h, C.byref(d)))   # (the records are staged before the call returns)
+
+    def attach_skin(self, indices, weights, n_bones: int) -> None:
+        """ptamd_scene_rig_attach_skin: four influences per corner (indices uint16[n_faces, 3, 4], weights float32[n_faces, 3, 4])
+        over `n_bones` bones; a set-up call, replaces a skin attached before."""
+        idx, w = _skin_arrays(self.n_faces, indices, weights)
+        N.check(self.ctx._lib.ptamd_scene_rig_attach_skin(self.ctx._h, self.handle, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                          w.ctypes.data_as(C.POINTER(C.c_float)), n_bones))
+
+    def skin(self, transforms, normal_matrices=None, stream=None) -> None:
+        """ptamd_scene_rig_skin: the scene's geometry = the rest pose skinned under one transform per bone, its tree refitted;
+        asynchronous on `stream`.  `transforms` (n_bones x 3 x 4) and `normal_matrices` (n_bones x 3 x 3 or None) are numpy
+        arrays, or float32 CUDA tensors on the context's device (contiguous; they stay alive and unmodified until the skin's
+        kernels have run), read in stream order without a copy."""
+        d = N.SceneRigSkinDesc()
+        d.rig = self.handle
+        d.stream = _stream_handle(stream)
+        keep = None
+        if type(transforms).__module__.startswith("torch") or type(normal_matrices).__module__.startswith("torch"):
+            import torch
+            for name, x, per_bone in (("transforms", transforms, 12), ("normal_matrices", normal_matrices, 9)):
+                if x is None and per_bone == 9:
+                    continue
+                if not isinstance(x, torch.Tensor):
+                    raise ValueError("transforms and normal_matrices are both tensors or both host arrays")
+                if not x.is_cuda:
+                    raise ValueError(f"{name} must live in device memory (CPU tensors: pass numpy arrays)")
+                if x.device.index != self.ctx.device:
+                    raise ValueError(f"{name} lives on {x.device}, the context on device {self.ctx.device}")
+                if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() % per_bone:
+                    raise ValueError(f"{name} must be contiguous float32 of {per_bone} values a bone")
+            d.n_bones = transforms.numel() // 12
+            if normal_matrices is not None and normal_matrices.numel() != d.n_bones * 9:
+                raise ValueError("normal_matrices must hold n_bones x 9 floats")
+            d.transforms = transforms.data_ptr()
+            d.normal_matrices = normal_matrices.data_ptr() if normal_matrices is not None else None
+            d.flags = N.SKIN_DEVICE_TRANSFORMS
+        else:
+            n = np.asarray(transforms).size // 12    # (a count that is not the skin's is the library's to refuse)
+            keep = _pose_arrays(n, transforms, normal_matrices)
+            d.n_bones = n
+            d.transforms = keep[0].ctypes.data
+            d.normal_matrices = keep[1].ctypes.data if keep[1] is not None else None
+            d.flags = 0
+        N.check(self.ctx._lib.ptamd_scene_rig_skin(self.ctx._h, C.byref(d)))   # (host transforms are staged before the call returns)
 
     def faces(self) -> np.ndarray:
         """The posed records the last pose left, copied to host memory (synchronises the device): FACE_DTYPE[n_faces]."""

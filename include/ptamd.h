@@ -318,6 +318,67 @@ int ptamd_scene_rig_destroy(ptamd_context* ctx, ptamd_scene_rig* rig);
 int ptamd_host_pose_faces(const ptamd_face* rest, uint32_t n_faces, const uint32_t* group_sizes, uint32_t n_groups,
                           const float* transforms, const float* normal_matrices, ptamd_face* out);
 
+/* ---- Skinning a rigged scene from per-corner bone weights ----------------------------------------------------
+ * Rigid posing covers props and doors, not a character, a cloth patch or a bending pipe.  A SKIN hangs on a ptamd_scene_rig, which
+ * already owns the rest pose and the posed buffer.  Faces are a soup, so a CORNER (face i, vertex c in 0..2) carries the
+ * influences: exactly FOUR per corner, each a uint16 bone index and a float weight; bone_indices and bone_weights are n_faces x 3
+ * x 4 arrays in the storage order of the upload.  ptamd_scene_rig_skin takes one transform per bone and refits the scene from the
+ * skinned faces.
+ *
+ * The arithmetic (csrc/pt_skin.h, shared by the kernel and by ptamd_host_skin_faces).  A bone's record is the pose's: its
+ * transform in floats 0..11, its direction matrix in floats 12..20 (the supplied normal matrix, else the linear part).  For each
+ * corner, with bk the record of its k-th bone and wk its k-th weight, all operations binary32, unfused, in this order:
+ *     blended[j] = ((w0 * b0[j] + w1 * b1[j]) + w2 * b2[j]) + w3 * b3[j]        j = 0 .. 20
+ *     vertex' = the pose's point formula under blended      normal' = the pose's direction formula under blended
+ * Nothing is normalised: not the weights (a corner whose weights sum to 0.9 shrinks towards the origin), not the normals.  A
+ * weight of 0 does NOT shield a non-finite record entry (0 * inf is a NaN): a corner with fewer than four influences REPEATS A
+ * USED INDEX in the unused ones, with weight 0.  Four equal indices with weights (1, 0, 0, 0) on a finite record reproduce
+ * ptamd_host_pose_faces' vertices and normals bit for bit.  Texcoords and material_id are copied from the rest pose.
+ *
+ * The tangent.  A face has one tangent and no corner to take a matrix from, so it is DERIVED from the skinned vertices and the
+ * copied texcoords, by the scene loader's formula in the loader's order: e1 = v1 - v0, e2 = v2 - v0, du1, dv1, du2, dv2 the
+ * texcoord differences alike, f = 1.0f / (du1 * dv2 - du2 * dv1), tangent.x = f * (dv2 * e1.x - dv1 * e2.x), y and z alike.
+ * Consequence: a host that supplied tangents of its own in the rest pose gets the derived ones after the first skin (a face
+ * without a texcoord area gets the loader's NaN or infinity).
+ *
+ * Contract: the posed records, the scene's five tables, its margins and every later render are byte for byte what
+ * ptamd_scene_update produces from ptamd_host_skin_faces of the same inputs, wherever the mirror's value is not a NaN; the pose's
+ * NaN clause applies (a NaN of the mirror is a NaN on the device, of any payload).
+ *
+ * ptamd_scene_rig_attach_skin is a set-up call: it validates the indices on the host (one that is not below n_bones is
+ * PTAMD_ERR_ARG, n_bones outside 1..65536 PTAMD_ERR_LIMIT, a rig of another context or of a released scene PTAMD_ERR_ARG, a
+ * context that holds a captured launch PTAMD_ERR_LIMIT), packs one 80-byte skin record per face, allocates and synchronises.  It
+ * may be called again: it then waits for the device and replaces the skin.  Memory it adds: 80 bytes per face and 96 bytes per
+ * bone on the device, twice 96 bytes per bone in pinned host memory.  ptamd_scene_rig_pose stays legal on a rig with a skin: each
+ * pose or skin replaces the geometry from the rest pose.
+ *
+ * ptamd_scene_rig_skin is asynchronous on `stream` and follows ptamd_scene_rig_pose step for step: it stages the bone records in
+ * one of two pinned slots, waits on the stream for the scene's readers and its previous update, copies the records, runs the skin
+ * kernel into the rig's posed buffer and enqueues exactly what ptamd_scene_update_device enqueues for that buffer.  The transforms
+ * are read before the call returns.  With PTAMD_SKIN_DEVICE_TRANSFORMS in flags (a skeleton evaluated on the GPU) transforms and
+ * normal_matrices are DEVICE memory of the context's device instead, checked like ptamd_scene_update_device's faces; transforms
+ * must be aligned to 16 bytes.  Nothing is staged: a kernel builds the records from the arrays, which are read in stream order
+ * and stay alive and unmodified until it has run.  Ordering against launches, capture rules and "margins pending" are
+ * ptamd_scene_update_device's.  Refused before anything is enqueued, with PTAMD_ERR_ARG: a rig without a skin, n_bones that is
+ * not the skin's, a rig of another context or of a released scene, an unknown flag, a null pointer. */
+int ptamd_scene_rig_attach_skin(ptamd_context* ctx, ptamd_scene_rig* rig, const uint16_t* bone_indices, const float* bone_weights,
+                                uint32_t n_bones);
+#define PTAMD_SKIN_DEVICE_TRANSFORMS 1u
+typedef struct {
+  ptamd_scene_rig* rig;
+  const float* transforms;        /* n_bones x 12; a HOST array, a DEVICE array with PTAMD_SKIN_DEVICE_TRANSFORMS */
+  const float* normal_matrices;   /* n_bones x 9 in the same memory, or NULL: the linear part of each transform */
+  uint32_t n_bones;               /* must equal the attached skin's */
+  uint32_t flags;                 /* 0 or PTAMD_SKIN_DEVICE_TRANSFORMS */
+  void* stream;                   /* the skin is asynchronous on this stream */
+} ptamd_scene_rig_skin_desc;
+int ptamd_scene_rig_skin(ptamd_context* ctx, const ptamd_scene_rig_skin_desc* desc);
+/* The host definition of a skin, no device needed.  out may be rest.  PTAMD_ERR_LIMIT for n_bones outside 1..65536, PTAMD_ERR_ARG
+ * for a null pointer and for an index that is not below n_bones; nothing is written then. */
+int ptamd_host_skin_faces(const ptamd_face* rest, uint32_t n_faces, const uint16_t* bone_indices /* n_faces x 3 x 4 */,
+                          const float* bone_weights /* n_faces x 3 x 4 */, uint32_t n_bones, const float* transforms /* n_bones x 12 */,
+                          const float* normal_matrices /* n_bones x 9 or NULL */, ptamd_face* out);
+
 /* ptamd_scene_update_lights replaces the light table of an uploaded scene: lights is a HOST array of n_lights records, which must
  * equal the uploaded count (the LDS layout and ptamd_scene_info do not change); it is copied before the call returns.  Asynchronous
  * on `stream` and ordered against launches as ptamd_scene_update is.  No box changes (the boxes' origin margin follows the extent
