@@ -3,7 +3,7 @@
 #include "ptamd_host.h"
 #include "pt_refit.h"
 #include "pt_refit_device.h"
-#include "pt_skin.h"
+#include "pt_morph.h"
 
 #include <cstring>
 #include <memory>
@@ -136,6 +136,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_refit_device_kernels();
   if (e == hipSuccess) e = resolve_pose_kernels();
   if (e == hipSuccess) e = resolve_skin_kernels();
+  if (e == hipSuccess) e = resolve_morph_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

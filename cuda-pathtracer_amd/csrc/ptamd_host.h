@@ -2,7 +2,8 @@
 // tables, and the few helpers that cross files.  One subsystem per file:
 //   ptamd_context.cpp   last error, ptamd_create / ptamd_destroy, device utilities, counters, self-test, time stamps
 //   ptamd_scene.cpp     scene tables: upload, updates, margins, quality, release, reads, their host mirrors; cubemaps
-//   ptamd_pose.cpp      the scene rig: a scene posed from per-group transforms, or skinned from per-corner bone weights, on the device
+//   ptamd_pose.cpp      the scene rig: a scene posed from per-group transforms, skinned from per-corner bone weights, or morphed from
+//                       blend-shape targets, on the device
 //   ptamd_launch.cpp    the launch pipeline (camera_terms ... do_launch), ptamd_raytrace*, ray queries
 //   ptamd_denoise.cpp   the spatial and temporal denoiser, the history, their host mirrors
 //   ptamd_adaptive.cpp  adaptive sampling
@@ -200,7 +201,7 @@ bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam);
 int settle_margins(DeviceScene& s, hipStream_t stream, const char* who);
 void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p);
 int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing);
-// what the update calls share (ptamd_scene_update, _update_device, _update_lights, ptamd_scene_rig_pose, _rig_skin)
+// what the update calls share (ptamd_scene_update, _update_device, _update_lights, ptamd_scene_rig_pose, _rig_skin, _rig_morph)
 int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces);
 int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t stream);
 int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream);

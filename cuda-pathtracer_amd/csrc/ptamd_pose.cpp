@@ -1,8 +1,9 @@
 // ptamd_pose.cpp — the scene rig (include/ptamd.h: ptamd_scene_rig): an uploaded scene posed from one transform per group of
-// faces, or skinned from one transform per bone and four weighted bones per corner, on the device, in front of the refit
-// ptamd_scene_update_device runs (ptamd_scene.cpp: enqueue_device_refit).
+// faces, skinned from one transform per bone and four weighted bones per corner, or morphed from one weight per blend-shape target
+// (and then posed or skinned), on the device, in front of the refit ptamd_scene_update_device runs (ptamd_scene.cpp:
+// enqueue_device_refit).
 #include "ptamd_host.h"
-#include "pt_skin.h"
+#include "pt_morph.h"
 
 #include <cstring>
 #include <memory>
@@ -10,39 +11,44 @@
 
 namespace ptamd {
 
-// A table of kPoseRecordFloats floats per group or bone on the device, copied from two pinned slots that are filled in turn (the
-// host fills one while the copy out of the other may still be in flight)
+// A table of `floats` floats per record on the device (kPoseRecordFloats per group or bone, one per morph target), copied from two
+// pinned slots that are filled in turn (the host fills one while the copy out of the other may still be in flight)
 struct RecordTable {
-  uint32_t count = 0;
+  uint32_t count = 0, floats = kPoseRecordFloats;
   DeviceBuffer<float> records;
   PinnedBuffer<float> h_records[2];
   Event staged[2];                               // the copy out of h_records[i] has finished
   bool staged_valid[2] = { false, false };
   uint32_t stage_next = 0;
-  size_t bytes() const { return (size_t)count * kPoseRecordFloats * sizeof(float); }
+  size_t bytes() const { return (size_t)count * floats * sizeof(float); }
 };
 
 } // namespace ptamd
 
 // Belongs to one context and one uploaded scene.  rest: the rest pose as created; posed: what the last pose or skin left, the
 // buffer the refit reads; group_of: the group of every face; groups: the pose's records.  With a skin attached
-// (ptamd_scene_rig_attach_skin): skin, kSkinRecordWords words per face, and bones, the skin's records
+// (ptamd_scene_rig_attach_skin): skin, kSkinRecordWords words per face, and bones, the skin's records.  With morph targets attached
+// (ptamd_scene_rig_attach_morphs): morph_entries, kMorphEntryWords words per entry, face-major; morph_begin, the first entry of
+// every face and the entry count; weights, one float per target
 struct ptamd_scene_rig {
   const ptamd_context* ctx = nullptr;
   uint32_t scene_id = 0, n_faces = 0;
   ptamd::DeviceBuffer<float> rest, posed;
-  ptamd::DeviceBuffer<uint32_t> group_of, skin;
-  ptamd::RecordTable groups, bones;
+  ptamd::DeviceBuffer<uint32_t> group_of, skin, morph_begin, morph_entries;
+  ptamd::RecordTable groups, bones, weights;
 };
 static_assert(!std::is_copy_constructible<ptamd_scene_rig>::value, "a rig owns its device buffers");
+static_assert(PTAMD_MORPH_THEN_NOTHING == ptamd::kMorphThenNothing && PTAMD_MORPH_THEN_POSE == ptamd::kMorphThenPose &&
+              PTAMD_MORPH_THEN_SKIN == ptamd::kMorphThenSkin, "ptamd.h's PTAMD_MORPH_THEN_* are pt_morph.h's kernel forms");
 
 using namespace ptamd;
 
 namespace {
 
-int alloc_table(RecordTable& t, uint32_t count)
+int alloc_table(RecordTable& t, uint32_t count, uint32_t floats = kPoseRecordFloats)
 {
   t.count = count;
+  t.floats = floats;
   t.staged_valid[0] = t.staged_valid[1] = false;
   PT_HIP(t.records.alloc(t.bytes()));
   for (int k = 0; k < 2; ++k) {
@@ -64,6 +70,15 @@ int fill_slot(RecordTable& t, const float* transforms, const float* normal_matri
   return PTAMD_OK;
 }
 
+// ... and a morph's weights, one float per record, as they are
+int fill_weight_slot(RecordTable& t, const float* weights, uint32_t* slot)
+{
+  *slot = t.stage_next++ & 1u;
+  if (t.staged_valid[*slot]) PT_HIP(hipEventSynchronize(t.staged[*slot].get()));
+  std::memcpy(t.h_records[*slot].get(), weights, t.bytes());
+  return PTAMD_OK;
+}
+
 int copy_slot(RecordTable& t, uint32_t slot, hipStream_t stream)
 {
   PT_HIP(hipMemcpyAsync(t.records.get(), t.h_records[slot].get(), t.bytes(), hipMemcpyHostToDevice, stream));
@@ -72,7 +87,7 @@ int copy_slot(RecordTable& t, uint32_t slot, hipStream_t stream)
   return PTAMD_OK;
 }
 
-// What a pose and a skin refuse alike, before anything is enqueued; makes the context's device current
+// What a pose, a skin and a morph refuse alike, before anything is enqueued; makes the context's device current
 int rig_update_checks(const char* who, const ptamd_context* ctx, const ptamd_scene_rig* rig, hipStream_t stream)
 {
   if (rig->ctx != ctx) { set_error(std::string(who) + ": the rig belongs to another context"); return PTAMD_ERR_ARG; }
@@ -195,6 +210,76 @@ int ptamd_scene_rig_skin(ptamd_context* ctx, const ptamd_scene_rig_skin_desc* d)
   else if ((rc = copy_slot(rig->bones, slot, stream)) != PTAMD_OK)
     return rc;
   PT_HIP(launch_skin(rig->rest.get(), rig->skin.get(), rig->bones.records.get(), rig->posed.get(), rig->n_faces, stream));
+  return enqueue_device_refit(s, r, rig->posed.get(), stream);
+}
+
+int ptamd_scene_rig_attach_morphs(ptamd_context* ctx, ptamd_scene_rig* rig, const ptamd_morph_target* targets, uint32_t n_targets)
+{
+  const char* who = "ptamd_scene_rig_attach_morphs";
+  if (!ctx || !rig) { set_error("ptamd_scene_rig_attach_morphs: null argument"); return PTAMD_ERR_ARG; }
+  int rc = morph_targets_check(who, targets, n_targets, rig->n_faces, nullptr);
+  if (rc != PTAMD_OK || (rc = rig_update_checks(who, ctx, rig, nullptr)) != PTAMD_OK) return rc;
+  std::vector<uint32_t> begin, entries;
+  try {
+    morph_table(targets, n_targets, rig->n_faces, begin, entries);
+  } catch (const std::bad_alloc&) {
+    set_error("ptamd_scene_rig_attach_morphs: out of memory");
+    return PTAMD_ERR_LIMIT;
+  }
+  PT_HIP(hipDeviceSynchronize());   // (a morph kernel in flight may still read the table this one replaces)
+  rig->weights.count = 0;           // no targets until these are complete
+  PT_HIP(rig->morph_begin.alloc(begin.size() * sizeof(uint32_t)));
+  PT_HIP(rig->morph_entries.alloc(entries.empty() ? 16 : entries.size() * sizeof(uint32_t)));
+  PT_HIP(hipMemcpy(rig->morph_begin.get(), begin.data(), begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!entries.empty()) PT_HIP(hipMemcpy(rig->morph_entries.get(), entries.data(), entries.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if ((rc = alloc_table(rig->weights, n_targets, 1u)) != PTAMD_OK) { rig->weights.count = 0; return rc; }
+  PT_HIP(hipDeviceSynchronize());
+  return PTAMD_OK;
+}
+
+int ptamd_scene_rig_morph(ptamd_context* ctx, const ptamd_scene_rig_morph_desc* d)
+{
+  const char* who = "ptamd_scene_rig_morph";
+  if (!ctx || !d || !d->rig || !d->weights) { set_error("ptamd_scene_rig_morph: null argument"); return PTAMD_ERR_ARG; }
+  ptamd_scene_rig* rig = d->rig;
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  if (d->then > PTAMD_MORPH_THEN_SKIN) { set_error("ptamd_scene_rig_morph: unknown then"); return PTAMD_ERR_ARG; }
+  if (d->flags & ~(PTAMD_MORPH_DEVICE_WEIGHTS | PTAMD_MORPH_DEVICE_TRANSFORMS)) { set_error("ptamd_scene_rig_morph: unknown flag"); return PTAMD_ERR_ARG; }
+  const bool pose = d->then == PTAMD_MORPH_THEN_POSE, skin = d->then == PTAMD_MORPH_THEN_SKIN;
+  const bool device_weights = (d->flags & PTAMD_MORPH_DEVICE_WEIGHTS) != 0u, device_transforms = (d->flags & PTAMD_MORPH_DEVICE_TRANSFORMS) != 0u;
+  if (device_transforms && !skin) { set_error("ptamd_scene_rig_morph: PTAMD_MORPH_DEVICE_TRANSFORMS without PTAMD_MORPH_THEN_SKIN"); return PTAMD_ERR_ARG; }
+  if ((pose || skin) && !d->transforms) { set_error("ptamd_scene_rig_morph: null argument"); return PTAMD_ERR_ARG; }
+  RecordTable* table = pose ? &rig->groups : skin ? &rig->bones : nullptr;   // the records of what follows the morph
+  if (rig->ctx == ctx) {
+    if (rig->weights.count == 0) { set_error("ptamd_scene_rig_morph: the rig has no morph targets attached (ptamd_scene_rig_attach_morphs)"); return PTAMD_ERR_ARG; }
+    if (d->n_targets != rig->weights.count) { set_error("ptamd_scene_rig_morph: n_targets differs from the attached count"); return PTAMD_ERR_ARG; }
+    if (skin && rig->bones.count == 0) { set_error("ptamd_scene_rig_morph: the rig has no skin attached (ptamd_scene_rig_attach_skin)"); return PTAMD_ERR_ARG; }
+    if (table && d->n_transforms != table->count) { set_error("ptamd_scene_rig_morph: n_transforms differs from the rig's"); return PTAMD_ERR_ARG; }
+  }
+  int rc = rig_update_checks(who, ctx, rig, stream);
+  if (rc != PTAMD_OK) return rc;
+  if (rig->n_faces == 0) return PTAMD_OK;
+  if (device_weights && (rc = device_array_checks(who, "weights", ctx, d->weights, (size_t)d->n_targets * sizeof(float), true)) != PTAMD_OK) return rc;
+  if (device_transforms) {
+    if ((rc = device_array_checks(who, "transforms", ctx, d->transforms, (size_t)d->n_transforms * 12u * sizeof(float), true)) != PTAMD_OK) return rc;
+    if (d->normal_matrices && (rc = device_array_checks(who, "normal_matrices", ctx, d->normal_matrices, (size_t)d->n_transforms * 9u * sizeof(float), false)) != PTAMD_OK) return rc;
+  }
+  DeviceScene& s = ctx->scenes[rig->scene_id];
+  RefitParams r;
+  uint32_t weight_slot = 0, slot = 0;
+  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK) return rc;
+  if (!device_weights && (rc = fill_weight_slot(rig->weights, d->weights, &weight_slot)) != PTAMD_OK) return rc;
+  if (table && !device_transforms && (rc = fill_slot(*table, d->transforms, d->normal_matrices, &slot)) != PTAMD_OK) return rc;
+  // the tables and the posed buffer are overwritten only behind the scene's readers and its previous update
+  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
+  if (!device_weights && (rc = copy_slot(rig->weights, weight_slot, stream)) != PTAMD_OK) return rc;
+  if (device_transforms)
+    PT_HIP(launch_skin_records(d->transforms, d->normal_matrices, rig->bones.records.get(), rig->bones.count, stream));
+  else if (table && (rc = copy_slot(*table, slot, stream)) != PTAMD_OK)
+    return rc;
+  PT_HIP(launch_morph(d->then, rig->rest.get(), rig->morph_begin.get(), rig->morph_entries.get(), device_weights ? d->weights : rig->weights.records.get(),
+                      pose ? rig->group_of.get() : skin ? rig->skin.get() : nullptr, table ? table->records.get() : nullptr, rig->posed.get(),
+                      rig->n_faces, stream));
   return enqueue_device_refit(s, r, rig->posed.get(), stream);
 }
 

@@ -155,6 +155,10 @@ inline bool margins_cover(float extent, float margin_floor, float origin_far)
 bool pose_groups_cover(const uint32_t* group_sizes, uint32_t n_groups, uint32_t n_faces);
 // ---- skinning (skin.cpp): true when every one of a skin's n_faces x 12 bone indices is below n_bones
 bool skin_indices_valid(const uint16_t* bone_indices, uint32_t n_faces, uint32_t n_bones);
+// ---- morph targets (morph.cpp): what the mirror and ptamd_scene_rig_attach_morphs refuse alike (sets the error; the counts decide
+// before any list is read; *n_entries: the total), and the device's face-major entry table of checked targets (csrc/pt_morph.h)
+int morph_targets_check(const char* who, const ptamd_morph_target* targets, uint32_t n_targets, uint32_t n_faces, uint64_t* n_entries);
+void morph_table(const ptamd_morph_target* targets, uint32_t n_targets, uint32_t n_faces, std::vector<uint32_t>& begin, std::vector<uint32_t>& entries);
 
 // Host traversals with the same structure the kernels use (tests + stats cross-check; bvh_walks.cpp).
 struct HostHit { int32_t kind; int32_t index; float t; float u, v; };

@@ -87,6 +87,20 @@ class SceneRigSkinDesc(C.Structure):        # ptamd_scene_rig_skin_desc: host ar
                 ("flags", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class MorphTarget(C.Structure):             # ptamd_morph_target (include/ptamd.h): HOST arrays
+    _fields_ = [("faces", C.POINTER(C.c_uint32)), ("deltas", C.POINTER(C.c_float)), ("n_entries", C.c_uint32)]
+
+
+MORPH_THEN_NOTHING, MORPH_THEN_POSE, MORPH_THEN_SKIN = 0, 1, 2
+MORPH_DEVICE_WEIGHTS, MORPH_DEVICE_TRANSFORMS = 1, 2
+
+
+class SceneRigMorphDesc(C.Structure):       # ptamd_scene_rig_morph_desc: host arrays, device addresses with MORPH_DEVICE_*
+    _fields_ = [("rig", C.c_void_p), ("weights", C.c_void_p), ("n_targets", C.c_uint32), ("then", C.c_uint32),
+                ("transforms", C.c_void_p), ("normal_matrices", C.c_void_p), ("n_transforms", C.c_uint32), ("flags", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
 class SceneLightsDesc(C.Structure):         # ptamd_scene_lights_desc (include/ptamd.h)
     _fields_ = [("scene_id", C.c_uint32), ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("stream", C.c_void_p)]
 
@@ -215,6 +229,10 @@ SIGNATURES = {
     "ptamd_scene_rig_skin": (C.c_int, [C.c_void_p, C.POINTER(SceneRigSkinDesc)]),
     "ptamd_host_skin_faces": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint16), C.POINTER(C.c_float), C.c_uint32,
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Face)]),
+    "ptamd_scene_rig_attach_morphs": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MorphTarget), C.c_uint32]),
+    "ptamd_scene_rig_morph": (C.c_int, [C.c_void_p, C.POINTER(SceneRigMorphDesc)]),
+    "ptamd_host_morph_faces": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(MorphTarget), C.c_uint32, C.POINTER(C.c_float),
+                                         C.POINTER(Face)]),
     "ptamd_scene_update_lights": (C.c_int, [C.c_void_p, C.POINTER(SceneLightsDesc)]),
     "ptamd_scene_quality": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(SceneQualityInfo)]),
     "ptamd_host_scene_quality": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.POINTER(C.c_double)]),

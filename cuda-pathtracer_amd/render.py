@@ -441,6 +441,38 @@ def host_skin_faces(hs: HostScene, indices, weights, transforms, normal_matrices
     return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
 
 
+def _morph_targets(targets):
+    """(ptamd_morph_target array, what keeps its lists alive) of a list of (faces uint32[k], deltas float32[k, 18]) pairs"""
+    keep, arr = [], (N.MorphTarget * max(len(targets), 1))()
+    for t, (faces, deltas) in enumerate(targets):
+        f = np.asarray(faces)
+        if f.dtype != np.uint32 and f.size and (f.min() < 0 or f.max() > 0xffffffff):
+            raise ValueError("a face index does not fit 32 bits")
+        f = np.ascontiguousarray(f, dtype=np.uint32).reshape(-1)
+        d = np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1)
+        if d.size != f.size * 18:
+            raise ValueError(f"target {t}: deltas must hold 18 floats for each of its {f.size} faces")
+        keep.append((f, d))
+        arr[t].faces = f.ctypes.data_as(C.POINTER(C.c_uint32)) if f.size else None
+        arr[t].deltas = d.ctypes.data_as(C.POINTER(C.c_float)) if f.size else None
+        arr[t].n_entries = f.size
+    return arr, keep
+
+
+def host_morph_faces(hs: HostScene, targets, weights) -> HostScene:
+    """ptamd_host_morph_faces (no GPU): `hs` morphed under sparse blend-shape targets, a list of (faces uint32[k] strictly
+    ascending, deltas float32[k, 18]: nine vertex then nine normal coordinates) pairs, with one weight per target.  The tangents are
+    derived from the morphed vertices."""
+    arr, keep = _morph_targets(targets)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if w.size != len(targets):
+        raise ValueError(f"weights must hold one float for each of the {len(targets)} targets")
+    out = np.zeros(len(hs.faces), dtype=FACE_DTYPE)
+    N.check(N.load().ptamd_host_morph_faces(hs.faces.ctypes.data_as(C.POINTER(N.Face)), len(hs.faces), arr, len(targets),
+                                            w.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(N.Face))))
+    return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
+
+
 def host_scene_quality(scene: HostScene, faces_b=None) -> float:
     """ptamd_host_scene_quality (no GPU): the surface-area-heuristic cost of `scene`'s binary tree as an upload builds it, or
     refitted to `faces_b` (HostScene or face array)."""
@@ -572,6 +604,34 @@ def host_denoise(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_n
     return linear, rgba
 
 
+def _is_tensor(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+def _device_tensor(ctx, name: str, x, per: int, what: str) -> None:
+    """`x` is a contiguous float32 tensor of `per` values a `what` on the context's device, or a ValueError"""
+    if not x.is_cuda:
+        raise ValueError(f"{name} must live in device memory (CPU tensors: pass numpy arrays)")
+    if x.device.index != ctx.device:
+        raise ValueError(f"{name} lives on {x.device}, the context on device {ctx.device}")
+    if str(x.dtype) != "torch.float32" or not x.is_contiguous() or x.numel() % per:
+        raise ValueError(f"{name} must be contiguous float32 of {per} values a {what}")
+
+
+def _device_transforms(ctx, transforms, normal_matrices) -> int:
+    """The bone count of transforms (and normal matrices, or None) given as tensors on the context's device, or a ValueError"""
+    for name, x, per_bone in (("transforms", transforms, 12), ("normal_matrices", normal_matrices, 9)):
+        if x is None and per_bone == 9:
+            continue
+        if not _is_tensor(x):
+            raise ValueError("transforms and normal_matrices are both tensors or both host arrays")
+        _device_tensor(ctx, name, x, per_bone, "bone")
+    n = transforms.numel() // 12
+    if normal_matrices is not None and normal_matrices.numel() != n * 9:
+        raise ValueError("normal_matrices must hold n_bones x 9 floats")
+    return n
+
+
 class SceneRig:
     """A scene posed from per-group transforms on the device (ptamd_scene_rig_*): the rest pose, the posed records and one record
     per group, allocated once.  Close it before its context."""
@@ -619,22 +679,8 @@ class SceneRig:
         d.rig = self.handle
         d.stream = _stream_handle(stream)
         keep = None
-        if type(transforms).__module__.startswith("torch") or type(normal_matrices).__module__.startswith("torch"):
-            import torch
-            for name, x, per_bone in (("transforms", transforms, 12), ("normal_matrices", normal_matrices, 9)):
-                if x is None and per_bone == 9:
-                    continue
-                if not isinstance(x, torch.Tensor):
-                    raise ValueError("transforms and normal_matrices are both tensors or both host arrays")
-                if not x.is_cuda:
-                    raise ValueError(f"{name} must live in device memory (CPU tensors: pass numpy arrays)")
-                if x.device.index != self.ctx.device:
-                    raise ValueError(f"{name} lives on {x.device}, the context on device {self.ctx.device}")
-                if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() % per_bone:
-                    raise ValueError(f"{name} must be contiguous float32 of {per_bone} values a bone")
-            d.n_bones = transforms.numel() // 12
-            if normal_matrices is not None and normal_matrices.numel() != d.n_bones * 9:
-                raise ValueError("normal_matrices must hold n_bones x 9 floats")
+        if _is_tensor(transforms) or _is_tensor(normal_matrices):
+            d.n_bones = _device_transforms(self.ctx, transforms, normal_matrices)
             d.transforms = transforms.data_ptr()
             d.normal_matrices = normal_matrices.data_ptr() if normal_matrices is not None else None
             d.flags = N.SKIN_DEVICE_TRANSFORMS
@@ -646,6 +692,48 @@ class SceneRig:
             d.normal_matrices = keep[1].ctypes.data if keep[1] is not None else None
             d.flags = 0
         N.check(self.ctx._lib.ptamd_scene_rig_skin(self.ctx._h, C.byref(d)))   # (host transforms are staged before the call returns)
+
+    def attach_morphs(self, targets) -> None:
+        """ptamd_scene_rig_attach_morphs: sparse blend-shape targets, a list of (faces uint32[k] strictly ascending, deltas
+        float32[k, 18]) pairs; a set-up call, replaces targets attached before."""
+        arr, keep = _morph_targets(targets)
+        N.check(self.ctx._lib.ptamd_scene_rig_attach_morphs(self.ctx._h, self.handle, arr, len(targets)))
+
+    def morph(self, weights, then=None, transforms=None, normal_matrices=None, stream=None) -> None:
+        """ptamd_scene_rig_morph: the scene's geometry = the rest pose morphed under one weight per attached target and then
+        (`then`: None, "pose" or "skin") posed under one transform per group or skinned under one per bone in the same kernel,
+        its tree refitted; asynchronous on `stream`.  `weights` is a numpy array or a float32 CUDA tensor on the context's
+        device; with then="skin" `transforms` and `normal_matrices` may be such tensors too (SceneRig.skin's rules).  Tensors stay
+        alive and unmodified until the morph's kernels have run."""
+        thens = {None: N.MORPH_THEN_NOTHING, "pose": N.MORPH_THEN_POSE, "skin": N.MORPH_THEN_SKIN}
+        if then not in thens:
+            raise ValueError('then is None, "pose" or "skin"')
+        if (then is None) != (transforms is None):
+            raise ValueError("transforms go with then=\"pose\" or then=\"skin\", and only with them")
+        d = N.SceneRigMorphDesc()
+        d.rig, d.then, d.flags, d.stream = self.handle, thens[then], 0, _stream_handle(stream)
+        if _is_tensor(weights):
+            _device_tensor(self.ctx, "weights", weights, 1, "target")
+            d.weights, d.n_targets = weights.data_ptr(), weights.numel()
+            d.flags |= N.MORPH_DEVICE_WEIGHTS
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)   # (a count that is not the rig's is the library's to refuse)
+            d.weights, d.n_targets = w.ctypes.data, w.size
+        keep = None
+        if _is_tensor(transforms) or _is_tensor(normal_matrices):
+            if then != "skin":
+                raise ValueError("device transforms go with then=\"skin\" only")
+            d.n_transforms = _device_transforms(self.ctx, transforms, normal_matrices)
+            d.transforms = transforms.data_ptr()
+            d.normal_matrices = normal_matrices.data_ptr() if normal_matrices is not None else None
+            d.flags |= N.MORPH_DEVICE_TRANSFORMS
+        elif transforms is not None:
+            n = np.asarray(transforms).size // 12    # (a count that is not the rig's is the library's to refuse)
+            keep = _pose_arrays(n, transforms, normal_matrices)
+            d.n_transforms = n
+            d.transforms = keep[0].ctypes.data
+            d.normal_matrices = keep[1].ctypes.data if keep[1] is not None else None
+        N.check(self.ctx._lib.ptamd_scene_rig_morph(self.ctx._h, C.byref(d)))   # (host arrays are staged before the call returns)
 
     def faces(self) -> np.ndarray:
         """The posed records the last pose left, copied to host memory (synchronises the device): FACE_DTYPE[n_faces]."""

@@ -379,6 +379,85 @@ int ptamd_host_skin_faces(const ptamd_face* rest, uint32_t n_faces, const uint16
                           const float* bone_weights /* n_faces x 3 x 4 */, uint32_t n_bones, const float* transforms /* n_bones x 12 */,
                           const float* normal_matrices /* n_bones x 9 or NULL */, ptamd_face* out);
 
+/* ---- Morphing a rigged scene from sparse blend-shape targets ---------------------------------------------------
+ * The third standard deformer: faces, corrective shapes on a skinned character, a bulging pipe, a swelling sail.  MORPH TARGETS
+ * hang on a ptamd_scene_rig like a skin.  Faces are a soup, so a target is sparse over FACES: it lists the faces it moves,
+ * strictly ascending, and gives each 18 deltas.  Delta k (0..17) belongs to float k of ptamd_face: the nine vertex coordinates,
+ * then the nine normal coordinates, corner-major as in the record.  ptamd_scene_rig_morph takes one weight per target, morphs the
+ * rest pose, optionally poses or skins the result in the same kernel (glTF's order: morph, then skin), and refits the scene.
+ *
+ * The arithmetic (csrc/pt_morph.h, shared by the kernels and by ptamd_host_morph_faces).  Per face, with w[t] the weight of
+ * target t and d_t its deltas for this face, the targets that list the face are visited in ASCENDING TARGET INDEX, all operations
+ * binary32, unfused:
+ *     x[k] = x[k] + w[t] * d_t[k]        k = 0 .. 17, starting from the rest value; the product is rounded, then the sum
+ * A target whose weight compares equal to zero (+0.0 or -0.0) is SKIPPED on both sides: "off" means exactly the rest value, -0.0
+ * components included, and shields a non-finite delta.  A NaN weight is not skipped: it makes a NaN of every float of the faces
+ * its target lists, and of no other face.  Nothing is renormalised, neither the weights nor the normals.  Texcoords and
+ * material_id are copied from the rest pose.
+ *
+ * The tangent is DERIVED from the morphed vertices and the copied texcoords by the skin's formula (above).  Consequence: a host
+ * that supplied tangents of its own in the rest pose gets the derived ones after the first morph, with every weight zero too.
+ *
+ * Contract: the posed records, the scene's five tables, its margins and every later render are byte for byte what
+ * ptamd_scene_update produces from the composition of mirrors below on the same inputs, wherever the mirror's value is not a NaN;
+ * the pose's NaN clause applies (a NaN of the mirror is a NaN on the device, of any payload).
+ *     PTAMD_MORPH_THEN_NOTHING    ptamd_host_morph_faces
+ *     PTAMD_MORPH_THEN_POSE       ptamd_host_morph_faces, then ptamd_host_pose_faces of its result (which transforms the derived tangent)
+ *     PTAMD_MORPH_THEN_SKIN       ptamd_host_morph_faces, then ptamd_host_skin_faces of its result (which derives the tangent again)
+ * In the fused forms the morphed record never goes to memory.
+ *
+ * ptamd_scene_rig_attach_morphs is a set-up call like ptamd_scene_rig_attach_skin: it validates on the host, transposes the targets
+ * into one table of 80-byte entries (18 deltas and the target's index), face-major and within a face by ascending target, with one
+ * 32-bit range start per face, allocates and synchronises.  It may be called again: it then waits for the device and replaces the
+ * targets; a refused call leaves the attached ones.  Memory it adds: 80 bytes per entry, 4 bytes per face and 4 bytes per target
+ * on the device, twice 4 bytes per target in pinned host memory.  Refused: n_targets outside 1..65536 and more than 2^28 - 1
+ * entries over all targets (decided from the counts alone, before any list is read) with PTAMD_ERR_LIMIT; a face index that is
+ * not below n_faces, a face list that is not strictly ascending, a null list with n_entries > 0, a rig of another context or of
+ * a released scene with PTAMD_ERR_ARG; a context that holds a captured launch with PTAMD_ERR_LIMIT.
+ *
+ * ptamd_scene_rig_morph is asynchronous on `stream` and follows ptamd_scene_rig_skin step for step: it stages the weights, and
+ * the group or bone records of `transforms`, in pinned slots, waits on the stream for the scene's readers and its previous
+ * update, copies them, runs the morph kernel from the rest pose into the rig's posed buffer and enqueues exactly what
+ * ptamd_scene_update_device enqueues for that buffer.  Host arrays are read before the call returns.  transforms,
+ * normal_matrices and n_transforms are the pose's (one per group) with THEN_POSE, the skin's (one per bone) with THEN_SKIN, and
+ * ignored with THEN_NOTHING.  With PTAMD_MORPH_DEVICE_WEIGHTS weights is DEVICE memory of the context's device, aligned to 16
+ * bytes, read by the kernel in stream order and never copied; with PTAMD_MORPH_DEVICE_TRANSFORMS (THEN_SKIN only) transforms and
+ * normal_matrices are as with PTAMD_SKIN_DEVICE_TRANSFORMS.  Device arrays stay alive and unmodified until the kernels have run.
+ * Ordering against launches, capture rules and "margins pending" are ptamd_scene_update_device's.  Refused before anything is
+ * enqueued, with PTAMD_ERR_ARG: a rig without targets, n_targets or n_transforms that is not the rig's, THEN_SKIN on a rig without
+ * a skin, an unknown `then` or flag, DEVICE_TRANSFORMS without THEN_SKIN, a device pointer that is not device memory of the
+ * context's device or not aligned, a rig of another context or of a released scene, a null pointer.
+ *
+ * ptamd_scene_rig_pose and ptamd_scene_rig_skin behave on a rig with targets exactly as on one without: they start from the rest
+ * pose and ignore the targets. */
+typedef struct {
+  const uint32_t* faces;     /* n_entries face indices, strictly ascending, each < n_faces */
+  const float*    deltas;    /* n_entries x 18 */
+  uint32_t        n_entries; /* 0 allowed */
+} ptamd_morph_target;
+int ptamd_scene_rig_attach_morphs(ptamd_context* ctx, ptamd_scene_rig* rig, const ptamd_morph_target* targets, uint32_t n_targets);
+#define PTAMD_MORPH_THEN_NOTHING 0u
+#define PTAMD_MORPH_THEN_POSE    1u
+#define PTAMD_MORPH_THEN_SKIN    2u
+#define PTAMD_MORPH_DEVICE_WEIGHTS    1u   /* weights is DEVICE memory, 16-byte aligned, read in stream order */
+#define PTAMD_MORPH_DEVICE_TRANSFORMS 2u   /* only with THEN_SKIN: as PTAMD_SKIN_DEVICE_TRANSFORMS */
+typedef struct {
+  ptamd_scene_rig* rig;
+  const float* weights;           /* n_targets; a HOST array, a DEVICE array with PTAMD_MORPH_DEVICE_WEIGHTS */
+  uint32_t n_targets;             /* must equal the attached count */
+  uint32_t then;                  /* PTAMD_MORPH_THEN_* */
+  const float* transforms;        /* n_transforms x 12: groups (THEN_POSE) or bones (THEN_SKIN); ignored for THEN_NOTHING */
+  const float* normal_matrices;   /* n_transforms x 9 in the same memory, or NULL: the linear part of each transform */
+  uint32_t n_transforms;          /* must equal the rig's group count (THEN_POSE) or the attached skin's bone count (THEN_SKIN) */
+  uint32_t flags;                 /* 0 or PTAMD_MORPH_DEVICE_* */
+  void* stream;                   /* the morph is asynchronous on this stream */
+} ptamd_scene_rig_morph_desc;
+int ptamd_scene_rig_morph(ptamd_context* ctx, const ptamd_scene_rig_morph_desc* desc);
+/* The host definition of a morph, no device needed.  out may be rest.  Refuses what ptamd_scene_rig_attach_morphs refuses of the
+ * targets, and a null pointer with PTAMD_ERR_ARG; nothing is written then. */
+int ptamd_host_morph_faces(const ptamd_face* rest, uint32_t n_faces, const ptamd_morph_target* targets, uint32_t n_targets,
+                           const float* weights, ptamd_face* out);
+
 /* ptamd_scene_update_lights replaces the light table of an uploaded scene: lights is a HOST array of n_lights records, which must
  * equal the uploaded count (the LDS layout and ptamd_scene_info do not change); it is copied before the call returns.  Asynchronous
  * on `stream` and ordered against launches as ptamd_scene_update is.  No box changes (the boxes' origin margin follows the extent
