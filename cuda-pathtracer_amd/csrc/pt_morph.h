@@ -1,5 +1,5 @@
 // pt_morph.h — the arithmetic of morphing a scene from sparse blend-shape targets (ptamd_scene_rig_morph), written once for the
-// host mirror (host/morph.cpp: ptamd_host_morph_faces) and the device kernels (pt_morph.hip); DESIGN.md §13.
+// host mirror (host/morph.cpp: ptamd_host_morph_faces) and the device kernels (pt_rig.hip); DESIGN.md §13.
 //
 // Like pt_pose.h and pt_skin.h the header includes nothing of HIP, every side is compiled with -ffp-contract=off and calls the
 // functions below, so the morphed records of the device equal the mirror's byte for byte wherever the mirror's value is not a NaN
@@ -84,14 +84,15 @@ PT_RF_HD void mo_morph_face_packed(const float* weights, const uint32_t* entries
 
 #if defined(__HIPCC__)
 namespace ptamd {
-// What follows the morph in the same kernel, the morphed record still in registers (ptamd.h: PTAMD_MORPH_THEN_*)
+// What follows the morph, or stands alone, in the same kernel, the record still in registers (ptamd.h: PTAMD_MORPH_THEN_*)
 constexpr uint32_t kMorphThenNothing = 0, kMorphThenPose = 1, kMorphThenSkin = 2;
-// posed[i] = then(mo_morph_face_packed(weights, entries of face i, rest[i])) for n_faces faces.  then: nothing (`per_face` and
-// `records` are not read); ps_pose_face under records[per_face[i]] (per_face: the rig's group index); sk_skin_face under the skin
-// record per_face + i * kSkinRecordWords.  Every array is aligned to 16 bytes, every entry's target names a weight and every
-// index a record (ptamd_scene_rig_attach_morphs and _attach_skin checked them)
-hipError_t launch_morph(uint32_t then, const float* rest, const uint32_t* morph_begin, const uint32_t* entries, const float* weights,
-                        const uint32_t* per_face, const float* records, float* posed, uint32_t n_faces, hipStream_t stream);
-hipError_t resolve_morph_kernels();
+// posed[i] = then(morph ? mo_morph_face_packed(weights, entries of face i, rest[i]) : rest[i]) for n_faces faces.  Without `morph`,
+// `morph_begin`, `entries` and `weights` are not read.  then: nothing (`per_face` and `records` are not read; only behind a morph);
+// ps_pose_face under records[per_face[i]] (per_face: the rig's group index); sk_skin_face under the skin record per_face + i *
+// kSkinRecordWords.  Every array is aligned to 16 bytes, every entry's target names a weight and every index a record (the rig
+// built the group index; ptamd_scene_rig_attach_morphs and _attach_skin checked theirs: ptamd_rig.cpp)
+hipError_t launch_rig(bool morph, uint32_t then, const float* rest, const uint32_t* morph_begin, const uint32_t* entries, const float* weights,
+                      const uint32_t* per_face, const float* records, float* posed, uint32_t n_faces, hipStream_t stream);
+hipError_t resolve_rig_kernels();
 }
 #endif

@@ -1,5 +1,5 @@
 // pt_pose.h — the arithmetic of posing a scene from per-group transforms (ptamd_scene_rig_pose), written once for the host mirror
-// (host/pose.cpp: ptamd_host_pose_faces) and the device kernel (pt_pose.hip); DESIGN.md §13.
+// (host/pose.cpp: ptamd_host_pose_faces) and the device kernels (pt_rig.hip); DESIGN.md §13.
 //
 // Like pt_refit.h the header includes nothing of HIP, every side is compiled with -ffp-contract=off and calls the functions
 // below, so the posed records of the device equal the mirror's byte for byte wherever the mirror's value is not a NaN (a NaN is
@@ -58,12 +58,3 @@ PT_RF_HD void ps_pose_face(const float* rec, const float* in, float* out)
 }
 
 } // namespace ptamd
-
-#if defined(__HIPCC__)
-namespace ptamd {
-// posed[i] = ps_pose_face(records[group_of[i]], rest[i]) for n_faces faces; rest, posed and records are aligned to 16 bytes and
-// every group_of[i] names a record of the table (the rig built the index: ptamd_pose.cpp)
-hipError_t launch_pose(const float* rest, const uint32_t* group_of, const float* records, float* posed, uint32_t n_faces, hipStream_t stream);
-hipError_t resolve_pose_kernels();
-}
-#endif

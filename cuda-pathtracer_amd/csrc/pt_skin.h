@@ -1,5 +1,5 @@
 // pt_skin.h — the arithmetic of skinning a scene from per-corner bone weights (ptamd_scene_rig_skin), written once for the host
-// mirror (host/skin.cpp: ptamd_host_skin_faces), the device kernels (pt_skin.hip) and, for the tangent, the scene loader
+// mirror (host/skin.cpp: ptamd_host_skin_faces), the device kernels (pt_rig.hip) and, for the tangent, the scene loader
 // (host/scene_loader.cpp); DESIGN.md §13.
 //
 // Like pt_pose.h the header includes nothing of HIP, every side is compiled with -ffp-contract=off and calls the functions below,
@@ -94,12 +94,8 @@ PT_RF_HD void sk_unpack(const uint32_t* rec, uint16_t* idx, float* w)
 
 #if defined(__HIPCC__)
 namespace ptamd {
-// posed[i] = sk_skin_face(records, skin record i, rest[i]) for n_faces faces; rest, skin, records and posed are aligned to 16
-// bytes and every index of every skin record names a record of the table (ptamd_scene_rig_attach_skin checked them)
-hipError_t launch_skin(const float* rest, const uint32_t* skin, const float* records, float* posed, uint32_t n_faces, hipStream_t stream);
 // records[b] = ps_record(transforms + 12 b, normal_matrices ? normal_matrices + 9 b : null) for n_bones bones, from DEVICE
 // arrays; transforms and records are aligned to 16 bytes
 hipError_t launch_skin_records(const float* transforms, const float* normal_matrices, float* records, uint32_t n_bones, hipStream_t stream);
-hipError_t resolve_skin_kernels();
 }
 #endif

@@ -134,9 +134,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   hipError_t e = resolve_kernels();
   if (e == hipSuccess) e = resolve_refit_kernels();
   if (e == hipSuccess) e = resolve_refit_device_kernels();
-  if (e == hipSuccess) e = resolve_pose_kernels();
-  if (e == hipSuccess) e = resolve_skin_kernels();
-  if (e == hipSuccess) e = resolve_morph_kernels();
+  if (e == hipSuccess) e = resolve_rig_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

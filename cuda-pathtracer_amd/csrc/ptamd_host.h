@@ -2,7 +2,7 @@
 // tables, and the few helpers that cross files.  One subsystem per file:
 //   ptamd_context.cpp   last error, ptamd_create / ptamd_destroy, device utilities, counters, self-test, time stamps
 //   ptamd_scene.cpp     scene tables: upload, updates, margins, quality, release, reads, their host mirrors; cubemaps
-//   ptamd_pose.cpp      the scene rig: a scene posed from per-group transforms, skinned from per-corner bone weights, or morphed from
+//   ptamd_rig.cpp       the scene rig: a scene posed from per-group transforms, skinned from per-corner bone weights, or morphed from
 //                       blend-shape targets, on the device
 //   ptamd_launch.cpp    the launch pipeline (camera_terms ... do_launch), ptamd_raytrace*, ray queries
 //   ptamd_denoise.cpp   the spatial and temporal denoiser, the history, their host mirrors

@@ -1,11 +1,13 @@
-// ptamd_pose.cpp — the scene rig (include/ptamd.h: ptamd_scene_rig): an uploaded scene posed from one transform per group of
+// ptamd_rig.cpp — the scene rig (include/ptamd.h: ptamd_scene_rig): an uploaded scene posed from one transform per group of
 // faces, skinned from one transform per bone and four weighted bones per corner, or morphed from one weight per blend-shape target
 // (and then posed or skinned), on the device, in front of the refit ptamd_scene_update_device runs (ptamd_scene.cpp:
-// enqueue_device_refit).
+// enqueue_device_refit).  The three updates are one sequence (rig_update) under three sets of argument checks; the kernels are
+// pt_rig.hip's.
 #include "ptamd_host.h"
 #include "pt_morph.h"
 
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 
@@ -21,6 +23,38 @@ struct RecordTable {
   bool staged_valid[2] = { false, false };
   uint32_t stage_next = 0;
   size_t bytes() const { return (size_t)count * floats * sizeof(float); }
+
+  int alloc(uint32_t n, uint32_t floats_each = kPoseRecordFloats)
+  {
+    count = n;
+    floats = floats_each;
+    staged_valid[0] = staged_valid[1] = false;
+    PT_HIP(records.alloc(bytes()));
+    for (int k = 0; k < 2; ++k) {
+      PT_HIP(h_records[k].alloc(bytes()));
+      PT_HIP(staged[k].ensure());
+    }
+    PT_HIP(hipMemset(records.get(), 0, bytes()));
+    return PTAMD_OK;
+  }
+
+  // fill(the pinned slot whose last copy is two calls back), once that copy has finished; *slot says which
+  template <typename Fill>
+  int stage(Fill fill, uint32_t* slot)
+  {
+    *slot = stage_next++ & 1u;
+    if (staged_valid[*slot]) PT_HIP(hipEventSynchronize(staged[*slot].get()));
+    fill(h_records[*slot].get());
+    return PTAMD_OK;
+  }
+
+  int copy(uint32_t slot, hipStream_t stream)
+  {
+    PT_HIP(hipMemcpyAsync(records.get(), h_records[slot].get(), bytes(), hipMemcpyHostToDevice, stream));
+    PT_HIP(hipEventRecord(staged[slot].get(), stream));
+    staged_valid[slot] = true;
+    return PTAMD_OK;
+  }
 };
 
 } // namespace ptamd
@@ -45,48 +79,6 @@ using namespace ptamd;
 
 namespace {
 
-int alloc_table(RecordTable& t, uint32_t count, uint32_t floats = kPoseRecordFloats)
-{
-  t.count = count;
-  t.floats = floats;
-  t.staged_valid[0] = t.staged_valid[1] = false;
-  PT_HIP(t.records.alloc(t.bytes()));
-  for (int k = 0; k < 2; ++k) {
-    PT_HIP(t.h_records[k].alloc(t.bytes()));
-    PT_HIP(t.staged[k].ensure());
-  }
-  PT_HIP(hipMemset(t.records.get(), 0, t.bytes()));
-  return PTAMD_OK;
-}
-
-// The records of the caller's transforms into the slot whose last copy is two calls back; *slot says which
-int fill_slot(RecordTable& t, const float* transforms, const float* normal_matrices, uint32_t* slot)
-{
-  *slot = t.stage_next++ & 1u;
-  if (t.staged_valid[*slot]) PT_HIP(hipEventSynchronize(t.staged[*slot].get()));
-  float* staged = t.h_records[*slot].get();
-  for (uint32_t g = 0; g < t.count; ++g)
-    ps_record(transforms + (size_t)g * 12u, normal_matrices ? normal_matrices + (size_t)g * 9u : nullptr, staged + (size_t)g * kPoseRecordFloats);
-  return PTAMD_OK;
-}
-
-// ... and a morph's weights, one float per record, as they are
-int fill_weight_slot(RecordTable& t, const float* weights, uint32_t* slot)
-{
-  *slot = t.stage_next++ & 1u;
-  if (t.staged_valid[*slot]) PT_HIP(hipEventSynchronize(t.staged[*slot].get()));
-  std::memcpy(t.h_records[*slot].get(), weights, t.bytes());
-  return PTAMD_OK;
-}
-
-int copy_slot(RecordTable& t, uint32_t slot, hipStream_t stream)
-{
-  PT_HIP(hipMemcpyAsync(t.records.get(), t.h_records[slot].get(), t.bytes(), hipMemcpyHostToDevice, stream));
-  PT_HIP(hipEventRecord(t.staged[slot].get(), stream));
-  t.staged_valid[slot] = true;
-  return PTAMD_OK;
-}
-
 // What a pose, a skin and a morph refuse alike, before anything is enqueued; makes the context's device current
 int rig_update_checks(const char* who, const ptamd_context* ctx, const ptamd_scene_rig* rig, hipStream_t stream)
 {
@@ -95,6 +87,73 @@ int rig_update_checks(const char* who, const ptamd_context* ctx, const ptamd_sce
   int rc = update_scene_checks(who, ctx, rig->scene_id, rig->n_faces, rig->rest.get());
   if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
   PT_HIP(hipSetDevice(ctx->device));
+  return PTAMD_OK;
+}
+
+// One update of the posed records and the refit behind it
+struct RigUpdate {
+  const float* weights;                       // the morph's, one per attached target; null: no morph
+  bool device_weights;                        // ... on the device, read where they lie; else the host's, staged
+  uint32_t then;                              // what follows: nothing (only behind a morph), a pose under the groups' records, a skin under the bones'
+  const float *transforms, *normal_matrices;  // one per group or bone (normal_matrices or null); not looked at behind `nothing`
+  bool device_transforms;                     // ... on the device (a skin's only: pt_skin_records builds the table); else the host's, staged
+  hipStream_t stream;
+};
+
+// The entry point `who` has refused what only it can refuse.  In this order: the shared refusals, the empty scene, the device
+// arrays, the refit's buffers, the pinned slots; then, enqueued: the wait for the scene's readers, the weights, the records, the
+// face kernel, the refit
+int rig_update(const char* who, ptamd_context* ctx, ptamd_scene_rig* rig, const RigUpdate& u)
+{
+  int rc = rig_update_checks(who, ctx, rig, u.stream);
+  if (rc != PTAMD_OK) return rc;
+  if (rig->n_faces == 0) return PTAMD_OK;
+  const bool pose = u.then == kMorphThenPose, skin = u.then == kMorphThenSkin;
+  const bool stage_weights = u.weights && !u.device_weights;
+  RecordTable& weights = rig->weights;
+  RecordTable* table = pose ? &rig->groups : skin ? &rig->bones : nullptr;   // the records of what follows
+  if (u.device_weights && (rc = device_array_checks(who, "weights", ctx, u.weights, weights.bytes(), true)) != PTAMD_OK) return rc;
+  if (u.device_transforms) {
+    if ((rc = device_array_checks(who, "transforms", ctx, u.transforms, (size_t)table->count * 12u * sizeof(float), true)) != PTAMD_OK) return rc;
+    if (u.normal_matrices && (rc = device_array_checks(who, "normal_matrices", ctx, u.normal_matrices, (size_t)table->count * 9u * sizeof(float), false)) != PTAMD_OK) return rc;
+  }
+  DeviceScene& s = ctx->scenes[rig->scene_id];
+  RefitParams r;
+  uint32_t weight_slot = 0, slot = 0;
+  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK) return rc;
+  if (stage_weights && (rc = weights.stage([&](float* staged) { std::memcpy(staged, u.weights, weights.bytes()); }, &weight_slot)) != PTAMD_OK) return rc;
+  const auto records_of_transforms = [&](float* staged) {
+    for (uint32_t g = 0; g < table->count; ++g)
+      ps_record(u.transforms + (size_t)g * 12u, u.normal_matrices ? u.normal_matrices + (size_t)g * 9u : nullptr, staged + (size_t)g * kPoseRecordFloats);
+  };
+  if (table && !u.device_transforms && (rc = table->stage(records_of_transforms, &slot)) != PTAMD_OK) return rc;
+  // the tables and the posed buffer are overwritten only behind the scene's readers and its previous update
+  if ((rc = wait_for_readers(ctx, s, u.stream)) != PTAMD_OK) return rc;
+  if (stage_weights && (rc = weights.copy(weight_slot, u.stream)) != PTAMD_OK) return rc;
+  if (u.device_transforms)
+    PT_HIP(launch_skin_records(u.transforms, u.normal_matrices, table->records.get(), table->count, u.stream));
+  else if (table && (rc = table->copy(slot, u.stream)) != PTAMD_OK)
+    return rc;
+  PT_HIP(launch_rig(u.weights != nullptr, u.then, rig->rest.get(), rig->morph_begin.get(), rig->morph_entries.get(),
+                    u.device_weights ? u.weights : weights.records.get(), pose ? rig->group_of.get() : skin ? rig->skin.get() : nullptr,
+                    table ? table->records.get() : nullptr, rig->posed.get(), rig->n_faces, u.stream));
+  return enqueue_device_refit(s, r, rig->posed.get(), u.stream);
+}
+
+// What attaching a skin and attaching morph targets share: the per-face words they packed onto the device and a fresh table of
+// `count` records.  The table is absent (count 0) until all of it is complete
+struct PerFaceWords { DeviceBuffer<uint32_t>& into; const std::vector<uint32_t>& from; };
+int attach(RecordTable& t, uint32_t count, uint32_t floats, std::initializer_list<PerFaceWords> arrays)
+{
+  PT_HIP(hipDeviceSynchronize());   // (a kernel in flight may still read what this replaces)
+  t.count = 0;
+  for (const PerFaceWords& a : arrays) {
+    PT_HIP(a.into.alloc(a.from.empty() ? 16 : a.from.size() * sizeof(uint32_t)));   // (pointers stay valid for a scene without faces)
+    if (!a.from.empty()) PT_HIP(hipMemcpy(a.into.get(), a.from.data(), a.from.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  const int rc = t.alloc(count, floats);
+  if (rc != PTAMD_OK) { t.count = 0; return rc; }
+  PT_HIP(hipDeviceSynchronize());
   return PTAMD_OK;
 }
 
@@ -129,7 +188,7 @@ int ptamd_scene_rig_create(ptamd_context* ctx, uint32_t scene_id, const ptamd_fa
   PT_HIP(rig->rest.alloc(face_bytes ? face_bytes : 16));   // (pointers stay valid for a scene without faces)
   PT_HIP(rig->posed.alloc(face_bytes ? face_bytes : 16));
   PT_HIP(rig->group_of.alloc(n_faces ? (size_t)n_faces * sizeof(uint32_t) : 16));
-  if ((rc = alloc_table(rig->groups, n_groups)) != PTAMD_OK) return rc;
+  if ((rc = rig->groups.alloc(n_groups)) != PTAMD_OK) return rc;
   if (n_faces) {
     PT_HIP(hipMemcpy(rig->rest.get(), rest_faces, face_bytes, hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(rig->posed.get(), rest_faces, face_bytes, hipMemcpyHostToDevice));   // (ptamd_scene_rig_faces before the first pose)
@@ -142,22 +201,10 @@ int ptamd_scene_rig_create(ptamd_context* ctx, uint32_t scene_id, const ptamd_fa
 
 int ptamd_scene_rig_pose(ptamd_context* ctx, const ptamd_scene_rig_pose_desc* d)
 {
-  const char* who = "ptamd_scene_rig_pose";
   if (!ctx || !d || !d->rig || !d->transforms) { set_error("ptamd_scene_rig_pose: null argument"); return PTAMD_ERR_ARG; }
   ptamd_scene_rig* rig = d->rig;
-  hipStream_t stream = static_cast<hipStream_t>(d->stream);
   if (rig->ctx == ctx && d->n_groups != rig->groups.count) { set_error("ptamd_scene_rig_pose: n_groups differs from the rig's"); return PTAMD_ERR_ARG; }
-  int rc = rig_update_checks(who, ctx, rig, stream);
-  if (rc != PTAMD_OK) return rc;
-  if (rig->n_faces == 0) return PTAMD_OK;
-  DeviceScene& s = ctx->scenes[rig->scene_id];
-  RefitParams r;
-  uint32_t slot = 0;
-  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK || (rc = fill_slot(rig->groups, d->transforms, d->normal_matrices, &slot)) != PTAMD_OK) return rc;
-  // the record table and the posed buffer are overwritten only behind the scene's readers and its previous update
-  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK || (rc = copy_slot(rig->groups, slot, stream)) != PTAMD_OK) return rc;
-  PT_HIP(launch_pose(rig->rest.get(), rig->group_of.get(), rig->groups.records.get(), rig->posed.get(), rig->n_faces, stream));
-  return enqueue_device_refit(s, r, rig->posed.get(), stream);
+  return rig_update("ptamd_scene_rig_pose", ctx, rig, { nullptr, false, kMorphThenPose, d->transforms, d->normal_matrices, false, static_cast<hipStream_t>(d->stream) });
 }
 
 int ptamd_scene_rig_attach_skin(ptamd_context* ctx, ptamd_scene_rig* rig, const uint16_t* bone_indices, const float* bone_weights, uint32_t n_bones)
@@ -172,45 +219,18 @@ int ptamd_scene_rig_attach_skin(ptamd_context* ctx, ptamd_scene_rig* rig, const 
   std::vector<uint32_t> packed((size_t)rig->n_faces * kSkinRecordWords);
   for (uint32_t i = 0; i < rig->n_faces; ++i)
     sk_pack(bone_indices + (size_t)i * 12u, bone_weights + (size_t)i * 12u, packed.data() + (size_t)i * kSkinRecordWords);
-  PT_HIP(hipDeviceSynchronize());   // (a skin kernel in flight may still read the skin this one replaces)
-  rig->bones.count = 0;             // no skin until this one is complete
-  PT_HIP(rig->skin.alloc(packed.empty() ? 16 : packed.size() * sizeof(uint32_t)));
-  if (!packed.empty()) PT_HIP(hipMemcpy(rig->skin.get(), packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if ((rc = alloc_table(rig->bones, n_bones)) != PTAMD_OK) { rig->bones.count = 0; return rc; }
-  PT_HIP(hipDeviceSynchronize());
-  return PTAMD_OK;
+  return attach(rig->bones, n_bones, kPoseRecordFloats, { { rig->skin, packed } });
 }
 
 int ptamd_scene_rig_skin(ptamd_context* ctx, const ptamd_scene_rig_skin_desc* d)
 {
-  const char* who = "ptamd_scene_rig_skin";
   if (!ctx || !d || !d->rig || !d->transforms) { set_error("ptamd_scene_rig_skin: null argument"); return PTAMD_ERR_ARG; }
   ptamd_scene_rig* rig = d->rig;
-  hipStream_t stream = static_cast<hipStream_t>(d->stream);
   if (d->flags & ~PTAMD_SKIN_DEVICE_TRANSFORMS) { set_error("ptamd_scene_rig_skin: unknown flag"); return PTAMD_ERR_ARG; }
   if (rig->ctx == ctx && rig->bones.count == 0) { set_error("ptamd_scene_rig_skin: the rig has no skin attached (ptamd_scene_rig_attach_skin)"); return PTAMD_ERR_ARG; }
   if (rig->ctx == ctx && d->n_bones != rig->bones.count) { set_error("ptamd_scene_rig_skin: n_bones differs from the attached skin's"); return PTAMD_ERR_ARG; }
-  int rc = rig_update_checks(who, ctx, rig, stream);
-  if (rc != PTAMD_OK) return rc;
-  if (rig->n_faces == 0) return PTAMD_OK;
-  const bool on_device = (d->flags & PTAMD_SKIN_DEVICE_TRANSFORMS) != 0u;
-  if (on_device) {
-    if ((rc = device_array_checks(who, "transforms", ctx, d->transforms, (size_t)d->n_bones * 12u * sizeof(float), true)) != PTAMD_OK) return rc;
-    if (d->normal_matrices && (rc = device_array_checks(who, "normal_matrices", ctx, d->normal_matrices, (size_t)d->n_bones * 9u * sizeof(float), false)) != PTAMD_OK) return rc;
-  }
-  DeviceScene& s = ctx->scenes[rig->scene_id];
-  RefitParams r;
-  uint32_t slot = 0;
-  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK) return rc;
-  if (!on_device && (rc = fill_slot(rig->bones, d->transforms, d->normal_matrices, &slot)) != PTAMD_OK) return rc;
-  // the record table and the posed buffer are overwritten only behind the scene's readers and its previous update
-  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
-  if (on_device)
-    PT_HIP(launch_skin_records(d->transforms, d->normal_matrices, rig->bones.records.get(), rig->bones.count, stream));
-  else if ((rc = copy_slot(rig->bones, slot, stream)) != PTAMD_OK)
-    return rc;
-  PT_HIP(launch_skin(rig->rest.get(), rig->skin.get(), rig->bones.records.get(), rig->posed.get(), rig->n_faces, stream));
-  return enqueue_device_refit(s, r, rig->posed.get(), stream);
+  const bool device_transforms = (d->flags & PTAMD_SKIN_DEVICE_TRANSFORMS) != 0u;
+  return rig_update("ptamd_scene_rig_skin", ctx, rig, { nullptr, false, kMorphThenSkin, d->transforms, d->normal_matrices, device_transforms, static_cast<hipStream_t>(d->stream) });
 }
 
 int ptamd_scene_rig_attach_morphs(ptamd_context* ctx, ptamd_scene_rig* rig, const ptamd_morph_target* targets, uint32_t n_targets)
@@ -226,23 +246,13 @@ int ptamd_scene_rig_attach_morphs(ptamd_context* ctx, ptamd_scene_rig* rig, cons
     set_error("ptamd_scene_rig_attach_morphs: out of memory");
     return PTAMD_ERR_LIMIT;
   }
-  PT_HIP(hipDeviceSynchronize());   // (a morph kernel in flight may still read the table this one replaces)
-  rig->weights.count = 0;           // no targets until these are complete
-  PT_HIP(rig->morph_begin.alloc(begin.size() * sizeof(uint32_t)));
-  PT_HIP(rig->morph_entries.alloc(entries.empty() ? 16 : entries.size() * sizeof(uint32_t)));
-  PT_HIP(hipMemcpy(rig->morph_begin.get(), begin.data(), begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (!entries.empty()) PT_HIP(hipMemcpy(rig->morph_entries.get(), entries.data(), entries.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if ((rc = alloc_table(rig->weights, n_targets, 1u)) != PTAMD_OK) { rig->weights.count = 0; return rc; }
-  PT_HIP(hipDeviceSynchronize());
-  return PTAMD_OK;
+  return attach(rig->weights, n_targets, 1u, { { rig->morph_begin, begin }, { rig->morph_entries, entries } });
 }
 
 int ptamd_scene_rig_morph(ptamd_context* ctx, const ptamd_scene_rig_morph_desc* d)
 {
-  const char* who = "ptamd_scene_rig_morph";
   if (!ctx || !d || !d->rig || !d->weights) { set_error("ptamd_scene_rig_morph: null argument"); return PTAMD_ERR_ARG; }
   ptamd_scene_rig* rig = d->rig;
-  hipStream_t stream = static_cast<hipStream_t>(d->stream);
   if (d->then > PTAMD_MORPH_THEN_SKIN) { set_error("ptamd_scene_rig_morph: unknown then"); return PTAMD_ERR_ARG; }
   if (d->flags & ~(PTAMD_MORPH_DEVICE_WEIGHTS | PTAMD_MORPH_DEVICE_TRANSFORMS)) { set_error("ptamd_scene_rig_morph: unknown flag"); return PTAMD_ERR_ARG; }
   const bool pose = d->then == PTAMD_MORPH_THEN_POSE, skin = d->then == PTAMD_MORPH_THEN_SKIN;
@@ -256,31 +266,7 @@ int ptamd_scene_rig_morph(ptamd_context* ctx, const ptamd_scene_rig_morph_desc* 
     if (skin && rig->bones.count == 0) { set_error("ptamd_scene_rig_morph: the rig has no skin attached (ptamd_scene_rig_attach_skin)"); return PTAMD_ERR_ARG; }
     if (table && d->n_transforms != table->count) { set_error("ptamd_scene_rig_morph: n_transforms differs from the rig's"); return PTAMD_ERR_ARG; }
   }
-  int rc = rig_update_checks(who, ctx, rig, stream);
-  if (rc != PTAMD_OK) return rc;
-  if (rig->n_faces == 0) return PTAMD_OK;
-  if (device_weights && (rc = device_array_checks(who, "weights", ctx, d->weights, (size_t)d->n_targets * sizeof(float), true)) != PTAMD_OK) return rc;
-  if (device_transforms) {
-    if ((rc = device_array_checks(who, "transforms", ctx, d->transforms, (size_t)d->n_transforms * 12u * sizeof(float), true)) != PTAMD_OK) return rc;
-    if (d->normal_matrices && (rc = device_array_checks(who, "normal_matrices", ctx, d->normal_matrices, (size_t)d->n_transforms * 9u * sizeof(float), false)) != PTAMD_OK) return rc;
-  }
-  DeviceScene& s = ctx->scenes[rig->scene_id];
-  RefitParams r;
-  uint32_t weight_slot = 0, slot = 0;
-  if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK) return rc;
-  if (!device_weights && (rc = fill_weight_slot(rig->weights, d->weights, &weight_slot)) != PTAMD_OK) return rc;
-  if (table && !device_transforms && (rc = fill_slot(*table, d->transforms, d->normal_matrices, &slot)) != PTAMD_OK) return rc;
-  // the tables and the posed buffer are overwritten only behind the scene's readers and its previous update
-  if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
-  if (!device_weights && (rc = copy_slot(rig->weights, weight_slot, stream)) != PTAMD_OK) return rc;
-  if (device_transforms)
-    PT_HIP(launch_skin_records(d->transforms, d->normal_matrices, rig->bones.records.get(), rig->bones.count, stream));
-  else if (table && (rc = copy_slot(*table, slot, stream)) != PTAMD_OK)
-    return rc;
-  PT_HIP(launch_morph(d->then, rig->rest.get(), rig->morph_begin.get(), rig->morph_entries.get(), device_weights ? d->weights : rig->weights.records.get(),
-                      pose ? rig->group_of.get() : skin ? rig->skin.get() : nullptr, table ? table->records.get() : nullptr, rig->posed.get(),
-                      rig->n_faces, stream));
-  return enqueue_device_refit(s, r, rig->posed.get(), stream);
+  return rig_update("ptamd_scene_rig_morph", ctx, rig, { d->weights, device_weights, d->then, d->transforms, d->normal_matrices, device_transforms, static_cast<hipStream_t>(d->stream) });
 }
 
 int ptamd_scene_rig_faces(const ptamd_scene_rig* rig, const ptamd_face** out_device)

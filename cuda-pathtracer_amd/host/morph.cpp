@@ -1,6 +1,6 @@
 // morph.cpp — ptamd_host_morph_faces: the host definition of ptamd_scene_rig_morph's morphed records, no device needed, and the
 // face-major entry table ptamd_scene_rig_attach_morphs uploads.  The arithmetic is csrc/pt_morph.h's, the functions the kernels
-// call (csrc/pt_morph.hip).
+// call (csrc/pt_rig.hip).
 #include "ptamd_internal.h"
 #include "../csrc/pt_morph.h"
 

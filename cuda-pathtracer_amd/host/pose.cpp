@@ -1,5 +1,5 @@
 // pose.cpp — ptamd_host_pose_faces: the host definition of ptamd_scene_rig_pose's posed records, no device needed.  The arithmetic
-// is csrc/pt_pose.h's, the functions the kernel calls (csrc/pt_pose.hip).
+// is csrc/pt_pose.h's, the functions the kernel calls (csrc/pt_rig.hip).
 #include "ptamd_internal.h"
 #include "../csrc/pt_pose.h"
 

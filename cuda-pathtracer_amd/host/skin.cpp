@@ -1,5 +1,5 @@
 // skin.cpp — ptamd_host_skin_faces: the host definition of ptamd_scene_rig_skin's skinned records, no device needed.  The
-// arithmetic is csrc/pt_skin.h's, the functions the kernel calls (csrc/pt_skin.hip).
+// arithmetic is csrc/pt_skin.h's, the functions the kernel calls (csrc/pt_rig.hip).
 #include "ptamd_internal.h"
 #include "../csrc/pt_skin.h"
 

@@ -632,6 +632,18 @@ def _device_transforms(ctx, transforms, normal_matrices) -> int:
     return n
 
 
+def _rig_transforms(ctx, transforms, normal_matrices, device_route=True):
+    """(address of the transforms, address of the normal matrices or None, their count, on the device?, what to keep alive until
+    the call has returned) of transforms and normal matrices given as numpy arrays or, with `device_route`, as float32 CUDA tensors
+    on the context's device."""
+    if device_route and (_is_tensor(transforms) or _is_tensor(normal_matrices)):
+        n = _device_transforms(ctx, transforms, normal_matrices)
+        return transforms.data_ptr(), normal_matrices.data_ptr() if normal_matrices is not None else None, n, True, None
+    n = np.asarray(transforms).size // 12    # (a count that is not the rig's is the library's to refuse)
+    keep = _pose_arrays(n, transforms, normal_matrices)
+    return keep[0].ctypes.data, keep[1].ctypes.data if keep[1] is not None else None, n, False, keep
+
+
 class SceneRig:
     """A scene posed from per-group transforms on the device (ptamd_scene_rig_*): the rest pose, the posed records and one record
     per group, allocated once.  Close it before its context."""
@@ -652,15 +664,10 @@ class SceneRig:
     def pose(self, transforms, normal_matrices=None, stream=None) -> None:
         """ptamd_scene_rig_pose: the scene's geometry = the rest pose under `transforms` (float32[n_groups, 3, 4]; normal matrices
         float32[n_groups, 3, 3] or None), its tree refitted; asynchronous on `stream`."""
-        n = np.asarray(transforms).size // 12    # (a count that is not the rig's is the library's to refuse)
-        t, m = _pose_arrays(n, transforms, normal_matrices)
+        t, m, n, _, keep = _rig_transforms(self.ctx, transforms, normal_matrices, device_route=False)
         d = N.SceneRigPoseDesc()
-        d.rig = self.handle
-        fp = C.POINTER(C.c_float)
-        d.transforms = t.ctypes.data_as(fp)
-        d.normal_matrices = m.ctypes.data_as(fp) if m is not None else None
-        d.n_groups = n
-        d.stream = _stream_handle(stream)
+        d.rig, d.n_groups, d.stream = self.handle, n, _stream_handle(stream)
+        d.transforms, d.normal_matrices = C.cast(t, C.POINTER(C.c_float)), C.cast(m, C.POINTER(C.c_float))
         N.check(self.ctx._lib.ptamd_scene_rig_pose(self.ctx._h, C.byref(d)))   # (the records are staged before the call returns)
 
     def attach_skin(self, indices, weights, n_bones: int) -> None:
@@ -678,19 +685,8 @@ class SceneRig:
         d = N.SceneRigSkinDesc()
         d.rig = self.handle
         d.stream = _stream_handle(stream)
-        keep = None
-        if _is_tensor(transforms) or _is_tensor(normal_matrices):
-            d.n_bones = _device_transforms(self.ctx, transforms, normal_matrices)
-            d.transforms = transforms.data_ptr()
-            d.normal_matrices = normal_matrices.data_ptr() if normal_matrices is not None else None
-            d.flags = N.SKIN_DEVICE_TRANSFORMS
-        else:
-            n = np.asarray(transforms).size // 12    # (a count that is not the skin's is the library's to refuse)
-            keep = _pose_arrays(n, transforms, normal_matrices)
-            d.n_bones = n
-            d.transforms = keep[0].ctypes.data
-            d.normal_matrices = keep[1].ctypes.data if keep[1] is not None else None
-            d.flags = 0
+        d.transforms, d.normal_matrices, d.n_bones, on_device, keep = _rig_transforms(self.ctx, transforms, normal_matrices)
+        d.flags = N.SKIN_DEVICE_TRANSFORMS if on_device else 0
         N.check(self.ctx._lib.ptamd_scene_rig_skin(self.ctx._h, C.byref(d)))   # (host transforms are staged before the call returns)
 
     def attach_morphs(self, targets) -> None:
@@ -719,20 +715,11 @@ class SceneRig:
         else:
             w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)   # (a count that is not the rig's is the library's to refuse)
             d.weights, d.n_targets = w.ctypes.data, w.size
-        keep = None
-        if _is_tensor(transforms) or _is_tensor(normal_matrices):
-            if then != "skin":
-                raise ValueError("device transforms go with then=\"skin\" only")
-            d.n_transforms = _device_transforms(self.ctx, transforms, normal_matrices)
-            d.transforms = transforms.data_ptr()
-            d.normal_matrices = normal_matrices.data_ptr() if normal_matrices is not None else None
-            d.flags |= N.MORPH_DEVICE_TRANSFORMS
-        elif transforms is not None:
-            n = np.asarray(transforms).size // 12    # (a count that is not the rig's is the library's to refuse)
-            keep = _pose_arrays(n, transforms, normal_matrices)
-            d.n_transforms = n
-            d.transforms = keep[0].ctypes.data
-            d.normal_matrices = keep[1].ctypes.data if keep[1] is not None else None
+        if then != "skin" and (_is_tensor(transforms) or _is_tensor(normal_matrices)):
+            raise ValueError("device transforms go with then=\"skin\" only")
+        if transforms is not None:
+            d.transforms, d.normal_matrices, d.n_transforms, on_device, keep = _rig_transforms(self.ctx, transforms, normal_matrices)
+            d.flags |= N.MORPH_DEVICE_TRANSFORMS if on_device else 0
         N.check(self.ctx._lib.ptamd_scene_rig_morph(self.ctx._h, C.byref(d)))   # (host arrays are staged before the call returns)
 
     def faces(self) -> np.ndarray:

@@ -14,7 +14,7 @@ Default mode (this build), per scene:
 --lib PATH: the library at PATH instead (the parent commit's, which has no rig): only update_host_faces_*, from frames posed with
 numpy.  Run the two modes alternating in one session.
 --trace-only: nothing but warmed poses and as many device-to-device copies of the face bytes, for `rocprofv3 --kernel-trace
---memory-copy-trace --stats -- python scripts/gpu_pose.py --trace-only` in a run of its own (pt_pose_faces beside the refit's
+--memory-copy-trace --stats -- python scripts/gpu_pose.py --trace-only` in a run of its own (pt_rig_faces<false, pose> beside the refit's
 kernels and the copy).
 Writes one JSON object (stdout, and --out when given).
 """

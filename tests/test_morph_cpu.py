@@ -12,12 +12,8 @@ import pytest
 
 from conftest import ROOT
 from helpers import make_scene, random_soup
-from morph_cases import (assert_same_records, make_targets, make_weights, morph_kernel_metadata, rest_scene, restate, tangent, words)
+from rig_cases import assert_same_records, extent_of, make_targets, make_weights, rest_scene, restate_morph, tangent, words
 from test_pose_cpu import scene_2003
-
-
-def extent_of(hs):
-    return float(np.abs(hs.faces["vertices"]).max())
 
 
 def cases(P):
@@ -37,13 +33,13 @@ def test_the_mirror_equals_the_float32_restatement_bit_for_bit(P):
         assert len(targets) == 7 and len(targets[0][0]) == n and len(targets[1][0]) == 0 and 0 < len(targets[6][0]) < n // 20
         w = make_weights(6, 7, off=(3,))
         got = P.host_morph_faces(hs, targets, w)
-        want = restate(hs.faces, targets, w)
+        want = restate_morph(hs.faces, targets, w)
         assert_same_records(got.faces, want, f"{name}")
         assert not np.isnan(want[:, :18]).any()
         assert (got.faces["material_id"] == hs.faces["material_id"]).all() and (got.faces["texcoords"] == hs.faces["texcoords"]).all()
         assert (words(got.faces)[:, :18] != words(hs.faces)[:, :18]).any(axis=1).all(), f"{name}: target 0 moves every face"
         # the same steps with float64 intermediates round differently somewhere: this test can tell a contracted or widened build
-        wide = restate(hs.faces, targets, w, dtype=np.float64)
+        wide = restate_morph(hs.faces, targets, w, dtype=np.float64)
         differ = int((wide.view(np.uint32)[:, :18] != want.view(np.uint32)[:, :18]).sum())
         print(f"{name}: {n} faces, 7 targets, {sum(len(f) for f, _ in targets)} entries, {differ} words differ from the float64 evaluation")
         assert differ > 0, f"{name}: the data cannot tell binary32 steps from wider ones"
@@ -104,7 +100,7 @@ def test_zero_weights_mean_the_rest_pose_and_shield_non_finite_deltas(P):
     assert np.isnan(poisoned[hit][:, :18]).all() and np.isnan(poisoned[hit][:, 24:27]).all()
     np.testing.assert_array_equal(poisoned[~hit].view(np.uint32), words(base)[~hit])
     np.testing.assert_array_equal(poisoned[:, 18:24].view(np.uint32), words(faces)[:, 18:24])
-    assert_same_records(poisoned, restate(faces, targets, w), "a NaN weight")
+    assert_same_records(poisoned, restate_morph(faces, targets, w), "a NaN weight")
 
 
 def test_targets_are_visited_in_ascending_index(P):
@@ -116,8 +112,8 @@ def test_targets_are_visited_in_ascending_index(P):
     big, small = (every, np.full((n, 18), 1e8, np.float32)), (every, np.full((n, 18), 3.0, np.float32))
     w = np.ones(2, np.float32)
     ab, ba = P.host_morph_faces(hs, [big, small], w).faces, P.host_morph_faces(hs, [small, big], w).faces
-    assert_same_records(ab, restate(hs.faces, [big, small], w), "1e8 then 3")
-    assert_same_records(ba, restate(hs.faces, [small, big], w), "3 then 1e8")
+    assert_same_records(ab, restate_morph(hs.faces, [big, small], w), "1e8 then 3")
+    assert_same_records(ba, restate_morph(hs.faces, [small, big], w), "3 then 1e8")
     differ = int((words(ab)[:, :18] != words(ba)[:, :18]).sum())
     print(f"{differ} of {n * 18} words depend on the order")
     assert differ > 0
@@ -242,14 +238,3 @@ def test_desc_layout_matches_the_header(P, tmp_path):
             assert int(got[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
     assert [int(got[m]) for m in ("PTAMD_MORPH_THEN_NOTHING", "PTAMD_MORPH_THEN_POSE", "PTAMD_MORPH_THEN_SKIN")] == [N.MORPH_THEN_NOTHING, N.MORPH_THEN_POSE, N.MORPH_THEN_SKIN]
     assert [int(got[m]) for m in ("PTAMD_MORPH_DEVICE_WEIGHTS", "PTAMD_MORPH_DEVICE_TRANSFORMS")] == [N.MORPH_DEVICE_WEIGHTS, N.MORPH_DEVICE_TRANSFORMS]
-
-
-def test_the_morph_kernels_have_no_scratch_and_no_spills():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc on this host")
-    meta = morph_kernel_metadata()
-    names = sorted(meta)
-    assert len(names) == 3 and all(f"14pt_morph_facesILj{k}EE" in n for k, n in enumerate(names)), names
-    for n, m in sorted(meta.items()):
-        print(n, {k: m[k] for k in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")})
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (n, m)

@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 
 from helpers import make_scene, random_soup
-from morph_cases import assert_same_records, compose, identity, make_skin, make_targets, make_weights, matrices, rest_scene, skin_2003
+from rig_cases import (assert_same_records, assert_tables, compose, extent_of, identity, make_skin, make_targets, make_weights, matrices, rest_scene,
+                       skin_of, tables_of)
 from test_gpu_parity import assert_same
-from test_pose_gpu import assert_tables, extent_of
 from test_refit_device_gpu import same_bits, sync_render
 from test_refit_gpu import B, KINDS, SPP, TABLES, oracle, render
 
@@ -31,18 +31,6 @@ def gpu_ctx(P):
     errors = ctx.device_error_count()
     ctx.close()
     assert errors == 0
-
-
-def skin_of(name, hs, seed=17):
-    """(indices, weights, n_bones): 2003 gets the skin whose waves name many bones, the asset scenes 13 bones"""
-    if name == 2003:
-        return skin_2003(len(hs.faces)) + (97,)
-    return make_skin(seed, len(hs.faces), 13) + (13,)
-
-
-def tables_of(ctx, sid):
-    t = ctx.read_scene_tables(sid)
-    return {k: t[k].copy() for k in TABLES}, ctx.scene_margins(sid).copy()
 
 
 def transforms_of(then, sizes, n_bones, seed, extent, kind="scale"):

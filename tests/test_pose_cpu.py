@@ -11,8 +11,8 @@ import pytest
 
 from conftest import ROOT
 from helpers import make_scene, random_soup
-from pose_cases import (CUT_2003, assert_pose_kernel_has_no_scratch, assert_same_records, identity, matrices, rest_scene, restate,
-                        words)
+from rig_cases import (CUT_2003, assert_rig_kernels_have_no_scratch, assert_same_records, identity, matrices, rest_scene,
+                       restate_pose, words)
 
 
 def scene_2003(P):
@@ -35,13 +35,13 @@ def test_the_mirror_equals_the_float32_restatement_bit_for_bit(P, kind):
         extent = float(np.abs(hs.faces["vertices"]).max())
         t, nm = matrices(len(sizes), 7, extent, kind)
         got = P.host_pose_faces(hs, t, nm, sizes)
-        want = restate(hs.faces, sizes, t, nm)
+        want = restate_pose(hs.faces, sizes, t, nm)
         assert_same_records(got.faces, want, f"{name}/{kind}")
         assert not np.isnan(want[:, :9]).any()
         assert (got.faces["material_id"] == hs.faces["material_id"]).all() and (got.faces["texcoords"] == hs.faces["texcoords"]).all()
         assert (words(got.faces)[:, :18] != words(hs.faces)[:, :18]).any(axis=1).mean() > 0.9, f"{name}/{kind}: most faces should move"
         # the same steps with float64 intermediates round differently somewhere: this test can tell a contracted or widened build
-        wide = restate(hs.faces, sizes, t, nm, dtype=np.float64)
+        wide = restate_pose(hs.faces, sizes, t, nm, dtype=np.float64)
         differ = int((wide.view(np.uint32) != want.view(np.uint32)).sum())
         print(f"{name}/{kind}: {len(hs.faces)} faces, {len(sizes)} groups, {differ} words differ from the float64 evaluation")
         assert differ > 0, f"{name}/{kind}: the data cannot tell binary32 steps from wider ones"
@@ -67,7 +67,7 @@ def test_identity_maps_minus_zero_to_plus_zero_and_everything_else_to_itself(P):
     f["tangent"][7, 1] = -0.0
     hs.faces = f
     got = P.host_pose_faces(hs, identity(len(sizes)), None, sizes).faces
-    assert_same_records(got, restate(f, sizes, identity(len(sizes))), "identity")
+    assert_same_records(got, restate_pose(f, sizes, identity(len(sizes))), "identity")
     g, w = words(got), words(f)
     assert g[5, 5] == 0 and g[6, 9] == 0 and g[6, 12] == 0x80000000
     assert (g[:, :9] != 0x80000000).all()
@@ -85,7 +85,7 @@ def test_denormal_products_are_kept(P):
     t[0, :, :3] = np.eye(3, dtype=np.float32) * np.float32(1e-10)
     t[0, 0, 1] = np.float32(1e-10)
     got = P.host_pose_faces(hs, t)
-    want = restate(hs.faces, [4], t)
+    want = restate_pose(hs.faces, [4], t)
     assert_same_records(got.faces, want, "denormal products")
     v = got.faces["vertices"]
     assert (v != 0).all() and (np.abs(v) < np.finfo(np.float32).tiny).all(), "the products should be denormal and not flushed"
@@ -163,7 +163,7 @@ def test_the_mirror_is_clean_under_the_sanitizers(tmp_path):
     assert int(out.stdout.split()[1]) == 4 * (5 + 390 + 3)
 
 
-def test_the_pose_kernel_has_no_scratch_and_no_spills():
+def test_the_rig_kernels_have_no_scratch_and_no_spills():
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc on this host")
-    assert_pose_kernel_has_no_scratch()
+    assert_rig_kernels_have_no_scratch()

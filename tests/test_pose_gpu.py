@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import make_scene, random_rays, random_soup
-from pose_cases import assert_pose_kernel_has_no_scratch, assert_same_records, identity, matrices, rest_scene, rotation
+from rig_cases import assert_rig_kernels_have_no_scratch, assert_same_records, assert_tables, extent_of, identity, matrices, rest_scene, rotation
 from test_gpu_parity import assert_same
 from test_refit_device_gpu import same_bits, sync_render
 from test_refit_gpu import B, H, KINDS, SPP, TABLES, W, oracle, render
@@ -29,10 +29,6 @@ def gpu_ctx(P):
     assert errors == 0
 
 
-def extent_of(hs):
-    return float(np.abs(hs.faces["vertices"]).max())
-
-
 def with_lights(P, hs, lights):
     return P.HostScene(hs.faces, hs.mesh_sizes, hs.materials, lights, hs.textures, hs.texels, hs.camera, hs.cubemap)
 
@@ -42,18 +38,6 @@ def moved_lights(hs, shift):
     lights["vec"] += np.asarray(shift, np.float32)
     lights["radius"] *= np.float32(1.25)
     return lights
-
-
-def assert_tables(ctx, sid, want, what):
-    """The five tables word for word, and the margins.  A word may differ only where both sides hold a NaN (a NaN tangent of the
-    rest pose stays a NaN under any transform, of a payload each side forms its own way: the contract's NaN clause)."""
-    got = ctx.read_scene_tables(sid)
-    for t in TABLES:
-        assert got[t].size == want[t].size, f"{what}: size of table {t}"
-        g, w = got[t].view(np.uint32), want[t].view(np.uint32)
-        bad = np.flatnonzero((g != w) & ~(np.isnan(g.view(np.float32)) & np.isnan(w.view(np.float32))))
-        assert bad.size == 0, f"{what}: table {t} differs in {bad.size} words, first at {bad[:4].tolist()}"
-    same_bits(ctx.scene_margins(sid), want["scalars"], what + ": margins")
 
 
 # ---------------------------------------------------------------- posed records and tables
@@ -476,4 +460,5 @@ def test_group_count_limits(P, gpu_ctx, n_groups):
 # ---------------------------------------------------------------- compiled code
 
 def test_the_pose_kernel_has_no_scratch_and_no_spills():
-    assert_pose_kernel_has_no_scratch()
+    """... nor any other kernel of csrc/pt_rig.hip, on the machine the kernels run on"""
+    assert_rig_kernels_have_no_scratch()

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from skin_cases import (assert_same_records, identity, make_skin, matrices, one_hot_skin, rest_scene, restate, skin_2003,
-                        skin_kernel_metadata, words)
+from rig_cases import (assert_same_records, extent_of, identity, make_skin, matrices, one_hot_skin, rest_scene,
+                       restate_skin, skin_2003, words)
 from test_pose_cpu import scene_2003
 
 
@@ -22,10 +22,6 @@ def cases(P):
     yield (2003,) + scene_2003(P)
 
 
-def extent_of(hs):
-    return float(np.abs(hs.faces["vertices"]).max())
-
-
 @pytest.mark.parametrize("kind", ["rigid", "scale"])
 def test_the_mirror_equals_the_float32_restatement_bit_for_bit(P, kind):
     for name, hs, _ in cases(P):
@@ -34,13 +30,13 @@ def test_the_mirror_equals_the_float32_restatement_bit_for_bit(P, kind):
         assert not (w.sum(axis=2, dtype=np.float32) == 1.0).all(), "the weights should mostly not sum to exactly 1"
         t, nm = matrices(n_bones, 7, extent_of(hs), kind)
         got = P.host_skin_faces(hs, idx, w, t, nm)
-        want = restate(hs.faces, idx, w, t, nm)
+        want = restate_skin(hs.faces, idx, w, t, nm)
         assert_same_records(got.faces, want, f"{name}/{kind}")
         assert not np.isnan(want[:, :18]).any()
         assert (got.faces["material_id"] == hs.faces["material_id"]).all() and (got.faces["texcoords"] == hs.faces["texcoords"]).all()
         assert (words(got.faces)[:, :18] != words(hs.faces)[:, :18]).any(axis=1).mean() > 0.9, f"{name}/{kind}: most faces should move"
         # the same steps with float64 intermediates round differently somewhere: this test can tell a contracted or widened build
-        wide = restate(hs.faces, idx, w, t, nm, dtype=np.float64)
+        wide = restate_skin(hs.faces, idx, w, t, nm, dtype=np.float64)
         differ = int((wide.view(np.uint32) != want.view(np.uint32)).sum())
         print(f"{name}/{kind}: {len(hs.faces)} faces, {n_bones} bones, {differ} words differ from the float64 evaluation")
         assert differ > 0, f"{name}/{kind}: the data cannot tell binary32 steps from wider ones"
@@ -130,14 +126,3 @@ def test_the_mirror_is_clean_under_the_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and out.stdout.startswith("ok "), (out.stdout, out.stderr)
     assert int(out.stdout.split()[1]) == 4 * (5 + 390 + 0) + 3
-
-
-def test_the_skin_kernels_have_no_scratch_and_no_spills():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc on this host")
-    meta = skin_kernel_metadata()
-    names = sorted(meta)
-    assert len(names) == 2 and "13pt_skin_facesE" in names[0] and "15pt_skin_recordsE" in names[1], names
-    for n, m in meta.items():
-        print(n, {k: m[k] for k in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")})
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (n, m)
