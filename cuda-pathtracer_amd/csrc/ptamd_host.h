@@ -43,7 +43,19 @@ struct DeviceScene {
   uint32_t n_nodes4 = 0, depth4 = 0;
   float extent = 0.0f;       // largest finite |coordinate| of the scene (bvh_builder.cpp)
   bool all_finite = true;    // no NaN or infinite vertex coordinate
-  uint32_t n_skipped = 0;    // nodes whose box test the restart kernel's skip forms leave out; their link table lies behind `nodes` (host/skip_links.cpp)
+  uint32_t n_skipped = 0;    // nodes whose box test the restart kernel's skip forms leave out (host/skip_links.cpp)
+  // the skip forms' link table lies behind `nodes` (links: there is one).  n_culled: the (leaf, octant) pairs it leaves out NOW; they
+  // hold for the triangles they were proven for, so every update of the faces puts links_plain (the table of the skip set alone) back
+  // in front of its kernels (restore_plain_links), and ptamd_scene_update, which has the faces, culls again from the host copies
+  // below (cull_on: the upload culled, so it does)
+  bool links = false, cull_on = false;
+  uint32_t n_culled = 0;
+  DeviceBuffer<uint32_t> links_plain;
+  Bvh topology;                          // nodes as uploaded (topology words and miss links never change) and room for the records of new faces
+  std::vector<uint32_t> record_face;     // per triangle record its face
+  std::vector<uint8_t> skip_set, cull_bits;   // the set; scratch of the re-cull, kept with link_words for the next update
+  std::vector<uint32_t> link_words;
+  PinnedBuffer<uint32_t> h_links[2];     // a recomputed table on its way to the device, in step with h_stage (same slot, same event)
   float reach = 0.0f;        // origin reach: largest |coordinate| of an origin the path forms, light spheres included (bvh_builder.cpp)
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
   ptamd_scene_info info{};
@@ -101,6 +113,7 @@ struct ptamd_context {
   std::vector<ptamd::DeviceScene> scenes;
   std::vector<ptamd::DeviceCubemap> cubemaps;
   uint32_t frame_counter = 0; // raytrace.cu:296 `static unsigned int seed`
+  int32_t last_restart_form = -1;   // PT_RS_* of the context's last megakernel launch (-1: none yet, or another kernel): ptamd_last_restart_form
   ptamd::DeviceBuffer<unsigned long long> d_stats;   // 32 words: 0..12 counters, 14 self-test, 15 error flag, 16..27 phase cycles, 28 the ray queue's head
   ptamd::DeviceBuffer<float> d_gamma;     // 258 floats: the gamma step of the tonemap as a table (pt_kernels.hip: gamma_byte); empty with PTAMD_GAMMA_TABLE=0
   // persistent variant: ring of tile ticket counters (one per in-flight launch) and grid sizing

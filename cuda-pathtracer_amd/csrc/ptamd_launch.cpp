@@ -230,7 +230,7 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   // the flat form of the restart kernel: a flat scene (its compact records exist) under a one-colour environment
   p.round_form = (ctx->knobs.generic_round ? PT_ROUND_GENERIC : 0u) | (ctx->knobs.flat_round && s.flat && ctx->cubemaps[l->cubemap_id].uniform ? PT_ROUND_FLAT : 0u);
   // the skip forms: the scene has a relinked link table behind its nodes (lay_out_lds takes the bit back where their LDS does not fit)
-  if (s.n_skipped && pl.resident) p.round_form |= PT_ROUND_SKIP;
+  if (s.links && pl.resident) p.round_form |= PT_ROUND_SKIP;
 }
 
 // Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
@@ -514,6 +514,8 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
   }
   if (restart && !pl.fma && ctx->d_timeline && p.n_static <= ctx->timeline_waves) p.timeline = ctx->d_timeline.get();
   if (split) p.tiles_per_ticket = 1;
+  // (what ptamd_last_restart_form reports: the instantiation pt_kernels.hip's table resolves this launch to, by the same rule)
+  ctx->last_restart_form = restart ? restart_select(pl.resident, stats, ad != nullptr, pl.fma, &p).variant : -1;
   hipError_t e = launch_form(form_of(pl, stats, ad != nullptr, &p), p, pl.n_blocks, restart ? mega_stream : pl.stream);
   if (e == hipSuccess && pl.pipelined) {
     PT_HIP(hipEventRecord(sc->mega_done[pl.slab].get(), mega_stream));

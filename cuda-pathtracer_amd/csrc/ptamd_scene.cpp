@@ -354,6 +354,17 @@ int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r)
   return PTAMD_OK;
 }
 
+// The link table of the skip set alone over the one with culled links, on the update's stream behind wait_for_readers and in front
+// of the kernels that move the triangles: whatever waits for `updated` (wait_for_update) reads links the new faces cannot belie
+int restore_plain_links(DeviceScene& s, hipStream_t stream)
+{
+  if (!s.n_culled) return PTAMD_OK;
+  PT_HIP(hipMemcpyAsync(reinterpret_cast<float*>(s.nodes.get()) + (size_t)s.n_nodes * 16, s.links_plain.get(), ((size_t)s.n_nodes * 8 + 8) * 4,
+                        hipMemcpyDeviceToDevice, stream));
+  s.n_culled = 0;
+  return PTAMD_OK;
+}
+
 // ... and what it enqueues behind wait_for_readers, for ptamd_scene_update_device (the caller's buffer) and ptamd_scene_rig_pose (the
 // rig's posed records) alike: extent reduction, the four refit kernels, `updated`, the margin copy; margins pending
 int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream)
@@ -361,6 +372,8 @@ int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hip
   // (the copies of earlier updates read d_margin behind their `updated`, possibly on another stream)
   for (int i = 0; i < 2; ++i)
     if (s.margin_ready_valid[i]) PT_HIP(hipStreamWaitEvent(stream, s.margin_ready[i].get(), 0));
+  const int rc = restore_plain_links(s, stream);   // (the host never sees these faces: no leaf stays culled)
+  if (rc != PTAMD_OK) return rc;
   PT_HIP(launch_extent(faces, s.n_faces, s.d_margin.get() + kMarginWords, s.d_margin.get(), stream));
   r.faces = faces;
   r.device_margin = s.d_margin.get() + 2;
@@ -423,14 +436,26 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
   // (8 words per node, then the eight entry nodes) for the restart kernel's skip forms
   std::vector<float> nodes_and_links(bvh.nodes);
   if (bvh.n_nodes * 64u + bvh.n_tris * 48u <= kLdsBudget && bvh.n_nodes <= kCompactMaxNodes && bvh.n_tris <= kCompactMaxTris && skip_links_fit(bvh)) {
-    std::vector<uint8_t> skip;
-    std::vector<uint32_t> words;
-    skip_set_of(bvh, ctx->knobs.skip_mode, ctx->knobs.skip_threshold, nullptr, skip);
-    for (uint8_t k : skip) d.n_skipped += k;
-    if (d.n_skipped) {
-      skip_link_table(bvh, skip, words);
-      nodes_and_links.resize(bvh.nodes.size() + words.size());
-      std::memcpy(nodes_and_links.data() + bvh.nodes.size(), words.data(), words.size() * 4);
+    const uint32_t mode = ctx->knobs.skip_mode;   // (PTAMD_SKIP=0: no table at all)
+    SkipTables t;
+    build_skip_tables(bvh, mode == PTAMD_SKIP_SET ? mode : (mode | PTAMD_SKIP_CULLED), ctx->knobs.skip_threshold, nullptr, t);
+    d.n_skipped = t.n_skipped; d.n_culled = t.n_culled;
+    d.links = t.n_skipped != 0u || t.n_culled != 0u;
+    if (d.links) {
+      nodes_and_links.resize(bvh.nodes.size() + t.words.size());
+      std::memcpy(nodes_and_links.data() + bvh.nodes.size(), t.words.data(), t.words.size() * 4);
+    }
+    if (t.n_culled) {
+      std::vector<uint32_t> plain;
+      skip_link_table(bvh, t.skip, plain);
+      if ((rc = upload(d.links_plain, plain.data(), plain.size() * 4))) return rc;
+      d.cull_on = true;
+      d.topology.nodes = bvh.nodes;
+      d.topology.n_nodes = bvh.n_nodes; d.topology.n_tris = bvh.n_tris;
+      d.topology.tris.resize((size_t)bvh.n_tris * 12);
+      d.skip_set = t.skip;
+      d.record_face.resize(bvh.n_tris);
+      for (uint32_t j = 0; j < bvh.n_tris; ++j) std::memcpy(&d.record_face[j], &bvh.tris[(size_t)j * 12 + 9], 4);
     }
   }
   if ((rc = upload(d.nodes, nodes_and_links.data(), nodes_and_links.size() * 4)) ||
@@ -491,8 +516,10 @@ int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
   const size_t bytes = (size_t)d->n_faces * sizeof(ptamd_face);
   // the first update of the scene: the staging buffers
   if (!s.d_faces) PT_HIP(s.d_faces.alloc(bytes));
+  const size_t link_words = (size_t)s.n_nodes * 8 + 8;
   for (int i = 0; i < 2; ++i) {
     if (!s.h_stage[i]) PT_HIP(s.h_stage[i].alloc(bytes));
+    if (s.cull_on && !s.h_links[i]) PT_HIP(s.h_links[i].alloc(link_words * 4));
     PT_HIP(s.staged[i].ensure());
   }
   PT_HIP(s.updated.ensure());
@@ -506,6 +533,16 @@ int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
   std::memcpy(s.h_stage[slot].get(), d->faces, bytes);
   if ((rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
   PT_HIP(hipMemcpyAsync(s.d_faces.get(), s.h_stage[slot].get(), bytes, hipMemcpyHostToDevice, stream));
+  if (s.cull_on) {
+    // the new faces are here: the leaves they let an octant pass by, over the set and the topology of the upload
+    Bvh& topo = s.topology;
+    for (uint32_t j = 0; j < s.n_bvh_tris; ++j) rf_tri_record(&d->faces[s.record_face[j]].vertices[0].x, s.record_face[j], &topo.tris[(size_t)j * 12]);
+    const uint32_t n_culled = cull_table(topo, s.cull_bits);
+    skip_link_table(topo, s.skip_set, s.link_words, n_culled ? &s.cull_bits : nullptr);
+    std::memcpy(s.h_links[slot].get(), s.link_words.data(), link_words * 4);
+    PT_HIP(hipMemcpyAsync(reinterpret_cast<float*>(s.nodes.get()) + (size_t)s.n_nodes * 16, s.h_links[slot].get(), link_words * 4, hipMemcpyHostToDevice, stream));
+    s.n_culled = n_culled;
+  }
   PT_HIP(hipEventRecord(s.staged[slot].get(), stream));
   s.staged_valid[slot] = true;
   r.faces = s.d_faces.get();
@@ -733,6 +770,20 @@ int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
 {
   if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_skip_count: bad argument"); return PTAMD_ERR_ARG; }
   *out = ctx->scenes[scene_id].n_skipped;
+  return PTAMD_OK;
+}
+
+int ptamd_last_restart_form(ptamd_context* ctx, int32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_last_restart_form: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->last_restart_form;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
+{
+  if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_cull_count: bad argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->scenes[scene_id].n_culled;
   return PTAMD_OK;
 }
 

@@ -411,7 +411,7 @@ extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* 
                                      const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
                                      uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out)
 {
-  if ((n_faces && !faces) || (n && (!rays || !out)) || !n_nodes || mode > PTAMD_SKIP_ALL) { ptamd::set_error("ptamd_host_skip_trace: bad argument"); return PTAMD_ERR_ARG; }
+  if ((n_faces && !faces) || (n && (!rays || !out)) || !n_nodes || (mode & ~PTAMD_SKIP_CULLED) > PTAMD_SKIP_ALL) { ptamd::set_error("ptamd_host_skip_trace: bad argument"); return PTAMD_ERR_ARG; }
   ptamd::Bvh bvh;
   int rc = ptamd::build_bvh(faces, n_faces, 1e-3f, 2, bvh, 0u);   // leaves of at most two, as an upload builds them
   if (rc != PTAMD_OK) return rc;
@@ -419,12 +419,16 @@ extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* 
   const uint32_t room = *n_nodes;
   *n_nodes = bvh.n_nodes;
   if ((skip_out || words_out) && room < bvh.n_nodes) { ptamd::set_error("ptamd_host_skip_trace: room for fewer nodes than the tree has"); return PTAMD_ERR_ARG; }
-  std::vector<uint8_t> skip;
-  std::vector<uint32_t> words;
-  ptamd::skip_set_of(bvh, mode, threshold, skip_in, skip);
-  ptamd::skip_link_table(bvh, skip, words);
-  // the set and the links do not depend on the boxes: a refit keeps both
+  ptamd::SkipTables t;
+  ptamd::build_skip_tables(bvh, mode, threshold, skip_in, t);
+  // the set and the skipped links do not depend on the boxes: a refit keeps both; the culled links are the new triangles' own
   if (faces_refit && (rc = ptamd::refit_bvh(bvh, faces_refit, n_faces, nullptr, 0)) != PTAMD_OK) return rc;
+  if (faces_refit && (mode & PTAMD_SKIP_CULLED)) {
+    const std::vector<uint8_t> kept(t.skip);
+    ptamd::build_skip_tables(bvh, PTAMD_SKIP_SET | PTAMD_SKIP_CULLED, 0.0f, kept.data(), t);
+  }
+  const std::vector<uint8_t>& skip = t.skip;
+  const std::vector<uint32_t>& words = t.words;
   for (uint32_t i = 0; i < n; ++i) {
     ptamd::HostHit h;
     uint64_t visits = 0;
@@ -438,5 +442,15 @@ extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* 
   if (counters) { counters[2] = 0; for (uint8_t s : skip) counters[2] += s; }
   if (skip_out && bvh.n_nodes) std::memcpy(skip_out, skip.data(), bvh.n_nodes);
   if (words_out) std::memcpy(words_out, words.data(), words.size() * 4);
+  return PTAMD_OK;
+}
+
+extern "C" int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out)
+{
+  if (n && (!edges || !out)) { ptamd::set_error("ptamd_host_faces_away: null argument"); return PTAMD_ERR_ARG; }
+  for (uint32_t i = 0; i < n; ++i) {
+    out[i] = 0;
+    for (uint32_t o = 0; o < 8; ++o) out[i] |= (uint8_t)((ptamd::record_faces_away(edges + (size_t)i * 6, edges + (size_t)i * 6 + 3, o) ? 1u : 0u) << o);
+  }
   return PTAMD_OK;
 }

@@ -182,19 +182,47 @@ void bvh4q_trace_host(const Bvh& bvh, const float dir[3], const float origin[3],
 //                      the end of its down-chain for o (the first node down the near children that is not skipped).
 //   words[n_nodes * 8 + o] = the node a walk of octant o starts at: the end of the root's down-chain; 0xFFFF for an empty tree.
 // Only for trees within the compact layout's code space (<= 896 nodes, <= 2047 records, leaves of <= 15).
-constexpr float kSkipThreshold = 0.6f;     // a node is skipped when more than this share of the training rays that test it pass
-// training rays: two per node of the tree, which keeps the selection cheaper than the tree's build
-constexpr uint32_t kSkipRaysPerNode = 2u, kSkipMinVisits = 16u;
+constexpr float kSkipThreshold = 0.6f;     // the pass-rate rule: a node is skipped when more than this share of the training rays that test it pass
+// training rays: two per node of the tree, which keeps the selection cheaper than the tree's build; PTAMD_SKIP_RAYS
+// (behind PTAMD_TUNING=1, read by the call that selects) draws more
+constexpr uint32_t kSkipRaysPerNode = 2u, kSkipMaxRaysPerNode = 256u, kSkipMinVisits = 16u;
 bool skip_links_fit(const Bvh& bvh);
-void skip_link_table(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words);
+
+// ---- back-facing leaves ("Culled leaves") ----
+// True only when a sign argument PROVES that Moller-Trumbore's determinant of the record {e1, e2}, in the operation order of
+// pt_kernels.hip: mt_test_asm (p = cross(d, e2) as three differences of two products, det = e1.z p.z + (e1.x p.x + e1.y p.y)), is
+// <= 0 for every direction d of ray octant `octant` (bit a set <=> d[a] < 0; a clear bit: +0, -0, denormals and up) whose components
+// are finite and below 2^86 in magnitude, so that the test's `det < 1e-7` rejects the record whatever the ray.  (Beyond 2^86 a product
+// can overflow and det is <= 0 or NaN; a NaN det is carried to `t > 0`, which rejects it: no hit either way.)  The argument: each
+// product d[a] * e2[b] is >= 0, <= 0 or zero by the signs of its factors alone; each difference must be of a term <= 0 and a term
+// >= 0 (or the other way round), which fixes its sign through the rounding, unless e1[i] is a zero (the term is one whatever the
+// finite difference); each e1[i] * p[i] must be <= 0; a sum of such terms is <= 0.  False for edges that are not finite or reach 2^40, and wherever one sign stays open.
+bool record_faces_away(const float e1[3], const float e2[3], uint32_t octant);
+// cull[n]: bit o set <=> no ray of octant o can hit anything below node n: every record of a leaf faces away, both children of an
+// interior node are culled (bottom-up).  An octant in which the root itself is culled keeps its whole chain (no bit set): every
+// walk starts at a node and every interior node's hit code names one.  Returns how many (leaf, octant) pairs are culled.
+uint32_t cull_table(const Bvh& bvh, std::vector<uint8_t>& cull);
+// The link table of a skip set (above).  cull (or null): a target that is culled for o is replaced by its own miss target for o
+// before the skip rule applies, the eight entry words too; a leaf of which only some records face away names the contiguous rest
+// of its range in its hit code for o where the rest is a prefix or a suffix.  (The words of a node that is itself culled for o are
+// never read; they follow the skip rule alone.)
+void skip_link_table(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words, const std::vector<uint8_t>* cull = nullptr);
 // The set a mode asks for (ptamd.h: PTAMD_SKIP_*): `given` (one byte per node, null: none; leaves never count), the default
-// selection at `threshold` (0: kSkipThreshold), the root alone, every interior node
-void skip_set_of(const Bvh& bvh, uint32_t mode, float threshold, const uint8_t* given, std::vector<uint8_t>& skip);
+// selection at `threshold` (0: kSkipThreshold), the root alone, every interior node.  rays_per_node 0: kSkipRaysPerNode, or PTAMD_SKIP_RAYS
+void skip_set_of(const Bvh& bvh, uint32_t mode, float threshold, const uint8_t* given, std::vector<uint8_t>& skip, uint32_t rays_per_node = 0u);
 // The default set: training rays leave the scene's own surfaces (area-weighted origins pushed 0.03 along a cosine-weighted
 // direction about the front normal, from a fixed-seed generator that uses +, *, / and sqrt only: the same set on every host);
 // nodes visited at least kSkipMinVisits times whose pass rate exceeds `threshold` join the set, the rays are walked again with
 // those skipped, until nothing is added.
-void select_skip_nodes(const Bvh& bvh, float threshold, std::vector<uint8_t>& skip);
+void select_skip_nodes(const Bvh& bvh, float threshold, std::vector<uint8_t>& skip, uint32_t rays_per_node = kSkipRaysPerNode);
+// What an upload (and ptamd_host_skip_trace) builds for `mode` (a PTAMD_SKIP_* mode, | PTAMD_SKIP_CULLED): the set, the cull bits
+// (empty without the flag, with PTAMD_SKIP_CULL=0 behind PTAMD_TUNING=1, or when nothing is culled) and the link table of both
+struct SkipTables {
+  std::vector<uint8_t> skip, cull;
+  std::vector<uint32_t> words;
+  uint32_t n_skipped = 0, n_culled = 0;   // nodes of the set; (leaf, octant) pairs culled
+};
+void build_skip_tables(const Bvh& bvh, uint32_t mode, float threshold, const uint8_t* given, SkipTables& out);
 // Mirror of the relinked walk over `words`; node_visits / node_passes (or null): per node, box tests and those that passed
 void skip_trace_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], HostHit& out,
                      uint64_t* nodes_visited, uint64_t* tris_tested, uint32_t* node_visits = nullptr, uint32_t* node_passes = nullptr);

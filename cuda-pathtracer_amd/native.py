@@ -304,6 +304,9 @@ SIGNATURES = {
     "ptamd_host_skip_trace": (C.c_int, [C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
                                         C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
+    "ptamd_scene_cull_count": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ptamd_last_restart_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "ptamd_host_faces_away": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

@@ -185,6 +185,19 @@ class Context:
         N.check(self._lib.ptamd_scene_skip_count(self._h, scene_id, C.byref(out)))
         return out.value
 
+    def scene_cull_count(self, scene_id: int) -> int:
+        """ptamd_scene_cull_count: (leaf, ray octant) pairs the scene's link table leaves out now."""
+        out = C.c_uint32(0)
+        N.check(self._lib.ptamd_scene_cull_count(self._h, scene_id, C.byref(out)))
+        return out.value
+
+    def last_restart_form(self) -> int:
+        """ptamd_last_restart_form: the restart kernel's instantiation the last megakernel launch took (FORM_FLAT_SKIP,
+        FORM_PLAIN_SKIP: over a link table; -1: no launch yet or another kernel)."""
+        out = C.c_int32(-1)
+        N.check(self._lib.ptamd_last_restart_form(self._h, C.byref(out)))
+        return out.value
+
     def scene_is_flat(self, scene_id: int, cubemap_id: int) -> bool:
         """ptamd_scene_is_flat: launches of the scene under the cubemap take the restart kernel's flat form."""
         out = C.c_int32()
@@ -514,14 +527,26 @@ def host_bvh_trace(scene: HostScene, rays: np.ndarray):
 
 
 SKIP_MODES = {"set": 0, "default": 1, "root": 2, "all": 3}
+SKIP_CULLED = 0x100
+FORM_FLAT_SKIP, FORM_PLAIN_SKIP = 9, 10
 
 
-def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=None, threshold: float = 0.0, refit_to=None) -> dict:
+def host_faces_away(edges: np.ndarray) -> np.ndarray:
+    """ptamd_host_faces_away: per record {e1.xyz, e2.xyz} the ray octants (bit o) for which its determinant is proven <= 0."""
+    edges = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros(len(edges), dtype=np.uint8)
+    N.check(N.load().ptamd_host_faces_away(edges.ctypes.data, len(edges), out.ctypes.data))
+    return out
+
+
+def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=None, threshold: float = 0.0, refit_to=None, cull=False) -> dict:
     """Host mirror of the relinked walk of the restart kernel's skip forms (ptamd_host_skip_trace, no GPU).  mode: "default"
     (the selection an upload makes, at `threshold` when given), "root", "all", or "set" with `skip` (one byte per node; None: no
-    node).  refit_to (HostScene or face array): the tree is refitted to those faces, set and links kept, before the rays are
-    walked.  Returns records int32[n,4] ({kind, index, t bits, box tests of the ray}), nodes, tris (visits and triangle tests), skip uint8[n_nodes] and words
-    uint32[n_nodes + 1, 8] (per node and octant hit | miss << 16 in node-index form; the last row holds the entry nodes)."""
+    node).  cull: leaves a ray octant can only meet from behind are taken out of that octant's links ("default" with cull is what
+    an upload builds).  refit_to (HostScene or face array): the tree is refitted to those faces, set and skipped links kept,
+    leaves culled again, before the rays are walked.  Returns records int32[n,4] ({kind, index, t bits, box tests of the ray}),
+    nodes, tris (visits and triangle tests), skip uint8[n_nodes] and words uint32[n_nodes + 1, 8] (per node and octant
+    hit | miss << 16 in node-index form; the last row holds the entry nodes)."""
     rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
     lib = N.load()
     faces = scene.faces.ctypes.data_as(C.POINTER(N.Face))
@@ -540,7 +565,7 @@ def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=Non
     skip_out = np.zeros(n_nodes.value, dtype=np.uint8)
     words = np.zeros((n_nodes.value + 1, 8), dtype=np.uint32)
     counters = (C.c_uint64 * 3)(0, 0, 0)
-    N.check(lib.ptamd_host_skip_trace(faces, fb_ptr, len(scene.faces), SKIP_MODES[mode], threshold,
+    N.check(lib.ptamd_host_skip_trace(faces, fb_ptr, len(scene.faces), SKIP_MODES[mode] | (SKIP_CULLED if cull else 0), threshold,
                                       given.ctypes.data if given is not None else None,
                                       rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), out.ctypes.data_as(C.POINTER(C.c_int32)),
                                       counters, C.byref(n_nodes), skip_out.ctypes.data, words.ctypes.data))

@@ -963,28 +963,53 @@ int ptamd_stream_synchronize(ptamd_context* ctx, void* stream);
  * the same record.  It pays at nodes nearly every ray passes.  An upload of a scene that takes the compact LDS layout chooses such a
  * SKIP SET from training rays that leave the scene's own surfaces (the same set on every host) and writes the relinked link table
  * behind the node table; launches the restart kernel's plain and flat forms would serve then take their skip forms.  A scene
- * update keeps the set.  With PTAMD_TUNING=1: PTAMD_SKIP=0 none (the old forms are launched), PTAMD_SKIP=root the root alone,
- * PTAMD_SKIP=all every interior node, PTAMD_SKIP_THRESHOLD=<pass rate> for the selection.
+ * update keeps the set.
  *
- * ptamd_scene_skip_count: how many nodes of an uploaded scene are skipped (0: its launches take the old forms).
+ * CULLED LEAVES.  The links are per ray octant, and for an octant a triangle's Moller-Trumbore determinant can be <= 0 whatever the
+ * direction (an axis-aligned rectangle seen from behind): its test rejects every such ray.  A leaf of such records alone, and a
+ * subtree of such leaves, is taken out of that octant's links at upload; a leaf with some such records at an end of its range
+ * names the rest.  This depends on the triangles: EVERY update of the scene's faces (ptamd_scene_update, ptamd_scene_update_device,
+ * the rig's pose / skin / morph) puts the table without culled links back, on the update's stream and before its kernels, so that
+ * launches ordered behind the update never read a link the new faces do not justify; ptamd_scene_update, which has the new faces on
+ * the host, then culls again for them.
+ *
+ * With PTAMD_TUNING=1: PTAMD_SKIP=0 no table (the old forms are launched), PTAMD_SKIP=root the root alone, PTAMD_SKIP=all every
+ * interior node, PTAMD_SKIP_THRESHOLD=<pass rate> for the selection, PTAMD_SKIP_RAYS=<training rays per node> (2),
+ * PTAMD_SKIP_CULL=0 no culled leaves.
+ *
+ * ptamd_scene_skip_count: how many nodes of an uploaded scene are skipped.  ptamd_scene_cull_count: how many (leaf, octant) pairs
+ * its link table leaves out now (0 after an update from device faces).  Both 0: no table, its launches take the old forms.
+ * ptamd_last_restart_form: the instantiation of the restart kernel the context's last megakernel launch took (PTAMD_FORM_FLAT_SKIP
+ * and PTAMD_FORM_PLAIN_SKIP are the two over a link table; another number another form; -1 no launch yet or another kernel).
  *
  * ptamd_host_skip_trace: host mirror of the relinked walk, no device needed.  The tree of `faces` as an upload builds it, the skip
  * set `mode` asks for (PTAMD_SKIP_SET: skip_in, one byte per node, NULL = none, leaves never count; PTAMD_SKIP_DEFAULT: the
  * selection at `threshold`, 0 = the default), then, where faces_refit is not NULL, the tree refitted to those faces with set and
- * links kept, then every ray through the walk.  rays as ptamd_host_bvh_trace; out: n * {kind, index, t bits, box tests of this
- * ray}; counters (optional, 3 words): [0] += node
- * visits, [1] += triangle tests, [2] = skipped nodes.  *n_nodes: in, the room of skip_out and words_out in nodes; out, the tree's
- * node count.  skip_out (optional): the set, one byte per node.  words_out (optional): (n_nodes + 1) * 8 words, per node and ray
- * octant `hit code | miss code << 16` in node-index form (a node index, 0xFFFF the end of the walk, 0x8000 | count << 11 | first
- * record a leaf's hit code), then the eight entry nodes, one per octant.  PTAMD_ERR_LIMIT for trees outside the compact layout. */
+ * links kept, then every ray through the walk.  mode | PTAMD_SKIP_CULLED: leaves culled per octant as well, and culled again for
+ * faces_refit (PTAMD_SKIP_DEFAULT | PTAMD_SKIP_CULLED is what an upload builds).  rays as ptamd_host_bvh_trace; out: n * {kind,
+ * index, t bits, box tests of this ray}; counters (optional, 3 words): [0] += node visits, [1] += triangle tests, [2] = skipped
+ * nodes.  *n_nodes: in, the room of skip_out and words_out in nodes; out, the tree's node count.  skip_out (optional): the set, one
+ * byte per node.  words_out (optional): (n_nodes + 1) * 8 words, per node and ray octant `hit code | miss code << 16` in
+ * node-index form (a node index, 0xFFFF the end of the walk, 0x8000 | count << 11 | first record a leaf's hit code), then the
+ * eight entry nodes, one per octant.  PTAMD_ERR_LIMIT for trees outside the compact layout.
+ *
+ * ptamd_host_faces_away: the sign proof behind the culled leaves, no device needed.  edges: n * {e1.xyz, e2.xyz} (e1 = v1 - v0,
+ * e2 = v2 - v0); out[i]: bit o set <=> the determinant of record i, in the kernels' operation order, is proven <= 0 for every
+ * direction of ray octant o (bit a of o set <=> direction[a] < 0) with finite components below 2^86 in magnitude. */
 #define PTAMD_SKIP_SET 0u
 #define PTAMD_SKIP_DEFAULT 1u
 #define PTAMD_SKIP_ROOT 2u
 #define PTAMD_SKIP_ALL 3u
+#define PTAMD_SKIP_CULLED 0x100u
+#define PTAMD_FORM_FLAT_SKIP 9
+#define PTAMD_FORM_PLAIN_SKIP 10
 int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
+int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
+int ptamd_last_restart_form(ptamd_context* ctx, int32_t* out);
 int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
                           const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
                           uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out);
+int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out);
 
 #ifdef __cplusplus
 }

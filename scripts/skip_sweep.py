@@ -3,7 +3,8 @@
 For every shipped scene that takes the compact LDS layout: the selection an upload makes at each threshold, evaluated on held-out
 rays the selection never saw — the rays of diffuse paths from the scene's camera (pinhole primaries over a pixel grid, cosine-weighted
 bounces about the front normal of the face hit, origin pushed 0.03 along the new direction, up to 4 bounces).  Prints nodes
-skipped, mean / 80th / 95th percentile of box tests per walk, and the selection's time against the tree build's.
+skipped, mean / 80th / 95th percentile of box tests per walk, and the selection's time against the tree build's; then the same
+with the leaves a ray octant can only meet from behind culled: the default set with them (what an upload builds), and they alone.
 
     python scripts/skip_sweep.py [--paths 2500] [--thresholds 0.5 0.55 0.6 0.65 0.7]
 """
@@ -77,11 +78,11 @@ def main():
             print(f"{name}: outside the compact layout")
             continue
         rays = path_rays(hs, args.paths)
-        def best_of(mode, reps=9):   # seconds of one call without rays (it builds the tree twice: once for its size)
+        def best_of(mode, reps=9, cull=False):   # seconds of one call without rays (it builds the tree twice: once for its size)
             ts = []
             for _ in range(reps):
                 t0 = time.perf_counter()
-                P.host_skip_trace(hs, rays[:0], mode=mode)
+                P.host_skip_trace(hs, rays[:0], mode=mode, cull=cull)
                 ts.append(time.perf_counter() - t0)
             return min(ts)
         t_build = best_of("set")
@@ -92,6 +93,13 @@ def main():
             per = r["records"][:, 3]
             print(f"  threshold {th if th is not None else 'none':>5}: skipped {int(r['skip'].sum()):3d}  mean {r['nodes'] / len(rays):6.2f}"
                   f"  p80 {np.percentile(per, 80):5.1f}  p95 {np.percentile(per, 95):5.1f}  tris {r['tris'] / len(rays):.2f}")
+        full = P.host_skip_trace(hs, rays, mode="set")["records"][:, :3]
+        for label, mode, cull in (("default set + culled leaves", "default", True), ("culled leaves alone", "set", True)):
+            r = P.host_skip_trace(hs, rays, mode=mode, cull=cull)
+            per = r["records"][:, 3]
+            assert (r["records"][:, :3] == full).all()
+            print(f"  {label:>27}: skipped {int(r['skip'].sum()):3d}  mean {r['nodes'] / len(rays):6.2f}  p80 {np.percentile(per, 80):5.1f}"
+                  f"  p95 {np.percentile(per, 95):5.1f}  tris {r['tris'] / len(rays):.2f}  table {(best_of(mode, 5, cull) - t_build) * 1e3:.2f} ms")
 
 
 if __name__ == "__main__":
