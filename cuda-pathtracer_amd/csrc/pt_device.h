@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_round.h"
+
 namespace ptamd {
 
 struct f3 { float x, y, z; };
@@ -480,11 +482,15 @@ struct KParams {
   // serves.  PT_ROUND_GENERIC: to the generic one (PTAMD_RS_GENERIC); PT_ROUND_FLAT: to the flat one (a flat scene under a one-colour
   // environment, ptamd_scene.cpp: scene_is_flat); PT_ROUND_SKIP: to the skip form of the plain or the flat one (the scene has a
   // relinked link table behind its nodes, host/skip_links.cpp, and the launch's LDS holds the entry nodes in front of the scene)
+  // PT_ROUND_DEFER (only ever next to PT_ROUND_SKIP): to the deferring copy of that skip form, whose rounds leave their sparse
+  // later leaf phases to the next round's first one (pt_round.h; PTAMD_LEAF_DEFER=0 clears it)
   uint32_t round_form;
+  uint32_t round_defer;  // the deferring forms read this in place of round_min: round_min (<= 64) | knob << 8, the knob of pt_round.h: round_leaf_defer as a lane count (<= 64) or 0xFF for PT_LEAF_DEFER_AUTO
 };
 #define PT_ROUND_GENERIC 1u
 #define PT_ROUND_FLAT 2u
 #define PT_ROUND_SKIP 4u
+#define PT_ROUND_DEFER 8u
 // LDS bytes in front of the scene's copy in the skip forms: the node a walk starts at, one word per ray octant
 #define PT_SKIP_ENTRY_BYTES 32u
 
@@ -500,7 +506,16 @@ struct KParams {
 #define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
 #define PT_RS_FLAT_SKIP 9   /* PT_RS_FLAT over the relinked links: the box tests of the scene's skip set are left out (KParams::round_form) */
 #define PT_RS_PLAIN_SKIP 10 /* ... and PT_RS_PLAIN */
-#define PT_RS_FORMS 11
+#define PT_RS_FLAT_SKIP_DEFER 11  /* PT_RS_FLAT_SKIP with deferred leaf phases (pt_round.h; KParams::round_form) */
+#define PT_RS_PLAIN_SKIP_DEFER 12 /* ... and PT_RS_PLAIN_SKIP */
+#define PT_RS_STATS_DEFER 13      /* PT_RS_STATS with them: the counters of a launch the deferring forms would have served */
+#define PT_RS_FORMS 14
+// what ptamd_last_restart_form answers for a form: the deferring copies report the form they are a copy of
+inline int restart_reported_form(int variant)
+{
+  return variant == PT_RS_FLAT_SKIP_DEFER ? PT_RS_FLAT_SKIP : variant == PT_RS_PLAIN_SKIP_DEFER ? PT_RS_PLAIN_SKIP : variant == PT_RS_STATS_DEFER ? PT_RS_STATS : variant;
+}
+inline bool restart_form_defers(int variant) { return variant == PT_RS_FLAT_SKIP_DEFER || variant == PT_RS_PLAIN_SKIP_DEFER || variant == PT_RS_STATS_DEFER; }
 
 // Which instantiation of the restart kernel serves a launch: the first rule that applies.  Host code.  p: the launch, or nullptr for
 // the occupancy query, which asks for the family's plain form.  contracted: the choice of pt_kernels_fma.hip, which compiles PLAIN,
@@ -510,7 +525,10 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
 {
   const auto full = [contracted](int variant) { return contracted ? PT_RS_PLAIN : variant; };
   if (list && !contracted) return { PT_RS_LIST, lds_resident };                // adaptive sampling's active list: instantiations of its own
-  if (stats) return { full(PT_RS_STATS), lds_resident };                      // counters are wanted: the instrumented build
+  // the launches the deferring forms serve (same test as the skip rule's below, whose bit PT_ROUND_DEFER comes with)
+  const bool defers = p && lds_resident && !contracted && (p->round_form & PT_ROUND_DEFER) && (p->round_form & PT_ROUND_SKIP) && !p->brute_walk && !p->timeline &&
+                      p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC);
+  if (stats) return { defers ? PT_RS_STATS_DEFER : full(PT_RS_STATS), lds_resident };   // counters are wanted: the instrumented build
   if (p && p->brute_walk) return { PT_RS_BRUTE, lds_resident };                // a far origin: every triangle record instead of the tree
   if (p && p->timeline) return { full(PT_RS_STAMPS), lds_resident };           // ptamd_set_timeline: four time stamps per wave
   if (!lds_resident && p && p->wide8) return { full(p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8), false };   // the knobs' quantised node forms
@@ -518,6 +536,7 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
   // the shipped instantiation of a resident scene is compiled for four launch constants (pt_megakernel_restart: LEAN): a static
   // camera, pools in LDS, no XCD regions, no interleaved bands; any other launch, or PTAMD_RS_GENERIC, reads them at run time
   if (p && !(p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC))) return { PT_RS_GENERIC, true };
+  if (defers) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP_DEFER : PT_RS_PLAIN_SKIP_DEFER, true };   // ... with deferred leaf phases
   if (p && (p->round_form & PT_ROUND_SKIP) && !contracted) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP : PT_RS_PLAIN_SKIP, true };   // the same two launches of a scene with a skip set
   if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment
   return { PT_RS_PLAIN, true };

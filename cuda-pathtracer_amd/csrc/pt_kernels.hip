@@ -1305,12 +1305,93 @@ PT_DEV void pool_load(const float4* slab, uint32_t e, Path& st)
   st.rng.v2 = f_as_u(c.x); st.rng.v3 = f_as_u(c.y); st.rng.v4 = f_as_u(c.z); st.rng.d = f_as_u(c.w);
 }
 
+// traverse_round (below) with deferred leaf phases: the same two loops, the round control taken from pt_round.h, and two more
+// steps: a pending lane is parked before the first box phase, and a round that ends after a box phase packs its parked lanes.
+template <bool STATS, bool NODES_IN_LDS>
+PT_DEV void traverse_round_deferring(const float4* nodes, const float4* tris, uint32_t n_nodes, f3 o, f3 d, Best& best, uint32_t& node,
+                                     uint32_t round_defer, uint32_t round_div, uint32_t round_div_m16, uint32_t walk_min, bool small_det, Counters& cnt)
+{
+  // KParams::round_defer: round_min and the knob in one kernel argument, taken apart here, round by round, so that the launch
+  // constant costs the persistent loop the one scalar register round_min costs the skip forms (the plain form has none to spare:
+  // tests/test_leaf_defer_cpu.py); the empty asm keeps the two halves from being hoisted out of that loop as two
+  asm volatile("" : "+s"(round_defer));
+  const uint32_t round_min = round_defer & 0xFFu;
+  const uint32_t leaf_defer_knob = (round_defer >> 8) == 0xFFu ? PT_LEAF_DEFER_AUTO : round_defer >> 8;
+  Walk w;
+  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS && PT_ASM_WALK);
+  w.best = best;
+  const uint32_t n_start = (uint32_t)__popcll(__ballot(node != PT_END));   // (a pending lane enters like any other)
+  const uint32_t t_eff = round_threshold(n_start, round_min, round_div, round_div_m16);
+  const uint32_t leaf_defer = round_leaf_defer(leaf_defer_knob, t_eff);
+  // The round's three scalars in one register, for the same budget: the threshold (<= 64) in bits 0..7, leaf_defer (<= 64) in
+  // bits 8..15, bit 16 set in the round's first iteration.  The empty asm keeps the compiler from taking the word apart again.
+  uint32_t ctl = t_eff | ((leaf_defer < 255u ? leaf_defer : 255u) << 8) | 0x10000u;
+  asm volatile("" : "+s"(ctl));
+  if (STATS) w.alive = (uint32_t)__popcll(__ballot(1));
+  const uint32_t lds_nodes = (uint32_t)(uintptr_t)nodes;
+  // (`node` itself stays live through the first box phase and is decoded where it is needed: one register, none across shading)
+  if (NODES_IN_LDS && !STATS && PT_ASM_WALK) {
+    // codes as the links hold them: a continuation is a box's LDS address or 0xFFFF
+    uint32_t state = round_is_pending(node) ? round_pending_leaf(node) : walk_lds_state(lds_nodes, node);
+    const uint32_t lnk = walk_lds_link_offset(w);
+    uint32_t leaf_first, leaf_count;
+    for (;;) {
+      const bool first = (ctl >> 16) != 0u;
+      walk_to_leaf_lds_state(state, lnk, w, leaf_first, leaf_count, walk_min);
+      // a pending lane ran no box test: the loop left its state, the leaf code, alone, and the continuation the wrapper took from
+      // the link word "read last" is not one; the carried one is
+      if (first && round_is_pending(node)) state = round_pending_continuation(node);
+      const uint32_t unfinished = (uint32_t)__popcll(__ballot(state != 0xFFFFu || leaf_count != 0u));
+      if (!round_leaf_phase_runs(first, unfinished, (ctl >> 8) & 0xFFu)) break;   // (the parked lanes keep their leaf_count)
+      if (leaf_count != 0u) walk_leaf<STATS, true>(tris, w, leaf_first, leaf_count, cnt.tris, cnt.wave_tri_iters, small_det);
+      leaf_count = 0u;
+      if (round_ends((uint32_t)__popcll(__ballot(state != 0xFFFFu)), ctl & 0xFFu)) break;
+      ctl &= 0xFFFFu;
+    }
+    // a lane still parked was deferred: its leaf and its continuation go out as a pending word
+    w.node = leaf_count != 0u ? round_pending_pack(0x8000u | (leaf_count << 11) | leaf_first, state) : walk_lds_node(lds_nodes, state);
+  } else {
+    // codes in node-index form: a continuation is a node index (below 0x8000: the scene has a link table, so it is within the
+    // compact layout's code space) or 0xFFFF for PT_END
+    w.node = round_is_pending(node) ? PT_END : node;   // (a pending lane sits out the first box phase)
+    for (;;) {
+      const bool first = (ctl >> 16) != 0u;
+      uint32_t leaf_first, leaf_count;
+      walk_to_leaf<STATS>(nodes, w, leaf_first, leaf_count, cnt.nodes, cnt.wave_node_iters, walk_min);
+      if (first && round_is_pending(node)) {
+        leaf_first = round_pending_leaf(node) & 0x7FFu;
+        leaf_count = (round_pending_leaf(node) >> 11) & 0xFu;
+        w.node = round_pending_continuation(node) == 0xFFFFu ? PT_END : round_pending_continuation(node);
+      }
+      const uint32_t unfinished = (uint32_t)__popcll(__ballot(w.node != PT_END || leaf_count != 0u));
+      if (!round_leaf_phase_runs(first, unfinished, (ctl >> 8) & 0xFFu)) {
+        if (leaf_count != 0u) w.node = round_pending_pack(0x8000u | (leaf_count << 11) | leaf_first, w.node == PT_END ? 0xFFFFu : w.node);
+        break;
+      }
+      if (leaf_count != 0u) walk_leaf<STATS>(tris, w, leaf_first, leaf_count, cnt.tris, cnt.wave_tri_iters, small_det);
+      if (round_ends((uint32_t)__popcll(__ballot(w.node != PT_END)), ctl & 0xFFu)) break;
+      ctl &= 0xFFFFu;
+    }
+  }
+  best = w.best;
+  node = w.node;
+  if (STATS) { cnt.idle3[0] += w.idle_unstarted; cnt.idle3[1] += w.idle_finished; cnt.idle3[2] += w.idle_parked; }
+}
+
 // One round of the nearest-hit search for the lanes that call it: walks continue from (best, node) and the round ends
 // once fewer than min(round_min, entering lanes / round_div) are unfinished.  node == PT_END on return: finished.
-template <bool STATS, bool NODES_IN_LDS>
+// DEFER (the deferring forms; the round control is pt_round.h's): a box phase that is not the round's first ends the round without
+// its leaf phase when fewer than leaf_defer lanes are unfinished.  A lane parked at a leaf then returns a PENDING word in `node`
+// (its leaf code and its continuation) and enters the next round parked: it sits out that round's first box phase (the box loop
+// masks every state >= 0x8000 out) and tests its leaf in the first leaf phase, which always runs.
+template <bool STATS, bool NODES_IN_LDS, bool DEFER = false>
 PT_DEV void traverse_round(const float4* nodes, const float4* tris, uint32_t n_nodes, f3 o, f3 d, Best& best, uint32_t& node,
                            uint32_t round_min, uint32_t round_div, uint32_t round_div_m16, uint32_t walk_min, bool small_det, Counters& cnt)
 {
+  if constexpr (DEFER) {   // (round_min: KParams::round_defer, which holds the knob beside it)
+    traverse_round_deferring<STATS, NODES_IN_LDS>(nodes, tris, n_nodes, o, d, best, node, round_min, round_div, round_div_m16, walk_min, small_det, cnt);
+    return;
+  }
   Walk w;
   walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS && PT_ASM_WALK);
   w.best = best;
@@ -2037,7 +2118,7 @@ template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
 pt_megakernel_restart(PT_KERNEL_PARAMS)
 {
-  constexpr bool STATS = VARIANT == PT_RS_STATS;
+  constexpr bool STATS = VARIANT == PT_RS_STATS || VARIANT == PT_RS_STATS_DEFER;
   constexpr uint32_t THREADS = LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS;
   // The shipped instantiation (LDS-resident scene, PT_RS_PLAIN) serves only the common launch, which fixes four launch constants:
   // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
@@ -2046,9 +2127,12 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   // reads the compact record and has no texel fetch, normal map, cubemap lookup or refraction branch
   // PT_RS_FLAT_SKIP and PT_RS_PLAIN_SKIP are those two over the scene's relinked links (stage_scene: SKIP): box tests nearly every
   // ray passes are left out, and a walk starts at the entry node of its ray's octant instead of the root
-  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && (VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_PLAIN_SKIP);
-  constexpr bool FLAT = LDS_RESIDENT && (VARIANT == PT_RS_FLAT || VARIANT == PT_RS_FLAT_SKIP);
-  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || VARIANT == PT_RS_PLAIN_SKIP || FLAT);
+  // PT_RS_FLAT_SKIP_DEFER, PT_RS_PLAIN_SKIP_DEFER and PT_RS_STATS_DEFER are the two skip forms and the instrumented form with
+  // deferred leaf phases (traverse_round: DEFER); nothing else in them differs from the form they copy
+  constexpr bool DEFER = LDS_RESIDENT && (VARIANT == PT_RS_FLAT_SKIP_DEFER || VARIANT == PT_RS_PLAIN_SKIP_DEFER || VARIANT == PT_RS_STATS_DEFER);
+  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && (VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_PLAIN_SKIP || VARIANT == PT_RS_FLAT_SKIP_DEFER || VARIANT == PT_RS_PLAIN_SKIP_DEFER);
+  constexpr bool FLAT = LDS_RESIDENT && (VARIANT == PT_RS_FLAT || VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_FLAT_SKIP_DEFER);
+  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || VARIANT == PT_RS_PLAIN_SKIP || VARIANT == PT_RS_PLAIN_SKIP_DEFER || FLAT);
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
   // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
   // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
@@ -2266,7 +2350,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         traverse_round4<STATS, VARIANT == PT_RS_WIDE8 ? 1 : (VARIANT == PT_RS_WIDE4Q ? 2 : 0)>(p, p.nodes4, s_tris, stk, st.o, st.d, best, cur, sp, p.round_min, p.round_div, p.round_div_m16, p.walk_min4, p.small_det != 0u, cnt);
         node = cur == PT_NONE ? PT_END : 0u;
       } else {
-        traverse_round<STATS, LDS_RESIDENT>(s_nodes, s_tris, p.n_nodes, st.o, st.d, best, node, p.round_min, p.round_div, p.round_div_m16, p.walk_min, p.small_det != 0u, cnt);
+        traverse_round<STATS, LDS_RESIDENT, DEFER>(s_nodes, s_tris, p.n_nodes, st.o, st.d, best, node, DEFER ? p.round_defer : p.round_min, p.round_div, p.round_div_m16, p.walk_min, p.small_det != 0u, cnt);
       }
       if (STATS) {   // fetch_events: rounds of this wave; fetch_rays: walks that completed in them
         if (lane == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) cnt.fetch_events++;
@@ -2993,6 +3077,7 @@ static const void* restart_entry(int variant, bool lds_resident)
     PT_RS_ENTRY(PT_RS_LIST, false); PT_RS_ENTRY(PT_RS_LIST, true);
     PT_RS_ENTRY(PT_RS_FLAT, true);
     PT_RS_ENTRY(PT_RS_FLAT_SKIP, true); PT_RS_ENTRY(PT_RS_PLAIN_SKIP, true);
+    PT_RS_ENTRY(PT_RS_FLAT_SKIP_DEFER, true); PT_RS_ENTRY(PT_RS_PLAIN_SKIP_DEFER, true); PT_RS_ENTRY(PT_RS_STATS_DEFER, true);
 #endif
     default: return nullptr;
   }

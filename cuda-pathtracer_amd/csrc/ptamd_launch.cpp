@@ -230,7 +230,11 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   // the flat form of the restart kernel: a flat scene (its compact records exist) under a one-colour environment
   p.round_form = (ctx->knobs.generic_round ? PT_ROUND_GENERIC : 0u) | (ctx->knobs.flat_round && s.flat && ctx->cubemaps[l->cubemap_id].uniform ? PT_ROUND_FLAT : 0u);
   // the skip forms: the scene has a relinked link table behind its nodes (lay_out_lds takes the bit back where their LDS does not fit)
-  if (s.links && pl.resident) p.round_form |= PT_ROUND_SKIP;
+  // ... and their deferring copies (pt_round.h).  Left to itself the knob defers in the flat form only: measured, the headline
+  // gains 2.4 % and the plain form's scenes nothing (profiles/r23_leaf_defer_ab.txt); a lane count given through PTAMD_LEAF_DEFER
+  // defers in both
+  const bool defer = ctx->knobs.leaf_defer != 0u && (ctx->knobs.leaf_defer != PT_LEAF_DEFER_AUTO || (p.round_form & PT_ROUND_FLAT));
+  if (s.links && pl.resident) p.round_form |= PT_ROUND_SKIP | (defer ? PT_ROUND_DEFER : 0u);
 }
 
 // Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
@@ -287,7 +291,7 @@ void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, con
     const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
     const auto fits = [&](size_t scene) { return (((scene + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES) * blocks_wanted + 1024u <= 160u * 1024u; };
     // the skip forms keep their eight entry nodes in front of the scene's copy (pt_kernels.hip: stage_scene)
-    if ((p.round_form & PT_ROUND_SKIP) && !(ctx->knobs.pool_in_lds && fits(pl.lds + PT_SKIP_ENTRY_BYTES))) p.round_form &= ~PT_ROUND_SKIP;
+    if ((p.round_form & PT_ROUND_SKIP) && !(ctx->knobs.pool_in_lds && fits(pl.lds + PT_SKIP_ENTRY_BYTES))) p.round_form &= ~(PT_ROUND_SKIP | PT_ROUND_DEFER);
     const size_t scene_lds = pl.lds + ((p.round_form & PT_ROUND_SKIP) ? PT_SKIP_ENTRY_BYTES : 0u);
     // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
     // there whatever the knob, at one workgroup per CU when two do not fit
@@ -488,6 +492,7 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
   if (urc != PTAMD_OK) return urc;
   p.round_min = ctx->knobs.round_min;
   p.round_div = ctx->knobs.round_div;
+  p.round_defer = ctx->knobs.round_min | ((ctx->knobs.leaf_defer == PT_LEAF_DEFER_AUTO ? 0xFFu : ctx->knobs.leaf_defer) << 8);
   p.round_div_m16 = (65536u + ctx->knobs.round_div - 1u) / ctx->knobs.round_div;
   p.walk_min = ctx->knobs.walk_min;
   p.walk_min4 = ctx->knobs.walk_min4;
@@ -515,7 +520,9 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
   if (restart && !pl.fma && ctx->d_timeline && p.n_static <= ctx->timeline_waves) p.timeline = ctx->d_timeline.get();
   if (split) p.tiles_per_ticket = 1;
   // (what ptamd_last_restart_form reports: the instantiation pt_kernels.hip's table resolves this launch to, by the same rule)
-  ctx->last_restart_form = restart ? restart_select(pl.resident, stats, ad != nullptr, pl.fma, &p).variant : -1;
+  const int restart_form = restart ? restart_select(pl.resident, stats, ad != nullptr, pl.fma, &p).variant : -1;
+  ctx->last_restart_form = restart_reported_form(restart_form);   // (the deferring copies answer as the forms they copy)
+  ctx->last_restart_deferred = restart_form_defers(restart_form);
   hipError_t e = launch_form(form_of(pl, stats, ad != nullptr, &p), p, pl.n_blocks, restart ? mega_stream : pl.stream);
   if (e == hipSuccess && pl.pipelined) {
     PT_HIP(hipEventRecord(sc->mega_done[pl.slab].get(), mega_stream));

@@ -46,6 +46,7 @@ constexpr Knob kKnobs[] = {
   number("PTAMD_ROUND_DIV", kClamped, &S::round_div, 1, 64),
   number("PTAMD_WALK_MIN", kClamped, &S::walk_min, 1, 64),
   number("PTAMD_WALK_MIN4", kClamped, &S::walk_min4, 1, 64),
+  number("PTAMD_LEAF_DEFER", kClamped, &S::leaf_defer, 0, 64),
   on_off("PTAMD_SHORT_RCP", &S::short_rcp),
   on_off("PTAMD_WIDE8", &S::wide8),
   on_off("PTAMD_WIDE4Q", &S::wide4q),

@@ -18,6 +18,7 @@ struct TuningSettings {
   // measured (round 2 sweep, 1080p x 4 spp x 4 bounces; re-run with scripts/gpu_ab.sh): round_min 16-32 and walk_min 4-6 are a flat optimum
   uint32_t round_min = 16, round_div = 4; // PTAMD_ROUND_MIN, PTAMD_ROUND_DIV
   uint32_t walk_min = 7;                  // restart kernel: a box phase ends once fewer lanes than this still walk (PTAMD_WALK_MIN; 4 / 5 / 7 / 8 / 10 / 12: 9331 / 9372 / 9405 / 9377 / 9338 / 9273 Msamples/s with the final shading code)
+  uint32_t leaf_defer = 0xFFFFFFFFu;      // restart kernel's skip forms: after a box phase that is not its round's first, the round ends without its leaf phase when fewer lanes than this are unfinished; the parked lanes test their leaves in the next round's first leaf phase (csrc/pt_round.h).  0xFFFFFFFF: the round's own threshold, in the flat skip form only (the plain one keeps its rounds: it gains nothing, profiles/r23_leaf_defer_ab.txt); PTAMD_LEAF_DEFER: 0 off (the skip forms as they were), or a lane count for both forms
   uint32_t walk_min4 = 16;                // the same threshold for the four-wide walk (PTAMD_WALK_MIN4; 1/4/8/16/24: 813/902/960/994/971 Msamples/s)
   bool short_rcp = true;                  // restart kernel: 7-instruction exact 1/det where the scene allows it (PTAMD_SHORT_RCP=0: always the full division)
   bool wide8 = false;                     // PTAMD_WIDE8=1: big scenes walk the eight-wide quantised nodes (measured 8 % slower: DESIGN.md §4)

@@ -4,6 +4,7 @@
 // walk has a version of its own of is written once: the ray set-up, the leaf test and the result.  Contract of every walk:
 // the record the reference's brute-force loop returns (bvh_builder.cpp).
 #include "ptamd_internal.h"
+#include "../csrc/pt_round.h"
 
 #include <algorithm>
 #include <cmath>
@@ -325,6 +326,41 @@ void skip_count_host(const Bvh& bvh, const uint32_t* words, const float dir[3], 
   skip_walk<false>(bvh, words, dir, origin, h, nullptr, nullptr, node_visits, node_passes);
 }
 
+// The same walk as the sequence of what a lane of the device's box loop does (ptamd.h: ptamd_host_skip_events): one word per leaf
+// it parks at, `box tests since the last word << 8 | records of the leaf << 1 | 1 when the leaf's miss code ends the walk`, and a
+// last word with no records for the box tests after the last leaf (a walk that ends on a box's miss code) where there are any.
+void skip_events_host(const Bvh& bvh, const uint32_t* words, const float dir[3], const float origin[3], std::vector<uint32_t>& events)
+{
+  const Ray ray(dir, origin);
+  const uint32_t oct = ray.octant();
+  Best best;
+  uint32_t boxes = 0;
+  uint32_t node = words[(size_t)bvh.n_nodes * 8 + oct];
+  while (node != 0xFFFFu) {
+    const float* q = &bvh.nodes[(size_t)node * 16];
+    ++boxes;
+    float tnear = -std::numeric_limits<float>::infinity(), tfar = std::numeric_limits<float>::infinity();
+    for (int a = 0; a < 3; ++a) {
+      float t0 = std::fma(q[a], ray.inv[a], ray.noi[a]);
+      float t1 = std::fma(q[4 + a], ray.inv[a], ray.noi[a]);
+      tnear = std::fmax(tnear, std::fmin(t0, t1));
+      tfar = std::fmin(tfar, std::fmax(t0, t1));
+    }
+    const bool hit = tnear <= tfar && tfar >= 0.0f && tnear <= best.t;
+    const uint32_t word = words[(size_t)node * 8 + oct];
+    uint32_t code = hit ? (word & 0xFFFFu) : (word >> 16);
+    if (code >= 0x8000u && code != 0xFFFFu) {
+      const uint32_t count = (code >> 11) & 0xFu;
+      test_leaf(bvh, code & 0x7FFu, count, ray, best, nullptr);
+      code = word >> 16;
+      events.push_back(boxes << 8 | count << 1 | (code == 0xFFFFu ? 1u : 0u));
+      boxes = 0;
+    }
+    node = code;
+  }
+  if (boxes) events.push_back(boxes << 8);
+}
+
 } // namespace ptamd
 
 namespace {
@@ -443,6 +479,48 @@ extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* 
   if (skip_out && bvh.n_nodes) std::memcpy(skip_out, skip.data(), bvh.n_nodes);
   if (words_out) std::memcpy(words_out, words.data(), words.size() * 4);
   return PTAMD_OK;
+}
+
+extern "C" int ptamd_host_skip_events(const ptamd_face* faces, uint32_t n_faces, uint32_t mode, float threshold, const float* rays, uint32_t n,
+                                      uint32_t* offsets, uint32_t* events, uint64_t* n_events)
+{
+  if ((n_faces && !faces) || (n && !rays) || !offsets || !n_events || (mode & ~PTAMD_SKIP_CULLED) > PTAMD_SKIP_ALL) { ptamd::set_error("ptamd_host_skip_events: bad argument"); return PTAMD_ERR_ARG; }
+  ptamd::Bvh bvh;
+  const int rc = ptamd::build_bvh(faces, n_faces, 1e-3f, 2, bvh, 0u);
+  if (rc != PTAMD_OK) return rc;
+  if (!ptamd::skip_links_fit(bvh)) { ptamd::set_error("ptamd_host_skip_events: the tree is outside the compact layout's code space"); return PTAMD_ERR_LIMIT; }
+  ptamd::SkipTables t;
+  ptamd::build_skip_tables(bvh, mode, threshold, nullptr, t);
+  const uint64_t room = *n_events;
+  uint64_t total = 0;
+  std::vector<uint32_t> ev;
+  for (uint32_t i = 0; i < n; ++i) {
+    ev.clear();
+    ptamd::skip_events_host(bvh, t.words.data(), rays + (size_t)i * 6, rays + (size_t)i * 6 + 3, ev);
+    offsets[i] = (uint32_t)total;
+    if (events && total + ev.size() <= room && !ev.empty()) std::memcpy(events + total, ev.data(), ev.size() * 4);
+    total += ev.size();
+  }
+  offsets[n] = (uint32_t)total;
+  *n_events = total;
+  return PTAMD_OK;
+}
+
+extern "C" uint32_t ptamd_host_round_threshold(uint32_t n_start, uint32_t round_min, uint32_t round_div)
+{
+  if (!round_div) round_div = 1u;
+  return round_threshold(n_start, round_min, round_div, (65536u + round_div - 1u) / round_div);
+}
+extern "C" uint32_t ptamd_host_round_leaf_defer(uint32_t knob, uint32_t t_eff) { return round_leaf_defer(knob, t_eff); }
+extern "C" int ptamd_host_round_leaf_phase_runs(int first, uint32_t unfinished, uint32_t leaf_defer) { return round_leaf_phase_runs(first != 0, unfinished, leaf_defer) ? 1 : 0; }
+extern "C" int ptamd_host_round_ends(uint32_t unfinished, uint32_t t_eff) { return round_ends(unfinished, t_eff) ? 1 : 0; }
+extern "C" uint32_t ptamd_host_round_pending_pack(uint32_t leaf_code, uint32_t continuation) { return round_pending_pack(leaf_code, continuation); }
+extern "C" int ptamd_host_round_pending_unpack(uint32_t node, uint32_t* leaf_code, uint32_t* continuation)
+{
+  if (!round_is_pending(node)) return 0;
+  if (leaf_code) *leaf_code = round_pending_leaf(node);
+  if (continuation) *continuation = round_pending_continuation(node);
+  return 1;
 }
 
 extern "C" int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out)

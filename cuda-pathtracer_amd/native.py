@@ -307,6 +307,15 @@ SIGNATURES = {
     "ptamd_scene_cull_count": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ptamd_last_restart_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ptamd_host_faces_away": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptamd_last_restart_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "ptamd_host_skip_events": (C.c_int, [C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_host_round_threshold": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ptamd_host_round_leaf_defer": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "ptamd_host_round_leaf_phase_runs": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32]),
+    "ptamd_host_round_ends": (C.c_int, [C.c_uint32, C.c_uint32]),
+    "ptamd_host_round_pending_pack": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "ptamd_host_round_pending_unpack": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

@@ -198,6 +198,13 @@ class Context:
         N.check(self._lib.ptamd_last_restart_form(self._h, C.byref(out)))
         return out.value
 
+    def last_restart_deferred(self) -> bool:
+        """ptamd_last_restart_deferred: the last megakernel launch took a deferring instantiation of the restart kernel (its
+        rounds leave sparse leaf phases to the next round's first one; last_restart_form still names the skip form it copies)."""
+        out = C.c_int32(0)
+        N.check(self._lib.ptamd_last_restart_deferred(self._h, C.byref(out)))
+        return out.value != 0
+
     def scene_is_flat(self, scene_id: int, cubemap_id: int) -> bool:
         """ptamd_scene_is_flat: launches of the scene under the cubemap take the restart kernel's flat form."""
         out = C.c_int32()
@@ -570,6 +577,58 @@ def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=Non
                                       rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), out.ctypes.data_as(C.POINTER(C.c_int32)),
                                       counters, C.byref(n_nodes), skip_out.ctypes.data, words.ctypes.data))
     return {"records": out, "nodes": counters[0], "tris": counters[1], "skip": skip_out, "words": words}
+
+
+def host_skip_events(scene: HostScene, rays: np.ndarray, mode="default", threshold: float = 0.0, cull=False):
+    """The relinked walk of every ray as the sequence of what a lane of the device's box loop does (ptamd_host_skip_events, no
+    GPU): (offsets uint32[n + 1], events uint32[offsets[-1]]); ray i owns events[offsets[i]:offsets[i + 1]], one word per leaf it
+    parks at: box tests since the last word << 8 | the leaf's records << 1 | 1 when the leaf's continuation ends the walk, and a
+    last word without records for box tests after the last leaf.  mode, threshold, cull: as host_skip_trace."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    lib = N.load()
+    faces = scene.faces.ctypes.data_as(C.POINTER(N.Face))
+    args = (faces, len(scene.faces), SKIP_MODES[mode] | (SKIP_CULLED if cull else 0), threshold, rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays))
+    offsets = np.zeros(len(rays) + 1, dtype=np.uint32)
+    n_events = C.c_uint64(0)
+    N.check(lib.ptamd_host_skip_events(*args, offsets.ctypes.data, None, C.byref(n_events)))
+    events = np.zeros(max(n_events.value, 1), dtype=np.uint32)
+    N.check(lib.ptamd_host_skip_events(*args, offsets.ctypes.data, events.ctypes.data, C.byref(n_events)))
+    return offsets, events[:n_events.value]
+
+
+LEAF_DEFER_AUTO = 0xFFFFFFFF
+
+
+class RoundControl:
+    """The restart kernel's round control (csrc/pt_round.h) as the host entry points run it: the same lines the kernel compiles."""
+
+    @staticmethod
+    def threshold(n_start: int, round_min: int, round_div: int) -> int:
+        return N.load().ptamd_host_round_threshold(n_start, round_min, round_div)
+
+    @staticmethod
+    def leaf_defer(knob: int, t_eff: int) -> int:
+        return N.load().ptamd_host_round_leaf_defer(knob, t_eff)
+
+    @staticmethod
+    def leaf_phase_runs(first: bool, unfinished: int, leaf_defer: int) -> bool:
+        return bool(N.load().ptamd_host_round_leaf_phase_runs(int(first), unfinished, leaf_defer))
+
+    @staticmethod
+    def ends(unfinished: int, t_eff: int) -> bool:
+        return bool(N.load().ptamd_host_round_ends(unfinished, t_eff))
+
+    @staticmethod
+    def pending_pack(leaf_code: int, continuation: int) -> int:
+        return N.load().ptamd_host_round_pending_pack(leaf_code, continuation)
+
+    @staticmethod
+    def pending_unpack(node: int):
+        """(leaf code, continuation) of a pending word, None for a node index or the end of the walk."""
+        leaf, cont = C.c_uint32(0), C.c_uint32(0)
+        if not N.load().ptamd_host_round_pending_unpack(node, C.byref(leaf), C.byref(cont)):
+            return None
+        return leaf.value, cont.value
 
 
 def host_bvh4_trace(scene: HostScene, rays: np.ndarray):

@@ -1006,10 +1006,40 @@ int ptamd_stream_synchronize(ptamd_context* ctx, void* stream);
 int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
 int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
 int ptamd_last_restart_form(ptamd_context* ctx, int32_t* out);
+int ptamd_last_restart_deferred(ptamd_context* ctx, int32_t* out);
 int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
                           const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
                           uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out);
 int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out);
+
+/* ---- deferred leaf phases of the restart kernel's skip forms ------------------------------------------
+ * A round of the restart kernel alternates box phases and leaf phases.  In the deferring copies of the two skip forms, a box
+ * phase that is not its round's first ends the round without its leaf phase when fewer than `leaf_defer` lanes are unfinished;
+ * the lanes parked at a leaf test it in the next round's first leaf phase, which always runs.  Results are bit-identical.
+ * Unset, the flat skip form defers at the round's own threshold min(PTAMD_ROUND_MIN, entering lanes / PTAMD_ROUND_DIV) and the
+ * plain one does not defer (measured: it gains nothing).  With PTAMD_TUNING=1: PTAMD_LEAF_DEFER=0 off (the skip forms as they
+ * were), =<lanes, 1..64> that threshold in both forms.
+ * ptamd_last_restart_deferred: 1 when the context's last megakernel launch took a deferring copy (ptamd_last_restart_form then
+ * still answers PTAMD_FORM_FLAT_SKIP / PTAMD_FORM_PLAIN_SKIP), else 0.
+ *
+ * ptamd_host_skip_events: the relinked walk of every ray as the sequence of what a lane of the device's box loop does, no device
+ * needed (mode, threshold, rays as ptamd_host_skip_trace, no caller-supplied set).  offsets: n + 1 words; ray i owns
+ * events[offsets[i] .. offsets[i + 1]), one word per leaf it parks at: box tests since the last word << 8 | the leaf's records
+ * << 1 | 1 when the leaf's continuation ends the walk, and a last word without records for box tests after the last leaf.
+ * *n_events: in, the room of `events` in words (events may be NULL: count only); out, the number of words of all rays.
+ *
+ * ptamd_host_round_*: the round control itself (csrc/pt_round.h, the lines the kernel compiles), for models and tests: the
+ * round's threshold; the effective leaf_defer of a knob value (0xFFFFFFFF: the threshold); whether a leaf phase runs (first: the
+ * round's first iteration; unfinished: lanes walking + lanes parked); whether the round ends after a leaf phase; a pending word
+ * of (leaf code, continuation), and its parts back (returns 0 for a word that is a node index or the end of the walk). */
+int ptamd_host_skip_events(const ptamd_face* faces, uint32_t n_faces, uint32_t mode, float threshold, const float* rays, uint32_t n,
+                           uint32_t* offsets, uint32_t* events, uint64_t* n_events);
+uint32_t ptamd_host_round_threshold(uint32_t n_start, uint32_t round_min, uint32_t round_div);
+uint32_t ptamd_host_round_leaf_defer(uint32_t knob, uint32_t t_eff);
+int ptamd_host_round_leaf_phase_runs(int first, uint32_t unfinished, uint32_t leaf_defer);
+int ptamd_host_round_ends(uint32_t unfinished, uint32_t t_eff);
+uint32_t ptamd_host_round_pending_pack(uint32_t leaf_code, uint32_t continuation);
+int ptamd_host_round_pending_unpack(uint32_t node, uint32_t* leaf_code, uint32_t* continuation);
 
 #ifdef __cplusplus
 }
