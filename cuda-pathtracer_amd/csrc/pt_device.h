@@ -494,28 +494,80 @@ struct KParams {
 // LDS bytes in front of the scene's copy in the skip forms: the node a walk starts at, one word per ray octant
 #define PT_SKIP_ENTRY_BYTES 32u
 
-// The restart kernel's forms: the VARIANT argument of pt_megakernel_restart<LDS_RESIDENT, VARIANT> (pt_kernels.hip)
+// The restart kernel's forms: the VARIANT argument of pt_megakernel_restart<LDS_RESIDENT, VARIANT> (pt_kernels.hip).  The numbers are
+// public (ptamd_last_restart_form); what a number stands for is its row of kRestartForms below and nothing else.
 #define PT_RS_PLAIN 0
 #define PT_RS_STATS 1
 #define PT_RS_STAMPS 2
 #define PT_RS_BRUTE 3
-#define PT_RS_WIDE8 4   /* scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one */
-#define PT_RS_WIDE4Q 5  /* ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q) */
-#define PT_RS_GENERIC 6 /* an LDS-resident scene in a launch the shipped instantiation does not serve (restart_select) */
-#define PT_RS_LIST 7    /* adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles */
-#define PT_RS_FLAT 8    /* PT_RS_PLAIN's launches of a flat scene under a uniform environment (KParams::round_form) */
-#define PT_RS_FLAT_SKIP 9   /* PT_RS_FLAT over the relinked links: the box tests of the scene's skip set are left out (KParams::round_form) */
-#define PT_RS_PLAIN_SKIP 10 /* ... and PT_RS_PLAIN */
-#define PT_RS_FLAT_SKIP_DEFER 11  /* PT_RS_FLAT_SKIP with deferred leaf phases (pt_round.h; KParams::round_form) */
-#define PT_RS_PLAIN_SKIP_DEFER 12 /* ... and PT_RS_PLAIN_SKIP */
-#define PT_RS_STATS_DEFER 13      /* PT_RS_STATS with them: the counters of a launch the deferring forms would have served */
+#define PT_RS_WIDE8 4
+#define PT_RS_WIDE4Q 5
+#define PT_RS_GENERIC 6
+#define PT_RS_LIST 7
+#define PT_RS_FLAT 8
+#define PT_RS_FLAT_SKIP 9
+#define PT_RS_PLAIN_SKIP 10
+#define PT_RS_FLAT_SKIP_DEFER 11
+#define PT_RS_PLAIN_SKIP_DEFER 12
+#define PT_RS_STATS_DEFER 13
 #define PT_RS_FORMS 14
-// what ptamd_last_restart_form answers for a form: the deferring copies report the form they are a copy of
-inline int restart_reported_form(int variant)
+
+// One form of the restart kernel: what the kernel compiles in for it, what a launch of it reports, and where it is compiled.  The kernel
+// reads its row at compile time, restart_entry (pt_kernels.hip) the last three columns, the launcher `reports` and `defer`.
+struct RestartTraits {
+  bool stats;      // instrumented: the launch's counters
+  bool stamps;     // four time stamps per wave (ptamd_set_timeline)
+  bool brute;      // every triangle record instead of the tree
+  int wide;        // node form of a scene walked from L2 (traverse_round4): 0 four-wide float nodes, 1 eight-wide quantised, 2 four-wide 64-byte quantised
+  bool list;       // takes 64 entries of adaptive sampling's active list per ticket, not tiles of the frame
+  bool lean;       // compiled for the four launch constants of restart_shipped_launch: their branches and argument reads leave the round
+  bool flat;       // the shading half reads the compact record: no texel fetch, normal map, cubemap lookup or refraction branch
+  bool skip;       // walks the scene's relinked links from the entry node of the ray's octant (stage_scene: SKIP)
+  bool defer;      // rounds leave their sparse later leaf phases to the next round's first one (traverse_round: DEFER; pt_round.h)
+  int reports;     // what ptamd_last_restart_form answers: a deferring copy reports the form it copies
+  bool resident, streamed, contracted;   // compiled with LDS_RESIDENT true, with it false; those also in pt_kernels_fma.hip
+};
+constexpr RestartTraits kRestartForms[] = {
+  //stats stamps brute wide list   lean   flat   skip   defer  reports           resident streamed contracted
+  // PLAIN: the shipped instantiation.  Of a resident scene it serves only the common launch (static camera, pools in LDS, no XCD
+  // regions, no interleaved bands); of a scene that does not fit in LDS, every launch of the four-wide walk from L2
+  { false, false, false, 0, false, true,  false, false, false, PT_RS_PLAIN,      true,  true,  true },
+  // STATS: counters are wanted
+  { true,  false, false, 0, false, false, false, false, false, PT_RS_STATS,      true,  true,  false },
+  // STAMPS: an instantiation of its own, since even switched off the four stamps cost the round loop 1.5 %
+  { false, true,  false, 0, false, false, false, false, false, PT_RS_STAMPS,     true,  true,  false },
+  // BRUTE: a camera or light too far out for the boxes' margins (ptamd_scene.cpp: far_origin_camera)
+  { false, false, true,  0, false, false, false, false, false, PT_RS_BRUTE,      true,  true,  true },
+  // WIDE8: scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one
+  { false, false, false, 1, false, false, false, false, false, PT_RS_WIDE8,      false, true,  false },
+  // WIDE4Q: ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q)
+  { false, false, false, 2, false, false, false, false, false, PT_RS_WIDE4Q,     false, true,  false },
+  // GENERIC: an LDS-resident scene in a launch the shipped instantiation does not serve: the same code with the four constants read at run time
+  { false, false, false, 0, false, false, false, false, false, PT_RS_GENERIC,    true,  false, true },
+  // LIST: adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles
+  { false, false, false, 0, true,  false, false, false, false, PT_RS_LIST,       true,  true,  false },
+  // FLAT: PLAIN's launches of a flat scene under a uniform environment (ptamd_scene.cpp: scene_is_flat; KParams::round_form)
+  { false, false, false, 0, false, true,  true,  false, false, PT_RS_FLAT,       true,  false, false },
+  // FLAT_SKIP: FLAT over the relinked links: box tests nearly every ray passes are left out (KParams::round_form)
+  { false, false, false, 0, false, true,  true,  true,  false, PT_RS_FLAT_SKIP,  true,  false, false },
+  // PLAIN_SKIP: ... and PLAIN
+  { false, false, false, 0, false, true,  false, true,  false, PT_RS_PLAIN_SKIP, true,  false, false },
+  // FLAT_SKIP_DEFER: FLAT_SKIP with deferred leaf phases; nothing else in it differs from the form it copies
+  { false, false, false, 0, false, true,  true,  true,  true,  PT_RS_FLAT_SKIP,  true,  false, false },
+  // PLAIN_SKIP_DEFER: ... and PLAIN_SKIP
+  { false, false, false, 0, false, true,  false, true,  true,  PT_RS_PLAIN_SKIP, true,  false, false },
+  // STATS_DEFER: STATS with them: the counters of a launch the deferring forms would have served
+  { true,  false, false, 0, false, false, false, false, true,  PT_RS_STATS,      true,  false, false },
+};
+static_assert(sizeof kRestartForms / sizeof kRestartForms[0] == PT_RS_FORMS, "one row per PT_RS_* number");
+constexpr RestartTraits restart_traits(int variant) { return kRestartForms[variant]; }
+
+// The launch the lean forms of a resident scene are compiled for: a static camera, pools in LDS, no XCD regions, no interleaved bands
+// (and no PTAMD_RS_GENERIC); any other launch reads the four at run time, in GENERIC
+inline bool restart_shipped_launch(const KParams& p)
 {
-  return variant == PT_RS_FLAT_SKIP_DEFER ? PT_RS_FLAT_SKIP : variant == PT_RS_PLAIN_SKIP_DEFER ? PT_RS_PLAIN_SKIP : variant == PT_RS_STATS_DEFER ? PT_RS_STATS : variant;
+  return p.is_static && p.pool_lds_offset && !p.xcd_regions && p.ilv_ranks <= 1u && !(p.round_form & PT_ROUND_GENERIC);
 }
-inline bool restart_form_defers(int variant) { return variant == PT_RS_FLAT_SKIP_DEFER || variant == PT_RS_PLAIN_SKIP_DEFER || variant == PT_RS_STATS_DEFER; }
 
 // Which instantiation of the restart kernel serves a launch: the first rule that applies.  Host code.  p: the launch, or nullptr for
 // the occupancy query, which asks for the family's plain form.  contracted: the choice of pt_kernels_fma.hip, which compiles PLAIN,
@@ -525,18 +577,16 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
 {
   const auto full = [contracted](int variant) { return contracted ? PT_RS_PLAIN : variant; };
   if (list && !contracted) return { PT_RS_LIST, lds_resident };                // adaptive sampling's active list: instantiations of its own
-  // the launches the deferring forms serve (same test as the skip rule's below, whose bit PT_ROUND_DEFER comes with)
+  // the launches the deferring forms serve: the skip forms', with the bit PT_ROUND_DEFER, which only ever comes with PT_ROUND_SKIP
   const bool defers = p && lds_resident && !contracted && (p->round_form & PT_ROUND_DEFER) && (p->round_form & PT_ROUND_SKIP) && !p->brute_walk && !p->timeline &&
-                      p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC);
+                      restart_shipped_launch(*p);
   if (stats) return { defers ? PT_RS_STATS_DEFER : full(PT_RS_STATS), lds_resident };   // counters are wanted: the instrumented build
   if (p && p->brute_walk) return { PT_RS_BRUTE, lds_resident };                // a far origin: every triangle record instead of the tree
   if (p && p->timeline) return { full(PT_RS_STAMPS), lds_resident };           // ptamd_set_timeline: four time stamps per wave
   if (!lds_resident && p && p->wide8) return { full(p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8), false };   // the knobs' quantised node forms
   if (!lds_resident) return { PT_RS_PLAIN, false };                            // the four-wide walk from L2
-  // the shipped instantiation of a resident scene is compiled for four launch constants (pt_megakernel_restart: LEAN): a static
-  // camera, pools in LDS, no XCD regions, no interleaved bands; any other launch, or PTAMD_RS_GENERIC, reads them at run time
-  if (p && !(p->is_static && p->pool_lds_offset && !p->xcd_regions && p->ilv_ranks <= 1u && !(p->round_form & PT_ROUND_GENERIC))) return { PT_RS_GENERIC, true };
-  if (defers) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP_DEFER : PT_RS_PLAIN_SKIP_DEFER, true };   // ... with deferred leaf phases
+  if (p && !restart_shipped_launch(*p)) return { PT_RS_GENERIC, true };        // a resident scene in a launch the lean forms are not compiled for
+  if (defers) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP_DEFER : PT_RS_PLAIN_SKIP_DEFER, true };   // the skip forms with deferred leaf phases
   if (p && (p->round_form & PT_ROUND_SKIP) && !contracted) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP : PT_RS_PLAIN_SKIP, true };   // the same two launches of a scene with a skip set
   if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment
   return { PT_RS_PLAIN, true };

@@ -21,6 +21,9 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 #include "pt_adaptive.h"
+
+#include <utility>
+
 #ifndef PT_FMA_BUILD
 #include "pt_denoise.h"
 #endif
@@ -2103,41 +2106,33 @@ PT_DEV bool region_tile(const KParams& p, uint32_t ticket, uint32_t& col, uint32
 
 // per-wave time stamps of a launch (ptamd_set_timeline): [4 gwave + slot] = device clock at 0 kernel entry, 1 scene staged,
 // 2 the wave found no ticket (tail mode from here on), 3 exit
-// (an instantiation of its own, VARIANT == PT_RS_STAMPS: even switched off the four stamps cost the round loop 1.5 %)
+// (an instantiation of its own, RestartTraits::stamps: even switched off the four stamps cost the round loop 1.5 %)
 #define PT_STAMP(slot)                                                                                                   \
   do {                                                                                                                   \
-    if (VARIANT == PT_RS_STAMPS) {                                                                                       \
+    if (FORM.stamps) {                                                                                                   \
       unsigned long long* tl_ = PT_KARG(p, timeline);   /* (loaded by the whole wave: scalar) */                         \
       if ((threadIdx.x & 63u) == 0u)                                                                                     \
         tl_[(size_t)(blockIdx.x * (THREADS / 64u) + (threadIdx.x >> 6)) * 4u + (slot)] = wall_clock64();                 \
     }                                                                                                                    \
   } while (0)
-// (its instantiations, PT_RS_*, and which launch takes which: pt_device.h, restart_select)
+// (its instantiations, PT_RS_*: pt_device.h, kRestartForms, where each form is described once, and restart_select, which launch takes which)
 
 template <bool LDS_RESIDENT, int VARIANT>
 __global__ void __launch_bounds__(LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS, LDS_RESIDENT ? PT_RS_WAVES_PER_EU : PT_RS4_WAVES_PER_EU)
 pt_megakernel_restart(PT_KERNEL_PARAMS)
 {
-  constexpr bool STATS = VARIANT == PT_RS_STATS || VARIANT == PT_RS_STATS_DEFER;
+  constexpr RestartTraits FORM = restart_traits(VARIANT);   // what this form compiles in: its row of pt_device.h's table
+  constexpr bool STATS = FORM.stats;
   constexpr uint32_t THREADS = LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS;
-  // The shipped instantiation (LDS-resident scene, PT_RS_PLAIN) serves only the common launch, which fixes four launch constants:
-  // a static camera, pools in LDS, no XCD regions, no interleaved bands.  Their branches and kernel-argument reads leave the round.
-  // restart_select sends every other launch of a resident scene to PT_RS_GENERIC, the same code with the four read at run time.
-  // PT_RS_FLAT is the same launch of a flat scene under a uniform environment (ptamd_scene.cpp: scene_is_flat): the shading half
-  // reads the compact record and has no texel fetch, normal map, cubemap lookup or refraction branch
-  // PT_RS_FLAT_SKIP and PT_RS_PLAIN_SKIP are those two over the scene's relinked links (stage_scene: SKIP): box tests nearly every
-  // ray passes are left out, and a walk starts at the entry node of its ray's octant instead of the root
-  // PT_RS_FLAT_SKIP_DEFER, PT_RS_PLAIN_SKIP_DEFER and PT_RS_STATS_DEFER are the two skip forms and the instrumented form with
-  // deferred leaf phases (traverse_round: DEFER); nothing else in them differs from the form they copy
-  constexpr bool DEFER = LDS_RESIDENT && (VARIANT == PT_RS_FLAT_SKIP_DEFER || VARIANT == PT_RS_PLAIN_SKIP_DEFER || VARIANT == PT_RS_STATS_DEFER);
-  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && (VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_PLAIN_SKIP || VARIANT == PT_RS_FLAT_SKIP_DEFER || VARIANT == PT_RS_PLAIN_SKIP_DEFER);
-  constexpr bool FLAT = LDS_RESIDENT && (VARIANT == PT_RS_FLAT || VARIANT == PT_RS_FLAT_SKIP || VARIANT == PT_RS_FLAT_SKIP_DEFER);
-  constexpr bool LEAN = LDS_RESIDENT && (VARIANT == PT_RS_PLAIN || VARIANT == PT_RS_PLAIN_SKIP || VARIANT == PT_RS_PLAIN_SKIP_DEFER || FLAT);
+  constexpr bool DEFER = LDS_RESIDENT && FORM.defer;
+  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && FORM.skip;
+  constexpr bool FLAT = LDS_RESIDENT && FORM.flat;
+  constexpr bool LEAN = LDS_RESIDENT && FORM.lean;
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
   // of the round.  Entry i holds pixel list[i]; its sample k has frame number count + 1 + k (its own seed) and is parked at
   // samples_out[k][i].  Launched with the whole frame as row range, one tile per ticket, no XCD regions, no interleaved bands;
   // the pools of fresh paths live in LDS for a resident scene and in the global slab for the four-wide walk (ptamd_launch.cpp).
-  constexpr bool LIST = VARIANT == PT_RS_LIST;
+  constexpr bool LIST = FORM.list;
   // constants of the launch the shipped instantiation and the list form share: static camera, no XCD regions, no interleaved bands
   constexpr bool FIXED = LEAN || LIST;
   extern __shared__ float4 s_mem[];
@@ -2156,7 +2151,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   Stack4 stk;
   stk.top = s_mem;
   stk.top_n = WIDE ? p.treelet_nodes : 0u;
-  constexpr uint32_t NODE_F4 = VARIANT == PT_RS_WIDE4Q ? 4u : 8u;   // float4 per wide node
+  constexpr uint32_t NODE_F4 = FORM.wide == 2 ? 4u : 8u;   // float4 per wide node
   // float4s of the treelet's LDS region: chunk-major it is 64 KB whatever the number of nodes staged (plane stride fixed at compile time)
   const uint32_t treelet_f4 = !WIDE ? 0u : (PT_TREELET_SOA ? (p.treelet_nodes ? 8u * PT_TREELET_STRIDE : 0u) : p.treelet_nodes * NODE_F4);
   if (WIDE) {
@@ -2340,14 +2335,14 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
         walking = true;
         if (STATS) cnt.rays++;
       }
-      if (VARIANT == PT_RS_BRUTE) {
+      if (FORM.brute) {
         // a camera too far outside the scene for the boxes' margins (ptamd_scene.cpp: far_origin_camera): every triangle record, as
         // the reference does — the (t, face index) minimum does not depend on the order they are tested in
         for (uint32_t i = 0; i < p.n_bvh_tris; ++i) mt_test<false>(s_tris[i * 3u], s_tris[i * 3u + 1u], s_tris[i * 3u + 2u], st.o, st.d, best, false);
         if (STATS) cnt.tris += p.n_bvh_tris;
         node = PT_END;
       } else if (WIDE) {
-        traverse_round4<STATS, VARIANT == PT_RS_WIDE8 ? 1 : (VARIANT == PT_RS_WIDE4Q ? 2 : 0)>(p, p.nodes4, s_tris, stk, st.o, st.d, best, cur, sp, p.round_min, p.round_div, p.round_div_m16, p.walk_min4, p.small_det != 0u, cnt);
+        traverse_round4<STATS, FORM.wide>(p, p.nodes4, s_tris, stk, st.o, st.d, best, cur, sp, p.round_min, p.round_div, p.round_div_m16, p.walk_min4, p.small_det != 0u, cnt);
         node = cur == PT_NONE ? PT_END : 0u;
       } else {
         traverse_round<STATS, LDS_RESIDENT, DEFER>(s_nodes, s_tris, p.n_nodes, st.o, st.d, best, node, DEFER ? p.round_defer : p.round_min, p.round_div, p.round_div_m16, p.walk_min, p.small_det != 0u, cnt);
@@ -3060,28 +3055,28 @@ constexpr bool kContracted = false;
 constexpr bool kContracted = true;
 #endif
 
-// The restart kernel: (form, LDS_RESIDENT) -> its instantiation, nullptr where none is compiled: WIDE8 and WIDE4Q only ever serve a
-// scene walked from L2, GENERIC, FLAT and the two skip forms only a resident one, and the contracted build carries the first five alone
-// (restart_select).
+// The restart kernel: (form, LDS_RESIDENT) -> its instantiation, nullptr where none is compiled: the last three columns of the form's
+// row (pt_device.h: kRestartForms).  A discarded branch depends on V, so nothing is instantiated that the table does not name.
+template <int V>
+static const void* restart_entry_of(bool lds_resident)
+{
+  constexpr RestartTraits FORM = restart_traits(V);
+  if constexpr (FORM.contracted || !kContracted) {
+    if constexpr (FORM.resident) { if (lds_resident) return PT_FN(pt_megakernel_restart<true, V>); }
+    if constexpr (FORM.streamed) { if (!lds_resident) return PT_FN(pt_megakernel_restart<false, V>); }
+  }
+  return nullptr;
+}
+template <int... V>
+static const void* restart_entry_among(std::integer_sequence<int, V...>, int variant, bool lds_resident)
+{
+  const void* fn = nullptr;
+  ((variant == V ? void(fn = restart_entry_of<V>(lds_resident)) : void()), ...);
+  return fn;
+}
 static const void* restart_entry(int variant, bool lds_resident)
 {
-#define PT_RS_ENTRY(V, R) case (V) * 2 + ((R) ? 1 : 0): return PT_FN(pt_megakernel_restart<R, V>)
-  switch (variant * 2 + (lds_resident ? 1 : 0)) {
-    PT_RS_ENTRY(PT_RS_PLAIN, false); PT_RS_ENTRY(PT_RS_PLAIN, true);
-    PT_RS_ENTRY(PT_RS_BRUTE, false); PT_RS_ENTRY(PT_RS_BRUTE, true);
-    PT_RS_ENTRY(PT_RS_GENERIC, true);
-#ifndef PT_FMA_BUILD
-    PT_RS_ENTRY(PT_RS_STATS, false); PT_RS_ENTRY(PT_RS_STATS, true);
-    PT_RS_ENTRY(PT_RS_STAMPS, false); PT_RS_ENTRY(PT_RS_STAMPS, true);
-    PT_RS_ENTRY(PT_RS_WIDE8, false); PT_RS_ENTRY(PT_RS_WIDE4Q, false);
-    PT_RS_ENTRY(PT_RS_LIST, false); PT_RS_ENTRY(PT_RS_LIST, true);
-    PT_RS_ENTRY(PT_RS_FLAT, true);
-    PT_RS_ENTRY(PT_RS_FLAT_SKIP, true); PT_RS_ENTRY(PT_RS_PLAIN_SKIP, true);
-    PT_RS_ENTRY(PT_RS_FLAT_SKIP_DEFER, true); PT_RS_ENTRY(PT_RS_PLAIN_SKIP_DEFER, true); PT_RS_ENTRY(PT_RS_STATS_DEFER, true);
-#endif
-    default: return nullptr;
-  }
-#undef PT_RS_ENTRY
+  return restart_entry_among(std::make_integer_sequence<int, PT_RS_FORMS>(), variant, lds_resident);
 }
 
 // chunk-major treelet (PT_TREELET_SOA): bytes of its LDS region and the most 128-byte nodes it can hold (0: node-major, sized by the node count)
@@ -3098,7 +3093,7 @@ static KernelForm restart_form(bool lds_resident, bool stats, bool list, size_t 
   const RestartForm queried = restart_select(lds_resident, false, list, kContracted, nullptr);
   const uint32_t threads = restart_threads(lds_resident);
   KernelForm f = { restart_entry(launched.variant, launched.lds_resident), restart_entry(queried.variant, queried.lds_resident), threads,
-                   threads / 64u, lds_bytes, kFormSlotRestart, "restart" };
+                   threads / 64u, lds_bytes, kFormSlotRestart, "restart", launched.variant };
   if (kContracted) { f.cache_slot = kFormSlotRestartContracted; f.name = "contracted restart"; }
   else if (list) { f.cache_slot = kFormSlotRestartList; f.name = "restart (list form)"; }
   return f;

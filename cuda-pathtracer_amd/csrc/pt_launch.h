@@ -21,11 +21,12 @@ struct KernelForm {
   size_t lds_bytes;          // dynamic LDS of the launch
   uint32_t cache_slot;       // index into ptamd_context::occupancy (kFormSlot*)
   const char* name;          // the family, for error text
+  int restart_form = -1;     // the restart kernel: the PT_RS_* number of `fn` (pt_device.h: kRestartForms); -1: another family
 };
 enum : uint32_t { kFormSlotTile, kFormSlotPersistent, kFormSlotBlockwise, kFormSlotSplit, kFormSlotRestart, kFormSlotRestartContracted, kFormSlotRestartList, kFormSlots };
 // kernel: PTAMD_KERNEL_* with AUTO resolved.  lds_bytes: of the scene's copy; for the restart kernel the launch's dynamic LDS
 // (ptamd_launch.cpp: lay_out_lds).  list: the list form of adaptive sampling (pt_adaptive.h; KParams::adaptive names the state's device
-// block).  p: the launch, whose fields choose among the restart kernel's forms (pt_device.h: restart_select), or nullptr before it is
+// block).  p: the launch, whose fields choose among the restart kernel's forms (pt_device.h: restart_select, kRestartForms), or nullptr before it is
 // known: everything but `fn` is then already final.
 KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p);
 hipError_t form_blocks_per_cu(const KernelForm& f, int* out);

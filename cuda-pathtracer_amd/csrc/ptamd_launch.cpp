@@ -519,11 +519,11 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
   }
   if (restart && !pl.fma && ctx->d_timeline && p.n_static <= ctx->timeline_waves) p.timeline = ctx->d_timeline.get();
   if (split) p.tiles_per_ticket = 1;
-  // (what ptamd_last_restart_form reports: the instantiation pt_kernels.hip's table resolves this launch to, by the same rule)
-  const int restart_form = restart ? restart_select(pl.resident, stats, ad != nullptr, pl.fma, &p).variant : -1;
-  ctx->last_restart_form = restart_reported_form(restart_form);   // (the deferring copies answer as the forms they copy)
-  ctx->last_restart_deferred = restart_form_defers(restart_form);
-  hipError_t e = launch_form(form_of(pl, stats, ad != nullptr, &p), p, pl.n_blocks, restart ? mega_stream : pl.stream);
+  const KernelForm form = form_of(pl, stats, ad != nullptr, &p);
+  // (what ptamd_last_restart_form reports: the row of the form that is launched; the deferring copies answer as the forms they copy)
+  ctx->last_restart_form = form.restart_form < 0 ? -1 : restart_traits(form.restart_form).reports;
+  ctx->last_restart_deferred = form.restart_form >= 0 && restart_traits(form.restart_form).defer;
+  hipError_t e = launch_form(form, p, pl.n_blocks, restart ? mega_stream : pl.stream);
   if (e == hipSuccess && pl.pipelined) {
     PT_HIP(hipEventRecord(sc->mega_done[pl.slab].get(), mega_stream));
     PT_HIP(hipStreamWaitEvent(pl.stream, sc->mega_done[pl.slab].get(), 0));

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")
 MARKS = [  # (unique source anchor, marker name) — the marker goes in front of the anchor
     ("    if (!idle) {\n      if (!walking) {\n        best.t = PT_MAX_DIST;", "round_begin"),
-    ("      } else if (WIDE) {\n        traverse_round4<STATS, VARIANT == PT_RS_WIDE8", "traverse_begin"),
+    ("      } else if (WIDE) {\n        traverse_round4<STATS, FORM.wide>", "traverse_begin"),
     ("      if (node == PT_END) {\n        // the iteration's first variate", "traverse_end"),
     ("        if (path_post<STATS, FIXED, FLAT>(p, st, r1, n, cnt)) {\n          path_finish_sample(p, st);", "lights_end"),
     ("          path_finish_sample(p, st);\n          idle = true;\n          if (STATS) samples++;", "post_end"),

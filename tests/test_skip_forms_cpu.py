@@ -89,15 +89,15 @@ def old_rule(res, stats, lst, contracted, is_static, pool, xcd, ilv, round_form,
 
 
 def test_the_skip_bit_only_moves_the_plain_and_the_flat_forms_launches(tmp_path):
-    """tests/san/skip_form_choice_host.cpp: every combination of the launch's fields with PT_ROUND_SKIP set.  The skip forms take
+    """tests/san/form_choice_host.cpp over round_form 4..7: every combination of the launch's fields with PT_ROUND_SKIP set.  The skip forms take
     exactly the launches the plain and the flat form would have served, in the normal build; everything else, and the contracted
     build, chooses as without the bit."""
     assert os.path.exists(HIPCC), "the harness includes csrc/pt_device.h, which needs the HIP headers: no hipcc on this host"
-    exe = str(tmp_path / "skip_form_choice_host")
+    exe = str(tmp_path / "form_choice_host")
     subprocess.check_call([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra",
                            "-Wno-unused-parameter", "-I" + os.path.join(ROOT, "cuda-pathtracer_amd", "csrc"), "-o", exe,
-                           os.path.join(ROOT, "tests", "san", "skip_form_choice_host.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+                           os.path.join(ROOT, "tests", "san", "form_choice_host.cpp")])
+    out = subprocess.run([exe, "4", "8", "1"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
     import itertools
     seen = set()
