@@ -59,7 +59,11 @@ endif
 clean:
 	rm -f $(LIB) $(ORACLE) $(REFLIB) $(GLLIB)
 
-.PHONY: all lib oracle oracle-ref gl clean san
+# the flags every unit is compiled with, for tools that compile one to an ISA listing (scripts/kernel_listing.py): make -s hipflags
+hipflags:
+	@echo '$(HIPFLAGS)'
+
+.PHONY: all lib oracle oracle-ref gl clean san hipflags
 
 # sanitizer harness of the HOST half (parsers, decoders, builder): g++ with ASan + UBSan over the same sources the library is
 # built from; run by tests/test_sanitizers.py (GPU sanitizers are not available: the device half is covered by the parity suite)

@@ -69,21 +69,6 @@ namespace ptamd {
 #ifndef PT_RS_WAVES_PER_EU
 #define PT_RS_WAVES_PER_EU 6
 #endif
-#ifndef PT_CAM_FROM_KERNARG
-#define PT_CAM_FROM_KERNARG 1
-#endif
-#ifndef PT_LEAF_MIN
-#define PT_LEAF_MIN 64u /* lanes parked at a leaf that end a box phase early (64 = only when all are parked) */
-#endif
-#ifndef PT_ASM_WALK
-#define PT_ASM_WALK 1
-#endif
-#ifndef PT_ASM_LEAF_WIDE
-#define PT_ASM_LEAF_WIDE 0
-#endif
-#ifndef PT_ASM_LEAF_EXITS
-#define PT_ASM_LEAF_EXITS 7
-#endif
 #ifndef PT_ASM_LEAF
 #define PT_ASM_LEAF 1 /* hand-scheduled Moller-Trumbore (mt_test_asm) in the leaf phases of the LDS-resident restart kernel */
 #endif
@@ -133,7 +118,8 @@ PT_DEV void mt_test(float4 a, float4 b, float4 c, f3 o, f3 d, Best& best, bool s
 // lane that fails a test leaves by clearing its EXEC bit with the comparison itself (v_cmpx) instead of through hipcc's
 // s_and_saveexec / s_cbranch_execz / s_or_b64 group per early exit and its s_and / s_or chains for the (t, index) rule: 2 scalar
 // instructions per triangle instead of ~30.  The CU's single scalar pipe issues half as many instructions per clock as its vector
-// pipes and the resident kernel keeps both ~58 % busy (scripts/ubench/ifetch_rate.hip, profiles/r04_notes.md).
+// pipes and the resident kernel keeps both ~58 % busy (scripts/ubench/ifetch_rate.hip, profiles/r04_notes.md).  The three
+// s_cbranch_execz let a wave whose lanes have all failed skip the rest: −0.6 % on the headline without them, +0.8 % with them.
 // NaN behaviour is the reference's: every rejection is written as the negation it is in intersection.cuh:110-128
 // (`det < eps`, `u < 0 || u > 1`, `v < 0 || u + v > 1` reject; an unordered comparison does not), `t > 0` accepts.
 // The (t, index) rule `t < best.t || (t == best.t && idx < best.idx && best.idx != PT_END)`: among lanes with t <= best.t,
@@ -162,9 +148,7 @@ PT_DEV void mt_test_asm(float4 a, float4 b, float2 c, f3 o, f3 d, Best& best)
       "v_mul_f32 %[t1], %[e1z], %[pz]\n\t"
       "v_add_f32 %[det], %[t1], %[t0]\n\t"
       "v_cmpx_ngt_f32 vcc, 0x33d6bf95, %[det]\n\t"       // keep !(1e-7f > det)
-#if PT_ASM_LEAF_EXITS & 1
       "s_cbranch_execz 9f\n\t"
-#endif
       // inv_det = rcp_exact_in_range(det); t_vec = o - v0 fills the wait state a transcendental's consumer needs
       "v_rcp_f32 %[inv], %[det]\n\t"
       "v_sub_f32 %[v0x], %[ox], %[v0x]\n\t"
@@ -185,9 +169,7 @@ PT_DEV void mt_test_asm(float4 a, float4 b, float2 c, f3 o, f3 d, Best& best)
       "v_mul_f32 %[u], %[t0], %[inv]\n\t"
       "v_cmpx_ngt_f32 vcc, 0, %[u]\n\t"                  // keep !(u < 0)
       "v_cmpx_nlt_f32 vcc, 1.0, %[u]\n\t"                // keep !(u > 1)
-#if PT_ASM_LEAF_EXITS & 2
       "s_cbranch_execz 9f\n\t"
-#endif
       // qvec = cross(t_vec, e1)
       "v_mul_f32 %[qx], %[e1z], %[v0y]\n\t"
       "v_mul_f32 %[t0], %[e1y], %[v0z]\n\t"
@@ -208,9 +190,7 @@ PT_DEV void mt_test_asm(float4 a, float4 b, float2 c, f3 o, f3 d, Best& best)
       "v_cmpx_ngt_f32 vcc, 0, %[v]\n\t"                  // keep !(v < 0)
       "v_add_f32 %[t0], %[u], %[v]\n\t"
       "v_cmpx_nlt_f32 vcc, 1.0, %[t0]\n\t"               // keep !(u + v > 1)
-#if PT_ASM_LEAF_EXITS & 4
       "s_cbranch_execz 9f\n\t"
-#endif
       // t = dot(e2, qvec) * inv_det
       "v_mul_f32 %[t0], %[e2x], %[qx]\n\t"
       "v_mul_f32 %[t1], %[e2y], %[qy]\n\t"
@@ -297,7 +277,7 @@ PT_DEV void walk_init(Walk& w, f3 o, f3 d, uint32_t n_nodes, bool asm_scaled = f
 
 // Box tests until this lane holds a leaf (leaf_count != 0) or its walk is over.
 // walk_min > 1: the box phase also ends once fewer than walk_min lanes of the wave are still walking (the rest are
-// parked at a leaf or done); the walkers keep their place.
+// parked at a leaf or done); the walkers keep their place.  (Ending it once 8 – 32 lanes are PARKED instead measured ±0.5 %.)
 template <bool STATS>
 PT_DEV void walk_to_leaf(const float4* nodes, Walk& w, uint32_t& leaf_first, uint32_t& leaf_count,
                          uint32_t& n_nodes_visited, uint32_t& wave_node_iters, uint32_t walk_min = 1u)
@@ -341,9 +321,6 @@ PT_DEV void walk_to_leaf(const float4* nodes, Walk& w, uint32_t& leaf_first, uin
       leaf_count = count;
       break;
     }
-    // leave the box phase early once PT_LEAF_MIN lanes of the wave are parked at a leaf: they
-    // would otherwise idle until the slowest walker finds its own (the walkers keep their place)
-    if (PT_LEAF_MIN < 64 && (uint32_t)__popcll(__ballot(1)) + PT_LEAF_MIN <= lanes_in) break;
     if (walk_min > 1u && (uint32_t)__popcll(__ballot(1)) < walk_min) break;
   }
   w.node = node;
@@ -380,9 +357,7 @@ PT_DEV void walk_to_leaf_lds_state(uint32_t& state, uint32_t lnk, const Walk& w,
   uint32_t walkers;   // lanes still in the box loop; the loop runs while walkers >= walk_min (walk_min 1: until none is left)
   asm volatile(
       "s_mov_b64 %[save], exec\n\t"
-#ifdef PT_WALK_PRIO
       "s_setprio " PT_STR(PT_WALK_PRIO) "\n\t"
-#endif
       "v_cmp_gt_u32 vcc, 0x8000, %[st]\n\t"
       "s_and_b64 exec, exec, vcc\n\t"
       "s_cbranch_execz 2f\n\t"
@@ -422,9 +397,7 @@ PT_DEV void walk_to_leaf_lds_state(uint32_t& state, uint32_t lnk, const Walk& w,
       "s_cbranch_scc1 1b\n\t"
       "2:\n\t"
       "s_mov_b64 exec, %[save]\n\t"
-#ifdef PT_WALK_PRIO
       "s_setprio 0\n\t"
-#endif
       : [st] "+v"(state), [lw] "=&v"(link_word), [save] "=&s"(save), [walkers] "=&s"(walkers)
       : [wmin] "s"(walk_min), [lnk] "v"(lnk), [ix] "v"(w.inv.x), [iy] "v"(w.inv.y), [iz] "v"(w.inv.z),
         [nx] "v"(w.noi.x), [ny] "v"(w.noi.y), [nz] "v"(w.noi.z), [best] "v"(w.best.t * PT_T_SCALE)
@@ -483,15 +456,14 @@ PT_DEV void traverse_bvh(const float4* nodes, const float4* tris, uint32_t n_nod
                          uint32_t& wave_tri_iters, uint32_t* idle3)
 {
   Walk w;
-  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS && PT_ASM_WALK);
+  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS);
   if (STATS) w.alive = (uint32_t)__popcll(__ballot(1));
   // LDS byte address of the node table (low 32 bits of the flat address of an LDS object)
   const uint32_t lds_nodes = (uint32_t)(uintptr_t)nodes;
   for (;;) {
     uint32_t leaf_first, leaf_count;
-    if (NODES_IN_LDS && !STATS && PT_ASM_WALK) walk_to_leaf_lds(lds_nodes, w, leaf_first, leaf_count);
+    if (NODES_IN_LDS && !STATS) walk_to_leaf_lds(lds_nodes, w, leaf_first, leaf_count);
     else walk_to_leaf<STATS>(nodes, w, leaf_first, leaf_count, n_nodes_visited, wave_node_iters);
-    // a box phase can end early (PT_LEAF_MIN) with this lane still walking: no leaf and not at the end
     if (leaf_count != 0u) walk_leaf<STATS>(tris, w, leaf_first, leaf_count, n_tris, wave_tri_iters);
     else if (w.node == PT_END) break;
   }
@@ -550,7 +522,6 @@ PT_DEV ConstF as_constant(const float4* q) { return (ConstF)(uintptr_t)q; }
 // device functions use it must take the launch constants as its FIRST by-value argument — which is what this macro spells, so
 // that a kernel cannot be written otherwise by accident.
 #define PT_KERNEL_PARAMS const KParams p
-#if PT_CAM_FROM_KERNARG
 template <typename T>
 PT_DEV T karg_load(uint32_t byte_offset)
 {
@@ -560,17 +531,7 @@ PT_DEV T karg_load(uint32_t byte_offset)
   asm volatile("" : "+s"(q));
   return *(const __attribute__((address_space(4))) T*)(q + byte_offset);
 }
-#ifndef PT_KARG_ALL
-#define PT_KARG_ALL 1
-#endif
-#if PT_KARG_ALL
 #define PT_KARG(p, field) karg_load<decltype(KParams::field)>((uint32_t)__builtin_offsetof(KParams, field))
-#else
-#define PT_KARG(p, field) ((p).field)
-#endif
-#else
-#define PT_KARG(p, field) ((p).field)
-#endif
 
 PT_DEV Nearest nearest_lights(const KParams& p, f3 o, f3 d, Nearest n)
 {
@@ -790,16 +751,11 @@ PT_DEV void path_begin(const KParams& p, uint32_t x, uint32_t y, Path& st, uint3
   // The 14 camera constants are only needed here, once per tile in the persistent kernels: they are re-read from the
   // kernel-argument segment (KParams is every kernel's first argument) behind a compiler barrier instead of being kept
   // in SGPRs for the whole launch, where they cost the round loop a dozen scalar spills (v_writelane / v_readlane).
-#if PT_CAM_FROM_KERNARG
   ConstF cam = (ConstF)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(KParams, cam_pos));
   asm volatile("" : "+s"(cam));
   const f3 cam_pos = mk3(cam[0], cam[1], cam[2]), cam_p0 = mk3(cam[3], cam[4], cam[5]);
   const f3 cam_u = mk3(cam[6], cam[7], cam[8]), cam_v = mk3(cam[9], cam[10], cam[11]);
   const float focus_dist = cam[12], aperture = cam[13];
-#else
-  const f3 cam_pos = p.cam_pos, cam_p0 = p.cam_p0, cam_u = p.cam_u, cam_v = p.cam_v;
-  const float focus_dist = p.focus_dist, aperture = p.aperture;
-#endif
   // generateRay (intersection.cuh:75-97), pixel-invariant terms precomputed on the host
   const int half_w = (int)(width / 2u), half_h = (int)(PT_KARG(p, height) / 2u);
   const f3 screen_pos = (cam_p0 + (cam_u * (float)((int)x - half_w))) + (cam_v * (float)((int)y - half_h));
@@ -1128,7 +1084,7 @@ __global__ void __launch_bounds__(BLOCK, PT_TILE_WAVES_PER_EU) pt_megakernel(PT_
   extern __shared__ float4 s_mem[];
   const float4* s_nodes;
   const float4* s_tris;
-  stage_scene<KIND, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK>(p, s_mem, s_nodes, s_tris);
+  stage_scene<KIND, LDS_RESIDENT, LDS_RESIDENT && !STATS>(p, s_mem, s_nodes, s_tris);
 
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   // BLOCK/64 waves as a 2 x (BLOCK/128) grid of 8x8 tiles: the block covers 16 x (BLOCK/16) pixels
@@ -1159,7 +1115,7 @@ __global__ void __launch_bounds__(PT_PERSISTENT_THREADS, PT_PERSISTENT_WAVES_PER
   extern __shared__ float4 s_mem[];
   const float4* s_nodes;
   const float4* s_tris;
-  stage_scene<KIND, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK>(p, s_mem, s_nodes, s_tris);
+  stage_scene<KIND, LDS_RESIDENT, LDS_RESIDENT && !STATS>(p, s_mem, s_nodes, s_tris);
 
   const uint32_t lane = threadIdx.x & 63u;
   Counters cnt = {};
@@ -1321,7 +1277,7 @@ PT_DEV void traverse_round_deferring(const float4* nodes, const float4* tris, ui
   const uint32_t round_min = round_defer & 0xFFu;
   const uint32_t leaf_defer_knob = (round_defer >> 8) == 0xFFu ? PT_LEAF_DEFER_AUTO : round_defer >> 8;
   Walk w;
-  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS && PT_ASM_WALK);
+  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS);
   w.best = best;
   const uint32_t n_start = (uint32_t)__popcll(__ballot(node != PT_END));   // (a pending lane enters like any other)
   const uint32_t t_eff = round_threshold(n_start, round_min, round_div, round_div_m16);
@@ -1333,7 +1289,7 @@ PT_DEV void traverse_round_deferring(const float4* nodes, const float4* tris, ui
   if (STATS) w.alive = (uint32_t)__popcll(__ballot(1));
   const uint32_t lds_nodes = (uint32_t)(uintptr_t)nodes;
   // (`node` itself stays live through the first box phase and is decoded where it is needed: one register, none across shading)
-  if (NODES_IN_LDS && !STATS && PT_ASM_WALK) {
+  if (NODES_IN_LDS && !STATS) {
     // codes as the links hold them: a continuation is a box's LDS address or 0xFFFF
     uint32_t state = round_is_pending(node) ? round_pending_leaf(node) : walk_lds_state(lds_nodes, node);
     const uint32_t lnk = walk_lds_link_offset(w);
@@ -1396,7 +1352,7 @@ PT_DEV void traverse_round(const float4* nodes, const float4* tris, uint32_t n_n
     return;
   }
   Walk w;
-  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS && PT_ASM_WALK);
+  walk_init(w, o, d, n_nodes, NODES_IN_LDS && !STATS);
   w.best = best;
   w.node = node;
   const uint32_t n_start = (uint32_t)__popcll(__ballot(node != PT_END));
@@ -1405,7 +1361,7 @@ PT_DEV void traverse_round(const float4* nodes, const float4* tris, uint32_t n_n
   if (t_eff < 1u) t_eff = 1u;
   if (STATS) w.alive = (uint32_t)__popcll(__ballot(1));
   const uint32_t lds_nodes = (uint32_t)(uintptr_t)nodes;
-  if (NODES_IN_LDS && !STATS && PT_ASM_WALK) {
+  if (NODES_IN_LDS && !STATS) {
     uint32_t state = walk_lds_state(lds_nodes, w.node);
     const uint32_t lnk = walk_lds_link_offset(w);
     for (;;) {
@@ -1456,17 +1412,12 @@ struct Stack4 {
 #define PT_RS4_THREADS 1024     /* workgroup size of the wide-walk instantiation: ONE workgroup per CU, so one copy of the LDS treelet
                                    (256 / 512 / 1024 threads: atrium 1177 / 1233 / 1278, tessellated indoor 2868 / 2966 / 3081 Msamples/s) */
 #endif
-#ifndef PT_TREELET_SOA
-#define PT_TREELET_SOA 1        /* the LDS treelet chunk-major: 16-byte chunk q of node n at [q][n] instead of [n][q].  A wave's lanes read the
-                                   SAME chunk of DIFFERENT nodes: node-major, 128-byte (64-byte) nodes put them all on two (four) of the sixteen
-                                   4-bank groups — half of all LDS cycles of the atrium walk were bank conflicts (profiles/r04_base_*) —,
-                                   chunk-major they spread over all sixteen by node index */
-#endif
+// The LDS treelet is chunk-major: 16-byte chunk q of node n at [q][n] instead of [n][q].  A wave's lanes read the SAME chunk of
+// DIFFERENT nodes: node-major, 128-byte (64-byte) nodes put them all on two (four) of the sixteen 4-bank groups — half of all LDS
+// cycles of the atrium walk were bank conflicts (profiles/r04_base_*) —, chunk-major they spread over all sixteen by node index.
 #define PT_TREELET_STRIDE 512u  /* nodes per chunk plane of a 128-byte-node treelet (64-byte nodes: twice as many); the treelet's LDS region is
-                                   always 64 KB in this form, whatever the number of nodes staged */
-#ifndef PT_PUSH_BRANCHFREE
-#define PT_PUSH_BRANCHFREE 1    /* four-wide float walk: hit children pushed without branches when the LDS part of the stack has room */
-#endif
+                                   always 64 KB (pt_launch.h: kRestartTreeletRegionBytes), whatever the number of nodes staged */
+static_assert(8u * PT_TREELET_STRIDE * 16u == kRestartTreeletRegionBytes, "lay_out_lds sizes the treelet's region: eight chunk planes of 16-byte words");
 #ifndef PT_RS4_WAVES_PER_EU
 #define PT_RS4_WAVES_PER_EU 4   /* measured on the atrium (leaf records fetched in one batch): 4 / 5 / 6 waves per SIMD = 1069 / 954 / 798 Msamples/s (5 and 6 spill) */
 #endif
@@ -1497,13 +1448,10 @@ PT_DEV uint2 stack4_read(const Stack4& s, uint32_t k)
   return s.spill[(size_t)(k - s.lds_entries) * 64u];
 }
 
-#ifndef PT_POP_BATCH
-#define PT_POP_BATCH 1          /* pops after a leaf read four stack entries per LDS round trip (stack4_pop4) */
-#endif
 // The pop that follows a leaf.  A hit has usually just shortened the ray, so most of what the lane stacked on its way down lies
 // beyond it now: the plain loop below discards those entries one LDS round trip at a time (a leaf phase of the atrium took 7 000
 // cycles, most of them here: profiles/r04_notes.md).  This form reads the four entries under the top in ONE round trip and takes
-// the first whose distance does not lie beyond the best hit; entries in the global continuation of the stack go one by one.
+// the first whose distance does not lie beyond the best hit (+2.3 % on the atrium); entries in the global continuation of the stack go one by one.
 // (Used after leaves only: behind the hand-scheduled visit, whose pop already has its first entry read ahead, the same loop
 // measured -2 % against the visit's own one-entry-at-a-time asm loop.)
 PT_DEV uint32_t stack4_pop4(const Stack4& s, uint32_t& sp, float best_t)
@@ -1543,10 +1491,7 @@ PT_DEV uint32_t stack4_pop(const Stack4& s, uint32_t& sp, float best_t)
   return PT_NONE;
 }
 
-#ifndef PT_ASM_FETCH
-#define PT_ASM_FETCH 1          /* four-wide float walk: a node's eight 16-byte words fetched by fetch_node4 (below) instead of compiled loads */
-#endif
-// A visit's fetch: lanes whose node lies in the LDS treelet (cur < top_n; chunk-major, PT_TREELET_SOA) read it there, the others
+// A visit's fetch of the four-wide float walk: lanes whose node lies in the LDS treelet (cur < top_n; chunk-major) read it there, the others
 // read their node's line from L2 — BOTH KINDS IN FLIGHT TOGETHER.  Compiled, the two branches load into the same registers and the
 // compiler orders them: the global loads first, then `s_waitcnt vmcnt(..)` in front of every ds_read (it cannot know that the two
 // write disjoint lanes), so the treelet's LDS latency — bank conflicts included — came AFTER the memory latency in every box
@@ -1591,9 +1536,6 @@ PT_DEV void fetch_node4(const float4* nodes4, const Stack4& stk, uint32_t cur, u
         [p6] "i"(6u * PLANE_BYTES), [p7] "i"(7u * PLANE_BYTES)
       : "vcc", "scc", "memory");
 }
-#ifndef PT_ASM_SELECT
-#define PT_ASM_SELECT 1         /* four-wide float walk: what follows the box tests of a visit — ranks, pushes, the nearest child or a pop — hand-scheduled */
-#endif
 // Second half of a visit of the four-wide float walk, hand-scheduled: from the four box-test results (m0..m3: the lanes whose
 // child c was hit; tn: entry distances; refs / ord: the node's references and order words) to the reference the lane processes
 // next.  Hit children that are not the nearest go on the lane's LDS stack at sp + rank (rank = hit children farther along the
@@ -1692,70 +1634,43 @@ PT_DEV uint32_t walk4_select_asm(const Stack4& stk, const Walk& w, unsigned long
 // The arithmetic of a visit on a fetched node: tests the four child boxes, stacks the hit ones, returns the nearest (or pops).
 PT_DEV uint32_t walk4_compute(float4 lx, float4 ly, float4 lz, float4 hx, float4 hy, float4 hz, uint4 refs, uint4 ord, const Stack4& stk, const Walk& w, uint32_t& sp);
 
-// Visits interior node `cur`: fetches it (LDS treelet or L2), then walk4_compute.
+// Visits interior node `cur`: fetches it (LDS treelet or L2: fetch_node4), tests its boxes and selects by hand (walk4_select_asm);
+// a wave with a lane whose LDS stack part is nearly full goes through walk4_compute.
 template <bool STATS, uint32_t PLANE_BYTES = PT_TREELET_STRIDE * 16u>
 PT_DEV uint32_t walk4_visit(const float4* nodes4, const Stack4& stk, const Walk& w, uint32_t cur, uint32_t& sp, Counters* cnt = nullptr)
 {
-  float4 lx, ly, lz, hx, hy, hz;
-  uint4 refs, ord;
-#if PT_ASM_FETCH && PT_TREELET_SOA
-  {
-    pt_f4v r0, r1, r2, r3, r4, r5, r6, r7;
-    long long tv0 = 0;
-    if (STATS) tv0 = clock64();
-    pt_u2v ahead;
-    fetch_node4<PLANE_BYTES>(nodes4, stk, cur, sp, r0, r1, r2, r3, r4, r5, r6, r7, ahead);
-    if (STATS && cnt) { const long long tv1 = clock64(); if (PT_WAVE_ONE()) cnt->cyc[6] += (unsigned long long)(tv1 - tv0); }
-#if PT_ASM_SELECT
-    // Usual case, decided for the whole wave: four more entries fit into the LDS part of every lane's stack (then every entry a pop
-    // of this visit can reach is in LDS too)
-    if (__ballot(sp + 4u > stk.lds_entries) == 0ull) {
-      const float aix = __builtin_fabsf(w.inv.x), aiy = __builtin_fabsf(w.inv.y), aiz = __builtin_fabsf(w.inv.z);
-      float tn[4];
-      unsigned long long m[4];
+  pt_f4v r0, r1, r2, r3, r4, r5, r6, r7;
+  long long tv0 = 0;
+  if (STATS) tv0 = clock64();
+  pt_u2v ahead;
+  fetch_node4<PLANE_BYTES>(nodes4, stk, cur, sp, r0, r1, r2, r3, r4, r5, r6, r7, ahead);
+  if (STATS && cnt) { const long long tv1 = clock64(); if (PT_WAVE_ONE()) cnt->cyc[6] += (unsigned long long)(tv1 - tv0); }
+  // Usual case, decided for the whole wave: four more entries fit into the LDS part of every lane's stack (then every entry a pop
+  // of this visit can reach is in LDS too)
+  if (__ballot(sp + 4u > stk.lds_entries) == 0ull) {
+    const float aix = __builtin_fabsf(w.inv.x), aiy = __builtin_fabsf(w.inv.y), aiz = __builtin_fabsf(w.inv.z);
+    float tn[4];
+    unsigned long long m[4];
 #define PT_CHILD(c, X)                                                                                                   \
-      {                                                                                                                  \
-        const float tcx = __builtin_fmaf(r0.X, w.inv.x, w.noi.x), tcy = __builtin_fmaf(r1.X, w.inv.y, w.noi.y),           \
-                    tcz = __builtin_fmaf(r2.X, w.inv.z, w.noi.z);                                                        \
-        const float n0x = __builtin_fmaf(-r3.X, aix, tcx), f0x = __builtin_fmaf(r3.X, aix, tcx);                          \
-        const float n0y = __builtin_fmaf(-r4.X, aiy, tcy), f0y = __builtin_fmaf(r4.X, aiy, tcy);                          \
-        const float n0z = __builtin_fmaf(-r5.X, aiz, tcz), f0z = __builtin_fmaf(r5.X, aiz, tcz);                          \
-        const float tnear = __builtin_fmaxf(__builtin_fmaxf(n0x, n0y), n0z);                                             \
-        const float tfar = __builtin_fminf(__builtin_fminf(f0x, f0y), f0z);                                              \
-        tn[c] = __builtin_fmaxf(tnear, 0.0f);                                                                            \
-        m[c] = __ballot(tn[c] <= __builtin_fminf(tfar, w.best.t));                                                       \
-      }
-      PT_CHILD(0, x) PT_CHILD(1, y) PT_CHILD(2, z) PT_CHILD(3, w)
-#undef PT_CHILD
-      return walk4_select_asm(stk, w, m[0], m[1], m[2], m[3], tn[0], tn[1], tn[2], tn[3], r6, r7, ahead, sp);
+    {                                                                                                                    \
+      const float tcx = __builtin_fmaf(r0.X, w.inv.x, w.noi.x), tcy = __builtin_fmaf(r1.X, w.inv.y, w.noi.y),             \
+                  tcz = __builtin_fmaf(r2.X, w.inv.z, w.noi.z);                                                          \
+      const float n0x = __builtin_fmaf(-r3.X, aix, tcx), f0x = __builtin_fmaf(r3.X, aix, tcx);                            \
+      const float n0y = __builtin_fmaf(-r4.X, aiy, tcy), f0y = __builtin_fmaf(r4.X, aiy, tcy);                            \
+      const float n0z = __builtin_fmaf(-r5.X, aiz, tcz), f0z = __builtin_fmaf(r5.X, aiz, tcz);                            \
+      const float tnear = __builtin_fmaxf(__builtin_fmaxf(n0x, n0y), n0z);                                               \
+      const float tfar = __builtin_fminf(__builtin_fminf(f0x, f0y), f0z);                                                \
+      tn[c] = __builtin_fmaxf(tnear, 0.0f);                                                                              \
+      m[c] = __ballot(tn[c] <= __builtin_fminf(tfar, w.best.t));                                                         \
     }
-#endif
-    lx = make_float4(r0.x, r0.y, r0.z, r0.w); ly = make_float4(r1.x, r1.y, r1.z, r1.w); lz = make_float4(r2.x, r2.y, r2.z, r2.w);
-    hx = make_float4(r3.x, r3.y, r3.z, r3.w); hy = make_float4(r4.x, r4.y, r4.z, r4.w); hz = make_float4(r5.x, r5.y, r5.z, r5.w);
-    refs = make_uint4(f_as_u(r6.x), f_as_u(r6.y), f_as_u(r6.z), f_as_u(r6.w));
-    ord = make_uint4(f_as_u(r7.x), f_as_u(r7.y), f_as_u(r7.z), f_as_u(r7.w));
-    return walk4_compute(lx, ly, lz, hx, hy, hz, refs, ord, stk, w, sp);
+    PT_CHILD(0, x) PT_CHILD(1, y) PT_CHILD(2, z) PT_CHILD(3, w)
+#undef PT_CHILD
+    return walk4_select_asm(stk, w, m[0], m[1], m[2], m[3], tn[0], tn[1], tn[2], tn[3], r6, r7, ahead, sp);
   }
-#endif
-  if (cur < stk.top_n) {
-#if PT_TREELET_SOA
-    constexpr uint32_t S = PT_TREELET_STRIDE;
-    const LdsCU4 q = treelet_lds(stk) + cur;
-#else
-    constexpr uint32_t S = 1u;
-    const LdsCU4 q = treelet_lds(stk) + cur * 8u;
-#endif
-    lx = lds_f4(q); ly = lds_f4(q + S); lz = lds_f4(q + 2u * S); hx = lds_f4(q + 3u * S); hy = lds_f4(q + 4u * S); hz = lds_f4(q + 5u * S);
-    refs = lds_u4(q + 6u * S);
-    ord = lds_u4(q + 7u * S);
-  } else {
-    const float4* q = nodes4 + (size_t)cur * 8u;
-    lx = q[0]; ly = q[1]; lz = q[2]; hx = q[3]; hy = q[4]; hz = q[5];
-    refs = *reinterpret_cast<const uint4*>(q + 6);
-    ord = *reinterpret_cast<const uint4*>(q + 7);
-  }
-  // (references and order words are needed last, but fetched with the boxes: one round trip per visit)
-  asm volatile("" : "+v"(refs.x), "+v"(refs.y), "+v"(refs.z), "+v"(refs.w), "+v"(ord.x), "+v"(ord.y), "+v"(ord.z), "+v"(ord.w));
+  const float4 lx = make_float4(r0.x, r0.y, r0.z, r0.w), ly = make_float4(r1.x, r1.y, r1.z, r1.w), lz = make_float4(r2.x, r2.y, r2.z, r2.w);
+  const float4 hx = make_float4(r3.x, r3.y, r3.z, r3.w), hy = make_float4(r4.x, r4.y, r4.z, r4.w), hz = make_float4(r5.x, r5.y, r5.z, r5.w);
+  const uint4 refs = make_uint4(f_as_u(r6.x), f_as_u(r6.y), f_as_u(r6.z), f_as_u(r6.w));
+  const uint4 ord = make_uint4(f_as_u(r7.x), f_as_u(r7.y), f_as_u(r7.z), f_as_u(r7.w));
   return walk4_compute(lx, ly, lz, hx, hy, hz, refs, ord, stk, w, sp);
 }
 
@@ -1786,7 +1701,6 @@ PT_DEV uint32_t walk4_compute(float4 lx, float4 ly, float4 lz, float4 hx, float4
   const uint32_t nhit = (uint32_t)__builtin_popcount(hit);
   const uint32_t ref[4] = { refs.x, refs.y, refs.z, refs.w };
   uint32_t next = PT_NONE;
-#if PT_PUSH_BRANCHFREE
   // Usual case, decided for the whole wave: four more entries fit into the LDS part of every lane's stack.  Then every child is
   // written without a branch — a hit child that is not the nearest to slot sp + rank, the others to slot sp + 3, which lies at or
   // above the new top of the stack (at most three are pushed) and is free.
@@ -1805,7 +1719,6 @@ PT_DEV uint32_t walk4_compute(float4 lx, float4 ly, float4 lz, float4 hx, float4
     sp += nhit - 1u;
     return next;
   }
-#endif
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     if ((hit >> c) & 1u) {
@@ -1855,13 +1768,8 @@ PT_DEV uint32_t walk8_visit(const float4* nodes8, const Stack4& stk, const Walk&
 {
   uint4 hd, ra, rb, pa, pb, pc;
   if (cur < stk.top_n) {
-#if PT_TREELET_SOA
     constexpr uint32_t S = PT_TREELET_STRIDE;
     const LdsCU4 q = treelet_lds(stk) + cur;
-#else
-    constexpr uint32_t S = 1u;
-    const LdsCU4 q = treelet_lds(stk) + cur * 8u;
-#endif
     hd = lds_u4(q); ra = lds_u4(q + S); rb = lds_u4(q + 2u * S); pa = lds_u4(q + 3u * S); pb = lds_u4(q + 4u * S); pc = lds_u4(q + 5u * S);
   } else {
     const uint4* q = reinterpret_cast<const uint4*>(nodes8) + (size_t)cur * 8u;
@@ -1923,13 +1831,8 @@ PT_DEV uint32_t walk4q_visit(const float4* nodesq, const Stack4& stk, const Walk
 {
   uint4 hd, rf, pa, pb;
   if (cur < stk.top_n) {
-#if PT_TREELET_SOA
     constexpr uint32_t S = 2u * PT_TREELET_STRIDE;
     const LdsCU4 q = treelet_lds(stk) + cur;
-#else
-    constexpr uint32_t S = 1u;
-    const LdsCU4 q = treelet_lds(stk) + cur * 4u;
-#endif
     hd = lds_u4(q); rf = lds_u4(q + S); pa = lds_u4(q + 2u * S); pb = lds_u4(q + 3u * S);
   } else {
     const uint4* q = reinterpret_cast<const uint4*>(nodesq) + (size_t)cur * 4u;
@@ -2048,24 +1951,19 @@ PT_DEV void traverse_round4(const KParams& p, const float4* nodes4, const float4
 #pragma unroll
       for (uint32_t k = 0; k < 3u; ++k)
         if (k < count) { r[3 * k] = t[TS * k]; r[3 * k + 1] = t[TS * k + 1]; r[3 * k + 2] = t[TS * k + 2]; }
-      if (!STATS && PT_ASM_LEAF_WIDE && small_det) {   // (wave-uniform)
+      // (the compiled test: the hand-scheduled mt_test_asm measured level here — the atrium keeps the scalar pipe 0.34 busy)
 #pragma unroll
-        for (uint32_t k = 0; k < 3u; ++k)
-          if (k < count) mt_test_asm(r[3 * k], r[3 * k + 1], make_float2(r[3 * k + 2].x, r[3 * k + 2].y), w.o, w.d, w.best);
-      } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 3u; ++k)
-          if (k < count) {
-            if (STATS) {
-              const unsigned long long act = __ballot(1);
-              if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)act) - 1)) ++cnt.wave_tri_iters;
-            }
-            mt_test<false>(r[3 * k], r[3 * k + 1], r[3 * k + 2], w.o, w.d, w.best, small_det);
+      for (uint32_t k = 0; k < 3u; ++k)
+        if (k < count) {
+          if (STATS) {
+            const unsigned long long act = __ballot(1);
+            if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)act) - 1)) ++cnt.wave_tri_iters;
           }
-      }
+          mt_test<false>(r[3 * k], r[3 * k + 1], r[3 * k + 2], w.o, w.d, w.best, small_det);
+        }
       if (STATS) cnt.tris += count < 3u ? count : 3u;
       if (count > 3u) walk_leaf<STATS>(tris, w, first + 3u, count - 3u, cnt.tris, cnt.wave_tri_iters, small_det, TS);
-      cur = PT_POP_BATCH ? stack4_pop4(stk, sp, w.best.t) : stack4_pop(stk, sp, w.best.t);
+      cur = stack4_pop4(stk, sp, w.best.t);
     }
     if (STATS && PT_WAVE_ONE()) cnt.cyc[2] += (unsigned long long)(clock64() - tb1);
     if ((uint32_t)__popcll(__ballot(cur != PT_NONE)) < t_eff) break;
@@ -2125,7 +2023,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   constexpr bool STATS = FORM.stats;
   constexpr uint32_t THREADS = LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS;
   constexpr bool DEFER = LDS_RESIDENT && FORM.defer;
-  constexpr bool SKIP = LDS_RESIDENT && PT_ASM_WALK && FORM.skip;
+  constexpr bool SKIP = LDS_RESIDENT && FORM.skip;
   constexpr bool FLAT = LDS_RESIDENT && FORM.flat;
   constexpr bool LEAN = LDS_RESIDENT && FORM.lean;
   // The list form (adaptive sampling): a ticket names 64 consecutive entries of the active list ("chunk") times a sample index k
@@ -2139,7 +2037,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   const float4* s_nodes;
   const float4* s_tris;
   PT_STAMP(0);
-  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK, SKIP>(p, s_mem, s_nodes, s_tris);
+  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS, SKIP>(p, s_mem, s_nodes, s_tris);
   // scenes that do not fit in LDS are walked in the four-wide form; LDS then holds the waves' stacks
   constexpr bool WIDE = !LDS_RESIDENT;
 
@@ -2153,14 +2051,10 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   stk.top_n = WIDE ? p.treelet_nodes : 0u;
   constexpr uint32_t NODE_F4 = FORM.wide == 2 ? 4u : 8u;   // float4 per wide node
   // float4s of the treelet's LDS region: chunk-major it is 64 KB whatever the number of nodes staged (plane stride fixed at compile time)
-  const uint32_t treelet_f4 = !WIDE ? 0u : (PT_TREELET_SOA ? (p.treelet_nodes ? 8u * PT_TREELET_STRIDE : 0u) : p.treelet_nodes * NODE_F4);
+  const uint32_t treelet_f4 = (WIDE && p.treelet_nodes) ? 8u * PT_TREELET_STRIDE : 0u;
   if (WIDE) {
-#if PT_TREELET_SOA
     constexpr uint32_t PLANE = PT_TREELET_STRIDE * (8u / NODE_F4);   // nodes per chunk plane
     for (uint32_t i = threadIdx.x; i < p.treelet_nodes * NODE_F4; i += blockDim.x) s_mem[(i % NODE_F4) * PLANE + i / NODE_F4] = p.nodes4[i];
-#else
-    stage_to_lds(s_mem, p.nodes4, p.treelet_nodes * NODE_F4);
-#endif
     __syncthreads();
   }
   PT_STAMP(1);
@@ -2570,7 +2464,7 @@ __global__ void __launch_bounds__(PT_SP_THREADS, PT_SP_WAVES_PER_EU) pt_megakern
   extern __shared__ float4 s_mem[];
   const float4* s_nodes;
   const float4* s_tris;
-  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS && PT_ASM_WALK>(p, s_mem, s_nodes, s_tris); // zeroes nothing: control words are set below
+  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS>(p, s_mem, s_nodes, s_tris); // zeroes nothing: control words are set below
   float4* rays = s_mem + (LDS_RESIDENT ? (p.n_nodes * 4u + p.n_bvh_tris * 3u) : 0u); // [NS][64][2]
   uint32_t* word = reinterpret_cast<uint32_t*>(rays + NS * 64u * 2u);               // [NS] n << 16 | claimed
   uint32_t* done = word + NS;                                                          // [NS]
@@ -2683,7 +2577,7 @@ __global__ void __launch_bounds__(PT_SP_THREADS, PT_SP_WAVES_PER_EU) pt_megakern
           if (!have && rank < got) {
             const uint32_t r = base + rank;
             const float4 ra = rays[(b * 64u + r) * 2u + 0u], rb = rays[(b * 64u + r) * 2u + 1u];
-            walk_init(w, mk3(ra.w, rb.x, rb.y), mk3(ra.x, ra.y, ra.z), p.n_nodes, LDS_RESIDENT && !STATS && PT_ASM_WALK);
+            walk_init(w, mk3(ra.w, rb.x, rb.y), mk3(ra.x, ra.y, ra.z), p.n_nodes, LDS_RESIDENT && !STATS);
             have = true;
             my_slot = (b << 8) | r;
           }
@@ -2700,7 +2594,7 @@ __global__ void __launch_bounds__(PT_SP_THREADS, PT_SP_WAVES_PER_EU) pt_megakern
       }
       if (have) {
         uint32_t leaf_first, leaf_count;
-        if (LDS_RESIDENT && !STATS && PT_ASM_WALK) walk_to_leaf_lds(lds_nodes, w, leaf_first, leaf_count);
+        if (LDS_RESIDENT && !STATS) walk_to_leaf_lds(lds_nodes, w, leaf_first, leaf_count);
         else walk_to_leaf<STATS>(s_nodes, w, leaf_first, leaf_count, cnt.nodes, cnt.wave_node_iters);
         if (leaf_count != 0u) {
           walk_leaf<STATS>(s_tris, w, leaf_first, leaf_count, cnt.tris, cnt.wave_tri_iters);
@@ -2929,7 +2823,7 @@ __global__ void __launch_bounds__(THREADS, WPE) pt_trace_queue_kernel(PT_KERNEL_
         for (uint32_t k = 0; k < 3u; ++k)
           if (k < count) mt_test<false>(r[3 * k], r[3 * k + 1], r[3 * k + 2], w.o, w.d, w.best, small_det);
         if (count > 3u) walk_leaf<false>(p.tris_bvh, w, first + 3u, count - 3u, cnt.tris, cnt.wave_tri_iters, small_det);
-        cur = PT_POP_BATCH ? stack4_pop4(stk, sp, w.best.t) : stack4_pop(stk, sp, w.best.t);
+        cur = stack4_pop4(stk, sp, w.best.t);
       }
       if (cur == PT_NONE) {   // the walk is over: light spheres, the record, and the lane is free again
         Nearest nr;
@@ -3079,8 +2973,6 @@ static const void* restart_entry(int variant, bool lds_resident)
   return restart_entry_among(std::make_integer_sequence<int, PT_RS_FORMS>(), variant, lds_resident);
 }
 
-// chunk-major treelet (PT_TREELET_SOA): bytes of its LDS region and the most 128-byte nodes it can hold (0: node-major, sized by the node count)
-uint32_t restart_treelet_region_bytes() { return PT_TREELET_SOA ? 8u * PT_TREELET_STRIDE * 16u : 0u; }
 uint32_t restart_threads(bool lds_resident) { return lds_resident ? PT_RS_THREADS : PT_RS4_THREADS; }
 // wide walk: resident workgroups per CU the launch bounds aim for (their LDS share holds the treelet and the waves' stacks)
 uint32_t restart_wide_blocks_per_cu() { return (PT_RS4_WAVES_PER_EU * 256u) / PT_RS4_THREADS; }

@@ -33,7 +33,8 @@ hipError_t form_blocks_per_cu(const KernelForm& f, int* out);
 // n_blocks: the grid of every form that takes tickets (the tile kernels' follows from the launch's rows).  Nothing to do: hipSuccess
 hipError_t launch_form(const KernelForm& f, const KParams& p, uint32_t n_blocks, hipStream_t stream);
 uint32_t restart_threads(bool lds_resident);
-uint32_t restart_treelet_region_bytes();   // != 0: the wide walk's LDS treelet is chunk-major in a region of this size (pt_kernels.hip: PT_TREELET_SOA)
+// the wide walk's LDS treelet: chunk-major in a region of this size whenever a node is staged (pt_kernels.hip: PT_TREELET_STRIDE)
+constexpr uint32_t kRestartTreeletRegionBytes = 64u * 1024u;
 uint32_t restart_wide_blocks_per_cu();
 hipError_t launch_resolve(const KParams& p, hipStream_t stream);
 // gamma step of the tonemap as a table (pt_kernels.hip: gamma_byte): 258 floats, and its exhaustive check

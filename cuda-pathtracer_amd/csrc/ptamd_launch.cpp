@@ -315,13 +315,12 @@ void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, con
   // (the list form keeps them in the global slab: it is compiled for that)
   const uint32_t pools = (ctx->knobs.pool_in_lds && ctx->knobs.pool_in_lds_wide && !ad) ? waves * PT_POOL_LDS_BYTES : 0u;
   // (the same LDS bytes hold twice as many 64-byte nodes)
-  // chunk-major treelet (pt_kernels.hip: PT_TREELET_SOA): a region of fixed size whatever the number of nodes staged
-  const uint32_t region = restart_treelet_region_bytes();
+  // the treelet is chunk-major: a region of fixed size whatever the number of nodes staged
+  const uint32_t region = kRestartTreeletRegionBytes;
   uint32_t treelet_want = ctx->knobs.treelet_nodes * (128u / node_bytes);
-  if (region && treelet_want > region / node_bytes) treelet_want = region / node_bytes;
-  uint32_t treelet = treelet_want < p.n_nodes4 ? treelet_want : p.n_nodes4;
-  if (!region && treelet * node_bytes + waves * 512u * 4u + pools > share) treelet = (share - pools - waves * 512u * 4u) / node_bytes;   // keep >= 4 stack entries
-  const uint32_t treelet_bytes = region ? (treelet ? region : 0u) : treelet * node_bytes;
+  if (treelet_want > region / node_bytes) treelet_want = region / node_bytes;
+  const uint32_t treelet = treelet_want < p.n_nodes4 ? treelet_want : p.n_nodes4;
+  const uint32_t treelet_bytes = treelet ? region : 0u;
   uint32_t fit = (share - pools - treelet_bytes) / (waves * 512u);
   if (const char* ev = tuning_env("PTAMD_STACK_LDS")) { int v = std::atoi(ev); if (v >= 1 && (uint32_t)v <= fit) fit = (uint32_t)v; }   // tuning knob
   p.treelet_nodes = treelet;

@@ -6,9 +6,9 @@ scheduling barriers, so the listing differs slightly from the shipped code).   p
 VARIANT=6 counts the generic instantiation of a resident scene (PT_RS_GENERIC) instead of the shipped one (0), VARIANT=8 the flat
 one (PT_RS_FLAT: flat scenes under a uniform environment), VARIANT=9 / 10 the skip forms of the flat and the shipped one
 (PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP)."""
-import os, re, subprocess, sys, tempfile, collections
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")
+import os, re, sys, collections
+from kernel_listing import CSRC, listing
+SRC = os.path.join(CSRC, "pt_kernels.hip")
 MARKS = [  # (unique source anchor, marker name) — the marker goes in front of the anchor
     ("    if (!idle) {\n      if (!walking) {\n        best.t = PT_MAX_DIST;", "round_begin"),
     ("      } else if (WIDE) {\n        traverse_round4<STATS, FORM.wide>", "traverse_begin"),
@@ -27,14 +27,7 @@ def marked_listing():
     for anchor, name in MARKS:
         assert s.count(anchor) == 1, (name, s.count(anchor))
         s = s.replace(anchor, 'asm volatile("; PT_MARK %s" ::: "memory");\n' % name + anchor)
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "pt_kernels.hip"); open(src, "w").write(s)
-        out = os.path.join(td, "k.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                               "-fno-vectorize", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cuda-pathtracer_amd", "host"),
-                               "-I" + os.path.join(ROOT, "cuda-pathtracer_amd", "csrc"), "-x", "hip", "--cuda-device-only", "-S", "-o", out, src],
-                              stderr=subprocess.DEVNULL)
-        return open(out).read().split("\n")
+    return listing("pt_kernels.hip", s).split("\n")
 
 
 def regions(lines, variant):

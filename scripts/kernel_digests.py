@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the gfx950 code of every kernel and device function in pt_kernels.hip and pt_kernels_fma.hip.
 
-Compiles each translation unit device-only to assembly with the Makefile's code-generation flags and hashes each function's
+Takes each translation unit's listing as the Makefile compiles it (scripts/kernel_listing.py) and hashes each function's
 body (comments dropped, basic-block label numbers normalised, so adding a function elsewhere does not move the digest of another).  Used by
 tests/test_denoise_cpu.py to show that a change leaves the code of existing kernels byte for byte as it was:
 
@@ -11,23 +11,20 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_listing
+
 UNITS = ("pt_kernels.hip", "pt_kernels_fma.hip")
 
 
-def listing(unit, out_dir):
-    out = os.path.join(out_dir, unit + ".s")
-    inc = ["-I" + os.path.join(ROOT, d) for d in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
-                           "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", unit)])
-    with open(out) as f:
-        return f.read()
+def listing(unit, out_dir=None):
+    """kernel_listing.listing(unit) in the form this script had it first: the text, and a copy in out_dir/<unit>.s"""
+    text = kernel_listing.listing(unit)
+    if out_dir is not None:
+        with open(os.path.join(out_dir, unit + ".s"), "w") as f:
+            f.write(text)
+    return text
 
 
 def function_digests(text):
@@ -51,8 +48,7 @@ def function_digests(text):
 
 
 def digests():
-    with tempfile.TemporaryDirectory() as d:
-        return {unit: function_digests(listing(unit, d)) for unit in UNITS}
+    return {unit: function_digests(listing(unit)) for unit in UNITS}
 
 
 if __name__ == "__main__":

@@ -4,10 +4,8 @@ scenes and group cuts, matrices, skins, targets and weights from a seed, the res
 pt_morph.h's arithmetic in numpy, the composition of mirrors a morph stands for, the comparisons, and the rig kernels' metadata."""
 import json
 import os
-import re
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -275,15 +273,8 @@ RIG_KERNELS = {"12pt_rig_facesILb0ELj1EE": 76, "12pt_rig_facesILb0ELj2EE": 106, 
 def kernel_metadata(unit):
     """{kernel name: metadata} of csrc/`unit`'s code object, compiled here with the Makefile's code-generation flags."""
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    import kernel_digests
-    with tempfile.TemporaryDirectory() as d:
-        text = kernel_digests.listing(unit, d)
-    out = {}
-    for n in re.findall(r"\.name:\s+(_ZN5ptamd\S+)", text):
-        i = text.index(".name:           " + n)
-        block = text[i:i + 4000].split("\n  - ")[0]
-        out[n] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-    return out
+    import kernel_listing
+    return kernel_listing.all_metadata(kernel_listing.listing(unit))
 
 
 def assert_rig_kernels_have_no_scratch():

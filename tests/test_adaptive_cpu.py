@@ -5,12 +5,15 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
+import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
+from kernel_listing import metadata as _meta   # noqa: E402
 f32 = np.float32
 
 
@@ -195,24 +198,14 @@ def test_argument_errors_are_reported_not_crashed(P):
 
 # ---------------------------------------------------------------- gfx950 code
 
-def _listing(unit, d):
-    inc = ["-I" + os.path.join(ROOT, x) for x in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    out = os.path.join(d, unit + ".s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", unit)], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _meta(text, name):
-    i = text.index(".name:           " + name)
-    block = text[i:i + 4000].split("\n  - ")[0]
-    return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
+def _listing(unit):
+    if kernel_listing.hipcc() is None:
+        pytest.skip("no hipcc on this host")
+    return kernel_listing.listing(unit)
 
 
 def test_select_and_resolve_kernels_have_no_scratch():
-    with tempfile.TemporaryDirectory() as d:
-        text = _listing("pt_adaptive.hip", d)
+    text = _listing("pt_adaptive.hip")
     names = re.findall(r"\.name:\s+(_ZN5ptamd\d+pt_adaptive_\w+)", text)
     assert len(names) == 5, names
     for n in names:
@@ -224,8 +217,7 @@ def test_list_form_of_the_restart_kernel_keeps_nothing_in_scratch_for_resident_s
     """The list form of an LDS-resident scene is compiled for the launch constants of the shipped instantiation (PT_RS_PLAIN: static
     camera, pools in LDS, no XCD regions, no interleaved bands) and, like it, keeps nothing in scratch.  The four-wide list form may
     keep no more than the shipped four-wide kernel it derives from, which is not free of scratch itself."""
-    with tempfile.TemporaryDirectory() as d:
-        text = _listing("pt_kernels.hip", d)
+    text = _listing("pt_kernels.hip")
     pre = "_ZN5ptamd21pt_megakernel_restartI"
     m = _meta(text, pre + "Lb1ELi7EEEvNS_7KParamsE")
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m

@@ -263,13 +263,10 @@ def test_existing_kernels_compile_to_the_same_code(digests):
 
 def test_new_kernels_have_no_scratch(digests):
     import re
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        text = digests.listing("pt_kernels.hip", d)
+    import kernel_listing
+    text = kernel_listing.listing("pt_kernels.hip")
     names = re.findall(r"\.name:\s+(_ZN5ptamd(?:17pt_denoise_kernel|18pt_features_kernel)\S+)", text)
     assert len(names) == 6, names
     for n in names:
-        i = text.index(".name:           " + n)
-        block = text[i:i + 4000].split("\n  - ")[0]
-        meta = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
+        meta = kernel_listing.metadata(text, n)
         assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_spill_count"] == 0 and meta["sgpr_spill_count"] == 0, (n, meta)

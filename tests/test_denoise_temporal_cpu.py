@@ -5,7 +5,7 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
+import sys
 
 import numpy as np
 import pytest
@@ -14,6 +14,8 @@ import denoise_cases as D
 import temporal_ref as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
 STEP = 0.02   # radians per frame of the camera path (render.py: orbit_camera), as the GPU tests
 
 
@@ -249,18 +251,11 @@ def test_temporal_beats_the_spatial_filter_on_a_camera_path(P, camera_path, name
 # ---------------------------------------------------------------- gfx950 code
 
 def test_temporal_kernels_have_no_scratch():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    inc = ["-I" + os.path.join(ROOT, d) for d in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "t.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                               "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                               os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_denoise_temporal.hip")])
-        text = open(out).read()
+    text = kernel_listing.listing("pt_denoise_temporal.hip")
     names = re.findall(r"\.name:\s+(_ZN5ptamd18pt_temporal_kernel\S+)", text)
     assert len(names) == 4, names
     for n in names:
-        block = text[text.index(".name:           " + n):][:4000].split("\n  - ")[0]
-        meta = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
+        meta = kernel_listing.metadata(text, n)
         assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_spill_count"] == 0 and meta["sgpr_spill_count"] == 0, (n, meta)

@@ -3,14 +3,17 @@ the brute-force oracle on the NEW faces, argument errors, and the register budge
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import ASSETS, ROOT
 from helpers import make_scene, random_rays, random_soup, wide_case
+
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
+from kernel_listing import metadata as _meta   # noqa: E402  (test_refit_device_cpu takes it from here)
 
 TABLES = ("nodes", "tris_bvh", "nodes4", "tris_brute", "shade")
 SHIPPED = ["indoor", "crate_land", "color_sample", "island", "sss_crate"]
@@ -190,24 +193,12 @@ def test_argument_errors_are_reported_not_crashed(P):
 
 # ---------------------------------------------------------------- gfx950 code
 
-def _meta(text, name):
-    i = text.index(".name:           " + name)
-    block = text[i:i + 4000].split("\n  - ")[0]
-    return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-
-
 def test_refit_kernels_have_no_scratch():
     """Every kernel of csrc/pt_refit.hip: no private segment, no spilled register (the per-octant ordering of a wide node's four
     children is written as compares on registers, not as a run-time indexed array)."""
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    inc = ["-I" + os.path.join(ROOT, x) for x in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "pt_refit.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                               "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                               os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_refit.hip")], stderr=subprocess.DEVNULL)
-        text = open(out).read()
+    text = kernel_listing.listing("pt_refit.hip")
     names = re.findall(r"\.name:\s+(_ZN5ptamd\d+pt_refit_\w+)", text)
     assert len(names) == 4, names
     for n in names:

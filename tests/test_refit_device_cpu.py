@@ -3,14 +3,12 @@ independent float64 evaluation, argument errors, and the register budgets of the
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_refit_cpu import _meta
+from test_refit_cpu import _meta, kernel_listing
 from test_refit_gpu import case
 
 
@@ -78,15 +76,9 @@ def test_argument_errors_are_reported_not_crashed(P):
 def test_device_update_kernels_have_no_scratch():
     """Every kernel of csrc/pt_refit_device.hip, cross-compiled for gfx950 by the recipe of test_refit_kernels_have_no_scratch: no
     private segment, no spilled register."""
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    inc = ["-I" + os.path.join(ROOT, x) for x in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "pt_refit_device.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                               "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                               os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_refit_device.hip")], stderr=subprocess.DEVNULL)
-        text = open(out).read()
+    text = kernel_listing.listing("pt_refit_device.hip")
     names = re.findall(r"\.name:\s+(_ZN5ptamd\d+pt_\w+)", text)
     assert len(names) == 3 and all(any(k in n for n in names) for k in ("pt_refit_extent_partials", "pt_refit_extent_final", "pt_scene_quality")), names
     for n in names:

@@ -8,8 +8,7 @@ the shipped one's (6 waves per SIMD, no scratch, no more SGPR spills), and the s
 import importlib.util
 import os
 import re
-import shutil
-import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -19,7 +18,9 @@ from helpers import make_scene, random_soup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(ROOT, "assets")
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
+from kernel_listing import body, metadata   # noqa: E402
 PLAIN = "_ZN5ptamd21pt_megakernel_restartILb1ELi0EEEvNS_7KParamsE"
 FLAT = "_ZN5ptamd21pt_megakernel_restartILb1ELi8EEEvNS_7KParamsE"
 
@@ -74,33 +75,13 @@ def _isa_regions():
 
 
 @pytest.fixture(scope="module")
-def listings(tmp_path_factory):
+def listings():
     """(listing of pt_kernels.hip as the Makefile compiles it, lines of the marked listing of scripts/isa_regions.py)"""
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    out = str(tmp_path_factory.mktemp("isa") / "pt_kernels.s")
-    inc = ["-I" + os.path.join(ROOT, d) for d in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-
-    def plain():
-        subprocess.check_call([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                               "-ffp-contract=off", "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only",
-                               "-S", "-o", out, os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")])
-        return open(out).read()
-
     with ThreadPoolExecutor(2) as ex:
-        a, b = ex.submit(plain), ex.submit(_isa_regions().marked_listing)
+        a, b = ex.submit(kernel_listing.listing, "pt_kernels.hip"), ex.submit(_isa_regions().marked_listing)
         return a.result(), b.result()
-
-
-def metadata(text, kernel):
-    i = text.index(".name:           " + kernel)
-    block = text[i:i + 4000].split("\n  - ")[0]
-    return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-
-
-def body(text, kernel):
-    i = text.index("\n" + kernel + ":")
-    return text[i:text.index(".Lfunc_end", i)]
 
 
 def test_flat_instantiation_keeps_the_shipped_budget(listings):

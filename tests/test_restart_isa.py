@@ -5,40 +5,24 @@ no interleaved bands).  With those constants out of the round it runs at 6 waves
 32 bytes per lane in scratch and spilled 19 SGPRs to VGPR lanes.  The generic instantiation stays as it was."""
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
+from kernel_listing import body, metadata   # noqa: E402
+
 SHIPPED = "_ZN5ptamd21pt_megakernel_restartILb1ELi0EEEvNS_7KParamsE"
 GENERIC = "_ZN5ptamd21pt_megakernel_restartILb1ELi6EEEvNS_7KParamsE"
 
 
 @pytest.fixture(scope="module")
-def listing(tmp_path_factory):
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+def listing():
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    out = str(tmp_path_factory.mktemp("isa") / "pt_kernels.s")
-    inc = ["-I" + os.path.join(ROOT, d) for d in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    # the flags of the Makefile's HIPFLAGS that decide code generation
-    subprocess.check_call([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                           "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")])
-    return open(out).read()
-
-
-def metadata(text, kernel):
-    """The kernel's entry in the code object's amdhsa.kernels metadata: {key: int}."""
-    i = text.index(".name:           " + kernel)
-    block = text[i:i + 4000].split("\n  - ")[0]
-    return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-
-
-def body(text, kernel):
-    i = text.index("\n" + kernel + ":")
-    return text[i:text.index(".Lfunc_end", i)]
+    return kernel_listing.listing("pt_kernels.hip")
 
 
 def test_shipped_restart_instantiation_has_no_scratch_and_fits_six_waves(listing):

@@ -6,39 +6,27 @@ codes instead of deriving them, and a walk starts at the entry node of its ray's
 plain one."""
 import os
 import re
-import shutil
 import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import kernel_listing   # noqa: E402
+from kernel_listing import body, metadata   # noqa: E402,F401  (test_leaf_defer_cpu takes them from here)
+
 KERNEL = "_ZN5ptamd21pt_megakernel_restartILb1ELi%dEEEvNS_7KParamsE"
 PLAIN, FLAT, FLAT_SKIP, PLAIN_SKIP = (KERNEL % v for v in (0, 8, 9, 10))
 
 
 @pytest.fixture(scope="module")
-def listing(tmp_path_factory):
+def listing():
     """the listing of pt_kernels.hip as the Makefile compiles it"""
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+    if kernel_listing.hipcc() is None:
         pytest.skip("no hipcc on this host")
-    out = str(tmp_path_factory.mktemp("isa") / "pt_kernels.s")
-    inc = ["-I" + os.path.join(ROOT, d) for d in ("include", "cuda-pathtracer_amd/host", "cuda-pathtracer_amd/csrc")]
-    subprocess.check_call([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                           "-ffp-contract=off", "-fno-slp-vectorize", "-fno-vectorize", *inc, "-x", "hip", "--cuda-device-only",
-                           "-S", "-o", out, os.path.join(ROOT, "cuda-pathtracer_amd", "csrc", "pt_kernels.hip")])
-    return open(out).read()
-
-
-def metadata(text, kernel):
-    i = text.index(".name:           " + kernel)
-    block = text[i:i + 4000].split("\n  - ")[0]
-    return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-
-
-def body(text, kernel):
-    i = text.index("\n" + kernel + ":")
-    return text[i:text.index(".Lfunc_end", i)]
+    return kernel_listing.listing("pt_kernels.hip")
 
 
 @pytest.mark.parametrize("form,parent,sgpr_spills", [(FLAT_SKIP, FLAT, 0), (PLAIN_SKIP, PLAIN, 5)], ids=["flat", "plain"])
