@@ -78,18 +78,21 @@ PT_HD void tm_add(const TemporalParams& t, TmHistory& h, size_t j, float w)
   h.sw = h.sw + w;
 }
 
-// pass "reproject" of pixel (x, y): history, blend, n'
-PT_HD void tm_reproject(const DenoiseParams& q, const TemporalParams& t, uint32_t x, uint32_t y)
+// pass "reproject" of pixel (x, y): history, blend, n'.  The body both forms share: xh = {the point that is projected into the
+// previous camera and held against the taps' planes, t_p}; usable false: the pixel has no history whatever the previous call left.
+// The plain form (tm_reproject) gives the pixel's own record; the motion form (pt_denoise_motion.h) the point moved back to where
+// it stood at the previous call.
+PT_HD void tm_reproject_from(const DenoiseParams& q, const TemporalParams& t, uint32_t x, uint32_t y, float4 xh, bool usable)
 {
   const size_t i = (size_t)y * q.width + x;
-  const float4 np = q.geo_n[i], xp = q.geo_x[i];
+  const float4 np = q.geo_n[i];
   const uint32_t kind = dn_kind(np);
   const f3 e = xyz(t.e_in[i]);
   const float l = dn_lum(e);
   TmHistory h = { mk3(0.0f), 0.0f, 0.0f, 0.0f, 0.0f };
   float px = 0.0f, py = 0.0f;
-  if (t.has_history != 0u && kind != PT_FEAT_LIGHT &&
-      tm_project(q, t, kind == PT_FEAT_MESH ? xyz(xp) - t.prev_pos : dn_ray_dir(q, x, y), px, py)) {
+  if (t.has_history != 0u && kind != PT_FEAT_LIGHT && usable &&
+      tm_project(q, t, kind == PT_FEAT_MESH ? xyz(xh) - t.prev_pos : dn_ray_dir(q, x, y), px, py)) {
     // 2x2 bilinear taps, weights renormalised over the taps that count
     const float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py);
     const float fx = px - fx0, fy = py - fy0;
@@ -97,7 +100,7 @@ PT_HD void tm_reproject(const DenoiseParams& q, const TemporalParams& t, uint32_
     for (int k = 0; k < 4; ++k) {
       const int dx = k & 1, dy = k >> 1;
       size_t j = 0;
-      if (!tm_tap_ok(q, t, kind, np, xp, x0 + dx, y0 + dy, j)) continue;
+      if (!tm_tap_ok(q, t, kind, np, xh, x0 + dx, y0 + dy, j)) continue;
       tm_add(t, h, j, (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy));
     }
     if (!(h.sw > 0.0f)) {   // none counted: the consistent taps of the 3x3 around the rounded position, equal weights
@@ -106,7 +109,7 @@ PT_HD void tm_reproject(const DenoiseParams& q, const TemporalParams& t, uint32_
       for (int dy = -1; dy <= 1; ++dy)
         for (int dx = -1; dx <= 1; ++dx) {
           size_t j = 0;
-          if (tm_tap_ok(q, t, kind, np, xp, xr + dx, yr + dy, j)) tm_add(t, h, j, 1.0f);
+          if (tm_tap_ok(q, t, kind, np, xh, xr + dx, yr + dy, j)) tm_add(t, h, j, 1.0f);
         }
     }
   }
@@ -131,6 +134,12 @@ PT_HD void tm_reproject(const DenoiseParams& q, const TemporalParams& t, uint32_
   t.mom_out[i] = make_float2(m1, m2);
   t.len[i] = n;
   if (t.length_out) t.length_out[i] = n;
+}
+
+// the plain form: the surface point stood still since the previous call
+PT_HD void tm_reproject(const DenoiseParams& q, const TemporalParams& t, uint32_t x, uint32_t y)
+{
+  tm_reproject_from(q, t, x, y, q.geo_x[(size_t)y * q.width + x], true);
 }
 
 // pass "moments": the temporal variance replaces the spatial one where the history is 4 calls or longer.  m2 - m1^2 is the variance

@@ -59,6 +59,9 @@ hipError_t launch_adaptive_resolve_list(const AdaptiveParams& a, hipStream_t str
 hipError_t launch_adaptive_resolve(const AdaptiveParams& a, hipStream_t stream);
 // temporal half (pt_denoise_temporal.hip): 0 reproject and blend, 1 temporal variance, 2 capture, 3 plain output
 hipError_t launch_temporal_pass(const DenoiseParams& q, const TemporalParams& t, int pass, hipStream_t stream);
+// ... and pass 0 in its motion form (pt_denoise_motion.hip): reproject along the faces' motion since the previous call, and blend
+struct MotionParams;
+hipError_t launch_motion_reproject(const DenoiseParams& q, const TemporalParams& t, const MotionParams& m, hipStream_t stream);
 
 } // namespace ptamd
 

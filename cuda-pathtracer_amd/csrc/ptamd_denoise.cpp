@@ -3,6 +3,7 @@
 #include "ptamd_host.h"
 #include "pt_denoise.h"
 #include "pt_denoise_temporal.h"
+#include "pt_denoise_motion.h"
 
 #include <cmath>
 #include <cstring>
@@ -121,6 +122,13 @@ struct ptamd_denoise_history {
   float4* geo_x[2] = {};
   float2* moments[2] = {};
   float* len = nullptr;        // n' of the last call (what the capture pass writes into color.w)
+  // ptamd_denoise_temporal_motion: the triangle records (the scene's tris_brute, 48 bytes per face) as the last motion call found
+  // them, and the scene, face count and geometry serial they belong to.  Allocated at the first motion call and again when the
+  // scene or the face count changes.  stale: a plain call came since; the records no longer describe the history's last frame.
+  ptamd::DeviceBuffer<float4> snapshot;
+  uint32_t snap_scene = 0, snap_faces = 0;
+  uint64_t snap_serial = 0;
+  bool snap_stale = false;
 };
 static_assert(!std::is_copy_constructible<ptamd_denoise_history>::value, "a history owns its device block");
 
@@ -294,25 +302,47 @@ int ptamd_denoise_history_view_of(const ptamd_denoise_history* h, ptamd_denoise_
   return PTAMD_OK;
 }
 
-int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc* td)
+// One temporal call.  motion: ptamd_denoise_temporal_motion (include/ptamd.h): a cut when the history's snapshot belongs to another
+// scene or face count; pass 0 in its motion form when the scene's geometry serial moved past the snapshot's; the snapshot renewed
+// behind the call's passes.  Without it: ptamd_denoise_temporal, which only marks the snapshot stale.
+static int temporal_call(const char* who_, ptamd_context* ctx, const ptamd_denoise_temporal_desc* td, bool motion)
 {
-  static const char* who = "ptamd_denoise_temporal";
-  if (!ctx || !td || !td->history) { set_error("ptamd_denoise_temporal: null argument"); return PTAMD_ERR_ARG; }
+  const std::string who(who_);
+  if (!ctx || !td || !td->history) { set_error(who + ": null argument"); return PTAMD_ERR_ARG; }
   const ptamd_denoise_desc* d = &td->base;
   ptamd_denoise_history* hist = td->history;
-  if (!d->temporal_framebuffer || !d->surface_rgba8) { set_error("ptamd_denoise_temporal: null accumulator or surface"); return PTAMD_ERR_ARG; }
-  if (hist->ctx != ctx) { set_error("ptamd_denoise_temporal: the history belongs to another context"); return PTAMD_ERR_ARG; }
-  int rc = denoise_ids(who, ctx, d->scene_id, d->cubemap_id, d->stream);
+  if (!d->temporal_framebuffer || !d->surface_rgba8) { set_error(who + ": null accumulator or surface"); return PTAMD_ERR_ARG; }
+  if (hist->ctx != ctx) { set_error(who + ": the history belongs to another context"); return PTAMD_ERR_ARG; }
+  int rc = denoise_ids(who_, ctx, d->scene_id, d->cubemap_id, d->stream);
   if (rc != PTAMD_OK) return rc;
   DenoiseParams q;
   KParams p;
   TemporalParams t;
-  if ((rc = denoise_params(who, d, q, p)) != PTAMD_OK) return rc;
-  if ((rc = temporal_checks(who, td, hist->width, hist->height, t)) != PTAMD_OK) return rc;
+  if ((rc = denoise_params(who_, d, q, p)) != PTAMD_OK) return rc;
+  if ((rc = temporal_checks(who_, td, hist->width, hist->height, t)) != PTAMD_OK) return rc;
   PT_HIP(hipSetDevice(ctx->device));
   const hipStream_t stream = static_cast<hipStream_t>(d->stream);
   const size_t n = (size_t)d->width * d->height;
   if ((rc = denoise_workspace(ctx, n)) != PTAMD_OK) return rc;
+  // the snapshot: whether it can be held against the scene's records, and whether they moved since it was taken
+  const DeviceScene& scene = ctx->scenes[d->scene_id];
+  const size_t snap_bytes = (size_t)scene.n_faces * 48u;
+  bool cut = false, moved = false, take = false;
+  if (motion) {
+    const bool have = (bool)hist->snapshot;
+    cut = have && (hist->snap_scene != d->scene_id || hist->snap_faces != scene.n_faces);
+    if (!have || cut) {
+      PT_HIP(hist->snapshot.alloc(snap_bytes ? snap_bytes : 16u));   // (releasing the old one waits for the work in flight that may still use it)
+      hist->snap_scene = d->scene_id; hist->snap_faces = scene.n_faces;
+      hist->snap_stale = false;
+      take = true;
+    } else {
+      take = hist->snap_serial != scene.geometry_serial;
+      moved = take && !hist->snap_stale;   // (after a plain call the records are older than the history's last frame: unmoved for this call)
+    }
+  } else {
+    hist->snap_stale = true;
+  }
   q.acc = d->temporal_framebuffer;
   q.surface = static_cast<uint32_t*>(d->surface_rgba8);
   q.linear = d->linear_rgb;
@@ -324,7 +354,7 @@ int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc
   q.feat = feat;
   q.geo_n = hist->geo_n[cur];   // this call's geometry goes straight into the history
   q.geo_x = hist->geo_x[cur];
-  t.has_history = hist->valid != 0u && td->reset_history == 0u ? 1u : 0u;
+  t.has_history = hist->valid != 0u && td->reset_history == 0u && !cut ? 1u : 0u;
   temporal_camera(hist->camera, d->width, t);
   t.prev_n = hist->geo_n[prev]; t.prev_x = hist->geo_x[prev];
   t.e_in = img[0]; t.e_out = img[0];   // per pixel in place
@@ -336,7 +366,13 @@ int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc
   PT_HIP(launch_features(p, kind, feat, nullptr, stream));
   q.c_out = img[0];
   PT_HIP(launch_denoise_pass(q, 0, stream));
-  PT_HIP(launch_temporal_pass(q, t, 0, stream));
+  if (moved) {
+    MotionParams m;
+    m.now = scene.tris_brute.get(); m.prev = hist->snapshot.get(); m.n_faces = scene.n_faces;
+    PT_HIP(launch_motion_reproject(q, t, m, stream));
+  } else {
+    PT_HIP(launch_temporal_pass(q, t, 0, stream));
+  }
   t.capture_src = img[0];   // the integrated colour is the next call's colour history
   PT_HIP(launch_temporal_pass(q, t, 2, stream));
   if (d->levels == 0) {
@@ -354,6 +390,11 @@ int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc
       PT_HIP(launch_denoise_pass(q, 2, stream));
     }
   }
+  if (take) {   // in stream order behind the passes that read the old records; the host does not wait
+    if (snap_bytes) PT_HIP(hipMemcpyAsync(hist->snapshot.get(), scene.tris_brute.get(), snap_bytes, hipMemcpyDeviceToDevice, stream));
+    hist->snap_serial = scene.geometry_serial;
+  }
+  if (motion) hist->snap_stale = false;
   hist->last = cur;
   hist->camera = d->camera;
   hist->frame_nb = d->frame_nb;
@@ -361,19 +402,45 @@ int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc
   return PTAMD_OK;
 }
 
-int ptamd_host_denoise_temporal(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* td,
-                                ptamd_denoise_history_view* hv, float* linear_rgb, uint8_t* rgba8)
+int ptamd_denoise_temporal(ptamd_context* ctx, const ptamd_denoise_temporal_desc* td)
 {
-  static const char* who = "ptamd_host_denoise_temporal";
-  if (!features || !temporal_framebuffer || !td || !hv || !rgba8) { set_error("ptamd_host_denoise_temporal: null argument"); return PTAMD_ERR_ARG; }
-  if (!hv->color || !hv->moments || !hv->normal || !hv->position) { set_error("ptamd_host_denoise_temporal: null history buffer"); return PTAMD_ERR_ARG; }
+  return temporal_call("ptamd_denoise_temporal", ctx, td, false);
+}
+
+int ptamd_denoise_temporal_motion(ptamd_context* ctx, const ptamd_denoise_temporal_desc* td)
+{
+  return temporal_call("ptamd_denoise_temporal_motion", ctx, td, true);
+}
+
+int ptamd_denoise_history_geometry_read(ptamd_denoise_history* h, void* out, uint64_t* bytes, uint32_t* scene_id, uint64_t* serial)
+{
+  if (!h || !bytes) { set_error("ptamd_denoise_history_geometry_read: null argument"); return PTAMD_ERR_ARG; }
+  const uint64_t size = h->snapshot ? (uint64_t)h->snap_faces * 48u : 0u, room = *bytes;
+  *bytes = size;
+  if (scene_id) *scene_id = h->snap_scene;
+  if (serial) *serial = h->snap_serial;
+  if (!out) return PTAMD_OK;
+  if (room < size) { set_error("ptamd_denoise_history_geometry_read: the buffer is smaller than the snapshot"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(h->ctx->device));
+  PT_HIP(hipDeviceSynchronize());
+  if (size) PT_HIP(hipMemcpy(out, h->snapshot.get(), size, hipMemcpyDeviceToHost));
+  return PTAMD_OK;
+}
+
+// The host mirror of one temporal call; motion: pass "reproject" in its motion form over these two record arrays (else the plain form)
+static int host_temporal_call(const char* who_, const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* td,
+                              ptamd_denoise_history_view* hv, const MotionParams* motion, float* linear_rgb, uint8_t* rgba8)
+{
+  const std::string who(who_);
+  if (!features || !temporal_framebuffer || !td || !hv || !rgba8) { set_error(who + ": null argument"); return PTAMD_ERR_ARG; }
+  if (!hv->color || !hv->moments || !hv->normal || !hv->position) { set_error(who + ": null history buffer"); return PTAMD_ERR_ARG; }
   const ptamd_denoise_desc* d = &td->base;
   DenoiseParams q;
   KParams p;
   TemporalParams t;
-  int rc = denoise_params(who, d, q, p);
+  int rc = denoise_params(who_, d, q, p);
   if (rc != PTAMD_OK) return rc;
-  if ((rc = temporal_checks(who, td, hv->width, hv->height, t)) != PTAMD_OK) return rc;
+  if ((rc = temporal_checks(who_, td, hv->width, hv->height, t)) != PTAMD_OK) return rc;
   const size_t n = (size_t)d->width * d->height;
   std::vector<float4> ws;
   std::vector<float2> mom;
@@ -385,7 +452,7 @@ int ptamd_host_denoise_temporal(const float* features, const float* temporal_fra
     len.resize(n);
     surface.resize(n);
   } catch (const std::bad_alloc&) {
-    set_error("ptamd_host_denoise_temporal: out of memory");
+    set_error(who + ": out of memory");
     return PTAMD_ERR_LIMIT;
   }
   float4* img[2] = { ws.data() + 2 * n, ws.data() + 3 * n };
@@ -410,7 +477,8 @@ int ptamd_host_denoise_temporal(const float* features, const float* temporal_fra
   auto spatial = [&](void (*pass)(const DenoiseParams&, uint32_t, uint32_t)) { each([&](uint32_t x, uint32_t y) { pass(q, x, y); }); };
   q.c_out = img[0];
   spatial(dn_prepare);
-  each([&](uint32_t x, uint32_t y) { tm_reproject(q, t, x, y); });
+  if (motion) each([&](uint32_t x, uint32_t y) { mt_reproject(q, t, *motion, x, y); });
+  else each([&](uint32_t x, uint32_t y) { tm_reproject(q, t, x, y); });
   t.capture_src = img[0];
   for (size_t i = 0; i < n; ++i) tm_capture(q, t, i);
   if (d->levels == 0) {
@@ -437,6 +505,24 @@ int ptamd_host_denoise_temporal(const float* features, const float* temporal_fra
   hv->valid = 1u;
   std::memcpy(rgba8, surface.data(), n * 4);
   return PTAMD_OK;
+}
+
+int ptamd_host_denoise_temporal(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* td,
+                                ptamd_denoise_history_view* hv, float* linear_rgb, uint8_t* rgba8)
+{
+  return host_temporal_call("ptamd_host_denoise_temporal", features, temporal_framebuffer, td, hv, nullptr, linear_rgb, rgba8);
+}
+
+int ptamd_host_denoise_temporal_motion(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* td,
+                                       ptamd_denoise_history_view* hv, const float* tris_now, const float* tris_prev, uint32_t n_faces,
+                                       float* linear_rgb, uint8_t* rgba8)
+{
+  static const char* who = "ptamd_host_denoise_temporal_motion";
+  if (!tris_prev) return host_temporal_call(who, features, temporal_framebuffer, td, hv, nullptr, linear_rgb, rgba8);
+  if (n_faces && !tris_now) { set_error("ptamd_host_denoise_temporal_motion: tris_prev without tris_now"); return PTAMD_ERR_ARG; }
+  MotionParams m;
+  m.now = reinterpret_cast<const float4*>(tris_now); m.prev = reinterpret_cast<const float4*>(tris_prev); m.n_faces = n_faces;
+  return host_temporal_call(who, features, temporal_framebuffer, td, hv, &m, linear_rgb, rgba8);
 }
 
 } // extern "C"

@@ -79,6 +79,7 @@ struct DeviceScene {
   uint32_t stage_next = 0;
   Event updated;                                 // the last update's kernels have finished: lanes and other streams wait for it
   bool updated_valid = false;
+  uint64_t geometry_serial = 0;                  // counts the refits enqueued (ptamd_scene.cpp: enqueue_refit): the faces moved since a reader last looked
   // ptamd_scene_update_device: the new faces' extent is formed on the device (pt_refit_device.hip) and copied back behind the
   // update's kernels; until a reader of extent / all_finite / reach / margin_floor has waited for it (settle_margins) those four
   // are stale.  Two pinned slots used in turn, so a copy that lands late never overwrites the words of a newer update.

@@ -365,6 +365,18 @@ int restore_plain_links(DeviceScene& s, hipStream_t stream)
   return PTAMD_OK;
 }
 
+// The one place where an update of the faces enqueues its refit (ptamd_scene_update, _update_device, the rig's pose, skin and morph):
+// the four kernels, `updated` behind them, and the scene's geometry serial, by which a reader that keeps a copy of the triangle
+// records (ptamd_denoise_temporal_motion) knows them moved.  ptamd_scene_update_lights moves no face and does not come here.
+static int enqueue_refit(DeviceScene& s, const RefitParams& r, hipStream_t stream)
+{
+  PT_HIP(launch_refit(r, stream));
+  PT_HIP(hipEventRecord(s.updated.get(), stream));
+  s.updated_valid = true;
+  ++s.geometry_serial;
+  return PTAMD_OK;
+}
+
 // ... and what it enqueues behind wait_for_readers, for ptamd_scene_update_device (the caller's buffer) and ptamd_scene_rig_pose (the
 // rig's posed records) alike: extent reduction, the four refit kernels, `updated`, the margin copy; margins pending
 int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream)
@@ -377,9 +389,8 @@ int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hip
   PT_HIP(launch_extent(faces, s.n_faces, s.d_margin.get() + kMarginWords, s.d_margin.get(), stream));
   r.faces = faces;
   r.device_margin = s.d_margin.get() + 2;
-  PT_HIP(launch_refit(r, stream));
-  PT_HIP(hipEventRecord(s.updated.get(), stream));
-  s.updated_valid = true;
+  const int re = enqueue_refit(s, r, stream);
+  if (re != PTAMD_OK) return re;
   // extent and finiteness back to the host, behind the kernels: launches wait for `updated`, not for this copy
   const uint32_t slot = s.margin_next++ & 1u;
   PT_HIP(hipMemcpyAsync(s.h_margin.get() + (size_t)slot * kMarginWords, s.d_margin.get(), kMarginWords * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -546,9 +557,7 @@ int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
   PT_HIP(hipEventRecord(s.staged[slot].get(), stream));
   s.staged_valid[slot] = true;
   r.faces = s.d_faces.get();
-  PT_HIP(launch_refit(r, stream));
-  PT_HIP(hipEventRecord(s.updated.get(), stream));
-  s.updated_valid = true;
+  if ((rc = enqueue_refit(s, r, stream)) != PTAMD_OK) return rc;
   // (the values are here at once: whatever ptamd_scene_update_device left pending is superseded)
   s.extent = m.extent; s.all_finite = m.all_finite; s.reach = m.reach; s.margin_floor = m.margin_floor;
   s.margins_pending = false;

@@ -286,6 +286,11 @@ SIGNATURES = {
     "ptamd_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(DenoiseTemporalDesc)]),
     "ptamd_host_denoise_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseTemporalDesc), C.POINTER(DenoiseHistoryView),
                                               C.c_void_p, C.c_void_p]),
+    "ptamd_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseTemporalDesc)]),
+    "ptamd_denoise_history_geometry_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                                      C.POINTER(C.c_uint64)]),
+    "ptamd_host_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseTemporalDesc), C.POINTER(DenoiseHistoryView),
+                                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptamd_adaptive_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ptamd_adaptive_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_adaptive_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

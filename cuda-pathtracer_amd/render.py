@@ -287,10 +287,11 @@ class Context:
                          height: int, frame_nb: int, history: "DenoiseHistory", levels: int = 5, post_id: int = POST_NONE,
                          sigma_n: float = 0.0, sigma_l: float = 0.0, sigma_x: float = 0.0, alpha_color: float = 0.0,
                          alpha_moments: float = 0.0, reset_history: bool = False, history_length=None, linear=None,
-                         stream=None) -> None:
+                         stream=None, motion: bool = False) -> None:
         """Temporal + spatial denoise (ptamd_denoise_temporal): as denoise(), blended with what `history`
         integrated over the previous calls, which it then updates.  The accumulator must be an independent estimate (a new
-        accumulation since the last call on this history); history_length (optional) float32[height, width] receives n'."""
+        accumulation since the last call on this history); history_length (optional) float32[height, width] receives n'.
+        motion=True: ptamd_denoise_temporal_motion, which carries the history across updates of the scene's faces."""
         if history.ctx is not self:
             raise ValueError("the history belongs to another context")
         d = N.DenoiseTemporalDesc()
@@ -308,7 +309,8 @@ class Context:
         d.alpha_color, d.alpha_moments = alpha_color, alpha_moments
         d.reset_history = 1 if reset_history else 0
         d.history_length = _ptr(history_length) if history_length is not None else None
-        N.check(self._lib.ptamd_denoise_temporal(self._h, C.byref(d)))
+        call = self._lib.ptamd_denoise_temporal_motion if motion else self._lib.ptamd_denoise_temporal
+        N.check(call(self._h, C.byref(d)))
 
     def render_features(self, scene_id: int, cubemap_id: int, cam: N.Camera, width: int, height: int, features,
                         rays=None, stream=None) -> None:
@@ -858,6 +860,15 @@ class DenoiseHistory:
         N.check(self.ctx._lib.ptamd_stream_synchronize(self.ctx._h, None))
         return out
 
+    def read_geometry(self) -> dict:
+        """The snapshot of the scene's triangle records that denoise_temporal(motion=True) keeps
+        (ptamd_denoise_history_geometry_read; synchronises the device): tris uint8[48 * faces] (empty: none yet), scene_id, serial."""
+        n, sid, serial = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        N.check(self.ctx._lib.ptamd_denoise_history_geometry_read(self.handle, None, C.byref(n), None, None))
+        buf = np.zeros(n.value, np.uint8)
+        N.check(self.ctx._lib.ptamd_denoise_history_geometry_read(self.handle, buf.ctypes.data, C.byref(n), C.byref(sid), C.byref(serial)))
+        return {"tris": buf, "scene_id": sid.value, "serial": serial.value}
+
     def close(self) -> None:
         if self.handle:
             N.check(self.ctx._lib.ptamd_denoise_history_destroy(self.ctx._h, self.handle))
@@ -989,9 +1000,11 @@ class HostDenoiseHistory:
 def host_denoise_temporal(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_nb: int, history: HostDenoiseHistory,
                           levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_l: float = 0.0,
                           sigma_x: float = 0.0, alpha_color: float = 0.0, alpha_moments: float = 0.0,
-                          reset_history: bool = False):
+                          reset_history: bool = False, tris=None, prev_tris=None):
     """Host mirror of Context.denoise_temporal (ptamd_host_denoise_temporal) over `history`, which it updates.
-    Returns (linear float32[H, W, 3], rgba uint8[H, W, 4], history_length float32[H, W]), row 0 = top."""
+    Returns (linear float32[H, W, 3], rgba uint8[H, W, 4], history_length float32[H, W]), row 0 = top.
+    prev_tris (with tris): the motion form (ptamd_host_denoise_temporal_motion) between the triangle records of the previous
+    call and of this one, each the bytes or floats of a "tris_brute" table (host_scene_tables, Context.read_scene_tables)."""
     features = np.ascontiguousarray(features, dtype=np.float32)
     accum = np.ascontiguousarray(accum, dtype=np.float32)
     h, w = accum.shape[:2]
@@ -1008,9 +1021,31 @@ def host_denoise_temporal(features: np.ndarray, accum: np.ndarray, cam: N.Camera
     d.history_length = length.ctypes.data
     linear = np.zeros((h, w, 3), np.float32)
     rgba = np.zeros((h, w, 4), np.uint8)
-    N.check(N.load().ptamd_host_denoise_temporal(features.ctypes.data, accum.ctypes.data, C.byref(d), C.byref(history.view),
-                                                 linear.ctypes.data, rgba.ctypes.data))
+    if prev_tris is None:
+        N.check(N.load().ptamd_host_denoise_temporal(features.ctypes.data, accum.ctypes.data, C.byref(d), C.byref(history.view),
+                                                     linear.ctypes.data, rgba.ctypes.data))
+        return linear, rgba, length
+    if tris is None:
+        raise ValueError("prev_tris goes with tris")
+    rec = [_tri_records(a) for a in (tris, prev_tris)]
+    if rec[0].shape != rec[1].shape:
+        raise ValueError("tris and prev_tris must hold the same number of records")
+    N.check(N.load().ptamd_host_denoise_temporal_motion(features.ctypes.data, accum.ctypes.data, C.byref(d), C.byref(history.view),
+                                                        rec[0].ctypes.data, rec[1].ctypes.data, len(rec[0]), linear.ctypes.data,
+                                                        rgba.ctypes.data))
     return linear, rgba, length
+
+
+def _tri_records(a) -> np.ndarray:
+    """float32[n, 12] of a tris_brute table given as bytes or floats, in memory of its own aligned to 16 bytes"""
+    a = np.ascontiguousarray(a)
+    a = a.view(np.float32) if a.dtype == np.uint8 else a.astype(np.float32, copy=False)
+    if a.size % 12:
+        raise ValueError("a triangle record is 12 floats")
+    out = np.zeros(a.size + 4, np.float32)
+    out = out[(-out.ctypes.data // 4) % 4:][:a.size]
+    out[:] = a.reshape(-1)
+    return out.reshape(-1, 12)
 
 
 def orbit_camera(cam: N.Camera, angle: float, radius: float = 0.0) -> N.Camera:
@@ -1127,11 +1162,13 @@ class FrameRenderer:
 
     def denoise_temporal(self, history: DenoiseHistory, levels: int = 5, post_id: int = POST_NONE, sigma_n: float = 0.0,
                          sigma_l: float = 0.0, sigma_x: float = 0.0, alpha_color: float = 0.0, alpha_moments: float = 0.0,
-                         reset_history: bool = False, history_length=None, linear=None, stream=None, surface=None) -> None:
+                         reset_history: bool = False, history_length=None, linear=None, stream=None, surface=None,
+                         motion: bool = False) -> None:
         """Temporal + spatial denoise of the last render() into the renderer's surface (or `surface`).  Each call
         should follow a render(reset=True) (the camera moved): its accumulator is then an independent estimate.  When the
         accumulator went on converging without a reset since this renderer's last temporal call on `history`, the call resets
-        the history by itself, so that a static view is never counted twice."""
+        the history by itself, so that a static view is never counted twice.  motion=True: the history is carried across updates
+        of the scene's faces (Context.denoise_temporal)."""
         if self.rows != (0, self.height) or self.band_local or self.interleave is not None:
             raise ValueError("denoise_temporal() needs a full-frame renderer (no row band, band-local or interleaved buffers)")
         if self.last_frame_nb == 0:
@@ -1142,7 +1179,7 @@ class FrameRenderer:
                                   self.cam, self.width, self.height, self.last_frame_nb, history, levels=levels, post_id=post_id,
                                   sigma_n=sigma_n, sigma_l=sigma_l, sigma_x=sigma_x, alpha_color=alpha_color,
                                   alpha_moments=alpha_moments, reset_history=reset_history or continued,
-                                  history_length=history_length, linear=linear, stream=stream)
+                                  history_length=history_length, linear=linear, stream=stream, motion=motion)
         self._temporal_last = key
 
     # ---- adaptive sampling (ptamd_render_adaptive)

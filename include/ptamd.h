@@ -214,8 +214,10 @@ int ptamd_setup_function_tables(ptamd_context* ctx);
  * captured launch (until ptamd_release_captured: the captured launch has baked in the walk-or-every-face choice) and for a
  * `stream` that is capturing.
  *
- * Not tracked: a ptamd_denoise_history knows nothing about moved geometry (there are no motion vectors) and a
- * ptamd_adaptive_state's moments describe the old image: reset both after an update.
+ * Not tracked: a ptamd_adaptive_state's moments describe the old image: reset it after an update.  A ptamd_denoise_history is
+ * carried across updates by ptamd_denoise_temporal_motion ("Temporal reprojection across scene updates" below), which follows each
+ * face from its records before the update to those after it; the plain ptamd_denoise_temporal assumes the geometry stood still, and
+ * a history given only to it must still be reset after every update.
  *
  * What a refitted tree costs the renderer (measured on the 264 832-triangle atrium, 1080p x 4 spp x 4 bounces, beside a fresh
  * upload of the same faces; scripts/gpu_refit.py): 0.5 % / 0.8 % / 19 % of the sample rate at displacements of
@@ -869,6 +871,45 @@ int ptamd_denoise_history_view_of(const ptamd_denoise_history* history, ptamd_de
  * device; desc->history is ignored: `history` is read and updated instead (buffers allocated by the caller, width and height set). */
 int ptamd_host_denoise_temporal(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* desc,
                                 ptamd_denoise_history_view* history, float* linear_rgb, uint8_t* rgba8);
+
+/* ---- Temporal reprojection across scene updates (DESIGN.md §11 "Moved geometry") -------------------------------------------
+ * ptamd_denoise_temporal with a history that survives ptamd_scene_update, _update_device and the rig's pose, skin and morph.  An
+ * update keeps the topology, so the surface point a mesh pixel sees lies on the same face before and after it: from the pixel's
+ * barycentric coordinates on the face as it is now and the face's records as they were at the previous call, the call forms the
+ * point's previous position and reprojects THAT into the previous camera (csrc/pt_denoise_motion.h has the arithmetic).  Nothing
+ * else of the temporal call changes, and where the records did not change the result is ptamd_denoise_temporal's bit for bit.
+ *
+ * Same desc, same errors, asynchronous on base.stream.  The history owns a snapshot: a device copy of the scene's triangle
+ * records (48 bytes per face), allocated at the first call of this kind on the history and again when base.scene_id or the
+ * scene's face count differ from the snapshot's; every scene counts its updates of the faces in a serial
+ * (ptamd_scene_update_lights does not count).  Per call:
+ *   - the snapshot belongs to another scene id or face count: the call behaves as with reset_history (a cut);
+ *   - there is no snapshot yet, or the scene's serial is the snapshot's: the geometry did not move, the call is
+ *     ptamd_denoise_temporal's (its kernels, its time);
+ *   - otherwise the reprojection takes its motion form between the snapshot and the scene's records;
+ *   - behind the call's passes, when the serials differ or there was no snapshot, the scene's records are copied into the snapshot
+ *     in stream order.  Only the allocating calls wait for the device; no other call synchronises the host.
+ * The call reads the scene's tables in stream order like every denoiser call: issue it on the update's stream or behind an event.
+ *
+ * Mixing.  ptamd_denoise_temporal on the same history marks the snapshot stale (a host-side flag; its results do not change): the
+ * next call here treats the geometry as unmoved for that one call (the snapshot is older than the history's last frame) and
+ * renews the snapshot.  So the two calls may be mixed on one history; only a sequence of calls of THIS kind follows every update.
+ *
+ * Limits.  A surface that turns by more than acos(0.9) = 25.8 degrees between two calls loses its history (the normal test holds
+ * the current normal against the previous call's): the safe direction.  What an update does to the lighting (moved lights, the
+ * shadow of a moved object on one that stood still) lags as in any temporal filter.  Light pixels never have history. */
+int ptamd_denoise_temporal_motion(ptamd_context* ctx, const ptamd_denoise_temporal_desc* desc);
+
+/* The history's snapshot, for tests: waits for the device and copies it to `out` (host memory, *bytes of room); *bytes receives
+ * its size (0: no snapshot yet), scene_id and serial (both optional) what it belongs to.  out == NULL: the sizes only, no wait. */
+int ptamd_denoise_history_geometry_read(ptamd_denoise_history* history, void* out, uint64_t* bytes, uint32_t* scene_id, uint64_t* serial);
+
+/* Host mirror of ptamd_denoise_temporal_motion's arithmetic.  tris_prev == NULL: ptamd_host_denoise_temporal.  Otherwise the
+ * reprojection takes the motion form between tris_prev and tris_now: HOST arrays of n_faces records of 12 floats, aligned to 16
+ * bytes, as ptamd_host_scene_refit(which = 3) returns them.  A mesh pixel whose face index is not below n_faces has no history. */
+int ptamd_host_denoise_temporal_motion(const float* features, const float* temporal_framebuffer, const ptamd_denoise_temporal_desc* desc,
+                                       ptamd_denoise_history_view* history, const float* tris_now, const float* tris_prev, uint32_t n_faces,
+                                       float* linear_rgb, uint8_t* rgba8);
 
 /* ---- Adaptive sampling ----------------------------------------------------------------------------------
  * Per-pixel sample counts: rounds of samples go to the pixels whose luminance error estimate is still above a threshold.  A sample
