@@ -484,6 +484,8 @@ struct KParams {
   // relinked link table behind its nodes, host/skip_links.cpp, and the launch's LDS holds the entry nodes in front of the scene)
   // PT_ROUND_DEFER (only ever next to PT_ROUND_SKIP): to the deferring copy of that skip form, whose rounds leave their sparse
   // later leaf phases to the next round's first one (pt_round.h; PTAMD_LEAF_DEFER=0 clears it)
+  // PT_ROUND_TIGHT (only ever next to PT_ROUND_FLAT | PT_ROUND_SKIP | PT_ROUND_DEFER; round_form_tight below): to the tight copy of
+  // the flat deferring form, compiled for small_det != 0 (PTAMD_RS_TIGHT=0 clears it)
   uint32_t round_form;
   uint32_t round_defer;  // the deferring forms read this in place of round_min: round_min (<= 64) | knob << 8, the knob of pt_round.h: round_leaf_defer as a lane count (<= 64) or 0xFF for PT_LEAF_DEFER_AUTO
 };
@@ -491,6 +493,14 @@ struct KParams {
 #define PT_ROUND_FLAT 2u
 #define PT_ROUND_SKIP 4u
 #define PT_ROUND_DEFER 8u
+#define PT_ROUND_TIGHT 16u
+// Whether a launch with these round_form bits gets PT_ROUND_TIGHT beside them: one that would take the flat deferring form, of a scene
+// whose leaf test is the hand-written one (KParams::small_det), unless the knob says no.  Host code (ptamd_launch.cpp: fill_launch).
+inline bool round_form_tight(uint32_t round_form, uint32_t small_det, bool knob)
+{
+  const uint32_t needs = PT_ROUND_FLAT | PT_ROUND_SKIP | PT_ROUND_DEFER;
+  return knob && small_det != 0u && (round_form & needs) == needs;
+}
 // LDS bytes in front of the scene's copy in the skip forms: the node a walk starts at, one word per ray octant
 #define PT_SKIP_ENTRY_BYTES 32u
 
@@ -510,7 +520,8 @@ struct KParams {
 #define PT_RS_FLAT_SKIP_DEFER 11
 #define PT_RS_PLAIN_SKIP_DEFER 12
 #define PT_RS_STATS_DEFER 13
-#define PT_RS_FORMS 14
+#define PT_RS_FLAT_SKIP_TIGHT 14
+#define PT_RS_FORMS 15
 
 // One form of the restart kernel: what the kernel compiles in for it, what a launch of it reports, and where it is compiled.  The kernel
 // reads its row at compile time, restart_entry (pt_kernels.hip) the last three columns, the launcher `reports` and `defer`.
@@ -524,40 +535,44 @@ struct RestartTraits {
   bool flat;       // the shading half reads the compact record: no texel fetch, normal map, cubemap lookup or refraction branch
   bool skip;       // walks the scene's relinked links from the entry node of the ray's octant (stage_scene: SKIP)
   bool defer;      // rounds leave their sparse later leaf phases to the next round's first one (traverse_round: DEFER; pt_round.h)
+  bool tight;      // a deferring round compiled for small_det != 0, with its control in scalars of their own and the walk's position kept in
+                   // the box loop's terms across the shading half (traverse_round_tight)
   int reports;     // what ptamd_last_restart_form answers: a deferring copy reports the form it copies
   bool resident, streamed, contracted;   // compiled with LDS_RESIDENT true, with it false; those also in pt_kernels_fma.hip
 };
 constexpr RestartTraits kRestartForms[] = {
-  //stats stamps brute wide list   lean   flat   skip   defer  reports           resident streamed contracted
+  //stats stamps brute wide list   lean   flat   skip   defer  tight  reports           resident streamed contracted
   // PLAIN: the shipped instantiation.  Of a resident scene it serves only the common launch (static camera, pools in LDS, no XCD
   // regions, no interleaved bands); of a scene that does not fit in LDS, every launch of the four-wide walk from L2
-  { false, false, false, 0, false, true,  false, false, false, PT_RS_PLAIN,      true,  true,  true },
+  { false, false, false, 0, false, true,  false, false, false, false, PT_RS_PLAIN,      true,  true,  true },
   // STATS: counters are wanted
-  { true,  false, false, 0, false, false, false, false, false, PT_RS_STATS,      true,  true,  false },
+  { true,  false, false, 0, false, false, false, false, false, false, PT_RS_STATS,      true,  true,  false },
   // STAMPS: an instantiation of its own, since even switched off the four stamps cost the round loop 1.5 %
-  { false, true,  false, 0, false, false, false, false, false, PT_RS_STAMPS,     true,  true,  false },
+  { false, true,  false, 0, false, false, false, false, false, false, PT_RS_STAMPS,     true,  true,  false },
   // BRUTE: a camera or light too far out for the boxes' margins (ptamd_scene.cpp: far_origin_camera)
-  { false, false, true,  0, false, false, false, false, false, PT_RS_BRUTE,      true,  true,  true },
+  { false, false, true,  0, false, false, false, false, false, false, PT_RS_BRUTE,      true,  true,  true },
   // WIDE8: scenes that do not fit in LDS walked in the eight-wide quantised form (Bvh::nodes8) instead of the four-wide one
-  { false, false, false, 1, false, false, false, false, false, PT_RS_WIDE8,      false, true,  false },
+  { false, false, false, 1, false, false, false, false, false, false, PT_RS_WIDE8,      false, true,  false },
   // WIDE4Q: ... in the four-wide form with 64-byte quantised nodes (Bvh::nodes4q)
-  { false, false, false, 2, false, false, false, false, false, PT_RS_WIDE4Q,     false, true,  false },
+  { false, false, false, 2, false, false, false, false, false, false, PT_RS_WIDE4Q,     false, true,  false },
   // GENERIC: an LDS-resident scene in a launch the shipped instantiation does not serve: the same code with the four constants read at run time
-  { false, false, false, 0, false, false, false, false, false, PT_RS_GENERIC,    true,  false, true },
+  { false, false, false, 0, false, false, false, false, false, false, PT_RS_GENERIC,    true,  false, true },
   // LIST: adaptive sampling (pt_adaptive.h): the paths of the pixels on the active list, not of the frame's tiles
-  { false, false, false, 0, true,  false, false, false, false, PT_RS_LIST,       true,  true,  false },
+  { false, false, false, 0, true,  false, false, false, false, false, PT_RS_LIST,       true,  true,  false },
   // FLAT: PLAIN's launches of a flat scene under a uniform environment (ptamd_scene.cpp: scene_is_flat; KParams::round_form)
-  { false, false, false, 0, false, true,  true,  false, false, PT_RS_FLAT,       true,  false, false },
+  { false, false, false, 0, false, true,  true,  false, false, false, PT_RS_FLAT,       true,  false, false },
   // FLAT_SKIP: FLAT over the relinked links: box tests nearly every ray passes are left out (KParams::round_form)
-  { false, false, false, 0, false, true,  true,  true,  false, PT_RS_FLAT_SKIP,  true,  false, false },
+  { false, false, false, 0, false, true,  true,  true,  false, false, PT_RS_FLAT_SKIP,  true,  false, false },
   // PLAIN_SKIP: ... and PLAIN
-  { false, false, false, 0, false, true,  false, true,  false, PT_RS_PLAIN_SKIP, true,  false, false },
+  { false, false, false, 0, false, true,  false, true,  false, false, PT_RS_PLAIN_SKIP, true,  false, false },
   // FLAT_SKIP_DEFER: FLAT_SKIP with deferred leaf phases; nothing else in it differs from the form it copies
-  { false, false, false, 0, false, true,  true,  true,  true,  PT_RS_FLAT_SKIP,  true,  false, false },
+  { false, false, false, 0, false, true,  true,  true,  true,  false, PT_RS_FLAT_SKIP,  true,  false, false },
   // PLAIN_SKIP_DEFER: ... and PLAIN_SKIP
-  { false, false, false, 0, false, true,  false, true,  true,  PT_RS_PLAIN_SKIP, true,  false, false },
+  { false, false, false, 0, false, true,  false, true,  true,  false, PT_RS_PLAIN_SKIP, true,  false, false },
   // STATS_DEFER: STATS with them: the counters of a launch the deferring forms would have served
-  { true,  false, false, 0, false, false, false, false, true,  PT_RS_STATS,      true,  false, false },
+  { true,  false, false, 0, false, false, false, false, true,  false, PT_RS_STATS,      true,  false, false },
+  // FLAT_SKIP_TIGHT: FLAT_SKIP_DEFER's launches of a scene with small_det != 0 (KParams::round_form: PT_ROUND_TIGHT): the same rounds, tighter code
+  { false, false, false, 0, false, true,  true,  true,  true,  true,  PT_RS_FLAT_SKIP,  true,  false, false },
 };
 static_assert(sizeof kRestartForms / sizeof kRestartForms[0] == PT_RS_FORMS, "one row per PT_RS_* number");
 constexpr RestartTraits restart_traits(int variant) { return kRestartForms[variant]; }
@@ -586,6 +601,7 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
   if (!lds_resident && p && p->wide8) return { full(p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8), false };   // the knobs' quantised node forms
   if (!lds_resident) return { PT_RS_PLAIN, false };                            // the four-wide walk from L2
   if (p && !restart_shipped_launch(*p)) return { PT_RS_GENERIC, true };        // a resident scene in a launch the lean forms are not compiled for
+  if (defers && (p->round_form & PT_ROUND_FLAT) && (p->round_form & PT_ROUND_TIGHT)) return { PT_RS_FLAT_SKIP_TIGHT, true };   // the flat deferring form's tight copy
   if (defers) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP_DEFER : PT_RS_PLAIN_SKIP_DEFER, true };   // the skip forms with deferred leaf phases
   if (p && (p->round_form & PT_ROUND_SKIP) && !contracted) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP : PT_RS_PLAIN_SKIP, true };   // the same two launches of a scene with a skip set
   if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment

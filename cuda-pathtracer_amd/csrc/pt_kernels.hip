@@ -24,7 +24,14 @@
 
 #include <utility>
 
-#ifndef PT_FMA_BUILD
+// A side unit compiles this source once more for restart kernels of its own and nothing else: pt_kernels_fma.hip (the contracted
+// instantiations, PT_FMA_BUILD) and pt_kernels_tight.hip (the flat deferring form's tight copy, PT_TIGHT_BUILD: in a unit of its own,
+// where its code cannot move the compiler's choices in the kernels of this one)
+#if defined(PT_FMA_BUILD) || defined(PT_TIGHT_BUILD)
+#define PT_SIDE_UNIT 1
+#endif
+
+#ifndef PT_SIDE_UNIT
 #include "pt_denoise.h"
 #endif
 
@@ -424,17 +431,23 @@ PT_DEV void walk_to_leaf_lds(uint32_t lds_nodes, Walk& w, uint32_t& leaf_first, 
   w.node = walk_lds_node(lds_nodes, state);
 }
 
+// a leaf's records through the hand-written test (mt_test_asm: scenes with small_det only)
+PT_DEV void walk_leaf_asm(const float4* tris, Walk& w, uint32_t leaf_first, uint32_t leaf_count, uint32_t stride = 3u /* float4 per triangle record */)
+{
+  for (uint32_t k = 0; k < leaf_count; ++k) {
+    const float4* r = tris + (leaf_first + k) * stride;
+    const float4 a = r[0], b = r[1];
+    const float2 c = *reinterpret_cast<const float2*>(r + 2);
+    mt_test_asm(a, b, c, w.o, w.d, w.best);
+  }
+}
+
 template <bool STATS, bool ASM = false>
 PT_DEV void walk_leaf(const float4* tris, Walk& w, uint32_t leaf_first, uint32_t leaf_count, uint32_t& n_tris,
                       uint32_t& wave_tri_iters, bool small_det = false, uint32_t stride = 3u /* float4 per triangle record */)
 {
   if (ASM && !STATS && PT_ASM_LEAF && small_det) {   // (small_det is wave-uniform: one scalar branch per leaf phase)
-    for (uint32_t k = 0; k < leaf_count; ++k) {
-      const float4* r = tris + (leaf_first + k) * stride;
-      const float4 a = r[0], b = r[1];
-      const float2 c = *reinterpret_cast<const float2*>(r + 2);
-      mt_test_asm(a, b, c, w.o, w.d, w.best);
-    }
+    walk_leaf_asm(tris, w, leaf_first, leaf_count, stride);
     return;
   }
   for (uint32_t k = 0; k < leaf_count; ++k) {
@@ -1004,8 +1017,9 @@ PT_DEV void flush_counters(const KParams& p, const Counters& cnt, uint32_t sampl
 // host checks it (ptamd_host.h: kCompactMaxNodes) and walks bigger trees from global memory.
 // SKIP (the restart kernel's skip forms, COMPACT only): the link words come from the scene's relinked table behind p.nodes
 // (host/skip_links.cpp: the same codes with node indices for addresses, the targets that are skipped nodes already replaced), and
-// the scene's copy starts PT_SKIP_ENTRY_BYTES into s_mem, behind the eight nodes a walk starts at (node index, PT_END for no tree).
-template <int KIND, bool LDS_RESIDENT, bool COMPACT = false, bool SKIP = false>
+// the scene's copy starts PT_SKIP_ENTRY_BYTES into s_mem, behind the eight nodes a walk starts at (node index, PT_END for no tree;
+// ENTRY_STATES, the tight form: as the box loop's states instead, the node's LDS address or 0xFFFF).
+template <int KIND, bool LDS_RESIDENT, bool COMPACT = false, bool SKIP = false, bool ENTRY_STATES = false>
 PT_DEV void stage_scene(const KParams& p, float4* s_mem_, const float4*& s_nodes, const float4*& s_tris)
 {
   float4* const s_mem = SKIP ? s_mem_ + PT_SKIP_ENTRY_BYTES / 16u : s_mem_;
@@ -1020,7 +1034,8 @@ PT_DEV void stage_scene(const KParams& p, float4* s_mem_, const float4*& s_nodes
         const uint32_t* relinked = reinterpret_cast<const uint32_t*>(p.nodes + p.n_nodes * 4);
         if (SKIP && threadIdx.x < 8u) {
           const uint32_t e = relinked[p.n_nodes * 8u + threadIdx.x];
-          reinterpret_cast<uint32_t*>(s_mem_)[threadIdx.x] = e == 0xFFFFu ? PT_END : e;
+          if (ENTRY_STATES) reinterpret_cast<uint32_t*>(s_mem_)[threadIdx.x] = e == 0xFFFFu ? 0xFFFFu : base + e * 32u;
+          else reinterpret_cast<uint32_t*>(s_mem_)[threadIdx.x] = e == 0xFFFFu ? PT_END : e;
         }
         // box addresses are 15-bit codes: the host only launches this layout for <= kCompactMaxNodes nodes and the
         // kernels keep no static LDS in front of s_mem; should either ever change, stop here rather than walk garbage
@@ -1335,6 +1350,50 @@ PT_DEV void traverse_round_deferring(const float4* nodes, const float4* tris, ui
   best = w.best;
   node = w.node;
   if (STATS) { cnt.idle3[0] += w.idle_unstarted; cnt.idle3[1] += w.idle_finished; cnt.idle3[2] += w.idle_parked; }
+}
+
+// The deferring round of the flat skip form's tight copy (RestartTraits::tight): the rounds of traverse_round_deferring's LDS half,
+// decision for decision (pt_round.h), compiled for the one launch it serves.  What differs is integer and control work only:
+//   * the leaf phase is mt_test_asm's alone: the launcher sends a scene here only with small_det != 0 (pt_device.h: round_form_tight), so
+//     the compiled Moller-Trumbore loop and the join of the two are not in the round;
+//   * t_eff, leaf_defer and `first` are scalars of their own (the flat form has the registers the plain one lacks), and round_min and
+//     the knob come in apart;
+//   * `pos`, the lane's place between rounds, is in the box loop's own terms: a box's LDS address, 0xFFFF (the walk is over) or a
+//     pending word (pt_round.h, which tells the three apart: bit 15 and a low half other than 0xFFFF).  The entry words are staged as
+//     states (stage_scene: ENTRY_STATES), so no round converts a node index;
+//   * a fresh walk comes in as PT_WALK_FRESH and takes its entry word here, by the octant walk_init forms for the round anyway: one
+//     LDS read and a select for every lane instead of a second octant in a branch of the caller.  entries: the eight entry words.
+#define PT_WALK_FRESH 0xFFFFFFFFu   /* (no state, no pending word: pt_round.h keeps a low half of 0xFFFF for the end of a walk) */
+PT_DEV void traverse_round_tight(const float4* nodes, const float4* tris, const uint32_t* entries, uint32_t n_nodes, f3 o, f3 d, Best& best, uint32_t& pos,
+                                 uint32_t round_min, uint32_t leaf_defer_knob, uint32_t round_div, uint32_t round_div_m16, uint32_t walk_min)
+{
+  Walk w;
+  walk_init(w, o, d, n_nodes, true);
+  asm volatile("" : "+v"(w.oct));   // (formed once: the entry word's index and the link offset both come from this register)
+  w.best = best;
+  const uint32_t entry = entries[w.oct];
+  if (pos == PT_WALK_FRESH) pos = entry;
+  const uint32_t n_start = (uint32_t)__popcll(__ballot(pos != 0xFFFFu));   // (a pending lane enters like any other)
+  const uint32_t t_eff = round_threshold(n_start, round_min, round_div, round_div_m16);
+  const uint32_t leaf_defer = round_leaf_defer(leaf_defer_knob, t_eff);
+  const bool pending = round_is_pending(pos);
+  uint32_t state = pending ? round_pending_leaf(pos) : pos;
+  const uint32_t lnk = walk_lds_link_offset(w);
+  uint32_t leaf_first, leaf_count;
+  for (bool first = true;; first = false) {
+    walk_to_leaf_lds_state(state, lnk, w, leaf_first, leaf_count, walk_min);
+    // (a pending lane ran no box test: the continuation it carries is the one that counts, as in traverse_round_deferring)
+    if (first && pending) state = round_pending_continuation(pos);
+    // (the two masks apart: each is a compare's own result, and a leaf phase moves no state, so the first serves round_ends too)
+    const unsigned long long walking = __builtin_amdgcn_ballot_w64(state != 0xFFFFu), parked = __builtin_amdgcn_ballot_w64(leaf_count != 0u);
+    if (!round_leaf_phase_runs(first, (uint32_t)__popcll(walking | parked), leaf_defer)) break;   // (the parked lanes keep their leaf_count)
+    if (leaf_count != 0u) walk_leaf_asm(tris, w, leaf_first, leaf_count);
+    leaf_count = 0u;
+    if (round_ends((uint32_t)__popcll(walking), t_eff)) break;
+  }
+  // a lane still parked was deferred: its leaf and its continuation go out as a pending word
+  pos = leaf_count != 0u ? round_pending_pack(0x8000u | (leaf_count << 11) | leaf_first, state) : state;
+  best = w.best;
 }
 
 // One round of the nearest-hit search for the lanes that call it: walks continue from (best, node) and the round ends
@@ -2023,6 +2082,10 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   constexpr bool STATS = FORM.stats;
   constexpr uint32_t THREADS = LDS_RESIDENT ? PT_RS_THREADS : PT_RS4_THREADS;
   constexpr bool DEFER = LDS_RESIDENT && FORM.defer;
+  // the tight copy of the flat deferring form (traverse_round_tight): `node` holds the walk's place in the box loop's terms
+  constexpr bool TIGHT = DEFER && FORM.tight;
+  static_assert(!FORM.tight || (FORM.defer && FORM.skip && FORM.lean && !FORM.stats && PT_ASM_LEAF), "the tight round is the flat deferring skip form's");
+  constexpr uint32_t WALK_OVER = TIGHT ? 0xFFFFu : PT_END;   // `node` of a finished walk
   constexpr bool SKIP = LDS_RESIDENT && FORM.skip;
   constexpr bool FLAT = LDS_RESIDENT && FORM.flat;
   constexpr bool LEAN = LDS_RESIDENT && FORM.lean;
@@ -2037,7 +2100,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   const float4* s_nodes;
   const float4* s_tris;
   PT_STAMP(0);
-  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS, SKIP>(p, s_mem, s_nodes, s_tris);
+  stage_scene<2, LDS_RESIDENT, LDS_RESIDENT && !STATS, SKIP, TIGHT>(p, s_mem, s_nodes, s_tris);
   // scenes that do not fit in LDS are walked in the four-wide form; LDS then holds the waves' stacks
   constexpr bool WIDE = !LDS_RESIDENT;
 
@@ -2073,7 +2136,7 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   bool walking = false;  // its path is in the middle of a walk: (best, node, r1) are live
   Best best;
   best.t = PT_MAX_DIST; best.u = best.v = 0.f; best.idx = PT_END;
-  uint32_t node = PT_END;
+  uint32_t node = WALK_OVER;
   // wave-uniform: the pool holds the paths of ONE tile, entries [pool_rd, 64) not yet handed out
   uint32_t pool_rd = 64u, tile_x0 = 0, tile_y0 = 0, tile_k = 0;
   uint32_t tile_row_delta = 0;   // (frame row) - (row of the launch's buffers + row_begin): non-zero for interleaved bands
@@ -2222,7 +2285,8 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
     if (!idle) {
       if (!walking) {
         best.t = PT_MAX_DIST; best.u = 0.f; best.v = 0.f; best.idx = PT_END;
-        if (SKIP) node = reinterpret_cast<const uint32_t*>(s_mem)[(st.d.x < 0.f ? 1u : 0u) | (st.d.y < 0.f ? 2u : 0u) | (st.d.z < 0.f ? 4u : 0u)];   // (walk_init's octant)
+        if (TIGHT) node = PT_WALK_FRESH;   // (the round looks the entry word up: it forms the ray's octant anyway)
+        else if (SKIP) node = reinterpret_cast<const uint32_t*>(s_mem)[(st.d.x < 0.f ? 1u : 0u) | (st.d.y < 0.f ? 2u : 0u) | (st.d.z < 0.f ? 4u : 0u)];   // (walk_init's octant)
         else node = p.n_nodes ? 0u : PT_END;
         cur = p.n_nodes4 ? 0u : PT_NONE;
         sp = 0u;
@@ -2238,14 +2302,17 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
       } else if (WIDE) {
         traverse_round4<STATS, FORM.wide>(p, p.nodes4, s_tris, stk, st.o, st.d, best, cur, sp, p.round_min, p.round_div, p.round_div_m16, p.walk_min4, p.small_det != 0u, cnt);
         node = cur == PT_NONE ? PT_END : 0u;
+      } else if constexpr (TIGHT) {
+        traverse_round_tight(s_nodes, s_tris, reinterpret_cast<const uint32_t*>(s_mem), p.n_nodes, st.o, st.d, best, node, p.round_min, (p.round_defer >> 8) == 0xFFu ? PT_LEAF_DEFER_AUTO : p.round_defer >> 8,
+                             p.round_div, p.round_div_m16, p.walk_min);
       } else {
         traverse_round<STATS, LDS_RESIDENT, DEFER>(s_nodes, s_tris, p.n_nodes, st.o, st.d, best, node, DEFER ? p.round_defer : p.round_min, p.round_div, p.round_div_m16, p.walk_min, p.small_det != 0u, cnt);
       }
       if (STATS) {   // fetch_events: rounds of this wave; fetch_rays: walks that completed in them
         if (lane == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) cnt.fetch_events++;
-        if (node == PT_END) cnt.fetch_rays++;
+        if (node == WALK_OVER) cnt.fetch_rays++;
       }
-      if (node == PT_END) {
+      if (node == WALK_OVER) {
         // the iteration's first variate (raytrace.cu:70) is drawn here, after the search: intersect() draws nothing, so the
         // path's random stream is the same, and r1 need not live (in scratch, as it turned out) across the walk
         long long tl0 = 0;
@@ -2853,7 +2920,7 @@ __global__ void __launch_bounds__(256) pt_trace_rays_kernel(PT_KERNEL_PARAMS, co
   out[i] = make_int4(kind, index, (int)f_as_u(nr.t), 0);
 }
 
-#ifndef PT_FMA_BUILD   /* (not in the contracted translation unit: pt_kernels_fma.hip) */
+#ifndef PT_SIDE_UNIT   /* (not in the side units: pt_kernels_fma.hip, pt_kernels_tight.hip) */
 // ---------------------------------------------------------------- denoiser (ptamd_denoise, ptamd_render_features; pt_denoise.h)
 
 // Feature pass: per pixel of a full frame, the camera ray path_begin builds with the aperture offset zero (origin cam_pos,
@@ -2929,7 +2996,7 @@ hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t str
 // tile tickets (pt_launch.h: KernelForm).  The tables below map template arguments to entry points, one per family; megakernel_form
 // describes a launch's form, form_blocks_per_cu and launch_form serve every one of them, resolve_kernels walks the tables.
 #define PT_FN(...) reinterpret_cast<const void*>(__VA_ARGS__)
-#ifndef PT_FMA_BUILD   /* (the contracted instantiation, pt_kernels_fma.hip, only carries the restart kernel) */
+#ifndef PT_SIDE_UNIT   /* (the side units only carry the restart kernel) */
 static const void* const kTileEntries[2][2][2] = {   // [kind: every face, BVH][lds_resident][stats]
   { { PT_FN(pt_megakernel<1, false, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<1, false, true, PT_TILE_THREADS>) },
     { PT_FN(pt_megakernel<1, true, false, PT_TILE_THREADS>), PT_FN(pt_megakernel<1, true, true, PT_TILE_THREADS>) } },
@@ -2944,18 +3011,28 @@ static const void* const kSplitEntries[2][2] = {
 static const void* const kBlockwiseEntries[2][2] = {
   { PT_FN(pt_megakernel_blockwise<false, false>), PT_FN(pt_megakernel_blockwise<false, true>) },
   { PT_FN(pt_megakernel_blockwise<true, false>), PT_FN(pt_megakernel_blockwise<true, true>) } };
-constexpr bool kContracted = false;
-#else
+#endif
+#ifdef PT_FMA_BUILD
 constexpr bool kContracted = true;
+#else
+constexpr bool kContracted = false;
+#endif
+#ifdef PT_TIGHT_BUILD
+constexpr bool kTightUnit = true;
+#else
+constexpr bool kTightUnit = false;
 #endif
 
 // The restart kernel: (form, LDS_RESIDENT) -> its instantiation, nullptr where none is compiled: the last three columns of the form's
 // row (pt_device.h: kRestartForms).  A discarded branch depends on V, so nothing is instantiated that the table does not name.
+// A tight form is compiled in pt_kernels_tight.hip and nowhere else; this unit asks that one for its entry.
 template <int V>
 static const void* restart_entry_of(bool lds_resident)
 {
   constexpr RestartTraits FORM = restart_traits(V);
-  if constexpr (FORM.contracted || !kContracted) {
+  if constexpr (FORM.tight && !kTightUnit) {
+    if constexpr (!kContracted) return ptamd_tight_restart_entry(V, lds_resident ? 1 : 0);
+  } else if constexpr ((FORM.contracted || !kContracted) && FORM.tight == kTightUnit) {
     if constexpr (FORM.resident) { if (lds_resident) return PT_FN(pt_megakernel_restart<true, V>); }
     if constexpr (FORM.streamed) { if (!lds_resident) return PT_FN(pt_megakernel_restart<false, V>); }
   }
@@ -2979,7 +3056,7 @@ uint32_t restart_wide_blocks_per_cu() { return (PT_RS4_WAVES_PER_EU * 256u) / PT
 
 // lds_bytes: the staged scene (and the pools behind it) when lds_resident, else the treelet and stacks of the wide walk.  Occupancy is
 // asked of the family's plain form (no launch: restart_select's p == nullptr), whatever form the launch takes.
-static KernelForm restart_form(bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)
+[[maybe_unused]] static KernelForm restart_form(bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)   // (not used in pt_kernels_tight.hip)
 {
   const RestartForm launched = restart_select(lds_resident, stats, list, kContracted, p);
   const RestartForm queried = restart_select(lds_resident, false, list, kContracted, nullptr);
@@ -2991,7 +3068,7 @@ static KernelForm restart_form(bool lds_resident, bool stats, bool list, size_t 
   return f;
 }
 
-#ifndef PT_FMA_BUILD
+#ifndef PT_SIDE_UNIT
 KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)
 {
   const int r = lds_resident ? 1 : 0, s = stats ? 1 : 0;
@@ -3148,12 +3225,20 @@ hipError_t launch_trace_rays(const KParams& p, int kind, const float* rays_dev, 
   return hipGetLastError();
 }
 
-#else
+#elif defined(PT_FMA_BUILD)
 } // namespace (ptamd_fma in this translation unit)
 // The one C entry point of the contracted instantiation (pt_kernels_fma.hip): its form of a launch, for megakernel_form
 extern "C" void ptamd_fma_restart_form(int lds_resident, size_t lds_bytes, const ptamd_fma::KParams* p, ptamd_fma::KernelForm* out)
 {
   *out = ptamd::restart_form(lds_resident != 0, false, false, lds_bytes, p);
+}
+namespace ptamd {
+#else
+} // namespace (ptamd_tight in this translation unit)
+// The one C entry point of pt_kernels_tight.hip: the entry of a tight form, for restart_entry_of
+extern "C" const void* ptamd_tight_restart_entry(int variant, int lds_resident)
+{
+  return ptamd::restart_entry(variant, lds_resident != 0);
 }
 namespace ptamd {
 #endif

@@ -67,3 +67,5 @@ hipError_t launch_motion_reproject(const DenoiseParams& q, const TemporalParams&
 
 // the contracted instantiation of the restart kernel (pt_kernels_fma.hip) exports its form of a launch; megakernel_form asks it
 extern "C" void ptamd_fma_restart_form(int lds_resident, size_t lds_bytes, const ptamd::KParams* p, ptamd::KernelForm* out);
+// the unit of the restart kernel's tight forms (pt_kernels_tight.hip) exports their entries (nullptr: none compiled); restart_entry_of asks it
+extern "C" const void* ptamd_tight_restart_entry(int variant, int lds_resident);

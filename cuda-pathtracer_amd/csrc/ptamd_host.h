@@ -115,6 +115,7 @@ struct ptamd_context {
   std::vector<ptamd::DeviceCubemap> cubemaps;
   uint32_t frame_counter = 0; // raytrace.cu:296 `static unsigned int seed`
   bool last_restart_deferred = false;   // that launch took a deferring instantiation (pt_round.h): ptamd_last_restart_deferred
+  bool last_restart_tight = false;      // ... the tight copy of the flat deferring one (RestartTraits::tight): ptamd_last_restart_tight
   int32_t last_restart_form = -1;   // PT_RS_* of the context's last megakernel launch (-1: none yet, or another kernel): ptamd_last_restart_form
   ptamd::DeviceBuffer<unsigned long long> d_stats;   // 32 words: 0..12 counters, 14 self-test, 15 error flag, 16..27 phase cycles, 28 the ray queue's head
   ptamd::DeviceBuffer<float> d_gamma;     // 258 floats: the gamma step of the tonemap as a table (pt_kernels.hip: gamma_byte); empty with PTAMD_GAMMA_TABLE=0

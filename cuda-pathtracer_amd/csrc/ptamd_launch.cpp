@@ -235,6 +235,8 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   // defers in both
   const bool defer = ctx->knobs.leaf_defer != 0u && (ctx->knobs.leaf_defer != PT_LEAF_DEFER_AUTO || (p.round_form & PT_ROUND_FLAT));
   if (s.links && pl.resident) p.round_form |= PT_ROUND_SKIP | (defer ? PT_ROUND_DEFER : 0u);
+  // ... and the flat deferring form's tight copy, which holds the hand-written leaf test only: for scenes with small_det
+  if (round_form_tight(p.round_form, p.small_det, ctx->knobs.tight_round)) p.round_form |= PT_ROUND_TIGHT;
 }
 
 // Steps 2-4: the stream's sample scratch; pipelining (ptamd_context::lane), not for graph captures, counters, no_pipelining or the
@@ -291,7 +293,7 @@ void lay_out_lds(const ptamd_context* ctx, const DeviceScene& s, bool stats, con
     const size_t blocks_wanted = (24u + waves - 1u) / waves;             // 24 waves per CU
     const auto fits = [&](size_t scene) { return (((scene + 15u) & ~(size_t)15u) + (size_t)waves * PT_POOL_LDS_BYTES) * blocks_wanted + 1024u <= 160u * 1024u; };
     // the skip forms keep their eight entry nodes in front of the scene's copy (pt_kernels.hip: stage_scene)
-    if ((p.round_form & PT_ROUND_SKIP) && !(ctx->knobs.pool_in_lds && fits(pl.lds + PT_SKIP_ENTRY_BYTES))) p.round_form &= ~(PT_ROUND_SKIP | PT_ROUND_DEFER);
+    if ((p.round_form & PT_ROUND_SKIP) && !(ctx->knobs.pool_in_lds && fits(pl.lds + PT_SKIP_ENTRY_BYTES))) p.round_form &= ~(PT_ROUND_SKIP | PT_ROUND_DEFER | PT_ROUND_TIGHT);
     const size_t scene_lds = pl.lds + ((p.round_form & PT_ROUND_SKIP) ? PT_SKIP_ENTRY_BYTES : 0u);
     // The list form of adaptive sampling is compiled with its pools in LDS (no scratch, as the shipped instantiation): they go
     // there whatever the knob, at one workgroup per CU when two do not fit
@@ -522,6 +524,7 @@ int issue(ptamd_context* ctx, const DeviceScene& scene, bool stats, const Adapti
   // (what ptamd_last_restart_form reports: the row of the form that is launched; the deferring copies answer as the forms they copy)
   ctx->last_restart_form = form.restart_form < 0 ? -1 : restart_traits(form.restart_form).reports;
   ctx->last_restart_deferred = form.restart_form >= 0 && restart_traits(form.restart_form).defer;
+  ctx->last_restart_tight = form.restart_form >= 0 && restart_traits(form.restart_form).tight;
   hipError_t e = launch_form(form, p, pl.n_blocks, restart ? mega_stream : pl.stream);
   if (e == hipSuccess && pl.pipelined) {
     PT_HIP(hipEventRecord(sc->mega_done[pl.slab].get(), mega_stream));

@@ -796,6 +796,13 @@ int ptamd_last_restart_deferred(ptamd_context* ctx, int32_t* out)
   return PTAMD_OK;
 }
 
+int ptamd_last_restart_tight(ptamd_context* ctx, int32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_last_restart_tight: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->last_restart_tight ? 1 : 0;
+  return PTAMD_OK;
+}
+
 int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
 {
   if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_cull_count: bad argument"); return PTAMD_ERR_ARG; }

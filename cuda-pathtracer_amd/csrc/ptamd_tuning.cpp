@@ -52,6 +52,7 @@ constexpr Knob kKnobs[] = {
   on_off("PTAMD_WIDE4Q", &S::wide4q),
   on_off("PTAMD_RS_GENERIC", &S::generic_round),
   on_off("PTAMD_RS_FLAT", &S::flat_round),
+  on_off("PTAMD_RS_TIGHT", &S::tight_round),
   number("PTAMD_SKIP", kSkipWord, &S::skip_mode, 0, 0),
   { "PTAMD_SKIP_THRESHOLD", kOpenUnit, nullptr, nullptr, &S::skip_threshold, 0, 1 },
   on_off("PTAMD_POOL_LDS", &S::pool_in_lds),

@@ -24,6 +24,7 @@ struct TuningSettings {
   bool wide8 = false;                     // PTAMD_WIDE8=1: big scenes walk the eight-wide quantised nodes (measured 8 % slower: DESIGN.md §4)
   bool wide4q = false;                    // PTAMD_WIDE4Q=1: big scenes walk the 64-byte quantised four-wide nodes instead of the float ones (ahead by 2.8 % while the walk's LDS accesses went out as FLAT instructions, level since they are LDS instructions: profiles/r03_notes.md)
   bool generic_round = false;             // PTAMD_RS_GENERIC=1: resident scenes take the restart kernel's generic instantiation (launch constants read at run time), for A/B and tests
+  bool tight_round = true;                // PTAMD_RS_TIGHT=0: launches of the flat deferring form stay there instead of taking its tight copy (PT_RS_FLAT_SKIP_TIGHT), for A/B and tests
   bool flat_round = true;                 // PTAMD_RS_FLAT=0: flat scenes take PT_RS_PLAIN instead of the restart kernel's flat instantiation, for A/B and tests
   uint32_t skip_mode = PTAMD_SKIP_DEFAULT; // PTAMD_SKIP: 0 no node is skipped (PTAMD_SKIP_SET with no set: the old forms are launched), root, all
   float skip_threshold = 0.0f;            // PTAMD_SKIP_THRESHOLD: the selection's pass rate (0: kSkipThreshold)

@@ -313,6 +313,7 @@ SIGNATURES = {
     "ptamd_last_restart_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ptamd_host_faces_away": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptamd_last_restart_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "ptamd_last_restart_tight": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ptamd_host_skip_events": (C.c_int, [C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_host_round_threshold": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),

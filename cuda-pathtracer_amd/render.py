@@ -205,6 +205,13 @@ class Context:
         N.check(self._lib.ptamd_last_restart_deferred(self._h, C.byref(out)))
         return out.value != 0
 
+    def last_restart_tight(self) -> bool:
+        """ptamd_last_restart_tight: the last megakernel launch took the tight copy of the flat deferring form (PTAMD_RS_TIGHT=0
+        keeps launches in the form it copies)."""
+        out = C.c_int32(0)
+        N.check(self._lib.ptamd_last_restart_tight(self._h, C.byref(out)))
+        return out.value != 0
+
     def scene_is_flat(self, scene_id: int, cubemap_id: int) -> bool:
         """ptamd_scene_is_flat: launches of the scene under the cubemap take the restart kernel's flat form."""
         out = C.c_int32()

@@ -1048,6 +1048,7 @@ int ptamd_scene_skip_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
 int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out);
 int ptamd_last_restart_form(ptamd_context* ctx, int32_t* out);
 int ptamd_last_restart_deferred(ptamd_context* ctx, int32_t* out);
+int ptamd_last_restart_tight(ptamd_context* ctx, int32_t* out);
 int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
                           const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
                           uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out);
@@ -1062,6 +1063,9 @@ int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out);
  * were), =<lanes, 1..64> that threshold in both forms.
  * ptamd_last_restart_deferred: 1 when the context's last megakernel launch took a deferring copy (ptamd_last_restart_form then
  * still answers PTAMD_FORM_FLAT_SKIP / PTAMD_FORM_PLAIN_SKIP), else 0.
+ * ptamd_last_restart_tight: 1 when that launch took the tight copy of the flat deferring form: the same rounds compiled for scenes
+ * whose coordinates stay within 1e8 (the hand-written leaf test alone, the round's control in scalars of their own, the walk's
+ * position kept in the box loop's terms between rounds).  It is then deferred as well.  PTAMD_TUNING=1 PTAMD_RS_TIGHT=0: never.
  *
  * ptamd_host_skip_events: the relinked walk of every ray as the sequence of what a lane of the device's box loop does, no device
  * needed (mode, threshold, rays as ptamd_host_skip_trace, no caller-supplied set).  offsets: n + 1 words; ray i owns

@@ -5,14 +5,15 @@ them in the ISA listing (block placement follows the source closely enough for t
 scheduling barriers, so the listing differs slightly from the shipped code).   python3 scripts/isa_regions.py [--dump REGION]
 VARIANT=6 counts the generic instantiation of a resident scene (PT_RS_GENERIC) instead of the shipped one (0), VARIANT=8 the flat
 one (PT_RS_FLAT: flat scenes under a uniform environment), VARIANT=9 / 10 the skip forms of the flat and the shipped one
-(PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP)."""
+(PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP), VARIANT=11 the flat deferring form (PT_RS_FLAT_SKIP_DEFER) and VARIANT=14 its tight copy
+(PT_RS_FLAT_SKIP_TIGHT), which is compiled in a unit of its own, pt_kernels_tight.hip: its counts come from that unit's listing."""
 import os, re, sys, collections
 from kernel_listing import CSRC, listing
 SRC = os.path.join(CSRC, "pt_kernels.hip")
 MARKS = [  # (unique source anchor, marker name) — the marker goes in front of the anchor
     ("    if (!idle) {\n      if (!walking) {\n        best.t = PT_MAX_DIST;", "round_begin"),
     ("      } else if (WIDE) {\n        traverse_round4<STATS, FORM.wide>", "traverse_begin"),
-    ("      if (node == PT_END) {\n        // the iteration's first variate", "traverse_end"),
+    ("      if (node == WALK_OVER) {\n        // the iteration's first variate", "traverse_end"),
     ("        if (path_post<STATS, FIXED, FLAT>(p, st, r1, n, cnt)) {\n          path_finish_sample(p, st);", "lights_end"),
     ("          path_finish_sample(p, st);\n          idle = true;\n          if (STATS) samples++;", "post_end"),
     ("  if (!STATIC && !p.is_static) {\n    st.acc = found ? inter.diffuse_col : env_lookup<FLAT>(p, st.d);", "resolve_end"),
@@ -21,18 +22,28 @@ MARKS = [  # (unique source anchor, marker name) — the marker goes in front of
 ]
 
 
-def marked_listing():
-    """The ISA listing (lines) of pt_kernels.hip compiled with a marker in front of every anchor of MARKS."""
+TIGHT_UNIT = "pt_kernels_tight.hip"   # compiles pt_kernels.hip once more, for the tight forms alone
+TIGHT_VARIANTS = ("14",)
+
+
+def marked_listing(tight=False):
+    """The ISA listing (lines) of pt_kernels.hip compiled with a marker in front of every anchor of MARKS.  tight: of
+    pt_kernels_tight.hip, the same marked text behind that unit's own lines."""
     s = open(SRC).read()
     for anchor, name in MARKS:
         assert s.count(anchor) == 1, (name, s.count(anchor))
         s = s.replace(anchor, 'asm volatile("; PT_MARK %s" ::: "memory");\n' % name + anchor)
-    return listing("pt_kernels.hip", s).split("\n")
+    if not tight:
+        return listing("pt_kernels.hip", s).split("\n")
+    unit = open(os.path.join(CSRC, TIGHT_UNIT)).read()
+    include = '#include "pt_kernels.hip"\n'
+    assert unit.count(include) == 1
+    return listing(TIGHT_UNIT, unit.replace(include, s)).split("\n")
 
 
 def regions(lines, variant):
     """[(region name, Counter, (first line, end line))] of pt_megakernel_restart<true, variant> in a marked listing."""
-    start = [i for i, l in enumerate(lines) if l.startswith("_ZN5ptamd21pt_megakernel_restartILb1ELi%sEEEvNS_7KParamsE:" % variant)][0]
+    start = [i for i, l in enumerate(lines) if re.match(r"_ZN\d+ptamd\w*21pt_megakernel_restartILb1ELi%sEEEvNS_7KParamsE:" % variant, l)][0]
     end = [i for i, l in enumerate(lines) if i > start and re.match(r"\.Lfunc_end\d+:", l)][0]
     marks = [(i, re.search(r"; PT_MARK (\w+)", lines[i]).group(1)) for i in range(start, end) if "; PT_MARK" in lines[i]]
     bounds = [(start, "prologue")] + marks + [(end, "end")]
@@ -53,7 +64,7 @@ def regions(lines, variant):
 
 
 if __name__ == "__main__":
-    lines = marked_listing()
+    lines = marked_listing(tight=os.environ.get("VARIANT", "0") in TIGHT_VARIANTS)
     dump = sys.argv[2] if len(sys.argv) > 2 and sys.argv[1] == "--dump" else None
     for n, c, (a, b) in regions(lines, os.environ.get("VARIANT", "0")):
         print("%-16s %s" % (n, dict(c)))
