@@ -47,10 +47,19 @@ struct DeviceScene {
   // the skip forms' link table lies behind `nodes` (links: there is one).  n_culled: the (leaf, octant) pairs it leaves out NOW; they
   // hold for the triangles they were proven for, so every update of the faces puts links_plain (the table of the skip set alone) back
   // in front of its kernels (restore_plain_links), and ptamd_scene_update, which has the faces, culls again from the host copies
-  // below (cull_on: the upload culled, so it does)
-  bool links = false, cull_on = false;
+  // below (cull_on: the upload culled, so it does).  ptamd_scene_relink culls again on the device, from the records the device holds
+  // and the set's bytes there (relink_on: unless the upload ran under PTAMD_SKIP_CULL=0); links_plain and skip_bytes exist for
+  // every scene with a table.  Its count comes back through two pinned words used in turn; until a reader of n_culled has waited
+  // for it (settle_cull_count) n_culled is stale (cull_pending), and an update of the faces supersedes it (restore_plain_links).
+  bool links = false, cull_on = false, relink_on = false;
   uint32_t n_culled = 0;
   DeviceBuffer<uint32_t> links_plain;
+  DeviceBuffer<uint8_t> skip_bytes;
+  PinnedBuffer<uint32_t> h_cull;                 // two slots of one word
+  Event cull_ready[2];                           // the copy into slot i has finished
+  bool cull_ready_valid[2] = { false, false };
+  uint32_t cull_next = 0, cull_slot = 0;
+  bool cull_pending = false;
   Bvh topology;                          // nodes as uploaded (topology words and miss links never change) and room for the records of new faces
   std::vector<uint32_t> record_face;     // per triangle record its face
   std::vector<uint8_t> skip_set, cull_bits;   // the set; scratch of the re-cull, kept with link_words for the next update

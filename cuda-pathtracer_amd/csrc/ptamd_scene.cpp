@@ -3,8 +3,10 @@
 #include "ptamd_host.h"
 #include "pt_refit.h"
 #include "pt_refit_device.h"
+#include "pt_relink.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace ptamd {
@@ -356,12 +358,26 @@ int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r)
 
 // The link table of the skip set alone over the one with culled links, on the update's stream behind wait_for_readers and in front
 // of the kernels that move the triangles: whatever waits for `updated` (wait_for_update) reads links the new faces cannot belie
+// A count that ptamd_scene_relink left pending stands for "possibly culled": the copy is made, and the count it supersedes is
+// never waited for.
 int restore_plain_links(DeviceScene& s, hipStream_t stream)
 {
-  if (!s.n_culled) return PTAMD_OK;
+  if (!s.n_culled && !s.cull_pending) return PTAMD_OK;
   PT_HIP(hipMemcpyAsync(reinterpret_cast<float*>(s.nodes.get()) + (size_t)s.n_nodes * 16, s.links_plain.get(), ((size_t)s.n_nodes * 8 + 8) * 4,
                         hipMemcpyDeviceToDevice, stream));
   s.n_culled = 0;
+  s.cull_pending = false;
+  return PTAMD_OK;
+}
+
+// Every reader of n_culled calls this first.  After ptamd_scene_relink the count is on its way back from the device, behind the
+// relink's kernel and nothing else: wait for that copy.
+int settle_cull_count(DeviceScene& s)
+{
+  if (!s.cull_pending) return PTAMD_OK;
+  PT_HIP(hipEventSynchronize(s.cull_ready[s.cull_slot].get()));
+  s.n_culled = s.h_cull.get()[s.cull_slot];
+  s.cull_pending = false;
   return PTAMD_OK;
 }
 
@@ -453,13 +469,17 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     d.n_skipped = t.n_skipped; d.n_culled = t.n_culled;
     d.links = t.n_skipped != 0u || t.n_culled != 0u;
     if (d.links) {
-      nodes_and_links.resize(bvh.nodes.size() + t.words.size());
+      // behind the table one word more: the count ptamd_scene_relink's kernel leaves (no launch reads it)
+      nodes_and_links.resize(bvh.nodes.size() + t.words.size() + 1u, 0.0f);
       std::memcpy(nodes_and_links.data() + bvh.nodes.size(), t.words.data(), t.words.size() * 4);
-    }
-    if (t.n_culled) {
+      // what a relink and restore_plain_links need, of every scene with a table: the set as bytes, the table of the set alone
       std::vector<uint32_t> plain;
       skip_link_table(bvh, t.skip, plain);
-      if ((rc = upload(d.links_plain, plain.data(), plain.size() * 4))) return rc;
+      if ((rc = upload(d.links_plain, plain.data(), plain.size() * 4)) || (rc = upload(d.skip_bytes, t.skip.data(), t.skip.size()))) return rc;
+      const char* knob = tuning_env("PTAMD_SKIP_CULL");
+      d.relink_on = !(knob && std::atoi(knob) == 0);
+    }
+    if (t.n_culled) {
       d.cull_on = true;
       d.topology.nodes = bvh.nodes;
       d.topology.n_nodes = bvh.n_nodes; d.topology.n_tris = bvh.n_tris;
@@ -553,6 +573,10 @@ int ptamd_scene_update(ptamd_context* ctx, const ptamd_scene_update_desc* d)
     std::memcpy(s.h_links[slot].get(), s.link_words.data(), link_words * 4);
     PT_HIP(hipMemcpyAsync(reinterpret_cast<float*>(s.nodes.get()) + (size_t)s.n_nodes * 16, s.h_links[slot].get(), link_words * 4, hipMemcpyHostToDevice, stream));
     s.n_culled = n_culled;
+    s.cull_pending = false;   // (a count a relink left pending is superseded)
+  } else if ((rc = restore_plain_links(s, stream)) != PTAMD_OK) {
+    // (an upload that culled nothing is not culled again here; what a relink culled held for the faces of its time)
+    return rc;
   }
   PT_HIP(hipEventRecord(s.staged[slot].get(), stream));
   s.staged_valid[slot] = true;
@@ -806,7 +830,69 @@ int ptamd_last_restart_tight(ptamd_context* ctx, int32_t* out)
 int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)
 {
   if (!ctx || !out || !live_scene(ctx, scene_id)) { set_error("ptamd_scene_cull_count: bad argument"); return PTAMD_ERR_ARG; }
-  *out = ctx->scenes[scene_id].n_culled;
+  DeviceScene& s = ctx->scenes[scene_id];
+  const int rc = settle_cull_count(s);
+  if (rc != PTAMD_OK) return rc;
+  *out = s.n_culled;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_relink(ptamd_context* ctx, uint32_t scene_id, void* stream)
+{
+  const char* who = "ptamd_scene_relink";
+  if (!ctx) { set_error("ptamd_scene_relink: null context"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_relink: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = update_capture_checks(who, ctx, st);
+  if (rc != PTAMD_OK) return rc;
+  DeviceScene& s = ctx->scenes[scene_id];
+  // no link table (not compact, PTAMD_SKIP=0, nothing skipped and nothing culled at upload), or one whose upload was told not to
+  // cull (PTAMD_SKIP_CULL=0): nothing to do.  The form a scene's launches take is fixed at upload.
+  if (!s.links || !s.relink_on || s.n_nodes == 0) return PTAMD_OK;
+  if (s.n_nodes > kRelinkMaxNodes || s.n_bvh_tris > kRelinkMaxTris || !s.links_plain || !s.skip_bytes) {
+    set_error("ptamd_scene_relink: the scene's link tables are inconsistent");
+    return PTAMD_ERR_ARG;
+  }
+  PT_HIP(hipSetDevice(ctx->device));
+  if (!s.h_cull) PT_HIP(s.h_cull.alloc(2u * sizeof(uint32_t)));
+  for (int i = 0; i < 2; ++i) PT_HIP(s.cull_ready[i].ensure());
+  PT_HIP(s.updated.ensure());
+  if ((rc = wait_for_readers(ctx, s, st)) != PTAMD_OK) return rc;
+  // (the copies of earlier relinks read the count word behind their `updated`, possibly on another stream)
+  for (int i = 0; i < 2; ++i)
+    if (s.cull_ready_valid[i]) PT_HIP(hipStreamWaitEvent(st, s.cull_ready[i].get(), 0));
+  RelinkParams r;
+  r.nodes = reinterpret_cast<const float*>(s.nodes.get());
+  r.tris_bvh = reinterpret_cast<const float*>(s.tris_bvh.get());
+  r.skip = s.skip_bytes.get();
+  r.words = reinterpret_cast<uint32_t*>(s.nodes.get()) + (size_t)s.n_nodes * 16;
+  r.n_nodes = s.n_nodes; r.n_tris = s.n_bvh_tris;
+  PT_HIP(launch_relink(r, st));
+  PT_HIP(hipEventRecord(s.updated.get(), st));
+  s.updated_valid = true;
+  // the count back to the host, behind the kernel: launches wait for `updated`, not for this copy
+  const uint32_t slot = s.cull_next++ & 1u;
+  PT_HIP(hipMemcpyAsync(s.h_cull.get() + slot, r.words + (size_t)s.n_nodes * 8 + 8, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  PT_HIP(hipEventRecord(s.cull_ready[slot].get(), st));
+  s.cull_ready_valid[slot] = true;
+  s.cull_slot = slot;
+  s.cull_pending = true;
+  return PTAMD_OK;
+}
+
+int ptamd_scene_links_read(ptamd_context* ctx, uint32_t scene_id, void* out, uint64_t* bytes)
+{
+  if (!ctx || !bytes) { set_error("ptamd_scene_links_read: bad argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_links_read: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  const DeviceScene& s = ctx->scenes[scene_id];
+  const uint64_t size = s.links ? ((uint64_t)s.n_nodes * 8u + 8u) * 4u : 0u;
+  const uint64_t room = *bytes;
+  *bytes = size;
+  if (!out) return PTAMD_OK;
+  if (room < size) { set_error("ptamd_scene_links_read: the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  PT_HIP(hipDeviceSynchronize());
+  if (size) PT_HIP(hipMemcpy(out, reinterpret_cast<const float*>(s.nodes.get()) + (size_t)s.n_nodes * 16, size, hipMemcpyDeviceToHost));
   return PTAMD_OK;
 }
 

@@ -481,6 +481,31 @@ extern "C" int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* 
   return PTAMD_OK;
 }
 
+extern "C" int ptamd_host_relink_words(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
+                                       const uint8_t* skip_in, uint32_t* words_out, uint32_t* n_nodes, uint32_t* n_culled)
+{
+  if ((n_faces && !faces) || !n_nodes || (mode & ~PTAMD_SKIP_CULLED) > PTAMD_SKIP_ALL) { ptamd::set_error("ptamd_host_relink_words: bad argument"); return PTAMD_ERR_ARG; }
+  ptamd::Bvh bvh;
+  int rc = ptamd::build_bvh(faces, n_faces, 1e-3f, 2, bvh, 0u);   // leaves of at most two, as an upload builds them
+  if (rc != PTAMD_OK) return rc;
+  if (!ptamd::skip_links_fit(bvh)) { ptamd::set_error("ptamd_host_relink_words: the tree is outside the compact layout's code space"); return PTAMD_ERR_LIMIT; }
+  const uint32_t room = *n_nodes;
+  *n_nodes = bvh.n_nodes;
+  if (words_out && room < bvh.n_nodes) { ptamd::set_error("ptamd_host_relink_words: room for fewer nodes than the tree has"); return PTAMD_ERR_ARG; }
+  // the set is the upload's: of the first faces; the culled links are those of the faces the records hold now
+  std::vector<uint8_t> skip;
+  ptamd::skip_set_of(bvh, mode & 0xFFu, threshold, skip_in, skip);
+  if (faces_refit && (rc = ptamd::refit_bvh(bvh, faces_refit, n_faces, nullptr, 0)) != PTAMD_OK) return rc;
+  std::vector<uint32_t> words;
+  const char* knob = ptamd::tuning_env("PTAMD_SKIP_CULL");
+  uint32_t pairs = 0;
+  if (knob && std::atoi(knob) == 0) ptamd::skip_link_table(bvh, skip, words);   // (a relink of such an upload does nothing)
+  else pairs = ptamd::relink_words(bvh, skip, words);
+  if (n_culled) *n_culled = pairs;
+  if (words_out) std::memcpy(words_out, words.data(), words.size() * 4);
+  return PTAMD_OK;
+}
+
 extern "C" int ptamd_host_skip_events(const ptamd_face* faces, uint32_t n_faces, uint32_t mode, float threshold, const float* rays, uint32_t n,
                                       uint32_t* offsets, uint32_t* events, uint64_t* n_events)
 {

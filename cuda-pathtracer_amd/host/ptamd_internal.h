@@ -207,6 +207,10 @@ uint32_t cull_table(const Bvh& bvh, std::vector<uint8_t>& cull);
 // of its range in its hit code for o where the rest is a prefix or a suffix.  (The words of a node that is itself culled for o are
 // never read; they follow the skip rule alone.)
 void skip_link_table(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words, const std::vector<uint8_t>* cull = nullptr);
+// The same words as skip_link_table(bvh, skip, words, cull_table(...) ? &cull : nullptr), formed the way the device forms them
+// (csrc/pt_relink.hip, ptamd_scene_relink): records, leaves, interior nodes in passes that each read the pass before, the keep mask
+// and the pair count, then one item per (node, octant).  Returns the (leaf, octant) pairs culled.
+uint32_t relink_words(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words);
 // The set a mode asks for (ptamd.h: PTAMD_SKIP_*): `given` (one byte per node, null: none; leaves never count), the default
 // selection at `threshold` (0: kSkipThreshold), the root alone, every interior node.  rays_per_node 0: kSkipRaysPerNode, or PTAMD_SKIP_RAYS
 void skip_set_of(const Bvh& bvh, uint32_t mode, float threshold, const uint8_t* given, std::vector<uint8_t>& skip, uint32_t rays_per_node = 0u);

@@ -1,7 +1,10 @@
 // skip_links.cpp — which box tests the LDS-resident walk leaves out, and the link table without them (ptamd_internal.h).
 //
-// A post-pass over build_bvh's tables: it reads the tree and writes nothing into it.
+// A post-pass over build_bvh's tables: it reads the tree and writes nothing into it.  The culled links' per-item steps are
+// csrc/pt_relink.h's, shared with the device (pt_relink.hip): cull_table and skip_link_table below run them one after the other and
+// are the reference formulation, relink_words runs them in the device's order.
 #include "ptamd_internal.h"
+#include "../csrc/pt_relink.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -21,9 +24,6 @@ Node node_of(const Bvh& bvh, uint32_t n)
   return { info >> 24, info & 0xFFFFFFu, child & 0x3FFFFFFFu, child >> 30 };
 }
 
-// the child of interior node n a ray of octant o visits first
-uint32_t down(const Node& nd, uint32_t n, uint32_t o) { return ((o >> nd.axis) & 1u) ? nd.right : n + 1u; }
-
 // xorshift64*: the training rays' generator.  unit(): 24 bits, [0, 1)
 struct Rng {
   uint64_t s;
@@ -35,85 +35,60 @@ struct Rng {
 
 bool skip_links_fit(const Bvh& bvh) { return bvh.n_nodes <= 896u && bvh.n_tris <= 2047u && bvh.max_leaf <= 15u; }
 
+bool record_faces_away(const float e1[3], const float e2[3], uint32_t octant) { return rl_record_faces_away(e1, e2, octant); }
+
 namespace {
 
-// the sign of a value that is known by the signs of its factors alone: zero, >= 0, <= 0; kOpen: not known
-enum Sign { kZero, kNonNeg, kNonPos, kOpen };
-// d * e for a direction component of the octant's class (negative: < 0; else +0, -0 or above) and a finite edge component
-Sign product_sign(bool d_negative, float e)
+// rl_record_bits of every record
+void record_bits_of(const Bvh& bvh, std::vector<uint8_t>& rec)
 {
-  if (e == 0.0f) return kZero;
-  return ((e < 0.0f) != d_negative) ? kNonPos : kNonNeg;
-}
-// a - b: fixed only for a term <= 0 less a term >= 0, or the other way round (rounding keeps the sign of such a difference)
-Sign difference_sign(Sign a, Sign b)
-{
-  if (a == kZero && b == kZero) return kZero;
-  if ((a == kNonPos || a == kZero) && (b == kNonNeg || b == kZero)) return kNonPos;
-  if ((a == kNonNeg || a == kZero) && (b == kNonPos || b == kZero)) return kNonNeg;
-  return kOpen;
-}
-// e * p <= 0 ?
-bool term_not_positive(float e, Sign p)
-{
-  if (e == 0.0f || p == kZero) return true;   // (p is finite for directions below 2^86: 0 * p is a zero whatever p's sign)
-  if (p == kOpen) return false;
-  return (e > 0.0f) == (p == kNonPos);
+  rec.resize(bvh.n_tris);
+  for (uint32_t j = 0; j < bvh.n_tris; ++j) rec[j] = (uint8_t)rl_record_bits(&bvh.tris[(size_t)j * 12], &bvh.tris[(size_t)j * 12 + 3]);
 }
 
 } // namespace
-
-bool record_faces_away(const float e1[3], const float e2[3], uint32_t octant)
-{
-  for (int k = 0; k < 3; ++k)
-    if (!(std::fabs(e1[k]) < 1099511627776.0f) || !(std::fabs(e2[k]) < 1099511627776.0f)) return false;   // 2^40; NaN fails too
-  const bool nx = octant & 1u, ny = (octant >> 1) & 1u, nz = (octant >> 2) & 1u;
-  // mt_test_asm: px = dy e2z - dz e2y, py = dz e2x - dx e2z, pz = dx e2y - dy e2x
-  const Sign px = difference_sign(product_sign(ny, e2[2]), product_sign(nz, e2[1]));
-  const Sign py = difference_sign(product_sign(nz, e2[0]), product_sign(nx, e2[2]));
-  const Sign pz = difference_sign(product_sign(nx, e2[1]), product_sign(ny, e2[0]));
-  return term_not_positive(e1[0], px) && term_not_positive(e1[1], py) && term_not_positive(e1[2], pz);
-}
 
 uint32_t cull_table(const Bvh& bvh, std::vector<uint8_t>& cull)
 {
   const uint32_t N = bvh.n_nodes;
   cull.assign(N, 0);
+  std::vector<uint8_t> rec;
+  record_bits_of(bvh, rec);
   // children lie behind their parent (DFS pre-order): one pass from the last node to the root
   for (uint32_t n = N; n-- > 0u;) {
     const Node nd = node_of(bvh, n);
-    if (!nd.count) { cull[n] = cull[n + 1u] & cull[nd.right]; continue; }
-    uint8_t bits = 0xFFu;
-    for (uint32_t k = 0; k < nd.count; ++k) {
-      const float* t = &bvh.tris[(size_t)(nd.first + k) * 12];
-      for (uint32_t o = 0; o < 8; ++o) if (!record_faces_away(t, t + 3, o)) bits &= (uint8_t)~(1u << o);
-    }
-    cull[n] = bits;
+    cull[n] = (uint8_t)(nd.count ? rl_leaf_bits(rec.data(), bvh.n_tris, f2u(bvh.nodes[(size_t)n * 16 + 3])) : rl_interior_bits(cull[n + 1u], cull[nd.right]));
   }
   uint32_t pairs = 0;
-  const uint8_t keep = N ? (uint8_t)~cull[0] : 0xFFu;   // (an octant whose root is culled keeps its chain)
+  const uint32_t keep = N ? rl_keep_mask(cull[0]) : 0xFFu;   // (an octant whose root is culled keeps its chain)
   for (uint32_t n = 0; n < N; ++n) {
-    cull[n] &= keep;
-    if (node_of(bvh, n).count) pairs += (uint32_t)__builtin_popcount(cull[n]);
+    cull[n] &= (uint8_t)keep;
+    if (node_of(bvh, n).count) pairs += rl_pair_count(cull[n]);
   }
   return pairs;
 }
 
 namespace {
 
-// a leaf's hit code for octant o: its whole range, or with `cull` the contiguous rest of it where the records that face away are
-// a prefix or a suffix
-uint32_t leaf_code(const Bvh& bvh, const Node& nd, uint32_t o, bool culling)
-{
-  uint32_t first = nd.first, count = nd.count;
-  if (culling) {
-    uint32_t a = 0, b = nd.count;   // records [a, b) stay
-    const auto away = [&](uint32_t k) { const float* t = &bvh.tris[(size_t)(nd.first + k) * 12]; return record_faces_away(t, t + 3, o); };
-    while (a < b && away(a)) ++a;
-    while (b > a && away(b - 1u)) --b;
-    if (a < b) { first = nd.first + a; count = b - a; }   // (none left: the leaf is culled and its words are not read)
+// What pt_relink.h's steps read, taken out of the tree: the nodes' info and child words, their miss links, the record bits
+struct RelinkInput {
+  std::vector<uint32_t> info, child, miss;
+  std::vector<uint8_t> rec;
+  RlTables tables(const Bvh& bvh, const uint8_t* skip, const uint8_t* cull) const
+  {
+    return { info.data(), child.data(), miss.data(), skip, rec.data(), cull, bvh.n_nodes, bvh.n_tris };
   }
-  return 0x8000u | (count << 11) | (first & 0x7FFu);
+};
+void relink_input(const Bvh& bvh, bool with_records, RelinkInput& in)
+{
+  const uint32_t N = bvh.n_nodes;
+  in.info.resize(N); in.child.resize(N); in.miss.resize((size_t)N * 8);
+  for (uint32_t n = 0; n < N; ++n) {
+    const float* q = &bvh.nodes[(size_t)n * 16];
+    in.info[n] = f2u(q[3]); in.child[n] = f2u(q[7]);
+    for (uint32_t o = 0; o < 8; ++o) in.miss[(size_t)n * 8 + o] = f2u(q[8 + o]);
+  }
+  if (with_records) record_bits_of(bvh, in.rec);
 }
 
 } // namespace
@@ -122,25 +97,48 @@ void skip_link_table(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vect
 {
   const uint32_t N = bvh.n_nodes;
   words.assign((size_t)N * 8 + 8, 0xFFFFu);
-  // where a walk of octant o that is sent to t tests next: past what is culled for o (on along its miss link), down the chain of
-  // what is skipped (a leaf is never skipped and both steps go forward in o's visiting order, so every chain ends)
-  const auto resolve = [&](uint32_t t, uint32_t o, bool culling) {
-    while (t != 0xFFFFFFFFu) {
-      if (culling && (((*cull)[t] >> o) & 1u)) t = f2u(bvh.nodes[(size_t)t * 16 + 8 + o]);
-      else if (skip[t]) t = down(node_of(bvh, t), t, o);
-      else break;
+  RelinkInput in;
+  relink_input(bvh, cull != nullptr, in);
+  const RlTables t = in.tables(bvh, skip.data(), cull ? cull->data() : nullptr);
+  for (uint32_t n = 0; n < N; ++n)
+    for (uint32_t o = 0; o < 8; ++o) words[(size_t)n * 8 + o] = rl_word(t, n, o, cull != nullptr);
+  for (uint32_t o = 0; o < 8 && N; ++o) words[(size_t)N * 8 + o] = rl_entry(t, o, cull != nullptr);
+}
+
+uint32_t relink_words(const Bvh& bvh, const std::vector<uint8_t>& skip, std::vector<uint32_t>& words)
+{
+  const uint32_t N = bvh.n_nodes;
+  words.assign((size_t)N * 8 + 8, 0xFFFFu);
+  if (!N) return 0u;
+  RelinkInput in;
+  relink_input(bvh, true, in);   // records: one item each
+  // leaves: one item each; an interior node starts at 0
+  std::vector<uint8_t> cull(N, 0), next(N, 0);
+  for (uint32_t n = 0; n < N; ++n)
+    if (rl_count(in.info[n])) cull[n] = (uint8_t)rl_leaf_bits(in.rec.data(), bvh.n_tris, in.info[n]);
+  // interior nodes: every pass forms all of them from the pass before (pass h settles the nodes of height h), until one changes nothing
+  for (uint32_t pass = 0; pass < N; ++pass) {
+    bool any = false;
+    next = cull;
+    for (uint32_t n = 0; n < N; ++n) {
+      const uint32_t right = rl_right(in.child[n]);
+      if (rl_count(in.info[n]) || n + 1u >= N || right >= N) continue;
+      next[n] = (uint8_t)rl_interior_bits(cull[n + 1u], cull[right]);
+      any = any || next[n] != cull[n];
     }
-    return t == 0xFFFFFFFFu ? 0xFFFFu : t;
-  };
-  for (uint32_t n = 0; n < N; ++n) {
-    const Node nd = node_of(bvh, n);
-    for (uint32_t o = 0; o < 8; ++o) {
-      const bool culling = cull && !(((*cull)[n] >> o) & 1u);
-      const uint32_t hit = nd.count ? leaf_code(bvh, nd, o, culling) : resolve(down(nd, n, o), o, culling);
-      words[(size_t)n * 8 + o] = hit | (resolve(f2u(bvh.nodes[(size_t)n * 16 + 8 + o]), o, culling) << 16);
-    }
+    if (!any) break;
+    cull.swap(next);
   }
-  for (uint32_t o = 0; o < 8 && N; ++o) words[(size_t)N * 8 + o] = resolve(0u, o, cull != nullptr);
+  const uint32_t keep = rl_keep_mask(cull[0]);
+  uint32_t pairs = 0;
+  for (uint32_t n = 0; n < N; ++n) {
+    cull[n] &= (uint8_t)keep;
+    if (rl_count(in.info[n])) pairs += rl_pair_count(cull[n]);
+  }
+  const bool any_culled = pairs != 0u;   // nothing culled: the plain table, no leaf range trimmed
+  const RlTables t = in.tables(bvh, skip.data(), cull.data());
+  for (uint32_t i = 0; i < N * 8u + 8u; ++i) words[i] = (i >> 3) < N ? rl_word(t, i >> 3, i & 7u, any_culled) : rl_entry(t, i & 7u, any_culled);
+  return pairs;
 }
 
 namespace {

@@ -316,6 +316,10 @@ SIGNATURES = {
     "ptamd_last_restart_tight": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ptamd_host_skip_events": (C.c_int, [C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_scene_relink": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptamd_scene_links_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_host_relink_words": (C.c_int, [C.POINTER(Face), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ptamd_host_round_threshold": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "ptamd_host_round_leaf_defer": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "ptamd_host_round_leaf_phase_runs": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32]),

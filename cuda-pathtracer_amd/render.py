@@ -191,6 +191,21 @@ class Context:
         N.check(self._lib.ptamd_scene_cull_count(self._h, scene_id, C.byref(out)))
         return out.value
 
+    def relink_scene(self, scene_id: int, stream=None) -> None:
+        """ptamd_scene_relink: the culled links of the scene's link table formed again, on the device, from the triangle records
+        it holds now (after update_scene_device or a rig's pose, skin or morph); asynchronous on `stream`.  A scene without a
+        link table: nothing is done."""
+        N.check(self._lib.ptamd_scene_relink(self._h, scene_id, _stream_handle(stream)))
+
+    def scene_links(self, scene_id: int) -> np.ndarray:
+        """ptamd_scene_links_read: the scene's link table as the device holds it, uint32[n_nodes + 1, 8] as host_skip_trace's
+        words (shape (0, 8): the scene has none); synchronises."""
+        n = C.c_uint64(0)
+        N.check(self._lib.ptamd_scene_links_read(self._h, scene_id, None, C.byref(n)))
+        words = np.zeros((n.value // 32, 8), dtype=np.uint32)
+        N.check(self._lib.ptamd_scene_links_read(self._h, scene_id, words.ctypes.data, C.byref(n)))
+        return words
+
     def last_restart_form(self) -> int:
         """ptamd_last_restart_form: the restart kernel's instantiation the last megakernel launch took (FORM_FLAT_SKIP,
         FORM_PLAIN_SKIP: over a link table; -1: no launch yet or another kernel)."""
@@ -586,6 +601,30 @@ def host_skip_trace(scene: HostScene, rays: np.ndarray, mode="default", skip=Non
                                       rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays), out.ctypes.data_as(C.POINTER(C.c_int32)),
                                       counters, C.byref(n_nodes), skip_out.ctypes.data, words.ctypes.data))
     return {"records": out, "nodes": counters[0], "tris": counters[1], "skip": skip_out, "words": words}
+
+
+def host_relink_words(scene: HostScene, mode="default", skip=None, threshold: float = 0.0, refit_to=None):
+    """ptamd_host_relink_words (no GPU): the link table with culled links as Context.relink_scene's kernel forms it, in the kernel's
+    order of steps.  mode, skip, threshold, refit_to: as host_skip_trace (the set is that of `scene`, the leaves are culled for
+    refit_to where given).  Returns (words uint32[n_nodes + 1, 8], the (leaf, octant) pairs culled)."""
+    lib = N.load()
+    faces = scene.faces.ctypes.data_as(C.POINTER(N.Face))
+    fb = None
+    if refit_to is not None:
+        fb = np.ascontiguousarray(refit_to.faces if isinstance(refit_to, HostScene) else refit_to, dtype=FACE_DTYPE)
+        if len(fb) != len(scene.faces):
+            raise ValueError("a refit keeps the face count")
+    fb_ptr = fb.ctypes.data_as(C.POINTER(N.Face)) if fb is not None else None
+    given = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+    n_nodes, n_culled = C.c_uint32(0), C.c_uint32(0)
+    N.check(lib.ptamd_host_relink_words(faces, None, len(scene.faces), 0, 0.0, None, None, C.byref(n_nodes), None))
+    if given is not None and len(given) != n_nodes.value:
+        raise ValueError("skip holds one byte per node")
+    words = np.zeros((n_nodes.value + 1, 8), dtype=np.uint32)
+    N.check(lib.ptamd_host_relink_words(faces, fb_ptr, len(scene.faces), SKIP_MODES[mode], threshold,
+                                        given.ctypes.data if given is not None else None, words.ctypes.data,
+                                        C.byref(n_nodes), C.byref(n_culled)))
+    return words, n_culled.value
 
 
 def host_skip_events(scene: HostScene, rays: np.ndarray, mode="default", threshold: float = 0.0, cull=False):

@@ -1012,14 +1012,37 @@ int ptamd_stream_synchronize(ptamd_context* ctx, void* stream);
  * names the rest.  This depends on the triangles: EVERY update of the scene's faces (ptamd_scene_update, ptamd_scene_update_device,
  * the rig's pose / skin / morph) puts the table without culled links back, on the update's stream and before its kernels, so that
  * launches ordered behind the update never read a link the new faces do not justify; ptamd_scene_update, which has the new faces on
- * the host, then culls again for them.
+ * the host, then culls again for them.  After an update from faces on the device the host has nothing to cull from:
+ * ptamd_scene_relink culls again there, when the caller asks for it.
+ *
+ * ptamd_scene_relink: the culled links formed again from the triangle records the device holds now, by one workgroup, into the
+ * table behind the node table; asynchronous on `stream`, nothing waits on the host.  After any sequence of updates of any kind the
+ * table and ptamd_scene_cull_count are then, byte for byte, what ptamd_scene_update leaves for the same faces: the skip set of the
+ * upload, the leaves culled for the faces of now (ptamd_host_relink_words is its host mirror).  Ordering and refusals are those of
+ * ptamd_scene_update_device: the call waits on `stream` for every launch still reading the scene and for the last update, launches
+ * enqueued after it on any stream read the new table; PTAMD_ERR_LIMIT while a captured launch pins the context's scenes and for a
+ * capturing stream, PTAMD_ERR_ARG for a null context and an id out of range or released.  A scene without a link table (not
+ * compact, PTAMD_SKIP=0, nothing skipped and nothing culled at upload) and one uploaded under PTAMD_SKIP_CULL=0: PTAMD_OK, nothing
+ * is done; the form a scene's launches take is fixed at upload.  A scene whose upload skipped something and culled nothing is
+ * relinked like any other (a pose can turn a rotated box axis-aligned).  No other call changes: an update from device faces alone
+ * still leaves the table without culled links.  ptamd_scene_cull_count after a relink waits for the count, which follows the kernel.
+ *
+ * ptamd_scene_links_read: the link table as the device holds it, (n_nodes + 1) * 8 words as words_out of ptamd_host_skip_trace
+ * (0 bytes: the scene has none); *bytes: in, the room of `out`; out, the table's size; out NULL: the size alone.  Synchronises
+ * the device, like ptamd_scene_table_read.
+ *
+ * ptamd_host_relink_words: what ptamd_scene_relink's kernel computes, on the host in the kernel's order of steps (records, leaves,
+ * interior nodes in passes that each read the pass before, the count, one item per node and octant), no device needed.  Arguments
+ * as ptamd_host_skip_trace's: the tree and the skip set of `faces` under `mode` (PTAMD_SKIP_CULLED is implied), refitted to
+ * faces_refit where given; words_out (optional) as there, *n_nodes in and out as there, *n_culled (optional): the (leaf, octant)
+ * pairs culled.  The words equal those of ptamd_host_skip_trace under mode | PTAMD_SKIP_CULLED on every input.
  *
  * With PTAMD_TUNING=1: PTAMD_SKIP=0 no table (the old forms are launched), PTAMD_SKIP=root the root alone, PTAMD_SKIP=all every
  * interior node, PTAMD_SKIP_THRESHOLD=<pass rate> for the selection, PTAMD_SKIP_RAYS=<training rays per node> (2),
  * PTAMD_SKIP_CULL=0 no culled leaves.
  *
  * ptamd_scene_skip_count: how many nodes of an uploaded scene are skipped.  ptamd_scene_cull_count: how many (leaf, octant) pairs
- * its link table leaves out now (0 after an update from device faces).  Both 0: no table, its launches take the old forms.
+ * its link table leaves out now (0 after an update from device faces, until ptamd_scene_relink).  Both 0 at upload: no table, its launches take the old forms.
  * ptamd_last_restart_form: the instantiation of the restart kernel the context's last megakernel launch took (PTAMD_FORM_FLAT_SKIP
  * and PTAMD_FORM_PLAIN_SKIP are the two over a link table; another number another form; -1 no launch yet or another kernel).
  *
@@ -1053,6 +1076,10 @@ int ptamd_host_skip_trace(const ptamd_face* faces, const ptamd_face* faces_refit
                           const uint8_t* skip_in, const float* rays, uint32_t n, int32_t* out, uint64_t* counters,
                           uint32_t* n_nodes, uint8_t* skip_out, uint32_t* words_out);
 int ptamd_host_faces_away(const float* edges, uint32_t n, uint8_t* out);
+int ptamd_scene_relink(ptamd_context* ctx, uint32_t scene_id, void* stream);
+int ptamd_scene_links_read(ptamd_context* ctx, uint32_t scene_id, void* out, uint64_t* bytes);
+int ptamd_host_relink_words(const ptamd_face* faces, const ptamd_face* faces_refit, uint32_t n_faces, uint32_t mode, float threshold,
+                            const uint8_t* skip_in, uint32_t* words_out, uint32_t* n_nodes, uint32_t* n_culled);
 
 /* ---- deferred leaf phases of the restart kernel's skip forms ------------------------------------------
  * A round of the restart kernel alternates box phases and leaf phases.  In the deferring copies of the two skip forms, a box
