@@ -62,6 +62,9 @@ hipError_t launch_temporal_pass(const DenoiseParams& q, const TemporalParams& t,
 // ... and pass 0 in its motion form (pt_denoise_motion.hip): reproject along the faces' motion since the previous call, and blend
 struct MotionParams;
 hipError_t launch_motion_reproject(const DenoiseParams& q, const TemporalParams& t, const MotionParams& m, hipStream_t stream);
+// guided upsample (pt_upsample.hip): 0 prepare the low frame's geometry records, 1 upsample to the full frame
+struct UpsampleParams;
+hipError_t launch_upsample_pass(const UpsampleParams& u, int pass, hipStream_t stream);
 
 } // namespace ptamd
 

@@ -24,17 +24,8 @@ int denoise_params(const char* who, const ptamd_denoise_desc* d, DenoiseParams& 
   if (d->post_id > 3) return fail("post_id out of range (0..3)");
   if (d->levels > PT_DN_MAX_LEVELS) return fail("levels out of range (0..8)");
   uint32_t n_sq = 7;
-  // (0 asks for a default; -0.0 compares equal to it and is neither that nor a positive value: refused like any negative one)
-  if (std::signbit(d->sigma_n)) return fail("sigma_n must be 0 or a power of two in 1..256");
-  if (d->sigma_n != 0.0f) {
-    int e = 0;
-    const float m = std::frexp(d->sigma_n, &e);
-    // (the weight cos^sigma_n has condition number sigma_n: include/ptamd.h on why the range ends at 256)
-    if (!(d->sigma_n >= 1.0f && d->sigma_n <= 256.0f) || m != 0.5f) return fail("sigma_n must be 0 or a power of two in 1..256 (larger exponents are not accurate in binary32)");
-    n_sq = (uint32_t)(e - 1);
-  }
-  if (!(d->sigma_l >= 0.0f) || !(d->sigma_x >= 0.0f) || std::isinf(d->sigma_l) || std::isinf(d->sigma_x) || std::signbit(d->sigma_l) || std::signbit(d->sigma_x))
-    return fail("sigma_l and sigma_x must be 0 (default) or positive and finite");
+  if (!sigma_n_squarings(d->sigma_n, n_sq)) return fail("sigma_n must be 0 or a power of two in 1..256 (larger exponents are not accurate in binary32)");
+  if (!sigma_in_range(d->sigma_l) || !sigma_in_range(d->sigma_x)) return fail("sigma_l and sigma_x must be 0 (default) or positive and finite");
   std::memset(&q, 0, sizeof q);
   std::memset(&p, 0, sizeof p);
   q.width = d->width; q.height = d->height; q.post_id = d->post_id;

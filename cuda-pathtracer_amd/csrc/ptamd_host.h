@@ -7,6 +7,7 @@
 //   ptamd_launch.cpp    the launch pipeline (camera_terms ... do_launch), ptamd_raytrace*, ray queries
 //   ptamd_denoise.cpp   the spatial and temporal denoiser, the history, their host mirrors
 //   ptamd_adaptive.cpp  adaptive sampling
+//   ptamd_upsample.cpp  the guided upsample of a low-resolution frame, its host mirror
 // Every device resource below has an owner (ptamd_owners.h): destroying a struct releases what it holds, so these structs are
 // move-only and nothing keeps a list of what to free.
 #pragma once
@@ -18,6 +19,7 @@
 #include "ptamd_owners.h"
 #include "ptamd_tuning.h"
 
+#include <cmath>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -188,6 +190,11 @@ struct ptamd_context {
   // allocation, grown at the first call of a larger frame
   ptamd::DeviceBuffer<float4> d_denoise;
   size_t denoise_pixels = 0;
+  // upsample workspace (ptamd_upsample): the low frame's geometry records and, when the call runs the feature passes itself, the
+  // feature records of both frames.  Apart from the denoiser's: a caller denoises at the low size and then upsamples, and the two
+  // must not resize each other.  Grown at the first call that needs more
+  ptamd::DeviceBuffer<float4> d_upsample;
+  size_t upsample_bytes = 0;
 };
 
 static_assert(!std::is_copy_constructible<ptamd::DeviceScene>::value && !std::is_copy_constructible<ptamd::DeviceCubemap>::value &&
@@ -233,6 +240,23 @@ int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t
 int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16);
 int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r);
 int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream);
+
+// ---- the sigmas of the denoiser and of the upsample (ptamd_denoise.cpp, ptamd_upsample.cpp)
+// sigma_n: 0 (the default, n_squarings left as it is) or a power of two in 1..256 = 2^n_squarings.  -0.0 compares equal to 0 and is
+// neither a default nor a positive value: refused like any negative one.  (The weight cos^sigma_n has condition number sigma_n:
+// include/ptamd.h on why the range ends at 256.)
+inline bool sigma_n_squarings(float sigma_n, uint32_t& n_squarings)
+{
+  if (std::signbit(sigma_n)) return false;
+  if (sigma_n == 0.0f) return true;
+  int e = 0;
+  const float m = std::frexp(sigma_n, &e);
+  if (!(sigma_n >= 1.0f && sigma_n <= 256.0f) || m != 0.5f) return false;
+  n_squarings = (uint32_t)(e - 1);
+  return true;
+}
+// a scale: 0 (default) or positive and finite
+inline bool sigma_in_range(float s) { return s >= 0.0f && !std::isinf(s) && !std::signbit(s); }
 
 // ---- ptamd_launch.cpp
 float frame_nb_inverse(float c);

@@ -156,6 +156,18 @@ class DenoiseHistoryView(C.Structure):    # ptamd_denoise_history_view (include/
 DENOISE_HISTORY_BYTES = 100                           # per pixel of a device history
 
 
+class UpsampleDesc(C.Structure):          # ptamd_upsample_desc (include/ptamd.h)
+    _fields_ = [("low_linear_rgb", C.c_void_p), ("low_width", C.c_uint32), ("low_height", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("camera", Camera),
+                ("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32),
+                ("surface_rgba8", C.c_void_p), ("linear_rgb", C.c_void_p), ("stream", C.c_void_p),
+                ("post_id", C.c_uint32), ("mode", C.c_uint32), ("sigma_n", C.c_float), ("sigma_x", C.c_float),
+                ("features_dev", C.c_void_p), ("low_features_dev", C.c_void_p)]
+
+
+UPSAMPLE_GUIDED, UPSAMPLE_BILINEAR = 0, 1             # ptamd_upsample_desc.mode
+
+
 class AdaptiveView(C.Structure):          # ptamd_adaptive_view (include/ptamd.h)
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("counts", C.c_void_p), ("moments", C.c_void_p),
                 ("list", C.c_void_p), ("active_count", C.c_void_p)]
@@ -291,6 +303,8 @@ SIGNATURES = {
                                                       C.POINTER(C.c_uint64)]),
     "ptamd_host_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseTemporalDesc), C.POINTER(DenoiseHistoryView),
                                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptamd_upsample": (C.c_int, [C.c_void_p, C.POINTER(UpsampleDesc)]),
+    "ptamd_host_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpsampleDesc), C.c_void_p, C.c_void_p]),
     "ptamd_adaptive_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ptamd_adaptive_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ptamd_adaptive_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import native as N
 from .scene import FACE_DTYPE, LIGHT_DTYPE, HostScene
+from .native import UPSAMPLE_GUIDED, UPSAMPLE_BILINEAR
 
 POST_NONE, POST_GRAYSCALE, POST_SEPIA, POST_INVERT = 0, 1, 2, 3
 REFERENCE_BOUNCES = 3  # static_samples = 1 -> max_bounces = 3 (raytrace.cu:243,66)
@@ -340,6 +341,27 @@ class Context:
         rays (optional) float32[height, width, 6] = {dir, origin}; device tensors, asynchronous on `stream`."""
         N.check(self._lib.ptamd_render_features(self._h, scene_id, cubemap_id, C.byref(cam), width, height, _ptr(features),
                                                 _ptr(rays) if rays is not None else None, _stream_handle(stream)))
+
+    def upsample(self, surface, low_linear, low_width: int, low_height: int, scene_id: int, cubemap_id: int, cam: N.Camera,
+                 width: int, height: int, mode: int = N.UPSAMPLE_GUIDED, post_id: int = POST_NONE, sigma_n: float = 0.0,
+                 sigma_x: float = 0.0, features=None, low_features=None, linear=None, stream=None) -> None:
+        """Guided upsample (ptamd_upsample) of `low_linear` (float32[low_height, low_width, 3], row 0 = top, left
+        unchanged) into `surface` (uint8[height, width, 4]) and, optionally, `linear` (float32[height, width, 3]); asynchronous
+        on `stream`.  features / low_features: the feature records of the two frames from render_features() (both, or neither:
+        the call then runs the passes itself).  A sigma of 0 takes the default."""
+        d = N.UpsampleDesc()
+        d.low_linear_rgb = _ptr(low_linear)
+        d.low_width, d.low_height, d.width, d.height = low_width, low_height, width, height
+        d.camera = cam
+        d.scene_id, d.cubemap_id = scene_id, cubemap_id
+        d.surface_rgba8 = _ptr(surface)
+        d.linear_rgb = _ptr(linear) if linear is not None else None
+        d.stream = _stream_handle(stream)
+        d.post_id, d.mode = post_id, mode
+        d.sigma_n, d.sigma_x = sigma_n, sigma_x
+        d.features_dev = _ptr(features) if features is not None else None
+        d.low_features_dev = _ptr(low_features) if low_features is not None else None
+        N.check(self._lib.ptamd_upsample(self._h, C.byref(d)))
 
     def trace_rays_queue(self, scene_id: int, rays, out, config: int = 0, refill_min: int = 8, stream=None) -> int:
         """The walk-only kernel fed from a ray queue (ptamd_trace_rays_queue): rays float32[n, 6] and out int32[n, 4] are device
@@ -733,6 +755,34 @@ def host_denoise(features: np.ndarray, accum: np.ndarray, cam: N.Camera, frame_n
     linear = np.zeros((h, w, 3), np.float32)
     rgba = np.zeros((h, w, 4), np.uint8)
     N.check(N.load().ptamd_host_denoise(features.ctypes.data, accum.ctypes.data, C.byref(d), linear.ctypes.data, rgba.ctypes.data))
+    return linear, rgba
+
+
+def host_upsample(features, low_features, low_linear: np.ndarray, cam: N.Camera, width: int, height: int,
+                  mode: int = N.UPSAMPLE_GUIDED, post_id: int = POST_NONE, sigma_n: float = 0.0, sigma_x: float = 0.0):
+    """Host mirror of Context.upsample (ptamd_host_upsample): features float32[height, width, 8] and low_features
+    float32[LH, LW, 8] (both None is legal in mode UPSAMPLE_BILINEAR), low_linear float32[LH, LW, 3], all with row 0 = top.
+    Returns (linear float32[height, width, 3], rgba uint8[height, width, 4])."""
+    low_linear = np.ascontiguousarray(low_linear, dtype=np.float32)
+    lh, lw = low_linear.shape[:2]
+    if low_linear.shape != (lh, lw, 3):
+        raise ValueError("low_linear must be float32[LH, LW, 3]")
+    if features is not None:
+        features = np.ascontiguousarray(features, dtype=np.float32)
+        if features.shape != (height, width, 8):
+            raise ValueError(f"features must be float32[{height}, {width}, 8]")
+    if low_features is not None:
+        low_features = np.ascontiguousarray(low_features, dtype=np.float32)
+        if low_features.shape != (lh, lw, 8):
+            raise ValueError(f"low_features must be float32[{lh}, {lw}, 8]")
+    d = N.UpsampleDesc()
+    d.low_width, d.low_height, d.width, d.height, d.camera = lw, lh, width, height, cam
+    d.post_id, d.mode, d.sigma_n, d.sigma_x = post_id, mode, sigma_n, sigma_x
+    linear = np.zeros((height, width, 3), np.float32)
+    rgba = np.zeros((height, width, 4), np.uint8)
+    N.check(N.load().ptamd_host_upsample(features.ctypes.data if features is not None else None,
+                                         low_features.ctypes.data if low_features is not None else None,
+                                         low_linear.ctypes.data, C.byref(d), linear.ctypes.data, rgba.ctypes.data))
     return linear, rgba
 
 
@@ -1227,6 +1277,18 @@ class FrameRenderer:
                                   alpha_moments=alpha_moments, reset_history=reset_history or continued,
                                   history_length=history_length, linear=linear, stream=stream, motion=motion)
         self._temporal_last = key
+
+    def upsample(self, low_linear, low_width: int, low_height: int, mode: int = N.UPSAMPLE_GUIDED, post_id: int = POST_NONE,
+                 sigma_n: float = 0.0, sigma_x: float = 0.0, features=None, low_features=None, surface=None, linear=None,
+                 stream=None) -> None:
+        """Guided upsample of a low-resolution frame of this renderer's camera and scene, usually what a
+        renderer of the low size wrote with denoise(linear=...), into the renderer's surface (or `surface`).  Full frames only;
+        the accumulator is neither read nor written."""
+        if self.rows != (0, self.height) or self.band_local or self.interleave is not None:
+            raise ValueError("upsample() needs a full-frame renderer (no row band, band-local or interleaved buffers)")
+        self.ctx.upsample(self.surface if surface is None else surface, low_linear, low_width, low_height, self.scene_id,
+                          self.cubemap_id, self.cam, self.width, self.height, mode=mode, post_id=post_id, sigma_n=sigma_n,
+                          sigma_x=sigma_x, features=features, low_features=low_features, linear=linear, stream=stream)
 
     # ---- adaptive sampling (ptamd_render_adaptive, DESIGN.md §12)
 

@@ -911,7 +911,58 @@ int ptamd_host_denoise_temporal_motion(const float* features, const float* tempo
                                        ptamd_denoise_history_view* history, const float* tris_now, const float* tris_prev, uint32_t n_faces,
                                        float* linear_rgb, uint8_t* rgba8);
 
-/* ---- Adaptive sampling ----------------------------------------------------------------------------------
+/* ---- Guided upsample ------------------------------------------------------------------------------------
+ * An opt-in pass beside the denoiser: a frame rendered and denoised at a low internal resolution is brought to the full size by
+ * a four-tap bilinear filter whose taps are weighted by how well their first hit agrees with the full pixel's own (the geometry
+ * half of the denoiser's weight, between the feature records of the two frames).  It reads a low frame of linear colours and
+ * writes a surface; it changes nothing any other entry point computes.  csrc/pt_upsample.h has the arithmetic.
+ *
+ * The two frames show the same camera: low pixel (xl, yl) and the full-frame position half + (pl - half_l) / r share one feature
+ * ray, with half = side / 2 (integer division) and r = (float)(low_width / 2) / (float)(width / 2) for BOTH axes.  A low frame of
+ * another aspect ratio is legal; taps outside it replicate its edge.
+ * Limits: both frames 2..65536 per side (a side of 1 has half = 0 and no ratio); low_width <= width and low_height <= height;
+ * width / 2 <= 8 * (low_width / 2).  One step outside them is refused with PTAMD_ERR_ARG before anything is enqueued. */
+#define PTAMD_UPSAMPLE_GUIDED 0u     /* (se + k sb) / (sw + k): the geometry-weighted mean, blended with the bilinear value sb, k = 0.01 */
+#define PTAMD_UPSAMPLE_BILINEAR 1u   /* sb alone: reads no features */
+
+typedef struct {
+  const float* low_linear_rgb;         /* device: low_width x low_height x 3 floats, row 0 = top, as ptamd_denoise writes linear_rgb (read only) */
+  uint32_t low_width, low_height;
+  uint32_t width, height;              /* the full frame */
+  ptamd_camera camera;                 /* of both frames */
+  uint32_t scene_id, cubemap_id;
+  void* surface_rgba8;                 /* out: width x height RGBA8, row 0 = top */
+  float* linear_rgb;                   /* optional out: width x height x 3 floats, row 0 = top: the colour before the output stage */
+  void* stream;                        /* hipStream_t; NULL = default stream */
+  uint32_t post_id;                    /* 0..3, as ptamd_raytrace */
+  uint32_t mode;                       /* PTAMD_UPSAMPLE_* */
+  float sigma_n;                       /* normal exponent, a power of two 1..256 (0: 128), as ptamd_denoise_desc */
+  float sigma_x;                       /* plane-distance scale in LOW pixels, > 0 (0: 1).  A sigma of -0.0, NaN or infinity is refused */
+  const void* features_dev;            /* optional: the full frame's feature records, as ptamd_render_features wrote them for this */
+  const void* low_features_dev;        /* camera, scene and cubemap; and the low frame's.  Both: no feature pass runs.  Both NULL:
+                                          the call runs both passes.  One of the two: PTAMD_ERR_ARG */
+} ptamd_upsample_desc;
+
+/* Upsamples the low frame into surface_rgba8 (and linear_rgb): asynchronous on `stream`; every input is left unchanged.  Call it
+ * after the ptamd_denoise (or whatever wrote low_linear_rgb) on the same stream, or behind an event.  Errors: PTAMD_ERR_ARG for
+ * null pointers, ids, post_id or mode out of range, a sigma out of range, frames outside the limits above, one feature pointer
+ * without the other.
+ * Workspace: the low frame's geometry records (32 bytes per low pixel) and, when the call runs the feature passes itself, the
+ * feature records of both frames (32 bytes per pixel of each) belong to the context, apart from the denoiser's workspace: a
+ * ptamd_denoise between two calls does not touch it.  It is sized at the first call that needs more (hipMalloc, a device
+ * synchronisation); later calls only enqueue.  Calls on ONE context share it: order them (one stream, or an event between
+ * streams). */
+int ptamd_upsample(ptamd_context* ctx, const ptamd_upsample_desc* desc);
+
+/* Host mirror of ptamd_upsample over host memory (the device kernels and this function execute the same binary32 operations):
+ * features float32[height x width x 8] and low_features float32[low_height x low_width x 8] as ptamd_render_features writes them
+ * (both NULL is legal in mode BILINEAR only), low_linear_rgb as in the desc; the colour (linear_rgb, optional) and the RGBA8 bytes
+ * of the full frame.  desc supplies camera, the sizes, post_id, mode and the sigmas (its pointers, stream and ids are ignored,
+ * except that one of features_dev / low_features_dev without the other is refused as on the device). */
+int ptamd_host_upsample(const float* features, const float* low_features, const float* low_linear_rgb, const ptamd_upsample_desc* desc,
+                        float* linear_rgb, uint8_t* rgba8);
+
+/* ---- Adaptive sampling----------------------------------------------------------------------------------
  * Per-pixel sample counts: rounds of samples go to the pixels whose luminance error estimate is still above a threshold.  A sample
  * of pixel (x, y) with frame number n depends only on n and the pixel, so a pixel that has taken c samples holds exactly the
  * accumulator and surface bytes of the reference's image after c frames.
