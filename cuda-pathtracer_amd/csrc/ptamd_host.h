@@ -239,7 +239,8 @@ int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t
 int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream);
 int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16);
 int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r);
-int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream);
+int prepare_margins(DeviceScene& s);   // ... its allocations alone: the reduction's words, the pinned slots, the events
+int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream, bool keep_links = false);
 
 // ---- the sigmas of the denoiser and of the upsample (ptamd_denoise.cpp, ptamd_upsample.cpp)
 // sigma_n: 0 (the default, n_squarings left as it is) or a power of two in 1..256 = 2^n_squarings.  -0.0 compares equal to 0 and is

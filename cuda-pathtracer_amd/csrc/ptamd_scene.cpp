@@ -1,9 +1,10 @@
-// ptamd_scene.cpp — a scene's device tables (include/ptamd.h): validation, the tables' host form, upload, the two updates,
-// margins, tree quality, release, table reads and the ptamd_host_scene_* mirrors; cubemaps.
+// ptamd_scene.cpp — a scene's device tables (include/ptamd.h): validation, the tables' host form, upload, the two updates, the
+// rebuild in place, margins, tree quality, release, table reads and the ptamd_host_scene_* mirrors; cubemaps.
 #include "ptamd_host.h"
 #include "pt_refit.h"
 #include "pt_refit_device.h"
 #include "pt_relink.h"
+#include "pt_build.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -248,6 +249,81 @@ int refit_scene_tables(SceneTables& t, const ptamd_face* faces, uint32_t n_faces
   return PTAMD_OK;
 }
 
+// The scene takes the compact LDS layout (the restart kernel's resident forms): its tree fits the budget and the link codes
+bool tree_is_compact(const Bvh& bvh)
+{
+  return bvh.n_nodes * 64u + bvh.n_tris * 48u <= kLdsBudget && bvh.n_nodes <= kCompactMaxNodes && bvh.n_tris <= kCompactMaxTris && skip_links_fit(bvh);
+}
+
+// The one step that turns a tree into the members of DeviceScene that depend on it, for ptamd_upload_scene and ptamd_scene_rebuild
+// alike: the node table with the link table behind it, the four-wide nodes (and the knob-only quantised forms), the leaf-major
+// records, what a refit needs (raw boxes, schedule, wide_child), the counts, the skip and cull members, the tree's part of
+// ptamd_scene_info and quality_built.  `d` holds nothing of a tree yet.
+int install_tree(const ptamd_context* ctx, const Bvh& bvh, uint32_t n_faces, DeviceScene& d)
+{
+  d.n_nodes = bvh.n_nodes; d.n_bvh_tris = bvh.n_tris;
+  d.n_nodes4 = bvh.n_nodes4; d.depth4 = bvh.depth4;
+  d.n_nodes8 = bvh.n_nodes8; d.depth8 = bvh.depth8;
+  // scenes that take the compact LDS layout: the box tests the walk leaves out, and the relinked link table behind the node table
+  // (8 words per node, then the eight entry nodes) for the restart kernel's skip forms
+  std::vector<float> nodes_and_links(bvh.nodes);
+  if (tree_is_compact(bvh)) {
+    const uint32_t mode = ctx->knobs.skip_mode;   // (PTAMD_SKIP=0: no table at all)
+    SkipTables t;
+    build_skip_tables(bvh, mode == PTAMD_SKIP_SET ? mode : (mode | PTAMD_SKIP_CULLED), ctx->knobs.skip_threshold, nullptr, t);
+    d.n_skipped = t.n_skipped; d.n_culled = t.n_culled;
+    d.links = t.n_skipped != 0u || t.n_culled != 0u;
+    if (d.links) {
+      // behind the table one word more: the count ptamd_scene_relink's kernel leaves (no launch reads it)
+      nodes_and_links.resize(bvh.nodes.size() + t.words.size() + 1u, 0.0f);
+      std::memcpy(nodes_and_links.data() + bvh.nodes.size(), t.words.data(), t.words.size() * 4);
+      // what a relink and restore_plain_links need, of every scene with a table: the set as bytes, the table of the set alone
+      std::vector<uint32_t> plain;
+      skip_link_table(bvh, t.skip, plain);
+      int rc;
+      if ((rc = upload(d.links_plain, plain.data(), plain.size() * 4)) || (rc = upload(d.skip_bytes, t.skip.data(), t.skip.size()))) return rc;
+      const char* knob = tuning_env("PTAMD_SKIP_CULL");
+      d.relink_on = !(knob && std::atoi(knob) == 0);
+    }
+    if (t.n_culled) {
+      d.cull_on = true;
+      d.topology.nodes = bvh.nodes;
+      d.topology.n_nodes = bvh.n_nodes; d.topology.n_tris = bvh.n_tris;
+      d.topology.tris.resize((size_t)bvh.n_tris * 12);
+      d.skip_set = t.skip;
+      d.record_face.resize(bvh.n_tris);
+      for (uint32_t j = 0; j < bvh.n_tris; ++j) std::memcpy(&d.record_face[j], &bvh.tris[(size_t)j * 12 + 9], 4);
+    }
+  }
+  int rc;
+  if ((rc = upload(d.nodes, nodes_and_links.data(), nodes_and_links.size() * 4)) ||
+      (rc = upload(d.nodes4, bvh.nodes4.data(), bvh.nodes4.size() * 4)) ||
+      (bvh.nodes8.empty() ? 0 : (rc = upload(d.nodes8, bvh.nodes8.data(), bvh.nodes8.size() * 4))) ||
+      (bvh.nodes4q.empty() ? 0 : (rc = upload(d.nodes4q, bvh.nodes4q.data(), bvh.nodes4q.size() * 4))) ||
+      (rc = upload_padded(d.tris_bvh, bvh.tris.data(), bvh.tris.size() * 4, 128)))   // (the merged wide walk reads eight 16-byte words from a leaf's first record)
+    return rc;
+  // what ptamd_scene_update needs: raw boxes, the children-first schedule, the wide nodes' children
+  d.refit_ok = !bvh.split && bvh.nodes8.empty() && bvh.nodes4q.empty();
+  if (d.refit_ok) {
+    if ((rc = upload(d.raw, bvh.raw.data(), bvh.raw.size() * 4)) ||
+        (rc = upload(d.refit_groups, bvh.refit_groups.data(), bvh.refit_groups.size() * 4)) ||
+        (rc = upload(d.refit_levels, bvh.refit_levels.data(), bvh.refit_levels.size() * 4)) ||
+        (rc = upload(d.refit_sched, bvh.refit_sched.data(), bvh.refit_sched.size() * 4)) ||
+        (rc = upload(d.wide_child, bvh.wide_child.data(), bvh.wide_child.size() * 4)))
+      return rc;
+    d.n_refit_groups = (uint32_t)bvh.refit_groups.size() / 4u; d.n_refit_levels = (uint32_t)bvh.refit_levels.size();
+    d.n_refit_sched = (uint32_t)bvh.refit_sched.size();
+    d.refit_top_first = bvh.refit_top_first; d.refit_top_levels = bvh.refit_top_levels;
+  }
+  d.quality_built = tree_quality(bvh.nodes.data(), bvh.n_nodes, n_faces);
+  d.info.n_nodes = bvh.n_nodes;
+  d.info.n_leaves = bvh.n_leaves; d.info.max_leaf_size = bvh.max_leaf; d.info.depth = bvh.depth;
+  d.info.node_bytes = 64; d.info.tri_bytes = 48;
+  d.info.n_nodes4 = d.n_nodes4; d.info.depth4 = d.depth4;
+  d.info.lds_bytes_bvh = bvh.n_nodes * 64u + bvh.n_tris * 48u;
+  return PTAMD_OK;
+}
+
 } // namespace
 
 // What the update calls refuse alike, in two steps (ptamd_scene_update checks the material ids between them)
@@ -349,6 +425,11 @@ int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r)
 {
   const int rc = refit_params(who, s, r);
   if (rc != PTAMD_OK) return rc;
+  return prepare_margins(s);
+}
+
+int prepare_margins(DeviceScene& s)
+{
   if (!s.d_margin) PT_HIP(s.d_margin.alloc((kMarginWords + 2u * kExtentMaxGroups) * sizeof(float)));
   if (!s.h_margin) PT_HIP(s.h_margin.alloc(2u * kMarginWords * sizeof(float)));
   for (int i = 0; i < 2; ++i) PT_HIP(s.margin_ready[i].ensure());
@@ -395,12 +476,13 @@ static int enqueue_refit(DeviceScene& s, const RefitParams& r, hipStream_t strea
 
 // ... and what it enqueues behind wait_for_readers, for ptamd_scene_update_device (the caller's buffer) and ptamd_scene_rig_pose (the
 // rig's posed records) alike: extent reduction, the four refit kernels, `updated`, the margin copy; margins pending
-int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream)
+int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream, bool keep_links)
 {
   // (the copies of earlier updates read d_margin behind their `updated`, possibly on another stream)
   for (int i = 0; i < 2; ++i)
     if (s.margin_ready_valid[i]) PT_HIP(hipStreamWaitEvent(stream, s.margin_ready[i].get(), 0));
-  const int rc = restore_plain_links(s, stream);   // (the host never sees these faces: no leaf stays culled)
+  // (the host never sees these faces: no leaf stays culled.  keep_links: ptamd_scene_rebuild's, culled for these very faces)
+  const int rc = keep_links ? PTAMD_OK : restore_plain_links(s, stream);
   if (rc != PTAMD_OK) return rc;
   PT_HIP(launch_extent(faces, s.n_faces, s.d_margin.get() + kMarginWords, s.d_margin.get(), stream));
   r.faces = faces;
@@ -416,6 +498,104 @@ int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hip
   s.margins_pending = true;
   return PTAMD_OK;
 }
+
+namespace {
+
+// ptamd_scene_quality's number for the tables as they stand on the device: per workgroup of kRefitThreads nodes a sum in a fixed
+// order, the groups added in index order (the same bits for the same tables); waits for `st`
+int device_quality(DeviceScene& s, hipStream_t st, double* now)
+{
+  *now = 0.0;
+  if (s.n_nodes == 0 || s.n_faces == 0) return PTAMD_OK;
+  const uint32_t groups = quality_groups(s.n_nodes);
+  if (!s.d_quality) PT_HIP(s.d_quality.alloc((size_t)(groups + 1u) * sizeof(double)));
+  PT_HIP(launch_quality(reinterpret_cast<const float*>(s.nodes.get()), s.n_nodes, s.d_quality.get(), st));
+  std::vector<double> part(groups + 1u);
+  PT_HIP(hipMemcpyAsync(part.data(), s.d_quality.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  PT_HIP(hipStreamSynchronize(st));
+  double sum = 0.0;
+  for (uint32_t g = 0; g < groups; ++g) sum += part[g];   // index order: the same bits for the same tables
+  *now = sum / part[groups];
+  return PTAMD_OK;
+}
+
+// ... and the same additions in the same order on the host (pt_refit_device.hip: pt_scene_quality folds a workgroup's terms by halves)
+double tree_quality_grouped(const float* nodes, uint32_t n_nodes, uint32_t n_faces)
+{
+  if (n_nodes == 0 || n_faces == 0) return 0.0;
+  double total = 0.0, sum[kRefitThreads];
+  for (uint32_t g = 0; g < quality_groups(n_nodes); ++g) {
+    for (uint32_t t = 0; t < kRefitThreads; ++t) {
+      const uint32_t k = g * kRefitThreads + t;
+      sum[t] = k < n_nodes ? rf_quality_term(nodes + (size_t)k * 16u) : 0.0;
+    }
+    for (uint32_t h = kRefitThreads / 2u; h > 0u; h >>= 1)
+      for (uint32_t t = 0; t < h; ++t) sum[t] += sum[t + h];
+    total += sum[0];
+  }
+  return total / rf_node_area(nodes);
+}
+
+// The device builder (pt_build.hip) over `faces`, and the topology tables of its tree.  handled = false: a node above the subtrees
+// needs one of partition's fallbacks, and the caller builds the same tree on the host.  Everything allocated here is freed on return.
+int device_build_tree(const float* faces, uint32_t n, hipStream_t stream, Bvh& bvh, bool& handled)
+{
+  handled = false;
+  DeviceBuffer<uint32_t> prims[2], owner, tag, large, slots, open, roots, order, ctl;
+  DeviceBuffer<BdNode> nodes;
+  BuildParams p;
+  std::memset(&p, 0, sizeof p);
+  p.n_faces = n; p.max_open = build_max_open(n); p.max_leaf = kMaxLeaf;
+  for (int i = 0; i < 2; ++i) PT_HIP(prims[i].alloc((size_t)n * 40u));
+  PT_HIP(owner.alloc((size_t)n * 4u));
+  PT_HIP(tag.alloc((size_t)n * 4u));
+  PT_HIP(large.alloc((size_t)n * 16u));
+  PT_HIP(slots.alloc((size_t)p.max_open * kBdSlotWords * 4u));
+  PT_HIP(open.alloc((size_t)p.max_open * 8u));
+  PT_HIP(roots.alloc((size_t)n * 8u));
+  PT_HIP(order.alloc((size_t)n * 4u));
+  PT_HIP(ctl.alloc(kBdCtlWords * 4u));
+  PT_HIP(nodes.alloc((size_t)n * 3u * sizeof(BdNode)));
+  p.faces = faces;
+  p.prims[0] = prims[0].get(); p.prims[1] = prims[1].get();
+  p.owner = owner.get(); p.tag = tag.get(); p.large = large.get(); p.slots = slots.get(); p.open = open.get(); p.roots = roots.get();
+  p.order = order.get(); p.ctl = ctl.get(); p.nodes = nodes.get();
+  uint32_t n_large = 0, unhandled = 0;
+  PT_HIP(run_device_build(p, stream, &n_large, &unhandled));
+  if (unhandled) return PTAMD_OK;
+  if (n_large > n) { set_error("ptamd_scene_rebuild: the device builder left an inconsistent tree (its node count)"); return PTAMD_ERR_HIP; }
+  std::vector<BdNode> h((size_t)2u * n + n_large);
+  std::vector<uint32_t> face_at(n);
+  PT_HIP(hipMemcpy(h.data(), nodes.get(), h.size() * sizeof(BdNode), hipMemcpyDeviceToHost));
+  PT_HIP(hipMemcpy(face_at.data(), order.get(), (size_t)n * 4u, hipMemcpyDeviceToHost));
+  handled = true;
+  return bvh_topology_of_build_nodes(h.data(), h.size(), n > kBuildGroupPrims ? 2u * n : 0u, face_at.data(), n, kBoxMargin, kMaxLeaf, bvh);
+}
+
+// the tree-dependent members of `t` (install_tree filled them) into `s`; what was sized by the old tree is dropped
+void take_tree(DeviceScene& s, DeviceScene& t)
+{
+  s.nodes = std::move(t.nodes); s.nodes4 = std::move(t.nodes4); s.nodes8 = std::move(t.nodes8); s.nodes4q = std::move(t.nodes4q);
+  s.tris_bvh = std::move(t.tris_bvh);
+  s.n_nodes = t.n_nodes; s.n_bvh_tris = t.n_bvh_tris; s.n_nodes4 = t.n_nodes4; s.depth4 = t.depth4; s.n_nodes8 = t.n_nodes8; s.depth8 = t.depth8;
+  s.n_skipped = t.n_skipped; s.links = t.links; s.cull_on = t.cull_on; s.relink_on = t.relink_on; s.n_culled = t.n_culled;
+  s.cull_pending = false;
+  s.links_plain = std::move(t.links_plain); s.skip_bytes = std::move(t.skip_bytes);
+  s.topology = std::move(t.topology); s.record_face = std::move(t.record_face); s.skip_set = std::move(t.skip_set);
+  s.cull_bits.clear(); s.link_words.clear();
+  for (int i = 0; i < 2; ++i) s.h_links[i] = PinnedBuffer<uint32_t>();
+  s.raw = std::move(t.raw); s.refit_groups = std::move(t.refit_groups); s.refit_levels = std::move(t.refit_levels);
+  s.refit_sched = std::move(t.refit_sched); s.wide_child = std::move(t.wide_child);
+  s.n_refit_groups = t.n_refit_groups; s.n_refit_levels = t.n_refit_levels; s.n_refit_sched = t.n_refit_sched;
+  s.refit_top_first = t.refit_top_first; s.refit_top_levels = t.refit_top_levels;
+  s.refit_ok = t.refit_ok;
+  s.quality_built = t.quality_built;
+  s.d_quality = DeviceBuffer<double>();
+  s.info.n_nodes = t.info.n_nodes; s.info.n_leaves = t.info.n_leaves; s.info.max_leaf_size = t.info.max_leaf_size; s.info.depth = t.info.depth;
+  s.info.n_nodes4 = t.info.n_nodes4; s.info.depth4 = t.info.depth4; s.info.lds_bytes_bvh = t.info.lds_bytes_bvh;
+}
+
+} // namespace
 
 } // namespace ptamd
 
@@ -449,51 +629,15 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
 
   PT_HIP(hipSetDevice(ctx->device));
   DeviceScene d;
-  d.n_faces = sc->n_faces; d.n_lights = sc->n_lights; d.n_nodes = bvh.n_nodes; d.n_bvh_tris = bvh.n_tris;
+  d.n_faces = sc->n_faces; d.n_lights = sc->n_lights;
   d.extent = bvh.extent; d.all_finite = bvh.all_finite; d.reach = bvh.reach; d.margin_floor = bvh.margin_floor;
-  d.n_nodes4 = bvh.n_nodes4; d.depth4 = bvh.depth4;
-  d.n_nodes8 = bvh.n_nodes8; d.depth8 = bvh.depth8;
   d.n_materials = sc->n_materials; d.n_textures = sc->n_textures;
   d.flat = flat;
   // device copy of the lights: the radius only ever enters as radius * radius (intersection.cuh:147) — the same binary32
   // product whoever forms it — so the table carries the square in its place and every sphere test saves the multiply
   std::vector<ptamd_light> dev_lights(sc->lights, sc->lights + sc->n_lights);
   for (ptamd_light& dl : dev_lights) dl.radius = dl.radius * dl.radius;
-  // scenes that take the compact LDS layout: the box tests the walk leaves out, and the relinked link table behind the node table
-  // (8 words per node, then the eight entry nodes) for the restart kernel's skip forms
-  std::vector<float> nodes_and_links(bvh.nodes);
-  if (bvh.n_nodes * 64u + bvh.n_tris * 48u <= kLdsBudget && bvh.n_nodes <= kCompactMaxNodes && bvh.n_tris <= kCompactMaxTris && skip_links_fit(bvh)) {
-    const uint32_t mode = ctx->knobs.skip_mode;   // (PTAMD_SKIP=0: no table at all)
-    SkipTables t;
-    build_skip_tables(bvh, mode == PTAMD_SKIP_SET ? mode : (mode | PTAMD_SKIP_CULLED), ctx->knobs.skip_threshold, nullptr, t);
-    d.n_skipped = t.n_skipped; d.n_culled = t.n_culled;
-    d.links = t.n_skipped != 0u || t.n_culled != 0u;
-    if (d.links) {
-      // behind the table one word more: the count ptamd_scene_relink's kernel leaves (no launch reads it)
-      nodes_and_links.resize(bvh.nodes.size() + t.words.size() + 1u, 0.0f);
-      std::memcpy(nodes_and_links.data() + bvh.nodes.size(), t.words.data(), t.words.size() * 4);
-      // what a relink and restore_plain_links need, of every scene with a table: the set as bytes, the table of the set alone
-      std::vector<uint32_t> plain;
-      skip_link_table(bvh, t.skip, plain);
-      if ((rc = upload(d.links_plain, plain.data(), plain.size() * 4)) || (rc = upload(d.skip_bytes, t.skip.data(), t.skip.size()))) return rc;
-      const char* knob = tuning_env("PTAMD_SKIP_CULL");
-      d.relink_on = !(knob && std::atoi(knob) == 0);
-    }
-    if (t.n_culled) {
-      d.cull_on = true;
-      d.topology.nodes = bvh.nodes;
-      d.topology.n_nodes = bvh.n_nodes; d.topology.n_tris = bvh.n_tris;
-      d.topology.tris.resize((size_t)bvh.n_tris * 12);
-      d.skip_set = t.skip;
-      d.record_face.resize(bvh.n_tris);
-      for (uint32_t j = 0; j < bvh.n_tris; ++j) std::memcpy(&d.record_face[j], &bvh.tris[(size_t)j * 12 + 9], 4);
-    }
-  }
-  if ((rc = upload(d.nodes, nodes_and_links.data(), nodes_and_links.size() * 4)) ||
-      (rc = upload(d.nodes4, bvh.nodes4.data(), bvh.nodes4.size() * 4)) ||
-      (bvh.nodes8.empty() ? 0 : (rc = upload(d.nodes8, bvh.nodes8.data(), bvh.nodes8.size() * 4))) ||
-      (bvh.nodes4q.empty() ? 0 : (rc = upload(d.nodes4q, bvh.nodes4q.data(), bvh.nodes4q.size() * 4))) ||
-      (rc = upload_padded(d.tris_bvh, bvh.tris.data(), bvh.tris.size() * 4, 128)) ||   // (the merged wide walk reads eight 16-byte words from a leaf's first record)
+  if ((rc = install_tree(ctx, bvh, sc->n_faces, d)) ||
       (rc = upload(d.tris_brute, brute.data(), brute.size() * 4)) ||
       (rc = upload(d.shade, shade.data(), shade.size() * 4)) ||
       (rc = upload(d.materials, mats.data(), mats.size() * 4)) ||
@@ -501,29 +645,13 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
       (rc = upload(d.textures, tex.data(), tex.size() * sizeof(TexDesc))) ||
       (rc = upload(d.texels, sc->texels, (size_t)sc->n_texel_floats * 4)))
     return rc;
-  // what ptamd_scene_update needs: raw boxes, the children-first schedule, the wide nodes' children; host copies of what an
-  // update checks (material ids) and recomputes (the origin reach from the lights)
-  d.refit_ok = !bvh.split && bvh.nodes8.empty() && bvh.nodes4q.empty();
+  // host copies of what an update checks (material ids) and recomputes (the origin reach from the lights)
   if (d.refit_ok) {
-    if ((rc = upload(d.raw, bvh.raw.data(), bvh.raw.size() * 4)) ||
-        (rc = upload(d.refit_groups, bvh.refit_groups.data(), bvh.refit_groups.size() * 4)) ||
-        (rc = upload(d.refit_levels, bvh.refit_levels.data(), bvh.refit_levels.size() * 4)) ||
-        (rc = upload(d.refit_sched, bvh.refit_sched.data(), bvh.refit_sched.size() * 4)) ||
-        (rc = upload(d.wide_child, bvh.wide_child.data(), bvh.wide_child.size() * 4)))
-      return rc;
-    d.n_refit_groups = (uint32_t)bvh.refit_groups.size() / 4u; d.n_refit_levels = (uint32_t)bvh.refit_levels.size();
-    d.n_refit_sched = (uint32_t)bvh.refit_sched.size();
-    d.refit_top_first = bvh.refit_top_first; d.refit_top_levels = bvh.refit_top_levels;
     d.material_ids.resize(sc->n_faces);
     for (uint32_t i = 0; i < sc->n_faces; ++i) d.material_ids[i] = sc->faces[i].material_id;
   }
   d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);   // (every scene: ptamd_scene_update_lights recomputes the reach from them)
-  d.quality_built = tree_quality(bvh.nodes.data(), bvh.n_nodes, sc->n_faces);
-  d.info.n_faces = sc->n_faces; d.info.n_lights = sc->n_lights; d.info.n_nodes = bvh.n_nodes;
-  d.info.n_leaves = bvh.n_leaves; d.info.max_leaf_size = bvh.max_leaf; d.info.depth = bvh.depth;
-  d.info.node_bytes = 64; d.info.tri_bytes = 48;
-  d.info.n_nodes4 = d.n_nodes4; d.info.depth4 = d.depth4;
-  d.info.lds_bytes_bvh = bvh.n_nodes * 64u + bvh.n_tris * 48u;
+  d.info.n_faces = sc->n_faces; d.info.n_lights = sc->n_lights;
   d.info.lds_bytes_brute = sc->n_faces * 48u;
   ctx->scenes.push_back(std::move(d));
   *out_scene_id = (uint32_t)ctx->scenes.size() - 1;
@@ -673,17 +801,8 @@ int ptamd_scene_quality(ptamd_context* ctx, uint32_t scene_id, void* stream, pta
   out->now = 0.0;
   if (s.n_nodes == 0 || s.n_faces == 0) return PTAMD_OK;
   PT_HIP(hipSetDevice(ctx->device));
-  const uint32_t groups = quality_groups(s.n_nodes);
-  if (!s.d_quality) PT_HIP(s.d_quality.alloc((size_t)(groups + 1u) * sizeof(double)));
   if ((rc = wait_for_update(s, st, false)) != PTAMD_OK) return rc;
-  PT_HIP(launch_quality(reinterpret_cast<const float*>(s.nodes.get()), s.n_nodes, s.d_quality.get(), st));
-  std::vector<double> part(groups + 1u);
-  PT_HIP(hipMemcpyAsync(part.data(), s.d_quality.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  PT_HIP(hipStreamSynchronize(st));
-  double sum = 0.0;
-  for (uint32_t g = 0; g < groups; ++g) sum += part[g];   // index order: the same bits for the same tables
-  out->now = sum / part[groups];
-  return PTAMD_OK;
+  return device_quality(s, st, &out->now);
 }
 
 int ptamd_host_scene_quality(const ptamd_scene_desc* sc, const ptamd_face* faces_b, double* out)
@@ -743,6 +862,98 @@ int ptamd_host_scene_refit(const ptamd_scene_desc* sc, const ptamd_face* faces_b
   *bytes = size[which];
   if (!out) return PTAMD_OK;
   if (room < size[which]) { set_error("ptamd_host_scene_refit: the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
+  if (size[which]) std::memcpy(out, src[which], size[which]);
+  return PTAMD_OK;
+}
+
+
+uint32_t ptamd_build_group_prims(void) { return kBuildGroupPrims; }
+
+int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, ptamd_scene_rebuild_info* out)
+{
+  const char* who = "ptamd_scene_rebuild";
+  if (!ctx || !d) { set_error("ptamd_scene_rebuild: null argument"); return PTAMD_ERR_ARG; }
+  if (d->flags & ~(uint32_t)PTAMD_REBUILD_HOST_BUILDER) { set_error("ptamd_scene_rebuild: unknown flag bits"); return PTAMD_ERR_ARG; }
+  int rc = update_scene_checks(who, ctx, d->scene_id, d->n_faces, d->faces);
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
+  DeviceScene& s = ctx->scenes[d->scene_id];
+  if (out) std::memset(out, 0, sizeof *out);
+  const uint32_t n = d->n_faces;
+  if (n == 0) return PTAMD_OK;
+  if ((rc = device_array_checks(who, "faces", ctx, d->faces, (size_t)n * sizeof(ptamd_face), true)) != PTAMD_OK) return rc;
+  if (n >= (1u << 24)) { set_error("ptamd_scene_rebuild: more than 2^24 faces"); return PTAMD_ERR_LIMIT; }
+  // a blocking call: every reader of the scene, whatever the stream holds, and the copies earlier updates left in flight
+  if ((rc = prepare_margins(s)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
+  PT_HIP(hipStreamSynchronize(stream));
+  for (int i = 0; i < 2; ++i) {
+    if (s.margin_ready_valid[i]) PT_HIP(hipEventSynchronize(s.margin_ready[i].get()));
+    if (s.cull_ready_valid[i]) PT_HIP(hipEventSynchronize(s.cull_ready[i].get()));
+  }
+  const float* faces = reinterpret_cast<const float*>(d->faces);
+  // the faces on the host, where a host builder needs them: material ids are the upload's
+  std::vector<ptamd_face> host_faces;
+  auto fetch_faces = [&]() -> int {
+    if (!host_faces.empty()) return PTAMD_OK;
+    host_faces.resize(n);
+    PT_HIP(hipMemcpy(host_faces.data(), d->faces, (size_t)n * sizeof(ptamd_face), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i) host_faces[i].material_id = s.material_ids[i];
+    return PTAMD_OK;
+  };
+  const ptamd_light* lights = s.host_lights.data();
+  const uint32_t n_lights = (uint32_t)s.host_lights.size();
+  Bvh bvh;
+  bool host_builder = (d->flags & PTAMD_REBUILD_HOST_BUILDER) != 0u, device_built = false;
+  if (!host_builder) {
+    if ((rc = device_build_tree(faces, n, stream, bvh, device_built)) != PTAMD_OK) return rc;
+    if (!device_built && ((rc = fetch_faces()) != PTAMD_OK ||
+                          (rc = build_bvh_binned(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, lights, n_lights)) != PTAMD_OK))
+      return rc;
+    // a tree that takes the compact LDS layout: the skip set is chosen with rays over the tree's geometry, on the host
+    if (tree_is_compact(bvh)) { host_builder = true; device_built = false; }
+  }
+  if (host_builder) {
+    if ((rc = fetch_faces()) != PTAMD_OK || (rc = build_bvh(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, 0u, lights, n_lights)) != PTAMD_OK) return rc;
+    if (bvh.split) { set_error("ptamd_scene_rebuild: the upload's builder pre-splits references (PTAMD_BVH_SPLIT_ALPHA): such a tree is not refitted"); return PTAMD_ERR_ARG; }
+  }
+  // the new tables beside the old ones; nothing of the scene has changed so far
+  DeviceScene fresh;
+  if ((rc = install_tree(ctx, bvh, n, fresh)) != PTAMD_OK) return rc;
+  take_tree(s, fresh);
+  // positions: the refit forms records, raw boxes, planes, four-wide boxes and orders from the faces, the reduction the margins
+  RefitParams r;
+  if ((rc = refit_params(who, s, r)) != PTAMD_OK || (rc = enqueue_device_refit(s, r, faces, stream, true)) != PTAMD_OK) return rc;
+  PT_HIP(hipStreamSynchronize(stream));
+  if ((rc = settle_margins(s, stream, who)) != PTAMD_OK || (rc = device_quality(s, stream, &s.quality_built)) != PTAMD_OK) return rc;
+  if (out) {
+    out->device_builder = device_built ? 1u : 0u;
+    out->n_nodes = s.n_nodes; out->n_nodes4 = s.n_nodes4; out->depth = s.info.depth;
+    out->quality = s.quality_built;
+  }
+  return PTAMD_OK;
+}
+
+int ptamd_host_scene_rebuild(const ptamd_scene_desc* sc, const ptamd_face* faces, uint32_t flags, uint32_t which, void* out, uint64_t* bytes)
+{
+  if (!sc || !bytes || which > 6u || (sc->n_faces && !faces)) { set_error("ptamd_host_scene_rebuild: bad argument"); return PTAMD_ERR_ARG; }
+  if (flags & ~(uint32_t)PTAMD_REBUILD_HOST_BUILDER) { set_error("ptamd_host_scene_rebuild: unknown flag bits"); return PTAMD_ERR_ARG; }
+  int rc = validate_scene_desc(sc);
+  SceneTables t;
+  if (rc != PTAMD_OK || (rc = make_scene_tables(sc, 0u, t)) != PTAMD_OK) return rc;   // (the material and texture words of the upload)
+  Bvh fresh;
+  rc = (flags & PTAMD_REBUILD_HOST_BUILDER) ? build_bvh(faces, sc->n_faces, kBoxMargin, kMaxLeaf, fresh, 0u, sc->lights, sc->n_lights)
+                                            : build_bvh_binned(faces, sc->n_faces, kBoxMargin, kMaxLeaf, fresh, sc->lights, sc->n_lights);
+  if (rc != PTAMD_OK) return rc;
+  t.bvh = std::move(fresh);
+  if ((rc = refit_scene_tables(t, faces, sc->n_faces, sc->lights, sc->n_lights)) != PTAMD_OK) return rc;
+  const float scalars[4] = { t.bvh.extent, t.bvh.reach, t.bvh.margin_floor, t.bvh.all_finite ? 1.0f : 0.0f };
+  const double quality = tree_quality_grouped(t.bvh.nodes.data(), t.bvh.n_nodes, sc->n_faces);
+  const void* src[7] = { t.bvh.nodes.data(), t.bvh.tris.data(), t.bvh.nodes4.data(), t.brute.data(), t.shade.data(), scalars, &quality };
+  const uint64_t size[7] = { t.bvh.nodes.size() * 4u, t.bvh.tris.size() * 4u, t.bvh.nodes4.size() * 4u, t.brute.size() * 4u, t.shade.size() * 4u, 16u, 8u };
+  const uint64_t room = *bytes;
+  *bytes = size[which];
+  if (!out) return PTAMD_OK;
+  if (room < size[which]) { set_error("ptamd_host_scene_rebuild: the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
   if (size[which]) std::memcpy(out, src[which], size[which]);
   return PTAMD_OK;
 }

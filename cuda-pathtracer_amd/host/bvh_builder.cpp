@@ -13,6 +13,7 @@
 // 48-byte {v0, e1, e2, global index} records.
 #include "ptamd_internal.h"
 #include "../csrc/pt_refit_device.h"
+#include "../csrc/pt_build.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,9 +37,7 @@ struct Box {
   }
   float half_area() const
   {
-    float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-    if (dx < 0.f || dy < 0.f || dz < 0.f) return 0.f;
-    return dx * dy + dy * dz + dz * dx;
+    return bd_half_area(lo, hi);
   }
 };
 
@@ -51,12 +50,12 @@ struct BuildNode {
   int axis = 0;
 };
 
-constexpr float kTravCost = 1.0f;
-constexpr int kBins = 32;
+constexpr float kTravCost = kBuildTravCost;
+constexpr int kBins = kBuildBins;   // the arithmetic of the binned branch: csrc/pt_build.h, shared with the device builder (pt_build.hip)
 
 // What one build is tuned by: the values every production build uses, and the PTAMD_BVH_* knobs over them (read_options).
 struct BuildOptions {
-  float isect_cost = 1.6f;            // SAH cost of one triangle test relative to one box test
+  float isect_cost = kBuildIsectCost;            // SAH cost of one triangle test relative to one box test
   uint32_t sweep_limit = 1u << 30;    // nodes with more primitives than this are split by binning (2048: round 2's builder)
   uint32_t max_leaf = 4;
   float split_alpha = 0.0f;           // pre-splitting (split_references) off unless asked for
@@ -105,7 +104,7 @@ struct Builder {
   Split find_split(uint32_t first, uint32_t count, const Box& box, const Box& cbox)
   {
     Split best;
-    const float inv_area = 1.0f / std::max(box.half_area(), 1e-30f);
+    const float inv_area = bd_inv_area(box.half_area());
     if (count <= opt.sweep_limit) {
       std::vector<float> right_area(count);
       for (int a = 0; a < 3; ++a) {
@@ -132,9 +131,9 @@ struct Builder {
       Box bbox[kBins];
       uint32_t bcnt[kBins];
       for (int b = 0; b < kBins; ++b) { bbox[b].reset(); bcnt[b] = 0; }
-      float scale = (float)kBins / ext;
+      const float scale = bd_bin_scale(ext);
       for (uint32_t i = first; i < first + count; ++i) {
-        int b = std::min(kBins - 1, std::max(0, (int)((prims[i].c[a] - cbox.lo[a]) * scale)));
+        const int b = bd_bin(prims[i].c[a], cbox.lo[a], scale);
         bbox[b].grow(prims[i].box);
         bcnt[b]++;
       }
@@ -152,10 +151,10 @@ struct Builder {
       for (int b = 1; b < kBins; ++b) {
         acc.grow(bbox[b - 1]); n += bcnt[b - 1];
         if (n == 0 || rcnt[b] == 0) continue;
-        float cost = kTravCost + opt.isect_cost * inv_area * (acc.half_area() * (float)n + rarea[b] * (float)rcnt[b]);
+        const float cost = bd_split_cost(opt.isect_cost, inv_area, acc.half_area(), n, rarea[b], rcnt[b]);
         if (cost < best.cost) {
           best.cost = cost; best.axis = a; best.binned = true;
-          best.plane = cbox.lo[a] + (float)b / scale;
+          best.plane = bd_plane(cbox.lo[a], b, scale);
         }
       }
     }
@@ -206,8 +205,7 @@ struct Builder {
     if (count == 1) return id;
 
     Split s = find_split(first, count, box, cbox);
-    const float leaf_cost = opt.isect_cost * (float)count;
-    if (count <= opt.max_leaf && (s.axis < 0 || leaf_cost <= s.cost)) return id; // leaf
+    if (bd_is_leaf(count, opt.max_leaf, s.axis, s.cost, opt.isect_cost)) return id; // leaf
 
     const uint32_t mid = partition(first, count, s);
     int l = build(first, mid, level + 1);
@@ -489,7 +487,7 @@ std::vector<Prim> prims_of_faces(const ptamd_face* faces, uint32_t n_faces)
     rf_face_box(&faces[i].vertices[0].x, fb);
     for (int a = 0; a < 3; ++a) {
       p.box.lo[a] = fb.lo[a]; p.box.hi[a] = fb.hi[a];
-      p.c[a] = 0.5f * p.box.lo[a] + 0.5f * p.box.hi[a];
+      p.c[a] = bd_centre(p.box.lo[a], p.box.hi[a]);
     }
   }
   return prims;
@@ -937,11 +935,10 @@ float origin_reach(const ptamd_light* lights, uint32_t n_lights, float extent)
 // numbering, miss links and binary tables; the same tree with four children per node (float nodes, on request 64-byte
 // quantised ones) and, on request, with eight.  Everything that depends on vertex positions alone is formed by the functions
 // refit_bvh forms it with.
-int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms,
-              const ptamd_light* lights, uint32_t n_lights)
+static int build_with(const BuildOptions& opt, const ptamd_face* faces, uint32_t n_faces, float margin, Bvh& out, uint32_t forms,
+                      const ptamd_light* lights, uint32_t n_lights)
 {
   out = Bvh();
-  const BuildOptions opt = read_options(max_leaf, n_faces);
   if (n_faces == 0) return PTAMD_OK;
   if (n_faces >= (1u << 24)) { set_error("build_bvh: more than 2^24 faces"); return PTAMD_ERR_LIMIT; }
 
@@ -973,6 +970,90 @@ int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t 
     const EightPlan plan = plan_eight(t);
     quantise_eight(t, collapse<8>(t, [&](int id) { return open_eight(t, plan, id); }), plan, out);
   }
+  return PTAMD_OK;
+}
+
+int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms,
+              const ptamd_light* lights, uint32_t n_lights)
+{
+  return build_with(read_options(max_leaf, n_faces), faces, n_faces, margin, out, forms, lights, n_lights);
+}
+
+// The options of the all-binned tree (csrc/pt_build.h): no knob reaches them
+static BuildOptions binned_options(uint32_t max_leaf)
+{
+  BuildOptions o;
+  o.sweep_limit = 0;
+  o.max_leaf = std::max(1u, std::min(15u, max_leaf));
+  return o;
+}
+
+int build_bvh_binned(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, const ptamd_light* lights,
+                     uint32_t n_lights)
+{
+  if (n_faces >= (1u << 24)) { set_error("build_bvh: more than 2^24 faces"); return PTAMD_ERR_LIMIT; }
+  return build_with(binned_options(max_leaf), faces, n_faces, margin, out, 0u, lights, n_lights);
+}
+
+// The device builder's nodes as a tree: walked from the root in Builder::build's order (a node, its left subtree, its right one), so
+// the BuildTree is the one Builder leaves for the same splits; every index and range is checked on the way.  Then build_bvh's
+// topology steps.  Boxes come from the build nodes (open_four ranks children by their area); every table of positions stays zero.
+int bvh_topology_of_build_nodes(const BdNode* nodes, size_t n_slots, uint32_t root, const uint32_t* order, uint32_t n_faces, float margin,
+                                uint32_t max_leaf, Bvh& out)
+{
+  out = Bvh();
+  if (n_faces == 0) return PTAMD_OK;
+  auto bad = [](const char* what) {
+    set_error(std::string("ptamd_scene_rebuild: the device builder left an inconsistent tree (") + what + ")");
+    return PTAMD_ERR_HIP;
+  };
+  BuildTree t;
+  t.opt = binned_options(max_leaf);
+  t.prims.resize(n_faces);
+  std::vector<uint8_t> seen(n_faces, 0);
+  for (uint32_t i = 0; i < n_faces; ++i) {
+    if (order[i] >= n_faces || seen[order[i]]) return bad("the primitive order is no permutation");
+    seen[order[i]] = 1;
+    t.prims[i].face = order[i];
+  }
+  t.nodes.reserve(2 * (size_t)n_faces);
+  struct Item { uint32_t id, first, count, level; int parent; bool right; };
+  std::vector<Item> stack;
+  stack.push_back({ root, 0u, n_faces, 0u, -1, false });
+  while (!stack.empty()) {
+    const Item it = stack.back();
+    stack.pop_back();
+    if (it.id >= n_slots) return bad("a node index is out of range");
+    const BdNode& d = nodes[it.id];
+    if (d.first != it.first || d.count != it.count || it.count == 0) return bad("a node's range is not its parent's share");
+    if (t.nodes.size() >= 2 * (size_t)n_faces) return bad("more nodes than a binary tree has");
+    const int id = (int)t.nodes.size();
+    t.nodes.emplace_back();
+    BuildNode& bn = t.nodes.back();
+    for (int a = 0; a < 3; ++a) { bn.box.lo[a] = d.lo[a]; bn.box.hi[a] = d.hi[a]; }
+    bn.first = d.first; bn.count = d.count;
+    t.depth = std::max(t.depth, it.level + 1);
+    if (it.parent >= 0) (it.right ? t.nodes[(size_t)it.parent].right : t.nodes[(size_t)it.parent].left) = id;
+    if (d.left < 0) {
+      if (d.count > t.opt.max_leaf) return bad("a leaf holds more than max_leaf primitives");
+      continue;
+    }
+    if (d.right < 0 || d.axis < 0 || d.axis > 2 || (size_t)d.left >= n_slots || (size_t)d.right >= n_slots) return bad("an interior node's words");
+    const uint32_t n_left = nodes[(size_t)d.left].count;
+    if (n_left == 0 || n_left >= d.count) return bad("a split leaves one side empty");
+    bn.axis = d.axis;
+    stack.push_back({ (uint32_t)d.right, d.first + n_left, d.count - n_left, it.level + 1, id, true });
+    stack.push_back({ (uint32_t)d.left, d.first, n_left, it.level + 1, id, false });
+  }
+  out.depth = t.depth;
+  t.margin = out.margin = margin;
+  flatten(t);
+  write_binary_nodes(t, miss_links(t), out);
+  plan_refit(out);
+  const WideTree<4> four = collapse<4>(t, [&](int id) { return open_four(t, id); });
+  const std::vector<uint32_t> refs4 =
+      wide_refs<4>(four, [&](size_t id) { return leaf_ref(t.leaf_info[id] & 0xFFFFFFu, t.leaf_info[id] >> 24); });
+  write_wide_refs(t, four, refs4, out);
   return PTAMD_OK;
 }
 

@@ -124,6 +124,17 @@ constexpr uint32_t kBvhForm8 = 1u, kBvhForm4q = 2u;
 int build_bvh(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, uint32_t forms = kBvhForm8 | kBvhForm4q,
               const ptamd_light* lights = nullptr, uint32_t n_lights = 0);
 
+// The tree of ptamd_scene_rebuild (DESIGN.md §13 "Rebuilding in place"; arithmetic: csrc/pt_build.h): build_bvh with every node split
+// by binning, isect_cost 1.6, no pre-splitting, the four-wide float nodes and no quantised form.  No tuning knob reaches it.
+int build_bvh_binned(const ptamd_face* faces, uint32_t n_faces, float margin, uint32_t max_leaf, Bvh& out, const ptamd_light* lights = nullptr,
+                     uint32_t n_lights = 0);
+// ... and its topology from the nodes the device builder left (csrc/pt_build.hip): node and link words, leaf ranges with their face
+// indices, the four-wide references, wide_child and the refit schedule; every table of vertex positions stays zero until a refit
+// forms it.  order: the face at every primitive position.  PTAMD_ERR_HIP when the nodes are no tree over the faces.
+struct BdNode;
+int bvh_topology_of_build_nodes(const BdNode* nodes, size_t n_slots, uint32_t root, const uint32_t* order, uint32_t n_faces, float margin,
+                                uint32_t max_leaf, Bvh& out);
+
 // The same topology for new vertex positions: triangle records, raw boxes (a leaf's from its faces, an interior node's from its
 // children's), node planes, four-wide child boxes and visiting orders, extent / reach / margin_floor — all formed by the functions
 // build_bvh forms them with (csrc/pt_refit.h), so the walks stay exact on the new faces whatever the deformation did to the

@@ -74,6 +74,18 @@ class SceneUpdateDeviceDesc(C.Structure):   # ptamd_scene_update_device_desc (in
     _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p)]
 
 
+REBUILD_HOST_BUILDER = 1
+
+
+class SceneRebuildDesc(C.Structure):        # ptamd_scene_rebuild_desc (include/ptamd.h): faces is a DEVICE address
+    _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class SceneRebuildInfo(C.Structure):        # ptamd_scene_rebuild_info (include/ptamd.h)
+    _fields_ = [("device_builder", C.c_uint32), ("n_nodes", C.c_uint32), ("n_nodes4", C.c_uint32), ("depth", C.c_uint32),
+                ("quality", C.c_double)]
+
+
 class SceneRigPoseDesc(C.Structure):        # ptamd_scene_rig_pose_desc (include/ptamd.h): transforms and normal matrices are HOST arrays
     _fields_ = [("rig", C.c_void_p), ("transforms", C.POINTER(C.c_float)), ("normal_matrices", C.POINTER(C.c_float)),
                 ("n_groups", C.c_uint32), ("stream", C.c_void_p)]
@@ -230,6 +242,9 @@ SIGNATURES = {
     "ptamd_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32)]),
     "ptamd_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDesc)]),
     "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
+    "ptamd_scene_rebuild": (C.c_int, [C.c_void_p, C.POINTER(SceneRebuildDesc), C.POINTER(SceneRebuildInfo)]),
+    "ptamd_host_scene_rebuild": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_build_group_prims": (C.c_uint32, []),
     "ptamd_scene_rig_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
                                          C.POINTER(C.c_void_p)]),
     "ptamd_scene_rig_pose": (C.c_int, [C.c_void_p, C.POINTER(SceneRigPoseDesc)]),

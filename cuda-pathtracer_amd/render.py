@@ -118,6 +118,35 @@ class Context:
         d.stream = _stream_handle(stream)
         N.check(self._lib.ptamd_scene_update_device(self._h, C.byref(d)))
 
+    def rebuild_scene_device(self, scene_id: int, faces, stream=None, host_builder=False) -> dict:
+        """ptamd_scene_rebuild: the scene stands for `faces` (a tensor as update_scene_device takes it) and its tree is a fresh one
+        over them, built on the device; a SceneRig in place of the tensor: its posed records; host_builder: by the upload's own builder, on the host, from a copy of the faces.  A
+        blocking call.  Returns ptamd_scene_rebuild_info as a dict (device_builder, n_nodes, n_nodes4, depth, quality)."""
+        import torch
+        d = N.SceneRebuildDesc()
+        d.scene_id = scene_id
+        if isinstance(faces, SceneRig):
+            # the records the rig's last pose, skin or morph left (ptamd_scene_rig_faces)
+            p = C.c_void_p()
+            N.check(self._lib.ptamd_scene_rig_faces(faces.handle, C.byref(p)))
+            d.faces = p.value; d.n_faces = faces.n_faces
+        else:
+            if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+                raise ValueError("rebuild_scene_device takes a torch tensor in device memory, or a SceneRig")
+            if faces.device.index != self.device:
+                raise ValueError(f"the faces live on {faces.device}, the context on device {self.device}")
+            if not ((faces.dtype == torch.float32 and faces.dim() == 2 and faces.shape[1] == 28) or
+                    (faces.dtype == torch.uint8 and faces.dim() == 2 and faces.shape[1] == 112)):
+                raise ValueError("faces must be float32 of shape (n, 28) or uint8 of shape (n, 112)")
+            if not faces.is_contiguous():
+                raise ValueError("faces must be contiguous")
+            d.faces = faces.data_ptr(); d.n_faces = faces.shape[0]
+        d.stream = _stream_handle(stream)
+        d.flags = N.REBUILD_HOST_BUILDER if host_builder else 0
+        info = N.SceneRebuildInfo()
+        N.check(self._lib.ptamd_scene_rebuild(self._h, C.byref(d), C.byref(info)))
+        return {n: getattr(info, n) for n, _ in N.SceneRebuildInfo._fields_}
+
     def scene_rig(self, scene_id: int, host_scene, group_sizes=None) -> "SceneRig":
         """ptamd_scene_rig_create: a rig of the uploaded scene with `host_scene` (a HostScene or a FACE_DTYPE array) as its rest
         pose, cut into groups of consecutive faces; group_sizes defaults to the HostScene's mesh_sizes."""
@@ -537,6 +566,27 @@ def host_morph_faces(hs: HostScene, targets, weights) -> HostScene:
     N.check(N.load().ptamd_host_morph_faces(hs.faces.ctypes.data_as(C.POINTER(N.Face)), len(hs.faces), arr, len(targets),
                                             w.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(N.Face))))
     return HostScene(out, hs.mesh_sizes, hs.materials, hs.lights, hs.textures, hs.texels, hs.camera, hs.cubemap, hs.unloaded_textures)
+
+
+def host_rebuild_tables(scene: HostScene, faces, host_builder=False) -> dict:
+    """ptamd_host_scene_rebuild (no GPU): the tables of `scene` after a rebuild to `faces` (HostScene or face array): the five tables
+    by name as bytes, "scalars" (float32 {extent, reach, margin floor, all finite}) and "quality" (float)."""
+    fb = np.ascontiguousarray(faces.faces if isinstance(faces, HostScene) else faces, dtype=FACE_DTYPE)
+    if len(fb) != len(scene.faces):
+        raise ValueError("a rebuild keeps the face count")
+    d = scene.desc()
+    flags = N.REBUILD_HOST_BUILDER if host_builder else 0
+    ptr = fb.ctypes.data_as(C.POINTER(N.Face))
+    out = {}
+    for which, name in enumerate(N.TABLE_NAMES + ("scalars", "quality")):
+        n = C.c_uint64(0)
+        N.check(N.load().ptamd_host_scene_rebuild(C.byref(d), ptr, flags, which, None, C.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        N.check(N.load().ptamd_host_scene_rebuild(C.byref(d), ptr, flags, which, buf.ctypes.data, C.byref(n)))
+        out[name] = buf
+    out["scalars"] = out["scalars"].view(np.float32)
+    out["quality"] = float(out["quality"].view(np.float64)[0])
+    return out
 
 
 def host_scene_quality(scene: HostScene, faces_b=None) -> float:

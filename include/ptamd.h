@@ -264,6 +264,54 @@ typedef struct {
 } ptamd_scene_update_device_desc;
 int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_device_desc* desc);
 
+/* ---- Rebuilding a scene's tree in place (DESIGN.md §13 "Rebuilding in place") ----------------------------------------------
+ *
+ * Every update above keeps the topology of the upload, and a tree refitted far from the faces it was built for walks slower
+ * (ptamd_scene_quality's now / built says how much).  ptamd_scene_rebuild gives the scene a FRESH tree over `faces`: after the call
+ * the scene stands for `faces` exactly as after ptamd_scene_update_device, and its tree is a new one over them.  The id, the
+ * materials, textures, lights and the material words of the shading records stay; the storage-order tables (which = 3, 4) stay in
+ * storage order; rigs attached to the scene stay valid (their records are in storage order; a later pose, skin or morph refits
+ * the NEW tree), and a caller with a rig passes ptamd_scene_rig_faces' pointer.  material_id of the supplied records is not read.
+ *
+ * The tree.  build_bvh's with every node split by binning: 32 bins per axis over the node's centroid box, the planes priced by the
+ * surface-area heuristic (triangle test 1.6 box tests) and scanned in a fixed order, the upload's leaf size, no pre-splitting.  It
+ * is built ON THE DEVICE (out->device_builder = 1), then numbered, linked, collapsed four-wide and scheduled by the upload's own
+ * host steps; triangle records, boxes and margins are formed by the refit every update runs.  ptamd_host_scene_rebuild is the host
+ * definition: the device's tables equal it byte for byte.  Three cases are built on the host from a copy of the faces
+ * (device_builder = 0): PTAMD_REBUILD_HOST_BUILDER, which asks for the UPLOAD'S builder (the tables of a fresh upload of the same
+ * faces, link table included); a new tree that takes the compact LDS layout, which is built as with that flag (its skip set is
+ * chosen with rays over the tree, on the host); and a node of more than ptamd_build_group_prims() primitives whose centroids
+ * coincide or that its plane does not part, where the host builds the same binned tree.
+ *
+ * A blocking call, like an upload: it waits for every launch still reading the scene and for `stream`, allocates the new tables
+ * beside the old ones and swaps them in only when every allocation and the build have succeeded; a failure before that leaves the
+ * scene as it was.  It counts as an update for readers that keep copies of the triangle records, leaves the margins settled (not
+ * pending), and sets ptamd_scene_info and ptamd_scene_quality's `built` from the new tree (built == now until the next update;
+ * both are the device's sum).
+ *
+ * Refused before anything is enqueued or allocated: everything ptamd_scene_update_device refuses (a released or out-of-range id, a
+ * face count that is not the uploaded one, faces that are not device memory of the context's device or not aligned to 16 bytes, a
+ * scene whose tree is not refitted, a captured launch pinning the context, a capturing stream) and, with PTAMD_ERR_ARG, unknown
+ * bits in flags. */
+#define PTAMD_REBUILD_HOST_BUILDER 1u
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_face* faces;   /* DEVICE array, n_faces records in the upload's storage order, 16-byte aligned */
+  uint32_t n_faces;          /* must equal the uploaded count */
+  void* stream;
+  uint32_t flags;            /* PTAMD_REBUILD_HOST_BUILDER: build on the host with the upload's own builder (faces are copied back) */
+} ptamd_scene_rebuild_desc;
+typedef struct { uint32_t device_builder; uint32_t n_nodes, n_nodes4, depth; double quality; } ptamd_scene_rebuild_info;
+int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* desc, ptamd_scene_rebuild_info* out /* may be NULL */);
+/* The host definition, no device needed: the tables of `scene` after a rebuild to `faces` (n_faces of them), which = 0..5 as
+ * ptamd_host_scene_refit numbers them, 6 = the tree's cost as ptamd_scene_rebuild reports it (one double).  flags 0: the binned
+ * tree; PTAMD_REBUILD_HOST_BUILDER: the upload's builder.  Either tree is then refitted to `faces` by ptamd_host_scene_refit's
+ * rule. */
+int ptamd_host_scene_rebuild(const ptamd_scene_desc* scene, const ptamd_face* faces, uint32_t flags, uint32_t which, void* out,
+                             uint64_t* bytes);
+/* Nodes of at most this many primitives are built by one workgroup each (csrc/pt_build.h: kBuildGroupPrims). */
+uint32_t ptamd_build_group_prims(void);
+
 /* ---- Posing a scene from per-group transforms; moving its lights --------------------------------------------
  * The common animation is rigid: each mesh moves as a whole.  A ptamd_scene_rig keeps a scene's REST POSE on the device, cut into
  * groups of consecutive faces (group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]) in storage order; empty groups are
