@@ -1,7 +1,9 @@
 // ptamd_host.h — what the translation units of the host API (include/ptamd.h) share: the context, a scene's and a cubemap's device
 // tables, and the few helpers that cross files.  One subsystem per file:
 //   ptamd_context.cpp   last error, ptamd_create / ptamd_destroy, device utilities, counters, self-test, time stamps
-//   ptamd_scene.cpp     scene tables: upload, updates, margins, quality, release, reads, their host mirrors; cubemaps
+//   ptamd_scene.cpp     scene tables: upload (install_tree), release, reads, info and flatness queries; cubemaps; fill_scene
+//   ptamd_scene_update.cpp  what changes an uploaded scene: the updates of faces and lights, relink, rebuild, margins, quality
+//   (host/scene_tables.cpp: the tables' host form and the ptamd_host_scene_* mirrors, without HIP)
 //   ptamd_rig.cpp       the scene rig: a scene posed from per-group transforms, skinned from per-corner bone weights, or morphed from
 //                       blend-shape targets, on the device
 //   ptamd_launch.cpp    the launch pipeline (camera_terms ... do_launch), ptamd_raytrace*, ray queries
@@ -26,88 +28,74 @@
 
 namespace ptamd {
 
-struct DeviceScene {
-  DeviceBuffer<float4> nodes;
+// Everything a scene's tree decides: what install_tree (ptamd_scene.cpp) fills, and what is sized by the tree and dies with it.
+// ptamd_scene_rebuild replaces this member as a whole; what must survive a rebuild is DeviceScene's own.
+struct SceneTree {
+  DeviceBuffer<float4> nodes;    // the binary nodes, and behind them the skip forms' link table (links: there is one)
   DeviceBuffer<float4> nodes4;   // the four-wide form of the same tree (8 float4 per node)
   DeviceBuffer<float4> nodes8;   // ... and the eight-wide quantised form (8 float4 per node): walked instead when PTAMD_WIDE8=1 (tuning)
   DeviceBuffer<float4> nodes4q;  // ... and the four-wide form in 64-byte quantised nodes (4 float4 per node, numbered as nodes4)
-  uint32_t n_nodes8 = 0, depth8 = 0;
   DeviceBuffer<float4> tris_bvh;
-  DeviceBuffer<float4> tris_brute;
-  DeviceBuffer<float4> shade;
+  uint32_t n_nodes = 0, n_nodes4 = 0, depth4 = 0, n_nodes8 = 0, depth8 = 0;
+  uint32_t n_bvh_tris = 0; // triangle records behind the BVH leaves (>= n_faces with split references)
+  uint32_t n_leaves = 0, max_leaf = 0, depth = 0;   // ptamd_scene_info's, with lds_bytes
+  uint32_t lds_bytes() const { return n_nodes * 64u + n_bvh_tris * 48u; }
+  uint32_t n_skipped = 0;    // nodes whose box test the restart kernel's skip forms leave out (host/skip_links.cpp)
+  // n_culled: the (leaf, octant) pairs the link table leaves out NOW; they hold for the triangles they were proven for, so every
+  // update of the faces puts links_plain (the table of the skip set alone) back in front of its kernels (restore_plain_links), and
+  // ptamd_scene_update, which has the faces, culls again from the host copies below (cull_on: the upload culled, so it does).
+  // ptamd_scene_relink culls again on the device, from the records the device holds and the set's bytes there (relink_on: unless
+  // the upload ran under PTAMD_SKIP_CULL=0); links_plain and skip_bytes exist for every scene with a table.  Its count comes back
+  // through DeviceScene::cull_count; while that is pending n_culled is stale.
+  bool links = false, cull_on = false, relink_on = false;
+  uint32_t n_culled = 0;
+  DeviceBuffer<uint32_t> links_plain;
+  DeviceBuffer<uint8_t> skip_bytes;
+  size_t n_link_words() const { return (size_t)n_nodes * 8 + 8; }
+  uint32_t* link_table() const { return reinterpret_cast<uint32_t*>(nodes.get()) + (size_t)n_nodes * 16; }
+  Bvh topology;                          // nodes as uploaded (topology words and miss links never change) and room for the records of new faces
+  std::vector<uint32_t> record_face;     // per triangle record its face
+  std::vector<uint8_t> skip_set, cull_bits;   // the set; scratch of the re-cull, kept with link_words for the next update
+  std::vector<uint32_t> link_words;
+  PinnedBuffer<uint32_t> h_links[2];     // a recomputed table on its way to the device, in step with DeviceScene::faces_up (same slot, same event)
+  bool refit_ok = false;     // the tree can be refitted (no pre-split references, no quantised node forms)
+  DeviceBuffer<float> raw;                 // raw boxes, 8 floats per node (pt_refit.h)
+  DeviceBuffer<uint32_t> refit_groups, refit_levels, refit_sched, wide_child;   // the children-first schedule (bvh_builder.cpp: plan_refit) and the wide nodes' children
+  uint32_t n_refit_groups = 0, n_refit_levels = 0, n_refit_sched = 0, refit_top_first = 0, refit_top_levels = 0;
+  double quality_built = 0.0;                    // ptamd_scene_quality: the cost of the tree as uploaded (tree_quality)
+  DeviceBuffer<double> d_quality;                // quality_groups(n_nodes) + 1 partial sums, allocated at the first query
+};
+
+struct DeviceScene {
+  SceneTree tree;
+  DeviceBuffer<float4> tris_brute, shade;
   bool flat = false;          // scene_is_flat: `shade` holds the compact records behind the general ones
   DeviceBuffer<int4> materials;
   DeviceBuffer<float4> lights;
   DeviceBuffer<TexDesc> textures;
   DeviceBuffer<float> texels;
-  uint32_t n_faces = 0, n_lights = 0, n_nodes = 0, n_materials = 0, n_textures = 0;
-  uint32_t n_bvh_tris = 0; // triangle records behind the BVH leaves (>= n_faces with split references)
-  uint32_t n_nodes4 = 0, depth4 = 0;
+  uint32_t n_faces = 0, n_lights = 0, n_materials = 0, n_textures = 0;
   float extent = 0.0f;       // largest finite |coordinate| of the scene (bvh_builder.cpp)
   bool all_finite = true;    // no NaN or infinite vertex coordinate
-  uint32_t n_skipped = 0;    // nodes whose box test the restart kernel's skip forms leave out (host/skip_links.cpp)
-  // the skip forms' link table lies behind `nodes` (links: there is one).  n_culled: the (leaf, octant) pairs it leaves out NOW; they
-  // hold for the triangles they were proven for, so every update of the faces puts links_plain (the table of the skip set alone) back
-  // in front of its kernels (restore_plain_links), and ptamd_scene_update, which has the faces, culls again from the host copies
-  // below (cull_on: the upload culled, so it does).  ptamd_scene_relink culls again on the device, from the records the device holds
-  // and the set's bytes there (relink_on: unless the upload ran under PTAMD_SKIP_CULL=0); links_plain and skip_bytes exist for
-  // every scene with a table.  Its count comes back through two pinned words used in turn; until a reader of n_culled has waited
-  // for it (settle_cull_count) n_culled is stale (cull_pending), and an update of the faces supersedes it (restore_plain_links).
-  bool links = false, cull_on = false, relink_on = false;
-  uint32_t n_culled = 0;
-  DeviceBuffer<uint32_t> links_plain;
-  DeviceBuffer<uint8_t> skip_bytes;
-  PinnedBuffer<uint32_t> h_cull;                 // two slots of one word
-  Event cull_ready[2];                           // the copy into slot i has finished
-  bool cull_ready_valid[2] = { false, false };
-  uint32_t cull_next = 0, cull_slot = 0;
-  bool cull_pending = false;
-  Bvh topology;                          // nodes as uploaded (topology words and miss links never change) and room for the records of new faces
-  std::vector<uint32_t> record_face;     // per triangle record its face
-  std::vector<uint8_t> skip_set, cull_bits;   // the set; scratch of the re-cull, kept with link_words for the next update
-  std::vector<uint32_t> link_words;
-  PinnedBuffer<uint32_t> h_links[2];     // a recomputed table on its way to the device, in step with h_stage (same slot, same event)
   float reach = 0.0f;        // origin reach: largest |coordinate| of an origin the path forms, light spheres included (bvh_builder.cpp)
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
-  ptamd_scene_info info{};
   // ---- ptamd_scene_update / ptamd_scene_release
   bool released = false;     // a tombstone: the tables are gone, the id stays taken
-  bool refit_ok = false;     // the tree can be refitted (no pre-split references, no quantised node forms)
   std::vector<uint32_t> material_ids;   // host copy: an update may not change them
   std::vector<ptamd_light> host_lights; // host copy, of every scene: the origin reach follows the new extent and the new lights
-  DeviceBuffer<float> raw;                 // raw boxes, 8 floats per node (pt_refit.h)
-  DeviceBuffer<uint32_t> refit_groups;     // the children-first schedule (bvh_builder.cpp: plan_refit) and the wide nodes' children
-  DeviceBuffer<uint32_t> refit_levels;
-  DeviceBuffer<uint32_t> refit_sched;
-  DeviceBuffer<uint32_t> wide_child;
-  uint32_t n_refit_groups = 0, n_refit_levels = 0, n_refit_sched = 0, refit_top_first = 0, refit_top_levels = 0;
-  // staging of an update's faces, allocated at the first update: two pinned host buffers used in turn (the host fills one while
-  // the copy out of the other may still be in flight), one device buffer
+  // staging of an update's faces, allocated at the first update: one device buffer, two pinned slots (ptamd_owners.h: Upload)
   DeviceBuffer<float> d_faces;
-  PinnedBuffer<ptamd_face> h_stage[2];
-  Event staged[2];                               // the copy out of h_stage[i] has finished
-  bool staged_valid[2] = { false, false };
-  uint32_t stage_next = 0;
+  Upload<ptamd_face> faces_up;
   Event updated;                                 // the last update's kernels have finished: lanes and other streams wait for it
   bool updated_valid = false;
-  uint64_t geometry_serial = 0;                  // counts the refits enqueued (ptamd_scene.cpp: enqueue_refit): the faces moved since a reader last looked
+  uint64_t geometry_serial = 0;                  // counts the refits enqueued (ptamd_scene_update.cpp: enqueue_refit): the faces moved since a reader last looked
   // ptamd_scene_update_device: the new faces' extent is formed on the device (pt_refit_device.hip) and copied back behind the
   // update's kernels; until a reader of extent / all_finite / reach / margin_floor has waited for it (settle_margins) those four
-  // are stale.  Two pinned slots used in turn, so a copy that lands late never overwrites the words of a newer update.
+  // are stale.  Two slots, so a copy that lands late never overwrites the words of a newer update.
   DeviceBuffer<float> d_margin;                  // kMarginWords floats, behind them the reduction's partials
-  PinnedBuffer<float> h_margin;                  // two slots of kMarginWords floats
-  Event margin_ready[2];                         // the copy into slot i has finished
-  bool margin_ready_valid[2] = { false, false };
-  uint32_t margin_next = 0, margin_slot = 0;
-  bool margins_pending = false;
-  // ptamd_scene_update_lights: the new table goes through two pinned slots used in turn, allocated at the first such update
-  PinnedBuffer<ptamd_light> h_lights[2];
-  Event lights_staged[2];                        // the copy out of h_lights[i] has finished
-  bool lights_staged_valid[2] = { false, false };
-  uint32_t lights_next = 0;
-  // ptamd_scene_quality
-  double quality_built = 0.0;                    // the cost of the tree as uploaded (tree_quality)
-  DeviceBuffer<double> d_quality;                // quality_groups(n_nodes) + 1 partial sums, allocated at the first query
+  ReadBack<float> margins;                       // kMarginWords floats a slot
+  ReadBack<uint32_t> cull_count;                 // ptamd_scene_relink: the pairs it culled, one word a slot, on their way to tree.n_culled
+  Upload<ptamd_light> lights_up;                 // ptamd_scene_update_lights: the new table's way to `lights`
 };
 
 struct DeviceCubemap {
@@ -206,7 +194,6 @@ namespace ptamd {
 constexpr size_t kLdsBudget = 64 * 1024;
 constexpr uint32_t kCompactMaxNodes = 896;   // 896 * 32 B = 28 KB of boxes below 0x8000 with 4 KB to spare for static LDS
 constexpr uint32_t kCompactMaxTris = 2047;   // a leaf's link code holds count << 11 | first triangle record in 15 bits (stage_scene)
-constexpr float kBoxMargin = 1e-3f; // absolute box inflation, DESIGN.md "Conservative boxes"
 constexpr uint32_t kTicketRing = 1024;
 constexpr uint32_t kMaxFramesPerSlab = 4;   // a batched launch parks at most this many frames at a time: longer batches are issued as consecutive launches of <= 4 frames (the same bits by the contract of frame_count), so a stream's slab bytes do not depend on frame_count
 
@@ -230,8 +217,12 @@ bool stream_is_capturing(hipStream_t stream);
 
 // ---- ptamd_scene.cpp
 bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam);
-int settle_margins(DeviceScene& s, hipStream_t stream, const char* who);
 void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p);
+bool tree_is_compact(const Bvh& bvh);
+int install_tree(const ptamd_context* ctx, const Bvh& bvh, uint32_t n_faces, SceneTree& t);
+
+// ---- ptamd_scene_update.cpp
+int settle_margins(DeviceScene& s, hipStream_t stream, const char* who);
 int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing);
 // what the update calls share (ptamd_scene_update, _update_device, _update_lights, ptamd_scene_rig_pose, _rig_skin, _rig_morph)
 int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces);
@@ -239,7 +230,6 @@ int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t
 int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream);
 int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16);
 int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r);
-int prepare_margins(DeviceScene& s);   // ... its allocations alone: the reduction's words, the pinned slots, the events
 int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream, bool keep_links = false);
 
 // ---- the sigmas of the denoiser and of the upsample (ptamd_denoise.cpp, ptamd_upsample.cpp)

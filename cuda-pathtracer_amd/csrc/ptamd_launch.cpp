@@ -139,12 +139,12 @@ int validate_launch(const ptamd_context* ctx, const ptamd_launch* l)
 uint32_t choose_wide_nodes(const ptamd_context* ctx, const DeviceScene& s, bool knobs, KParams& p)
 {
   const bool quantised_ok = knobs && s.extent <= kQuantisedMaxExtent;
-  if (quantised_ok && ctx->knobs.wide8 && s.n_nodes8 != 0) {
-    p.nodes4 = s.nodes8.get(); p.n_nodes4 = s.n_nodes8; p.wide8 = 1u;
-    return 7u * s.depth8 + 1u;   // a visit stacks all hit children but the nearest
+  if (quantised_ok && ctx->knobs.wide8 && s.tree.n_nodes8 != 0) {
+    p.nodes4 = s.tree.nodes8.get(); p.n_nodes4 = s.tree.n_nodes8; p.wide8 = 1u;
+    return 7u * s.tree.depth8 + 1u;   // a visit stacks all hit children but the nearest
   }
-  if (quantised_ok && ctx->knobs.wide4q && s.nodes4q) { p.nodes4 = s.nodes4q.get(); p.wide8 = 2u; }
-  return 3u * s.depth4 + 1u;
+  if (quantised_ok && ctx->knobs.wide4q && s.tree.nodes4q) { p.nodes4 = s.tree.nodes4q.get(); p.wide8 = 2u; }
+  return 3u * s.tree.depth4 + 1u;
 }
 
 // What the steps of a launch decided
@@ -191,9 +191,9 @@ int resolve_kernel(const ptamd_context* ctx, const ptamd_launch* l, bool stats, 
     return PTAMD_ERR_ARG;
   }
   const bool brute = pl.which == PTAMD_KERNEL_BRUTE_FORCE;
-  pl.lds = pl.launch_lds = brute ? s.info.lds_bytes_brute : s.info.lds_bytes_bvh;
+  pl.lds = pl.launch_lds = brute ? s.n_faces * 48u : s.tree.lds_bytes();
   // the LDS copy of a BVH addresses its boxes with 15 bits (pt_kernels.hip: stage_scene): 32 bytes per node, nodes first
-  pl.resident = pl.lds <= kLdsBudget && (brute || (s.n_nodes <= kCompactMaxNodes && s.n_bvh_tris <= kCompactMaxTris));
+  pl.resident = pl.lds <= kLdsBudget && (brute || (s.tree.n_nodes <= kCompactMaxNodes && s.tree.n_bvh_tris <= kCompactMaxTris));
   pl.stream = static_cast<hipStream_t>(l->stream);
   return PTAMD_OK;
 }
@@ -234,7 +234,7 @@ void fill_launch(const ptamd_context* ctx, const ptamd_launch* l, bool stats, co
   // gains 2.4 % and the plain form's scenes nothing (profiles/r23_leaf_defer_ab.txt); a lane count given through PTAMD_LEAF_DEFER
   // defers in both
   const bool defer = ctx->knobs.leaf_defer != 0u && (ctx->knobs.leaf_defer != PT_LEAF_DEFER_AUTO || (p.round_form & PT_ROUND_FLAT));
-  if (s.links && pl.resident) p.round_form |= PT_ROUND_SKIP | (defer ? PT_ROUND_DEFER : 0u);
+  if (s.tree.links && pl.resident) p.round_form |= PT_ROUND_SKIP | (defer ? PT_ROUND_DEFER : 0u);
   // ... and the flat deferring form's tight copy, which holds the hand-written leaf test only: for scenes with small_det
   if (round_form_tight(p.round_form, p.small_det, ctx->knobs.tight_round)) p.round_form |= PT_ROUND_TIGHT;
 }
@@ -716,19 +716,19 @@ int ptamd_trace_rays_queue(ptamd_context* ctx, uint32_t scene_id, const float* r
   if (n == 0) return PTAMD_OK;
   PT_HIP(hipSetDevice(ctx->device));
   const DeviceScene& s = ctx->scenes[scene_id];
-  if (s.n_nodes4 == 0) { set_error("ptamd_trace_rays_queue: the scene has no wide tree"); return PTAMD_ERR_ARG; }
+  if (s.tree.n_nodes4 == 0) { set_error("ptamd_trace_rays_queue: the scene has no wide tree"); return PTAMD_ERR_ARG; }
   hipStream_t st = static_cast<hipStream_t>(stream);
   KParams p;
   std::memset(&p, 0, sizeof p);
-  p.nodes4 = s.nodes4.get(); p.n_nodes4 = s.n_nodes4; p.tris_bvh = s.tris_bvh.get(); p.n_bvh_tris = s.n_bvh_tris;
+  p.nodes4 = s.tree.nodes4.get(); p.n_nodes4 = s.tree.n_nodes4; p.tris_bvh = s.tree.tris_bvh.get(); p.n_bvh_tris = s.tree.n_bvh_tris;
   p.lights = s.lights.get(); p.n_lights = s.n_lights;
   p.refill_min = refill_min < 1u ? 1u : (refill_min > 64u ? 64u : refill_min);
   p.walk_min4 = ctx->knobs.walk_min4;
   uint32_t threads, plane, bpc;
   trace_queue_shape(config, &threads, &plane, &bpc);
   const uint32_t waves = threads / 64u;
-  p.treelet_nodes = plane < s.n_nodes4 ? plane : s.n_nodes4;
-  const uint32_t need = 3u * s.depth4 + 1u;
+  p.treelet_nodes = plane < s.tree.n_nodes4 ? plane : s.tree.n_nodes4;
+  const uint32_t need = 3u * s.tree.depth4 + 1u;
   const uint32_t share = 160u * 1024u / bpc - 512u;
   const uint32_t treelet_bytes = plane * 128u;
   uint32_t fit = (share - treelet_bytes) / (waves * 512u);
@@ -757,6 +757,28 @@ int ptamd_trace_rays_queue(ptamd_context* ctx, uint32_t scene_id, const float* r
   if (e != hipSuccess) return hip_fail("ptamd_trace_rays_queue", e);
   cache.config = config; cache.lds = lds; cache.resident = resident;
   if (out_waves_per_cu) *out_waves_per_cu = (uint32_t)(resident < (int)bpc ? resident : (int)bpc) * waves;
+  return PTAMD_OK;
+}
+
+// ---- which form the context's last megakernel launch took (do_launch sets them)
+int ptamd_last_restart_form(ptamd_context* ctx, int32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_last_restart_form: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->last_restart_form;
+  return PTAMD_OK;
+}
+
+int ptamd_last_restart_deferred(ptamd_context* ctx, int32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_last_restart_deferred: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->last_restart_deferred ? 1 : 0;
+  return PTAMD_OK;
+}
+
+int ptamd_last_restart_tight(ptamd_context* ctx, int32_t* out)
+{
+  if (!ctx || !out) { set_error("ptamd_last_restart_tight: null argument"); return PTAMD_ERR_ARG; }
+  *out = ctx->last_restart_tight ? 1 : 0;
   return PTAMD_OK;
 }
 

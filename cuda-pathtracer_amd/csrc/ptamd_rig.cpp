@@ -1,6 +1,6 @@
 // ptamd_rig.cpp — the scene rig (include/ptamd.h: ptamd_scene_rig): an uploaded scene posed from one transform per group of
 // faces, skinned from one transform per bone and four weighted bones per corner, or morphed from one weight per blend-shape target
-// (and then posed or skinned), on the device, in front of the refit ptamd_scene_update_device runs (ptamd_scene.cpp:
+// (and then posed or skinned), on the device, in front of the refit ptamd_scene_update_device runs (ptamd_scene_update.cpp:
 // enqueue_device_refit).  The three updates are one sequence (rig_update) under three sets of argument checks; the kernels are
 // pt_rig.hip's.
 #include "ptamd_host.h"
@@ -14,45 +14,28 @@
 namespace ptamd {
 
 // A table of `floats` floats per record on the device (kPoseRecordFloats per group or bone, one per morph target), copied from two
-// pinned slots that are filled in turn (the host fills one while the copy out of the other may still be in flight)
+// pinned slots that are filled in turn (ptamd_owners.h: the host fills one while the copy out of the other may still be in flight)
 struct RecordTable {
   uint32_t count = 0, floats = kPoseRecordFloats;
   DeviceBuffer<float> records;
-  PinnedBuffer<float> h_records[2];
-  Event staged[2];                               // the copy out of h_records[i] has finished
-  bool staged_valid[2] = { false, false };
-  uint32_t stage_next = 0;
+  Upload<float> staging;
   size_t bytes() const { return (size_t)count * floats * sizeof(float); }
 
   int alloc(uint32_t n, uint32_t floats_each = kPoseRecordFloats)
   {
     count = n;
     floats = floats_each;
-    staged_valid[0] = staged_valid[1] = false;
+    staging = Upload<float>();   // (slots of another size, and no copy of theirs to wait for)
     PT_HIP(records.alloc(bytes()));
-    for (int k = 0; k < 2; ++k) {
-      PT_HIP(h_records[k].alloc(bytes()));
-      PT_HIP(staged[k].ensure());
-    }
+    PT_HIP(staging.ensure(bytes()));
     PT_HIP(hipMemset(records.get(), 0, bytes()));
-    return PTAMD_OK;
-  }
-
-  // fill(the pinned slot whose last copy is two calls back), once that copy has finished; *slot says which
-  template <typename Fill>
-  int stage(Fill fill, uint32_t* slot)
-  {
-    *slot = stage_next++ & 1u;
-    if (staged_valid[*slot]) PT_HIP(hipEventSynchronize(staged[*slot].get()));
-    fill(h_records[*slot].get());
     return PTAMD_OK;
   }
 
   int copy(uint32_t slot, hipStream_t stream)
   {
-    PT_HIP(hipMemcpyAsync(records.get(), h_records[slot].get(), bytes(), hipMemcpyHostToDevice, stream));
-    PT_HIP(hipEventRecord(staged[slot].get(), stream));
-    staged_valid[slot] = true;
+    PT_HIP(hipMemcpyAsync(records.get(), staging.host(slot), bytes(), hipMemcpyHostToDevice, stream));
+    PT_HIP(staging.sent(slot, stream));
     return PTAMD_OK;
   }
 };
@@ -121,12 +104,16 @@ int rig_update(const char* who, ptamd_context* ctx, ptamd_scene_rig* rig, const 
   RefitParams r;
   uint32_t weight_slot = 0, slot = 0;
   if ((rc = prepare_device_refit(who, s, r)) != PTAMD_OK) return rc;
-  if (stage_weights && (rc = weights.stage([&](float* staged) { std::memcpy(staged, u.weights, weights.bytes()); }, &weight_slot)) != PTAMD_OK) return rc;
-  const auto records_of_transforms = [&](float* staged) {
+  // each into the pinned slot whose last copy is two calls back, once that copy has finished
+  if (stage_weights) {
+    PT_HIP(weights.staging.acquire(&weight_slot));
+    std::memcpy(weights.staging.host(weight_slot), u.weights, weights.bytes());
+  }
+  if (table && !u.device_transforms) {
+    PT_HIP(table->staging.acquire(&slot));
     for (uint32_t g = 0; g < table->count; ++g)
-      ps_record(u.transforms + (size_t)g * 12u, u.normal_matrices ? u.normal_matrices + (size_t)g * 9u : nullptr, staged + (size_t)g * kPoseRecordFloats);
-  };
-  if (table && !u.device_transforms && (rc = table->stage(records_of_transforms, &slot)) != PTAMD_OK) return rc;
+      ps_record(u.transforms + (size_t)g * 12u, u.normal_matrices ? u.normal_matrices + (size_t)g * 9u : nullptr, table->staging.host(slot) + (size_t)g * kPoseRecordFloats);
+  }
   // the tables and the posed buffer are overwritten only behind the scene's readers and its previous update
   if ((rc = wait_for_readers(ctx, s, u.stream)) != PTAMD_OK) return rc;
   if (stage_weights && (rc = weights.copy(weight_slot, u.stream)) != PTAMD_OK) return rc;

@@ -162,6 +162,29 @@ inline bool margins_cover(float extent, float margin_floor, float origin_far)
   return (origin_far + extent) * (1.0f / 2097152.0f) <= margin_floor;
 }
 
+// ---- a scene's tables in their host form (scene_tables.cpp): what an upload sends to the device and the ptamd_host_scene_* mirrors return
+constexpr float kBoxMargin = 1e-3f; // absolute box inflation, DESIGN.md "Conservative boxes"
+constexpr size_t kShadeFloats = 28;   // 7 float4 per face (pt_kernels.hip: resolve_hit).  Round 4 re-measured on the atrium: a 128-byte stride (one line per record) -1.2 %, a 64-byte hot half + 64-byte cold half (one line, 17 MB instead of 30) level, -0.6 % on textured scenes (profiles/r04_notes.md)
+constexpr uint32_t kMaxLeaf = 2;   // 2 / 3 / 4 = 10902 / 10839 / 10160 Msamples/s on the headline now that a box test costs 16 VALU and a triangle test ~67 (round 3, PTAMD_BVH_MAX_LEAF sweep: every bench configuration >= leaves of three)
+int validate_scene_desc(const ptamd_scene_desc* sc);
+// The five tables a scene's geometry decides: the tree (binary nodes, leaf-major records, four-wide nodes), the storage-order
+// records and the shading records (flat scenes: the compact records behind them)
+struct SceneTables { Bvh bvh; std::vector<float> brute, shade; bool flat = false; };
+int make_scene_tables(const ptamd_scene_desc* sc, uint32_t forms, SceneTables& t);   // sc: validated (validate_scene_desc)
+// The surface-area-heuristic cost of a binary tree over the planes the walk tests (ptamd.h: ptamd_scene_quality), terms in node order
+double tree_quality(const float* nodes, uint32_t n_nodes, uint32_t n_faces);
+// What the calls that return a table share: *bytes is the room behind `out` on entry and the table's size on exit; a null `out`
+// only asks for the size; a buffer smaller than the table is refused in `who`'s name; else copy() moves the `size` bytes
+template <typename Copy>
+int sized_read(const char* who, uint64_t size, const void* out, uint64_t* bytes, Copy copy)
+{
+  const uint64_t room = *bytes;
+  *bytes = size;
+  if (!out) return PTAMD_OK;
+  if (room < size) { set_error(std::string(who) + ": the buffer is smaller than the table"); return PTAMD_ERR_ARG; }
+  return copy();
+}
+
 // ---- posing (pose.cpp): group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]); true when the sizes sum to n_faces
 bool pose_groups_cover(const uint32_t* group_sizes, uint32_t n_groups, uint32_t n_faces);
 // ---- skinning (skin.cpp): true when every one of a skin's n_faces x 12 bone indices is below n_bones

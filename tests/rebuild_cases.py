@@ -4,7 +4,7 @@ import numpy as np
 
 from helpers import make_scene
 
-MAX_LEAF = 2   # the leaf size every upload asks for (csrc/ptamd_scene.cpp: kMaxLeaf)
+MAX_LEAF = 2   # the leaf size every upload asks for (host/ptamd_internal.h: kMaxLeaf)
 LIGHTS = [((0.3, 0.4, 3.0), (1.0, 0.95, 0.9), 6.0, 0.5)]
 
 

@@ -1,5 +1,6 @@
 // rebuild_host.cpp — stand-alone harness of the host half of ptamd_scene_rebuild: csrc/pt_build.h, host/bvh_builder.cpp's
-// build_bvh_binned, bvh_topology_of_build_nodes and refit_bvh.  Test infrastructure: built by tests/test_rebuild_cpu.py with
+// build_bvh_binned, bvh_topology_of_build_nodes and refit_bvh, and the mirrors of host/scene_tables.cpp (run_mirrors: every table's
+// size against its closed form, a refit to the same faces, the refusals).  Test infrastructure: built by tests/test_rebuild_cpu.py with
 // g++ -fsanitize=address,undefined -ffp-contract=off over the host sources and run there; no device, no HIP.
 //
 // The shapes of tests/rebuild_cases.py, generated again here.  For each: the binned build, a refit to the same faces (the mirror's
@@ -207,10 +208,87 @@ void run(const char* shape, const std::vector<ptamd_face>& faces, bool expect_un
   }
 }
 
+// ---- the mirrors of host/scene_tables.cpp: ptamd_host_scene_refit, _rebuild and _quality on a scene of `faces` in `meshes`,
+// flat (one 1x1 map) or textured (a 2x2 map and a normal map: the general record with bit 30 of its material word)
+template <typename Read>
+bool read_table(Read read, uint32_t which, uint64_t want, std::vector<uint8_t>& out)
+{
+  uint64_t n = 0;
+  if (read(which, nullptr, &n) != PTAMD_OK || n != want) return false;
+  out.assign((size_t)n + 1u, 0xA5);
+  uint64_t room = n;
+  return read(which, out.data(), &room) == PTAMD_OK && room == n && out[(size_t)n] == 0xA5;
+}
+
+void run_mirrors(const char* shape, std::vector<ptamd_face> faces, std::vector<uint32_t> meshes, bool textured)
+{
+  const uint32_t n = (uint32_t)faces.size();
+  for (auto& f : faces) for (int k = 0; k < 3; ++k) f.normals[k] = { 0.f, 0.f, 1.f };
+  const ptamd_material material = { 0, textured ? 1 : -1, 1.0f, 0 };
+  const ptamd_texture_desc textures[2] = { { textured ? 2 : 1, textured ? 2 : 1, 4, 0u, 0u }, { 2, 2, 3, 0u, 16u } };
+  const std::vector<float> texels(28, 0.5f);
+  const ptamd_light light = { { 1.f, 1.f, 1.f }, { 0.f, 0.f, 2.f }, 5.f, 0.25f };
+  const ptamd_scene_desc sc = { faces.data(), n, meshes.data(), (uint32_t)meshes.size(), &material, 1u, &light, 1u, textures, textured ? 2u : 1u,
+                                texels.data(), textured ? 28u : 4u };
+  int32_t flat = -1;
+  expect(ptamd_scene_desc_is_flat(&sc, &flat) == PTAMD_OK && flat == (textured ? 0 : 1), "ptamd_scene_desc_is_flat", shape);
+  Bvh sweep, binned;
+  expect(build_bvh(faces.data(), n, kBoxMargin, kMaxLeaf, sweep, 0u, &light, 1u) == PTAMD_OK &&
+         build_bvh_binned(faces.data(), n, kBoxMargin, kMaxLeaf, binned, &light, 1u) == PTAMD_OK, "the builders", shape);
+  const uint64_t per_face[3] = { 48u, 48u, 112u + (textured ? 0u : 64u) };
+  std::vector<uint8_t> plain[6], same[6], twice[6], rebuilt[7];
+  for (uint32_t w = 0; w < 7u; ++w) {
+    const Bvh& b = w < 6u ? sweep : binned;
+    const uint64_t want = w == 0u ? b.n_nodes * 64ull : w == 2u ? b.n_nodes4 * 128ull : w == 5u ? 16u : w == 6u ? 8u : n * per_face[w == 1u ? 0u : w - 2u];
+    if (w < 6u) {
+      expect(read_table([&](uint32_t k, void* o, uint64_t* nb) { return ptamd_host_scene_refit(&sc, nullptr, nullptr, k, o, nb); }, w, want, plain[w]) &&
+             read_table([&](uint32_t k, void* o, uint64_t* nb) { return ptamd_host_scene_refit(&sc, faces.data(), nullptr, k, o, nb); }, w, want, same[w]) &&
+             read_table([&](uint32_t k, void* o, uint64_t* nb) { return ptamd_host_scene_refit(&sc, faces.data(), faces.data(), k, o, nb); }, w, want, twice[w]),
+             "ptamd_host_scene_refit: a table's size is not its closed form, or a read fails", shape);
+      expect(plain[w] == same[w] && plain[w] == twice[w], "a refit to the same faces changes a table", shape);
+    }
+    const uint64_t want_rebuilt = w == 0u ? binned.n_nodes * 64ull : w == 2u ? binned.n_nodes4 * 128ull : want;
+    for (uint32_t flags : { 0u, (uint32_t)PTAMD_REBUILD_HOST_BUILDER }) {
+      expect(read_table([&](uint32_t k, void* o, uint64_t* nb) { return ptamd_host_scene_rebuild(&sc, faces.data(), flags, k, o, nb); }, w,
+                        flags && w < 6u ? want : want_rebuilt, rebuilt[w]),
+             "ptamd_host_scene_rebuild: a table's size is not its closed form, or a read fails", shape);
+      if (flags && w < 6u) expect(rebuilt[w] == plain[w], "the rebuild with the upload's builder differs from the upload", shape);
+    }
+    // a buffer one byte short is refused and told the size; so is a table that does not exist
+    std::vector<uint8_t> small((size_t)(want > want_rebuilt ? want : want_rebuilt) + 1u);
+    uint64_t room = want - 1u;
+    if (want && w < 6u)
+      expect(ptamd_host_scene_refit(&sc, nullptr, nullptr, w, small.data(), &room) == PTAMD_ERR_ARG && room == want &&
+             g_err == "ptamd_host_scene_refit: the buffer is smaller than the table", "a short buffer is accepted (refit)", shape);
+    room = want_rebuilt - 1u;
+    if (want_rebuilt)
+      expect(ptamd_host_scene_rebuild(&sc, faces.data(), 0u, w, small.data(), &room) == PTAMD_ERR_ARG && room == want_rebuilt &&
+             g_err == "ptamd_host_scene_rebuild: the buffer is smaller than the table", "a short buffer is accepted (rebuild)", shape);
+  }
+  uint64_t nb = 0;
+  expect(ptamd_host_scene_refit(&sc, nullptr, nullptr, 6u, nullptr, &nb) == PTAMD_ERR_ARG && g_err == "ptamd_host_scene_refit: bad argument", "which = 6 (refit)", shape);
+  expect(ptamd_host_scene_rebuild(&sc, faces.data(), 0u, 7u, nullptr, &nb) == PTAMD_ERR_ARG && g_err == "ptamd_host_scene_rebuild: bad argument", "which = 7 (rebuild)", shape);
+  // the records: a flat face carries its texel (sign bit of the material word), a normal-mapped one flags its 7th float4 (bit 30)
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t word;
+    std::memcpy(&word, plain[4].data() + (size_t)i * 112u + 72u, 4);
+    expect(word == (textured ? 0x40000000u : 0x80000000u), "the material word of a shading record", shape);
+  }
+  double built = -1.0, moved = -1.0, grouped = -1.0;
+  expect(ptamd_host_scene_quality(&sc, nullptr, &built) == PTAMD_OK && ptamd_host_scene_quality(&sc, faces.data(), &moved) == PTAMD_OK &&
+         built == moved && (n ? built > 0.0 : built == 0.0), "ptamd_host_scene_quality", shape);
+  std::memcpy(&grouped, rebuilt[6].data(), 8);
+  expect(n ? grouped > 0.0 : grouped == 0.0, "the rebuild mirror's quality", shape);
+}
+
 } // namespace
 
 int main()
 {
+  run_mirrors("mirrors_0_faces", {}, {}, false);
+  run_mirrors("mirrors_1_face", grid(1, 3), { 1u }, false);
+  run_mirrors("mirrors_12_flat", grid(12, 4), { 5u, 7u }, false);
+  run_mirrors("mirrors_12_textured", grid(12, 4), { 5u, 7u }, true);
   const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
   for (uint32_t n : { 1u, 2u, 3u, T, T + 1u, 2u * T + 1u }) run(("grid" + std::to_string(n)).c_str(), grid(n, 5), false);
   {

@@ -181,10 +181,11 @@ def test_mirror_refusals(P, indoor):
 
 def test_the_builder_and_the_mirror_under_sanitizers(tmp_path):
     """tests/san/rebuild_host.cpp: pt_build.h, the binned builder, the tree made of build nodes and ptamd_host_scene_rebuild's steps
-    over the shapes above, built with ASan + UBSan as a program of its own and run once."""
+    over the shapes above; host/scene_tables.cpp's mirrors (ptamd_host_scene_refit, _rebuild, _quality) on 0 faces, 1 face and a
+    12-face scene of two meshes, flat and textured.  Built with ASan + UBSan as a program of its own and run once."""
     exe = str(tmp_path / "rebuild_host")
     pkg = os.path.join(ROOT, "cuda-pathtracer_amd")
-    srcs = [os.path.join(ROOT, "tests", "san", "rebuild_host.cpp")] + [os.path.join(pkg, "host", f) for f in ("bvh_builder.cpp", "bvh_walks.cpp", "skip_links.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "san", "rebuild_host.cpp")] + [os.path.join(pkg, "host", f) for f in ("bvh_builder.cpp", "bvh_walks.cpp", "skip_links.cpp", "scene_tables.cpp")]
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "host"),
                     "-o", exe] + srcs + ["-lpthread"], check=True)

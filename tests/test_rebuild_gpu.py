@@ -169,6 +169,45 @@ def test_a_compact_scene_is_rebuilt_as_a_fresh_upload_builds_it(P, O, indoor):
         assert ctx.device_error_count() == 0 and other.device_error_count() == 0
 
 
+def test_a_host_update_after_the_rebuild_finds_the_new_trees_host_copies(P, indoor):
+    """The handover from a rebuild to ptamd_scene_update, which culls again from the tree's HOST copies (topology, the face of every
+    record, the skip set, the pinned link words) and falls back on links_plain and the set's bytes on the device: upload(a),
+    rebuild(b), update(c) leaves what upload(b), update(c) leaves, table by table, and a relink of both too."""
+    cube = P.cubemap_for_scene(indoor)
+    b = P.deform(indoor, 0.6, 0.25, shading=True)
+    c = P.deform(indoor, 1.9, 0.05, shading=True)
+    assert P.host_relink_words(b)[1] > 0     # b culls at least one pair: the upload of b and the rebuild keep host copies
+    cam, size = c.camera_struct(), (64, 64)
+
+    def state(ctx, sid):
+        return (ctx.read_scene_tables(sid), ctx.scene_links(sid), ctx.scene_cull_count(sid), ctx.scene_skip_count(sid), ctx.scene_margins(sid),
+                ctx.scene_info(sid))
+
+    def assert_same_state(got, want, what):
+        assert_tables(got[0], want[0], what)
+        np.testing.assert_array_equal(got[1], want[1], err_msg=what + ": links")
+        assert got[2] == want[2] and got[3] == want[3], (what, got[2:4], want[2:4])
+        same_bits(got[4], want[4], what + ": margins")
+        assert got[5] == want[5], (what, got[5], want[5])
+
+    with P.Context(0) as ctx, P.Context(0) as other:
+        sid, cid = ctx.upload_scene(indoor), ctx.upload_cubemap(cube)
+        assert ctx.rebuild_scene_device(sid, device_faces(b))["device_builder"] == 0
+        ctx.update_scene(sid, c)
+        fresh, fresh_cid = other.upload_scene(b), other.upload_cubemap(cube)
+        assert other.scene_cull_count(fresh) > 0
+        other.update_scene(fresh, c)
+        got, want = state(ctx, sid), state(other, fresh)
+        assert got[1].size > 0
+        assert_same_state(got, want, "rebuild(b) + update(c) vs upload(b) + update(c)")
+        assert_same(*render(P, ctx, (sid, cid), cam, P.KERNEL_BVH_RESTART, size=size),
+                    *render(P, other, (fresh, fresh_cid), cam, P.KERNEL_BVH_RESTART, size=size), "restart kernel after the handover")
+        ctx.relink_scene(sid)
+        other.relink_scene(fresh)
+        assert_same_state(state(ctx, sid), state(other, fresh), "after a relink of both")
+        assert ctx.device_error_count() == 0 and other.device_error_count() == 0
+
+
 # ---------------------------------------------------------------- 5. ordering
 
 @pytest.mark.parametrize("share", [0, 2])
