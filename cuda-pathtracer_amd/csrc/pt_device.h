@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "pt_round.h"
+#include "pt_tight_tiles.h"
 
 namespace ptamd {
 
@@ -601,7 +602,9 @@ inline RestartForm restart_select(bool lds_resident, bool stats, bool list, bool
   if (!lds_resident && p && p->wide8) return { full(p->wide8 == 2u ? PT_RS_WIDE4Q : PT_RS_WIDE8), false };   // the knobs' quantised node forms
   if (!lds_resident) return { PT_RS_PLAIN, false };                            // the four-wide walk from L2
   if (p && !restart_shipped_launch(*p)) return { PT_RS_GENERIC, true };        // a resident scene in a launch the lean forms are not compiled for
-  if (defers && (p->round_form & PT_ROUND_FLAT) && (p->round_form & PT_ROUND_TIGHT)) return { PT_RS_FLAT_SKIP_TIGHT, true };   // the flat deferring form's tight copy
+  // the flat deferring form's tight copy, whose body parks a sample at a 32-bit byte offset (pt_tight_tiles.h): a launch whose slab does
+  // not fit in one stays in the form it copies, the next rule
+  if (defers && (p->round_form & PT_ROUND_FLAT) && (p->round_form & PT_ROUND_TIGHT) && tight_slab_fits(p->sample_count, p->row_end - p->row_begin, p->width)) return { PT_RS_FLAT_SKIP_TIGHT, true };
   if (defers) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP_DEFER : PT_RS_PLAIN_SKIP_DEFER, true };   // the skip forms with deferred leaf phases
   if (p && (p->round_form & PT_ROUND_SKIP) && !contracted) return { (p->round_form & PT_ROUND_FLAT) ? PT_RS_FLAT_SKIP : PT_RS_PLAIN_SKIP, true };   // the same two launches of a scene with a skip set
   if (p && (p->round_form & PT_ROUND_FLAT)) return { full(PT_RS_FLAT), true };   // a flat scene under a one-colour environment

@@ -2341,6 +2341,11 @@ pt_megakernel_restart(PT_KERNEL_PARAMS)
   flush_counters<STATS>(p, cnt, samples);
 }
 
+#ifdef PT_TIGHT_BUILD
+// the tight form's kernel body is its own, an explicit specialisation: the template's body above serves every other form
+#include "pt_tight_body.h"
+#endif
+
 // ---------------------------------------------------------------- the megakernel, blockwise form
 
 // Persistent WORKGROUPS with per-bounce ray compaction, octant sort and dynamic ray fetch.

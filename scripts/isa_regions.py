@@ -6,7 +6,10 @@ scheduling barriers, so the listing differs slightly from the shipped code).   p
 VARIANT=6 counts the generic instantiation of a resident scene (PT_RS_GENERIC) instead of the shipped one (0), VARIANT=8 the flat
 one (PT_RS_FLAT: flat scenes under a uniform environment), VARIANT=9 / 10 the skip forms of the flat and the shipped one
 (PT_RS_FLAT_SKIP, PT_RS_PLAIN_SKIP), VARIANT=11 the flat deferring form (PT_RS_FLAT_SKIP_DEFER) and VARIANT=14 its tight copy
-(PT_RS_FLAT_SKIP_TIGHT), which is compiled in a unit of its own, pt_kernels_tight.hip: its counts come from that unit's listing."""
+(PT_RS_FLAT_SKIP_TIGHT), which is compiled in a unit of its own, pt_kernels_tight.hip: its counts come from that unit's listing.
+The tight form's kernel body is its own (pt_tight_body.h, an explicit specialisation): its regions carry the same names, from
+anchors in that header (TIGHT_MARKS), and one more, restart_begin, which parts the restart step and the refill from the staging
+in front of them; path_post's regions are the shared function's."""
 import os, re, sys, collections
 from kernel_listing import CSRC, listing
 SRC = os.path.join(CSRC, "pt_kernels.hip")
@@ -24,18 +27,34 @@ MARKS = [  # (unique source anchor, marker name) — the marker goes in front of
 
 TIGHT_UNIT = "pt_kernels_tight.hip"   # compiles pt_kernels.hip once more, for the tight forms alone
 TIGHT_VARIANTS = ("14",)
+TIGHT_BODY = "pt_tight_body.h"        # the tight form's own kernel body, included by pt_kernels.hip in that unit only
+TIGHT_MARKS = [
+    ("    unsigned long long need = __ballot(st.xy == PT_TIGHT_IDLE);\n    while (need) {", "restart_begin"),
+    ("    if (st.xy != PT_TIGHT_IDLE) {\n      if (node == 0xFFFFu) {", "round_begin"),
+    ("      traverse_round_tight(s_nodes, s_tris, reinterpret_cast<const uint32_t*>(s_mem)", "traverse_begin"),
+    ("      if (node == 0xFFFFu) {\n        // the iteration's first variate", "traverse_end"),
+    ("        if (path_post<false, true, true>(p, st, r1, n, cnt)) {", "lights_end"),
+    ("          tight_park(p, st.xy, st.acc);\n          st.xy = PT_TIGHT_IDLE;", "post_end"),
+]
+
+
+def mark(s, marks):
+    for anchor, name in marks:
+        assert s.count(anchor) == 1, (name, s.count(anchor))
+        s = s.replace(anchor, 'asm volatile("; PT_MARK %s" ::: "memory");\n' % name + anchor)
+    return s
 
 
 def marked_listing(tight=False):
     """The ISA listing (lines) of pt_kernels.hip compiled with a marker in front of every anchor of MARKS.  tight: of
     pt_kernels_tight.hip, the same marked text behind that unit's own lines."""
-    s = open(SRC).read()
-    for anchor, name in MARKS:
-        assert s.count(anchor) == 1, (name, s.count(anchor))
-        s = s.replace(anchor, 'asm volatile("; PT_MARK %s" ::: "memory");\n' % name + anchor)
+    s = mark(open(SRC).read(), MARKS)
     if not tight:
         return listing("pt_kernels.hip", s).split("\n")
     unit = open(os.path.join(CSRC, TIGHT_UNIT)).read()
+    body = '#include "%s"\n' % TIGHT_BODY
+    assert s.count(body) == 1
+    s = s.replace(body, mark(open(os.path.join(CSRC, TIGHT_BODY)).read(), TIGHT_MARKS))
     include = '#include "pt_kernels.hip"\n'
     assert unit.count(include) == 1
     return listing(TIGHT_UNIT, unit.replace(include, s)).split("\n")
