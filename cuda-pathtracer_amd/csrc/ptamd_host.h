@@ -183,6 +183,10 @@ struct ptamd_context {
   // must not resize each other.  Grown at the first call that needs more
   ptamd::DeviceBuffer<float4> d_upsample;
   size_t upsample_bytes = 0;
+  // rebuild workspace (ptamd_scene_rebuild): the per-call buffers of the device builder and of the finishing step in one allocation
+  // (ptamd_scene_update.cpp: rebuild_workspace), made at the first rebuild and grown by a rebuild that needs more
+  ptamd::DeviceBuffer<uint8_t> d_rebuild;
+  size_t rebuild_bytes = 0;
 };
 
 static_assert(!std::is_copy_constructible<ptamd::DeviceScene>::value && !std::is_copy_constructible<ptamd::DeviceCubemap>::value &&
@@ -219,6 +223,7 @@ bool stream_is_capturing(hipStream_t stream);
 bool far_origin_camera(const DeviceScene& s, const ptamd_camera& cam);
 void fill_scene(const DeviceScene& s, const DeviceCubemap* cm, KParams& p);
 bool tree_is_compact(const Bvh& bvh);
+bool tree_is_compact(uint32_t n_nodes, uint32_t n_tris, uint32_t max_leaf);   // the same rule over the counts alone
 int install_tree(const ptamd_context* ctx, const Bvh& bvh, uint32_t n_faces, SceneTree& t);
 
 // ---- ptamd_scene_update.cpp

@@ -65,6 +65,12 @@ bool tree_is_compact(const Bvh& bvh)
   return bvh.n_nodes * 64u + bvh.n_tris * 48u <= kLdsBudget && bvh.n_nodes <= kCompactMaxNodes && bvh.n_tris <= kCompactMaxTris && skip_links_fit(bvh);
 }
 
+// ... from the counts of a tree that is still on the device (skip_links_fit's bounds on nodes and records are the two above)
+bool tree_is_compact(uint32_t n_nodes, uint32_t n_tris, uint32_t max_leaf)
+{
+  return (uint64_t)n_nodes * 64u + (uint64_t)n_tris * 48u <= kLdsBudget && n_nodes <= kCompactMaxNodes && n_tris <= kCompactMaxTris && max_leaf <= 15u;
+}
+
 // The one step that turns a tree into a SceneTree, for ptamd_upload_scene and ptamd_scene_rebuild alike: the node table with the
 // link table behind it, the four-wide nodes (and the knob-only quantised forms), the leaf-major records, what a refit needs (raw
 // boxes, schedule, wide_child), the counts, the skip and cull members, the tree's part of ptamd_scene_info and quality_built.
@@ -206,6 +212,20 @@ int ptamd_scene_table_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which
   const uint64_t size[5] = { (uint64_t)t.n_nodes * 64u, (uint64_t)t.n_bvh_tris * 48u, (uint64_t)t.n_nodes4 * 128u, (uint64_t)s.n_faces * 48u,
                              (uint64_t)s.n_faces * (kShadeFloats * 4u + (s.flat ? 64u : 0u)) };
   return read_device_table("ptamd_scene_table_read", ctx, src[which], size[which], out, bytes);
+}
+
+int ptamd_scene_plan_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which, void* out, uint64_t* bytes)
+{
+  if (!ctx || !bytes || which > 4u) { set_error("ptamd_scene_plan_read: bad argument"); return PTAMD_ERR_ARG; }
+  if (!live_scene(ctx, scene_id)) { set_error("ptamd_scene_plan_read: scene_id out of range or released"); return PTAMD_ERR_ARG; }
+  const SceneTree& t = ctx->scenes[scene_id].tree;
+  if (which == 4u) {
+    const uint32_t words[9] = { t.n_nodes, t.n_bvh_tris, t.n_leaves, t.max_leaf, t.depth, t.n_nodes4, t.depth4, t.refit_top_first, t.refit_top_levels };
+    return sized_read("ptamd_scene_plan_read", sizeof words, out, bytes, [&] { std::memcpy(out, words, sizeof words); return (int)PTAMD_OK; });
+  }
+  const void* src[4] = { t.refit_groups.get(), t.refit_levels.get(), t.refit_sched.get(), t.wide_child.get() };
+  const uint64_t size[4] = { (uint64_t)t.n_refit_groups * 16u, (uint64_t)t.n_refit_levels * 4u, (uint64_t)t.n_refit_sched * 4u, (uint64_t)t.n_nodes4 * 16u };
+  return read_device_table("ptamd_scene_plan_read", ctx, src[which], t.refit_ok ? size[which] : 0u, out, bytes);
 }
 
 int ptamd_upload_cubemap(ptamd_context* ctx, const float* faces, uint32_t size, uint32_t* out_cubemap_id)

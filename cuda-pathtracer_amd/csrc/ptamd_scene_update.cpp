@@ -5,6 +5,7 @@
 #include "pt_refit_device.h"
 #include "pt_relink.h"
 #include "pt_build.h"
+#include "pt_finish.h"
 
 #include <cstring>
 
@@ -217,36 +218,120 @@ static int device_quality(DeviceScene& s, hipStream_t st, double* now)
   return PTAMD_OK;
 }
 
-// The device builder (pt_build.hip) over `faces`, and the topology tables of its tree.  handled = false: a node above the subtrees
-// needs one of partition's fallbacks, and the caller builds the same tree on the host.  Everything allocated here is freed on return.
-static int device_build_tree(const float* faces, uint32_t n, hipStream_t stream, Bvh& bvh, bool& handled)
+// The workspace of ptamd_scene_rebuild, the context's: the per-call buffers of the builder (pt_build.hip) and, when asked for, of the
+// finishing step (pt_finish.hip) carved out of one allocation that is sized at the first rebuild, kept, and grown only by a
+// rebuild that needs more.  The call blocks, so one workspace serves every scene of the context in turn.
+static int rebuild_workspace(ptamd_context* ctx, uint32_t n, bool finish, BuildParams& p, FinishParams& f)
+{
+  std::memset(&p, 0, sizeof p);
+  std::memset(&f, 0, sizeof f);
+  p.n_faces = n; p.max_open = build_max_open(n); p.max_leaf = kMaxLeaf;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+  const size_t prims0 = take((size_t)n * 40u), prims1 = take((size_t)n * 40u), owner = take((size_t)n * 4u), tag = take((size_t)n * 4u),
+               large = take((size_t)n * 16u), slots = take((size_t)p.max_open * kBdSlotWords * 4u), open = take((size_t)p.max_open * 8u),
+               roots = take((size_t)n * 8u), order = take((size_t)n * 4u), ctl = take(kBdCtlWords * 4u),
+               nodes = take((size_t)n * 3u * sizeof(BdNode)), fin = at;
+  const FinishLayout l = finish_layout(n);
+  const size_t bytes = fin + (finish ? l.bytes : 0u);
+  if (!ctx->d_rebuild || ctx->rebuild_bytes < bytes) {
+    ctx->rebuild_bytes = 0;
+    PT_HIP(ctx->d_rebuild.alloc(bytes));
+    ctx->rebuild_bytes = bytes;
+  }
+  uint8_t* base = ctx->d_rebuild.get();
+  auto words = [&](size_t offset) { return reinterpret_cast<uint32_t*>(base + offset); };
+  p.prims[0] = words(prims0); p.prims[1] = words(prims1); p.owner = words(owner); p.tag = words(tag); p.large = words(large);
+  p.slots = words(slots); p.open = words(open); p.roots = words(roots); p.order = words(order); p.ctl = words(ctl);
+  p.nodes = reinterpret_cast<BdNode*>(base + nodes);
+  if (!finish) return PTAMD_OK;
+  f.nodes = p.nodes; f.order = p.order; f.n_faces = n; f.max_leaf = kMaxLeaf;
+  f.bfs = words(fin + l.bfs); f.seen = words(fin + l.seen); f.up = reinterpret_cast<FinUp*>(base + fin + l.up);
+  f.down = reinterpret_cast<FinDown*>(base + fin + l.down); f.ctl = words(fin + l.ctl); f.height_at = words(fin + l.height_at);
+  f.group_sched = words(fin + l.group_sched); f.top_list = words(fin + l.top_list); f.top_count = words(fin + l.top_count);
+  f.wide_root = words(fin + l.wide_root); f.wide_kids = words(fin + l.wide_kids); f.wide_count = words(fin + l.wide_count);
+  f.wide_block = words(fin + l.wide_block); f.refs4 = words(fin + l.refs4); f.wide_child4 = words(fin + l.wide_child4);
+  f.wide_room = n;
+  return PTAMD_OK;
+}
+
+// The device builder (pt_build.hip) over `faces`, into the workspace.  handled = false: a node above the subtrees needs one of
+// partition's fallbacks, and the caller builds the same tree on the host.
+static int device_build(const BuildParams& p, const float* faces, hipStream_t stream, uint32_t& n_large, bool& handled)
 {
   handled = false;
-  DeviceBuffer<uint32_t> prims[2], owner, tag, large, slots, open, roots, order, ctl;
-  DeviceBuffer<BdNode> nodes;
-  BuildParams p;
-  std::memset(&p, 0, sizeof p);
-  p.n_faces = n; p.max_open = build_max_open(n); p.max_leaf = kMaxLeaf;
-  const struct { DeviceBuffer<uint32_t>& buffer; size_t bytes; } words[] = {
-    { prims[0], (size_t)n * 40u }, { prims[1], (size_t)n * 40u }, { owner, (size_t)n * 4u }, { tag, (size_t)n * 4u }, { large, (size_t)n * 16u },
-    { slots, (size_t)p.max_open * kBdSlotWords * 4u }, { open, (size_t)p.max_open * 8u }, { roots, (size_t)n * 8u }, { order, (size_t)n * 4u },
-    { ctl, kBdCtlWords * 4u } };
-  for (const auto& w : words) PT_HIP(w.buffer.alloc(w.bytes));
-  PT_HIP(nodes.alloc((size_t)n * 3u * sizeof(BdNode)));
-  p.faces = faces;
-  p.prims[0] = prims[0].get(); p.prims[1] = prims[1].get();
-  p.owner = owner.get(); p.tag = tag.get(); p.large = large.get(); p.slots = slots.get(); p.open = open.get(); p.roots = roots.get();
-  p.order = order.get(); p.ctl = ctl.get(); p.nodes = nodes.get();
-  uint32_t n_large = 0, unhandled = 0;
-  PT_HIP(run_device_build(p, stream, &n_large, &unhandled));
+  BuildParams q = p;
+  q.faces = faces;
+  uint32_t unhandled = 0;
+  n_large = 0;
+  PT_HIP(run_device_build(q, stream, &n_large, &unhandled));
   if (unhandled) return PTAMD_OK;
-  if (n_large > n) { set_error("ptamd_scene_rebuild: the device builder left an inconsistent tree (its node count)"); return PTAMD_ERR_HIP; }
+  if (n_large > p.n_faces) { set_error("ptamd_scene_rebuild: the device builder left an inconsistent tree (its node count)"); return PTAMD_ERR_HIP; }
+  handled = true;
+  return PTAMD_OK;
+}
+
+// ... and the topology tables of its tree by the upload's host steps, from a copy of the build nodes and the face order
+static int host_finish_tree(const BuildParams& p, uint32_t n_large, Bvh& bvh)
+{
+  const uint32_t n = p.n_faces;
   std::vector<BdNode> h((size_t)2u * n + n_large);
   std::vector<uint32_t> face_at(n);
-  PT_HIP(hipMemcpy(h.data(), nodes.get(), h.size() * sizeof(BdNode), hipMemcpyDeviceToHost));
-  PT_HIP(hipMemcpy(face_at.data(), order.get(), (size_t)n * 4u, hipMemcpyDeviceToHost));
-  handled = true;
+  PT_HIP(hipMemcpy(h.data(), p.nodes, h.size() * sizeof(BdNode), hipMemcpyDeviceToHost));
+  PT_HIP(hipMemcpy(face_at.data(), p.order, (size_t)n * 4u, hipMemcpyDeviceToHost));
   return bvh_topology_of_build_nodes(h.data(), h.size(), n > kBuildGroupPrims ? 2u * n : 0u, face_at.data(), n, kBoxMargin, kMaxLeaf, bvh);
+}
+
+// install_tree's sibling for a tree that never leaves the device (PTAMD_REBUILD_DEVICE_FINISH): numbering, links, leaf records,
+// refit plan and four-wide references by pt_finish.hip's kernels, straight into the tables of `t` (a fresh one).  Sets what
+// install_tree sets for a tree that is not compact: the counts, refit_ok, the plan's sizes, no link table; quality_built is the
+// caller's device_quality once the refit has formed the planes.  done = false with PTAMD_OK: the tree takes the compact LDS
+// layout (tree_is_compact's rule over the counts read back) and is the host's to build; nothing of `t` is to be used then.
+static int device_finish_tree(FinishParams& f, uint32_t n_large, hipStream_t stream, SceneTree& t, bool& done)
+{
+  done = false;
+  const uint32_t n = f.n_faces;
+  f.n_slots = 2u * n + n_large;
+  f.root = n > kBuildGroupPrims ? 2u * n : 0u;
+  auto bad = [](uint32_t word) {
+    set_error("ptamd_scene_rebuild: the device builder left an inconsistent tree (check word " + std::to_string(word) + ")");
+    return PTAMD_ERR_HIP;
+  };
+  FinishCounts c;
+  std::vector<uint32_t> level_first;
+  uint32_t error = 0;
+  PT_HIP(finish_measure(f, stream, &c, &level_first, &error));
+  if (error) return bad(error);
+  if (tree_is_compact(c.n_nodes, n, c.max_leaf)) return PTAMD_OK;
+  auto room = [](size_t bytes) { return bytes ? bytes : (size_t)16; };
+  const uint32_t n_sched = c.n_leaves - 1u, levels_room = c.n_group_levels + c.n_top;
+  const size_t tri_bytes = (size_t)n * 48u + 128u;   // (the pad of install_tree's upload: the merged wide walk reads past a leaf's first record)
+  PT_HIP(t.nodes.alloc(room((size_t)c.n_nodes * 64u)));
+  PT_HIP(t.tris_bvh.alloc(tri_bytes));
+  PT_HIP(t.raw.alloc(room((size_t)c.n_nodes * 32u)));
+  PT_HIP(t.refit_groups.alloc(room((size_t)c.n_groups * 16u)));
+  PT_HIP(t.refit_levels.alloc(room((size_t)levels_room * 4u)));
+  PT_HIP(t.refit_sched.alloc(room((size_t)n_sched * 4u)));
+  PT_HIP(hipMemsetAsync(t.tris_bvh.get(), 0, tri_bytes, stream));
+  PT_HIP(hipMemsetAsync(t.raw.get(), 0, room((size_t)c.n_nodes * 32u), stream));
+  f.out_nodes = reinterpret_cast<uint32_t*>(t.nodes.get()); f.out_tris = reinterpret_cast<uint32_t*>(t.tris_bvh.get());
+  f.out_groups = t.refit_groups.get(); f.out_levels = t.refit_levels.get(); f.out_sched = t.refit_sched.get();
+  f.n_nodes = c.n_nodes; f.n_groups = c.n_groups; f.n_top = c.n_top; f.sched_room = n_sched; f.levels_room = levels_room;
+  uint32_t n_nodes4 = 0, depth4 = 0, top_levels = 0;
+  PT_HIP(finish_write(f, c, level_first, stream, &n_nodes4, &depth4, &top_levels, &error));
+  if (error) return bad(error);
+  PT_HIP(t.nodes4.alloc(room((size_t)n_nodes4 * 128u)));
+  PT_HIP(t.wide_child.alloc(room((size_t)n_nodes4 * 16u)));
+  PT_HIP(hipMemsetAsync(t.nodes4.get(), 0, room((size_t)n_nodes4 * 128u), stream));
+  PT_HIP(finish_scatter_refs(f.refs4, n_nodes4, reinterpret_cast<uint32_t*>(t.nodes4.get()), stream));
+  PT_HIP(hipMemcpyAsync(t.wide_child.get(), f.wide_child4, (size_t)n_nodes4 * 16u, hipMemcpyDeviceToDevice, stream));
+  t.n_nodes = c.n_nodes; t.n_bvh_tris = n; t.n_leaves = c.n_leaves; t.max_leaf = c.max_leaf; t.depth = c.depth;
+  t.n_nodes4 = n_nodes4; t.depth4 = depth4;
+  t.refit_ok = true;
+  t.n_refit_groups = c.n_groups; t.n_refit_levels = c.n_group_levels + top_levels; t.n_refit_sched = n_sched;
+  t.refit_top_first = c.n_group_levels; t.refit_top_levels = top_levels;
+  done = true;
+  return PTAMD_OK;
 }
 
 } // namespace ptamd
@@ -398,7 +483,11 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, p
 {
   const char* who = "ptamd_scene_rebuild";
   if (!ctx || !d) { set_error("ptamd_scene_rebuild: null argument"); return PTAMD_ERR_ARG; }
-  if (d->flags & ~(uint32_t)PTAMD_REBUILD_HOST_BUILDER) { set_error("ptamd_scene_rebuild: unknown flag bits"); return PTAMD_ERR_ARG; }
+  if (d->flags & ~(uint32_t)(PTAMD_REBUILD_HOST_BUILDER | PTAMD_REBUILD_DEVICE_FINISH)) { set_error("ptamd_scene_rebuild: unknown flag bits"); return PTAMD_ERR_ARG; }
+  if ((d->flags & PTAMD_REBUILD_HOST_BUILDER) && (d->flags & PTAMD_REBUILD_DEVICE_FINISH)) {
+    set_error("ptamd_scene_rebuild: PTAMD_REBUILD_DEVICE_FINISH finishes a tree the device built: not with PTAMD_REBUILD_HOST_BUILDER");
+    return PTAMD_ERR_ARG;
+  }
   int rc = update_scene_checks(who, ctx, d->scene_id, d->n_faces, d->faces);
   hipStream_t stream = static_cast<hipStream_t>(d->stream);
   if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
@@ -426,22 +515,32 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, p
   const ptamd_light* lights = s.host_lights.data();
   const uint32_t n_lights = (uint32_t)s.host_lights.size();
   Bvh bvh;
-  bool host_builder = (d->flags & PTAMD_REBUILD_HOST_BUILDER) != 0u, device_built = false;
+  bool host_builder = (d->flags & PTAMD_REBUILD_HOST_BUILDER) != 0u, device_built = false, device_finished = false;
+  const bool finish = (d->flags & PTAMD_REBUILD_DEVICE_FINISH) != 0u;
+  // the new tables beside the old ones; nothing of the scene changes before the move below
+  SceneTree fresh;
   if (!host_builder) {
-    if ((rc = device_build_tree(faces, n, stream, bvh, device_built)) != PTAMD_OK) return rc;
-    if (!device_built && ((rc = fetch_faces()) != PTAMD_OK ||
-                          (rc = build_bvh_binned(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, lights, n_lights)) != PTAMD_OK))
-      return rc;
-    // a tree that takes the compact LDS layout: the skip set is chosen with rays over the tree's geometry, on the host
-    if (tree_is_compact(bvh)) { host_builder = true; device_built = false; }
+    BuildParams p;
+    FinishParams f;
+    uint32_t n_large = 0;
+    if ((rc = rebuild_workspace(ctx, n, finish, p, f)) != PTAMD_OK || (rc = device_build(p, faces, stream, n_large, device_built)) != PTAMD_OK) return rc;
+    // PTAMD_REBUILD_DEVICE_FINISH: the tree stays where it was built, unless it turns out compact
+    if (device_built && finish && (rc = device_finish_tree(f, n_large, stream, fresh, device_finished)) != PTAMD_OK) return rc;
+    if (!device_finished) {
+      fresh = SceneTree();
+      if (device_built && (rc = host_finish_tree(p, n_large, bvh)) != PTAMD_OK) return rc;
+      if (!device_built && ((rc = fetch_faces()) != PTAMD_OK ||
+                            (rc = build_bvh_binned(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, lights, n_lights)) != PTAMD_OK))
+        return rc;
+      // a tree that takes the compact LDS layout: the skip set is chosen with rays over the tree's geometry, on the host
+      if (tree_is_compact(bvh)) { host_builder = true; device_built = false; }
+    }
   }
   if (host_builder) {
     if ((rc = fetch_faces()) != PTAMD_OK || (rc = build_bvh(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, 0u, lights, n_lights)) != PTAMD_OK) return rc;
     if (bvh.split) { set_error("ptamd_scene_rebuild: the upload's builder pre-splits references (PTAMD_BVH_SPLIT_ALPHA): such a tree is not refitted"); return PTAMD_ERR_ARG; }
   }
-  // the new tables beside the old ones; nothing of the scene has changed so far
-  SceneTree fresh;
-  if ((rc = install_tree(ctx, bvh, n, fresh)) != PTAMD_OK) return rc;
+  if (!device_finished && (rc = install_tree(ctx, bvh, n, fresh)) != PTAMD_OK) return rc;
   s.tree = std::move(fresh);
   s.cull_count.supersede();   // (drained above: a count of the old tree's is nobody's any more)
   // positions: the refit forms records, raw boxes, planes, four-wide boxes and orders from the faces, the reduction the margins
@@ -450,7 +549,7 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, p
   PT_HIP(hipStreamSynchronize(stream));
   if ((rc = settle_margins(s, stream, who)) != PTAMD_OK || (rc = device_quality(s, stream, &s.tree.quality_built)) != PTAMD_OK) return rc;
   if (out) {
-    out->device_builder = device_built ? 1u : 0u;
+    out->device_builder = device_finished ? 2u : device_built ? 1u : 0u;
     out->n_nodes = s.tree.n_nodes; out->n_nodes4 = s.tree.n_nodes4; out->depth = s.tree.depth;
     out->quality = s.tree.quality_built;
   }

@@ -223,6 +223,23 @@ int ptamd_host_scene_rebuild(const ptamd_scene_desc* sc, const ptamd_face* faces
   return read_host_table("ptamd_host_scene_rebuild", t, &quality, which, out, bytes);
 }
 
+int ptamd_host_scene_rebuild_plan(const ptamd_scene_desc* sc, const ptamd_face* faces, uint32_t flags, uint32_t which, void* out, uint64_t* bytes)
+{
+  const char* who = "ptamd_host_scene_rebuild_plan";
+  if (!sc || !bytes || which > 4u || (sc->n_faces && !faces)) { set_error("ptamd_host_scene_rebuild_plan: bad argument"); return PTAMD_ERR_ARG; }
+  if (flags & ~(uint32_t)PTAMD_REBUILD_HOST_BUILDER) { set_error("ptamd_host_scene_rebuild_plan: unknown flag bits"); return PTAMD_ERR_ARG; }
+  int rc = validate_scene_desc(sc);
+  if (rc != PTAMD_OK) return rc;
+  Bvh b;
+  rc = (flags & PTAMD_REBUILD_HOST_BUILDER) ? build_bvh(faces, sc->n_faces, kBoxMargin, kMaxLeaf, b, 0u, sc->lights, sc->n_lights)
+                                            : build_bvh_binned(faces, sc->n_faces, kBoxMargin, kMaxLeaf, b, sc->lights, sc->n_lights);
+  if (rc != PTAMD_OK) return rc;
+  const uint32_t counts[9] = { b.n_nodes, b.n_tris, b.n_leaves, b.max_leaf, b.depth, b.n_nodes4, b.depth4, b.refit_top_first, b.refit_top_levels };
+  const void* src[5] = { b.refit_groups.data(), b.refit_levels.data(), b.refit_sched.data(), b.wide_child.data(), counts };
+  const uint64_t size[5] = { b.refit_groups.size() * 4u, b.refit_levels.size() * 4u, b.refit_sched.size() * 4u, b.wide_child.size() * 4u, sizeof counts };
+  return sized_read(who, size[which], out, bytes, [&] { if (size[which]) std::memcpy(out, src[which], size[which]); return (int)PTAMD_OK; });
+}
+
 int ptamd_scene_desc_is_flat(const ptamd_scene_desc* sc, int32_t* out_flat)
 {
   if (!sc || !out_flat || (sc->n_faces && !sc->faces) || (sc->n_materials && !sc->materials) || (sc->n_textures && !sc->textures)) {

@@ -75,6 +75,10 @@ class SceneUpdateDeviceDesc(C.Structure):   # ptamd_scene_update_device_desc (in
 
 
 REBUILD_HOST_BUILDER = 1
+REBUILD_DEVICE_FINISH = 4
+# ptamd_scene_plan_read / ptamd_host_scene_rebuild_plan: which table, and the nine words of the last one
+PLAN_NAMES = ("refit_groups", "refit_levels", "refit_sched", "wide_child", "counts")
+PLAN_COUNTS = ("n_nodes", "n_bvh_tris", "n_leaves", "max_leaf", "depth", "n_nodes4", "depth4", "refit_top_first", "refit_top_levels")
 
 
 class SceneRebuildDesc(C.Structure):        # ptamd_scene_rebuild_desc (include/ptamd.h): faces is a DEVICE address
@@ -244,6 +248,8 @@ SIGNATURES = {
     "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
     "ptamd_scene_rebuild": (C.c_int, [C.c_void_p, C.POINTER(SceneRebuildDesc), C.POINTER(SceneRebuildInfo)]),
     "ptamd_host_scene_rebuild": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_scene_plan_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ptamd_host_scene_rebuild_plan": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_build_group_prims": (C.c_uint32, []),
     "ptamd_scene_rig_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Face), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
                                          C.POINTER(C.c_void_p)]),

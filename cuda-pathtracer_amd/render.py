@@ -118,9 +118,10 @@ class Context:
         d.stream = _stream_handle(stream)
         N.check(self._lib.ptamd_scene_update_device(self._h, C.byref(d)))
 
-    def rebuild_scene_device(self, scene_id: int, faces, stream=None, host_builder=False) -> dict:
+    def rebuild_scene_device(self, scene_id: int, faces, stream=None, host_builder=False, device_finish=False) -> dict:
         """ptamd_scene_rebuild: the scene stands for `faces` (a tensor as update_scene_device takes it) and its tree is a fresh one
-        over them, built on the device; a SceneRig in place of the tensor: its posed records; host_builder: by the upload's own builder, on the host, from a copy of the faces.  A
+        over them, built on the device; a SceneRig in place of the tensor: its posed records; host_builder: by the upload's own builder, on the host, from a copy of the faces;
+        device_finish: PTAMD_REBUILD_DEVICE_FINISH, the tree is numbered, linked, collapsed and scheduled on the device too.  A
         blocking call.  Returns ptamd_scene_rebuild_info as a dict (device_builder, n_nodes, n_nodes4, depth, quality)."""
         import torch
         d = N.SceneRebuildDesc()
@@ -142,7 +143,7 @@ class Context:
                 raise ValueError("faces must be contiguous")
             d.faces = faces.data_ptr(); d.n_faces = faces.shape[0]
         d.stream = _stream_handle(stream)
-        d.flags = N.REBUILD_HOST_BUILDER if host_builder else 0
+        d.flags = (N.REBUILD_HOST_BUILDER if host_builder else 0) | (N.REBUILD_DEVICE_FINISH if device_finish else 0)
         info = N.SceneRebuildInfo()
         N.check(self._lib.ptamd_scene_rebuild(self._h, C.byref(d), C.byref(info)))
         return {n: getattr(info, n) for n, _ in N.SceneRebuildInfo._fields_}
@@ -189,6 +190,11 @@ class Context:
             N.check(self._lib.ptamd_scene_table_read(self._h, scene_id, which, buf.ctypes.data, C.byref(n)))
             out[name] = buf
         return out
+
+    def read_scene_plan(self, scene_id: int) -> dict:
+        """The plan a refit of the scene's tree follows, as the device holds it (ptamd_scene_plan_read; synchronises): refit_groups,
+        refit_levels, refit_sched and wide_child as uint32 arrays, "counts" as a dict of native.PLAN_COUNTS."""
+        return _plan_tables(lambda which, out, n: self._lib.ptamd_scene_plan_read(self._h, scene_id, which, out, n))
 
     def upload_cubemap(self, faces: np.ndarray) -> int:
         faces = np.ascontiguousarray(faces, dtype=np.float32)
@@ -587,6 +593,31 @@ def host_rebuild_tables(scene: HostScene, faces, host_builder=False) -> dict:
     out["scalars"] = out["scalars"].view(np.float32)
     out["quality"] = float(out["quality"].view(np.float64)[0])
     return out
+
+
+def _plan_tables(read) -> dict:
+    """the five tables of ptamd_scene_plan_read / ptamd_host_scene_rebuild_plan through read(which, out, byref(size))"""
+    out = {}
+    for which, name in enumerate(N.PLAN_NAMES):
+        n = C.c_uint64(0)
+        N.check(read(which, None, C.byref(n)))
+        buf = np.zeros(n.value // 4, np.uint32)
+        N.check(read(which, buf.ctypes.data, C.byref(n)))
+        out[name] = buf
+    out["counts"] = dict(zip(N.PLAN_COUNTS, (int(v) for v in out["counts"])))
+    return out
+
+
+def host_rebuild_plan(scene: HostScene, faces, host_builder=False) -> dict:
+    """ptamd_host_scene_rebuild_plan (no GPU): the refit plan and the counts of `scene`'s tree after a rebuild to `faces` (HostScene
+    or face array), as Context.read_scene_plan returns them."""
+    fb = np.ascontiguousarray(faces.faces if isinstance(faces, HostScene) else faces, dtype=FACE_DTYPE)
+    if len(fb) != len(scene.faces):
+        raise ValueError("a rebuild keeps the face count")
+    d = scene.desc()
+    flags = N.REBUILD_HOST_BUILDER if host_builder else 0
+    ptr = fb.ctypes.data_as(C.POINTER(N.Face))
+    return _plan_tables(lambda which, out, n: N.load().ptamd_host_scene_rebuild_plan(C.byref(d), ptr, flags, which, out, n))
 
 
 def host_scene_quality(scene: HostScene, faces_b=None) -> float:

@@ -292,14 +292,26 @@ int ptamd_scene_update_device(ptamd_context* ctx, const ptamd_scene_update_devic
  * Refused before anything is enqueued or allocated: everything ptamd_scene_update_device refuses (a released or out-of-range id, a
  * face count that is not the uploaded one, faces that are not device memory of the context's device or not aligned to 16 bytes, a
  * scene whose tree is not refitted, a captured launch pinning the context, a capturing stream) and, with PTAMD_ERR_ARG, unknown
- * bits in flags. */
+ * bits in flags (bit value 2 is one), and PTAMD_REBUILD_HOST_BUILDER together with PTAMD_REBUILD_DEVICE_FINISH.
+ *
+ * PTAMD_REBUILD_DEVICE_FINISH (opt-in).  The tree the device built is also numbered, linked, collapsed four-wide and scheduled on
+ * the device (csrc/pt_finish.hip): faces, build nodes and tables never leave it, and nothing proportional to the face count
+ * crosses the bus in either direction.  out->device_builder = 2 then.  The result equals the unflagged call's byte for byte in
+ * every case; the cases the host builds without the flag it builds with it (device_builder = 0): the builder's fallback case
+ * above, and a new tree that takes the compact LDS layout, decided from the tree's counts read back from the device.  In place of
+ * the host's walk over the build nodes a check on the device guards the swap: every child index inside the node array, leaf
+ * counts that sum to n_faces, nodes = 2 leaves - 1, a face order that is a permutation; a violation returns PTAMD_ERR_HIP with
+ * the scene unchanged.  The context keeps the call's work buffers (about 560 bytes per face with the flag, 260 without) from the
+ * first rebuild on and frees them with ptamd_destroy. */
 #define PTAMD_REBUILD_HOST_BUILDER 1u
+#define PTAMD_REBUILD_DEVICE_FINISH 4u
 typedef struct {
   uint32_t scene_id;
   const ptamd_face* faces;   /* DEVICE array, n_faces records in the upload's storage order, 16-byte aligned */
   uint32_t n_faces;          /* must equal the uploaded count */
   void* stream;
-  uint32_t flags;            /* PTAMD_REBUILD_HOST_BUILDER: build on the host with the upload's own builder (faces are copied back) */
+  uint32_t flags;            /* PTAMD_REBUILD_HOST_BUILDER: build on the host with the upload's own builder (faces are copied back);
+                                PTAMD_REBUILD_DEVICE_FINISH: finish the device-built tree on the device */
 } ptamd_scene_rebuild_desc;
 typedef struct { uint32_t device_builder; uint32_t n_nodes, n_nodes4, depth; double quality; } ptamd_scene_rebuild_info;
 int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* desc, ptamd_scene_rebuild_info* out /* may be NULL */);
@@ -309,6 +321,17 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* desc
  * rule. */
 int ptamd_host_scene_rebuild(const ptamd_scene_desc* scene, const ptamd_face* faces, uint32_t flags, uint32_t which, void* out,
                              uint64_t* bytes);
+/* Test hooks: the plan a refit of the scene's tree follows, which no other call shows.  ptamd_scene_plan_read reads it from the
+ * device by ptamd_scene_table_read's conventions (it synchronises; out == NULL only asks for the size; a scene whose tree is not
+ * refitted has empty tables): which = 0 the groups {root node, nodes, first level, levels} of the subtrees one workgroup refits
+ * each, 1 the end of every level's entries in the schedule, 2 the schedule (interior nodes by group and ascending height), 3 per
+ * four-wide node and slot the binary node the child was made from (0xFFFFFFFF: empty), 4 the nine words {n_nodes, n_bvh_tris,
+ * n_leaves, max_leaf, depth, n_nodes4, depth4, first level of the top group, levels of the top group}.
+ * ptamd_host_scene_rebuild_plan is its host definition after a rebuild to `faces`, by ptamd_host_scene_rebuild's conventions and
+ * over the same trees (flags 0: the binned tree; PTAMD_REBUILD_HOST_BUILDER: the upload's builder). */
+int ptamd_scene_plan_read(ptamd_context* ctx, uint32_t scene_id, uint32_t which, void* out, uint64_t* bytes);
+int ptamd_host_scene_rebuild_plan(const ptamd_scene_desc* scene, const ptamd_face* faces, uint32_t flags, uint32_t which, void* out,
+                                  uint64_t* bytes);
 /* Nodes of at most this many primitives are built by one workgroup each (csrc/pt_build.h: kBuildGroupPrims). */
 uint32_t ptamd_build_group_prims(void);
 
