@@ -3,6 +3,7 @@
 #include "ptamd_host.h"
 #include "pt_refit.h"
 #include "pt_refit_device.h"
+#include "pt_reface.h"
 #include "pt_relink.h"
 #include "pt_morph.h"
 
@@ -135,6 +136,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   hipError_t e = resolve_kernels();
   if (e == hipSuccess) e = resolve_refit_kernels();
   if (e == hipSuccess) e = resolve_refit_device_kernels();
+  if (e == hipSuccess) e = resolve_reface_kernels();
   if (e == hipSuccess) e = resolve_rig_kernels();
   if (e == hipSuccess) e = resolve_relink_kernel();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);

@@ -119,6 +119,7 @@ struct ptamd_denoise_history {
   ptamd::DeviceBuffer<float4> snapshot;
   uint32_t snap_scene = 0, snap_faces = 0;
   uint64_t snap_serial = 0;
+  uint64_t snap_replace = 0;   // DeviceScene::replace_serial at the snapshot: after ptamd_scene_replace face i is another face, whatever the count
   bool snap_stale = false;
 };
 static_assert(!std::is_copy_constructible<ptamd_denoise_history>::value, "a history owns its device block");
@@ -321,10 +322,10 @@ static int temporal_call(const char* who_, ptamd_context* ctx, const ptamd_denoi
   bool cut = false, moved = false, take = false;
   if (motion) {
     const bool have = (bool)hist->snapshot;
-    cut = have && (hist->snap_scene != d->scene_id || hist->snap_faces != scene.n_faces);
+    cut = have && (hist->snap_scene != d->scene_id || hist->snap_faces != scene.n_faces || hist->snap_replace != scene.replace_serial);
     if (!have || cut) {
       PT_HIP(hist->snapshot.alloc(snap_bytes ? snap_bytes : 16u));   // (releasing the old one waits for the work in flight that may still use it)
-      hist->snap_scene = d->scene_id; hist->snap_faces = scene.n_faces;
+      hist->snap_scene = d->scene_id; hist->snap_faces = scene.n_faces; hist->snap_replace = scene.replace_serial;
       hist->snap_stale = false;
       take = true;
     } else {

@@ -29,7 +29,7 @@
 namespace ptamd {
 
 // Everything a scene's tree decides: what install_tree (ptamd_scene.cpp) fills, and what is sized by the tree and dies with it.
-// ptamd_scene_rebuild replaces this member as a whole; what must survive a rebuild is DeviceScene's own.
+// ptamd_scene_rebuild and ptamd_scene_replace replace this member as a whole; what must survive a rebuild is DeviceScene's own.
 struct SceneTree {
   DeviceBuffer<float4> nodes;    // the binary nodes, and behind them the skip forms' link table (links: there is one)
   DeviceBuffer<float4> nodes4;   // the four-wide form of the same tree (8 float4 per node)
@@ -81,7 +81,7 @@ struct DeviceScene {
   float margin_floor = 0.0f; // smallest inflation of any box face: what the slab test's rounding error must stay below
   // ---- ptamd_scene_update / ptamd_scene_release
   bool released = false;     // a tombstone: the tables are gone, the id stays taken
-  std::vector<uint32_t> material_ids;   // host copy: an update may not change them
+  std::vector<uint32_t> material_ids;   // host copy: an update may not change them (ptamd_scene_replace does, and copies the new ones back)
   std::vector<ptamd_light> host_lights; // host copy, of every scene: the origin reach follows the new extent and the new lights
   // staging of an update's faces, allocated at the first update: one device buffer, two pinned slots (ptamd_owners.h: Upload)
   DeviceBuffer<float> d_faces;
@@ -89,6 +89,7 @@ struct DeviceScene {
   Event updated;                                 // the last update's kernels have finished: lanes and other streams wait for it
   bool updated_valid = false;
   uint64_t geometry_serial = 0;                  // counts the refits enqueued (ptamd_scene_update.cpp: enqueue_refit): the faces moved since a reader last looked
+  uint64_t replace_serial = 0;                   // counts the calls of ptamd_scene_replace: face i is no longer the face it was, whatever the count (a reader that follows faces by index cuts)
   // ptamd_scene_update_device: the new faces' extent is formed on the device (pt_refit_device.hip) and copied back behind the
   // update's kernels; until a reader of extent / all_finite / reach / margin_floor has waited for it (settle_margins) those four
   // are stale.  Two slots, so a copy that lands late never overwrites the words of a newer update.
@@ -183,7 +184,8 @@ struct ptamd_context {
   // must not resize each other.  Grown at the first call that needs more
   ptamd::DeviceBuffer<float4> d_upsample;
   size_t upsample_bytes = 0;
-  // rebuild workspace (ptamd_scene_rebuild): the per-call buffers of the device builder and of the finishing step in one allocation
+  // rebuild workspace (ptamd_scene_rebuild, ptamd_scene_replace): the per-call buffers of the device builder, of the finishing step
+  // and of the replace's material pass in one allocation
   // (ptamd_scene_update.cpp: rebuild_workspace), made at the first rebuild and grown by a rebuild that needs more
   ptamd::DeviceBuffer<uint8_t> d_rebuild;
   size_t rebuild_bytes = 0;
@@ -230,7 +232,7 @@ int install_tree(const ptamd_context* ctx, const Bvh& bvh, uint32_t n_faces, Sce
 int settle_margins(DeviceScene& s, hipStream_t stream, const char* who);
 int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing);
 // what the update calls share (ptamd_scene_update, _update_device, _update_lights, ptamd_scene_rig_pose, _rig_skin, _rig_morph)
-int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces);
+int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces, bool same_count = true);
 int update_capture_checks(const char* who, const ptamd_context* ctx, hipStream_t stream);
 int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t stream);
 int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16);

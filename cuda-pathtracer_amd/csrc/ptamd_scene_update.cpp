@@ -1,8 +1,10 @@
 // ptamd_scene_update.cpp — what changes an uploaded scene (include/ptamd.h): the shared checks and waits of the update calls, the
-// refit from host faces, from device faces and behind the rig, the lights, relink and rebuild in place; the margins and the cull
+// refit from host faces, from device faces and behind the rig, the lights, relink, rebuild in place and the replacement of the
+// faces (another count, other materials); the margins and the cull
 // count on their way back from the device; tree quality.
 #include "ptamd_host.h"
 #include "pt_refit_device.h"
+#include "pt_reface.h"
 #include "pt_relink.h"
 #include "pt_build.h"
 #include "pt_finish.h"
@@ -49,12 +51,13 @@ int wait_for_update(const DeviceScene& s, hipStream_t stream, bool capturing)
 }
 
 // What the update calls refuse alike, in two steps (ptamd_scene_update checks the material ids between them)
-int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces)
+// (same_count = false: ptamd_scene_replace, the one call that brings a count of its own)
+int update_scene_checks(const char* who, const ptamd_context* ctx, uint32_t scene_id, uint32_t n_faces, const void* faces, bool same_count)
 {
   const std::string w(who);
   if (!live_scene(ctx, scene_id)) { set_error(w + ": scene_id out of range or released"); return PTAMD_ERR_ARG; }
   const DeviceScene& s = ctx->scenes[scene_id];
-  if (n_faces != s.n_faces) { set_error(w + ": n_faces differs from the uploaded count"); return PTAMD_ERR_ARG; }
+  if (same_count && n_faces != s.n_faces) { set_error(w + ": n_faces differs from the uploaded count"); return PTAMD_ERR_ARG; }
   if (n_faces && !faces) { set_error(w + ": null faces"); return PTAMD_ERR_ARG; }
   if (!s.tree.refit_ok) {
     set_error(w + ": this scene's tree is not refitted (built with PTAMD_WIDE8, PTAMD_WIDE4Q or PTAMD_BVH_SPLIT_ALPHA)");
@@ -218,20 +221,25 @@ static int device_quality(DeviceScene& s, hipStream_t st, double* now)
   return PTAMD_OK;
 }
 
-// The workspace of ptamd_scene_rebuild, the context's: the per-call buffers of the builder (pt_build.hip) and, when asked for, of the
-// finishing step (pt_finish.hip) carved out of one allocation that is sized at the first rebuild, kept, and grown only by a
-// rebuild that needs more.  The call blocks, so one workspace serves every scene of the context in turn.
-static int rebuild_workspace(ptamd_context* ctx, uint32_t n, bool finish, BuildParams& p, FinishParams& f)
+// The workspace of ptamd_scene_rebuild and ptamd_scene_replace, the context's: the per-call buffers of the builder (pt_build.hip),
+// when asked for of the finishing step (pt_finish.hip), and for a replace of the material pass (pt_reface.hip: `w`, null for a
+// rebuild) carved out of one allocation that is sized at the first call, kept, and grown only by a call that needs more.  The
+// calls block, so one workspace serves every scene of the context in turn.  build = false (PTAMD_REBUILD_HOST_BUILDER): the
+// material pass alone.
+static int rebuild_workspace(ptamd_context* ctx, uint32_t n, bool build, bool finish, BuildParams& p, FinishParams& f, RefaceParams* w)
 {
   std::memset(&p, 0, sizeof p);
   std::memset(&f, 0, sizeof f);
   p.n_faces = n; p.max_open = build_max_open(n); p.max_leaf = kMaxLeaf;
   size_t at = 0;
   auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
-  const size_t prims0 = take((size_t)n * 40u), prims1 = take((size_t)n * 40u), owner = take((size_t)n * 4u), tag = take((size_t)n * 4u),
-               large = take((size_t)n * 16u), slots = take((size_t)p.max_open * kBdSlotWords * 4u), open = take((size_t)p.max_open * 8u),
-               roots = take((size_t)n * 8u), order = take((size_t)n * 4u), ctl = take(kBdCtlWords * 4u),
-               nodes = take((size_t)n * 3u * sizeof(BdNode)), fin = at;
+  // the material pass: its result words with the ids behind them (one copy brings both back), its partials
+  const size_t ids = w ? take(kRefaceResultWords * 4u + (size_t)n * 4u) : 0u, partials = w ? take((size_t)reface_groups(n) * 8u) : 0u;
+  const size_t b = build ? 1u : 0u;
+  const size_t prims0 = take(b * n * 40u), prims1 = take(b * n * 40u), owner = take(b * n * 4u), tag = take(b * n * 4u),
+               large = take(b * n * 16u), slots = take(b * p.max_open * kBdSlotWords * 4u), open = take(b * p.max_open * 8u),
+               roots = take(b * n * 8u), order = take(b * n * 4u), ctl = take(b * kBdCtlWords * 4u),
+               nodes = take(b * n * 3u * sizeof(BdNode)), fin = at;
   const FinishLayout l = finish_layout(n);
   const size_t bytes = fin + (finish ? l.bytes : 0u);
   if (!ctx->d_rebuild || ctx->rebuild_bytes < bytes) {
@@ -241,6 +249,8 @@ static int rebuild_workspace(ptamd_context* ctx, uint32_t n, bool finish, BuildP
   }
   uint8_t* base = ctx->d_rebuild.get();
   auto words = [&](size_t offset) { return reinterpret_cast<uint32_t*>(base + offset); };
+  if (w) { w->result = words(ids); w->ids = words(ids) + kRefaceResultWords; w->partials = words(partials); }
+  if (!build) return PTAMD_OK;
   p.prims[0] = words(prims0); p.prims[1] = words(prims1); p.owner = words(owner); p.tag = words(tag); p.large = words(large);
   p.slots = words(slots); p.open = words(open); p.roots = words(roots); p.order = words(order); p.ctl = words(ctl);
   p.nodes = reinterpret_cast<BdNode*>(base + nodes);
@@ -331,6 +341,97 @@ static int device_finish_tree(FinishParams& f, uint32_t n_large, hipStream_t str
   t.n_refit_groups = c.n_groups; t.n_refit_levels = c.n_group_levels + top_levels; t.n_refit_sched = n_sched;
   t.refit_top_first = c.n_group_levels; t.refit_top_levels = top_levels;
   done = true;
+  return PTAMD_OK;
+}
+
+// What ptamd_scene_rebuild and ptamd_scene_replace refuse alike before they look at the scene: the flags
+static int rebuild_flag_checks(const char* who, uint32_t flags)
+{
+  const std::string w(who);
+  if (flags & ~(uint32_t)(PTAMD_REBUILD_HOST_BUILDER | PTAMD_REBUILD_DEVICE_FINISH)) { set_error(w + ": unknown flag bits"); return PTAMD_ERR_ARG; }
+  if ((flags & PTAMD_REBUILD_HOST_BUILDER) && (flags & PTAMD_REBUILD_DEVICE_FINISH)) {
+    set_error(w + ": PTAMD_REBUILD_DEVICE_FINISH finishes a tree the device built: not with PTAMD_REBUILD_HOST_BUILDER");
+    return PTAMD_ERR_ARG;
+  }
+  return PTAMD_OK;
+}
+
+// ... and how both block before they build: every reader of the scene, whatever the stream holds, and the copies earlier updates
+// left in flight
+static int rebuild_drain(const ptamd_context* ctx, DeviceScene& s, hipStream_t stream)
+{
+  int rc;
+  if ((rc = prepare_margins(s)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
+  PT_HIP(hipStreamSynchronize(stream));
+  PT_HIP(s.margins.drain());
+  PT_HIP(s.cull_count.drain());
+  return PTAMD_OK;
+}
+
+// The fresh tree of both calls: a SceneTree over `n` device faces, built beside the scene's own by the device builder (finished on
+// the host, or on the device with PTAMD_REBUILD_DEVICE_FINISH) or, in the three host-built cases, from a copy of the faces.
+// `ids`: the material ids that copy is given (ptamd_scene_rebuild: the upload's; null: the copy's own, which ptamd_scene_replace has
+// checked on the device).  `p` / `f`: rebuild_workspace's.  Nothing of the scene changes; built: ptamd_scene_rebuild_info's
+// device_builder.
+static int build_fresh_tree(const char* who, ptamd_context* ctx, const DeviceScene& s, const ptamd_face* device_faces, uint32_t n, uint32_t flags,
+                            const uint32_t* ids, const BuildParams& p, FinishParams& f, hipStream_t stream, SceneTree& fresh, uint32_t& built)
+{
+  int rc;
+  const float* faces = reinterpret_cast<const float*>(device_faces);
+  // the faces on the host, where a host builder needs them
+  std::vector<ptamd_face> host_faces;
+  auto fetch_faces = [&]() -> int {
+    if (!host_faces.empty()) return PTAMD_OK;
+    host_faces.resize(n);
+    PT_HIP(hipMemcpy(host_faces.data(), device_faces, (size_t)n * sizeof(ptamd_face), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; ids && i < n; ++i) host_faces[i].material_id = ids[i];
+    return PTAMD_OK;
+  };
+  const ptamd_light* lights = s.host_lights.data();
+  const uint32_t n_lights = (uint32_t)s.host_lights.size();
+  Bvh bvh;
+  bool host_builder = (flags & PTAMD_REBUILD_HOST_BUILDER) != 0u, device_built = false, device_finished = false;
+  const bool finish = (flags & PTAMD_REBUILD_DEVICE_FINISH) != 0u;
+  if (!host_builder) {
+    uint32_t n_large = 0;
+    if ((rc = device_build(p, faces, stream, n_large, device_built)) != PTAMD_OK) return rc;
+    // PTAMD_REBUILD_DEVICE_FINISH: the tree stays where it was built, unless it turns out compact
+    if (device_built && finish && (rc = device_finish_tree(f, n_large, stream, fresh, device_finished)) != PTAMD_OK) return rc;
+    if (!device_finished) {
+      fresh = SceneTree();
+      if (device_built && (rc = host_finish_tree(p, n_large, bvh)) != PTAMD_OK) return rc;
+      if (!device_built && ((rc = fetch_faces()) != PTAMD_OK ||
+                            (rc = build_bvh_binned(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, lights, n_lights)) != PTAMD_OK))
+        return rc;
+      // a tree that takes the compact LDS layout: the skip set is chosen with rays over the tree's geometry, on the host
+      if (tree_is_compact(bvh)) { host_builder = true; device_built = false; }
+    }
+  }
+  if (host_builder) {
+    if ((rc = fetch_faces()) != PTAMD_OK || (rc = build_bvh(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, 0u, lights, n_lights)) != PTAMD_OK) return rc;
+    if (bvh.split) { set_error(std::string(who) + ": the upload's builder pre-splits references (PTAMD_BVH_SPLIT_ALPHA): such a tree is not refitted"); return PTAMD_ERR_ARG; }
+  }
+  if (!device_finished && (rc = install_tree(ctx, bvh, n, fresh)) != PTAMD_OK) return rc;
+  built = device_finished ? 2u : device_built ? 1u : 0u;
+  return PTAMD_OK;
+}
+
+// ... and what both do once the fresh tree (and, for a replace, everything else sized by the count) has been moved in: positions.
+// The refit forms records, raw boxes, planes, four-wide boxes and orders from the faces, the reduction the margins; then the
+// quality of the tree as built, and the call's info.
+static int refit_fresh_tree(const char* who, DeviceScene& s, const ptamd_face* device_faces, hipStream_t stream, uint32_t built, ptamd_scene_rebuild_info* out)
+{
+  int rc;
+  s.cull_count.supersede();   // (drained before the build: a count of the old tree's is nobody's any more)
+  RefitParams r;
+  if ((rc = refit_params(who, s, r)) != PTAMD_OK || (rc = enqueue_device_refit(s, r, reinterpret_cast<const float*>(device_faces), stream, true)) != PTAMD_OK) return rc;
+  PT_HIP(hipStreamSynchronize(stream));
+  if ((rc = settle_margins(s, stream, who)) != PTAMD_OK || (rc = device_quality(s, stream, &s.tree.quality_built)) != PTAMD_OK) return rc;
+  if (out) {
+    out->device_builder = built;
+    out->n_nodes = s.tree.n_nodes; out->n_nodes4 = s.tree.n_nodes4; out->depth = s.tree.depth;
+    out->quality = s.tree.quality_built;
+  }
   return PTAMD_OK;
 }
 
@@ -483,12 +584,9 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, p
 {
   const char* who = "ptamd_scene_rebuild";
   if (!ctx || !d) { set_error("ptamd_scene_rebuild: null argument"); return PTAMD_ERR_ARG; }
-  if (d->flags & ~(uint32_t)(PTAMD_REBUILD_HOST_BUILDER | PTAMD_REBUILD_DEVICE_FINISH)) { set_error("ptamd_scene_rebuild: unknown flag bits"); return PTAMD_ERR_ARG; }
-  if ((d->flags & PTAMD_REBUILD_HOST_BUILDER) && (d->flags & PTAMD_REBUILD_DEVICE_FINISH)) {
-    set_error("ptamd_scene_rebuild: PTAMD_REBUILD_DEVICE_FINISH finishes a tree the device built: not with PTAMD_REBUILD_HOST_BUILDER");
-    return PTAMD_ERR_ARG;
-  }
-  int rc = update_scene_checks(who, ctx, d->scene_id, d->n_faces, d->faces);
+  int rc = rebuild_flag_checks(who, d->flags);
+  if (rc != PTAMD_OK) return rc;
+  rc = update_scene_checks(who, ctx, d->scene_id, d->n_faces, d->faces);
   hipStream_t stream = static_cast<hipStream_t>(d->stream);
   if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
   DeviceScene& s = ctx->scenes[d->scene_id];
@@ -497,63 +595,82 @@ int ptamd_scene_rebuild(ptamd_context* ctx, const ptamd_scene_rebuild_desc* d, p
   if (n == 0) return PTAMD_OK;
   if ((rc = device_array_checks(who, "faces", ctx, d->faces, (size_t)n * sizeof(ptamd_face), true)) != PTAMD_OK) return rc;
   if (n >= (1u << 24)) { set_error("ptamd_scene_rebuild: more than 2^24 faces"); return PTAMD_ERR_LIMIT; }
-  // a blocking call: every reader of the scene, whatever the stream holds, and the copies earlier updates left in flight
-  if ((rc = prepare_margins(s)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;
-  PT_HIP(hipStreamSynchronize(stream));
-  PT_HIP(s.margins.drain());
-  PT_HIP(s.cull_count.drain());
-  const float* faces = reinterpret_cast<const float*>(d->faces);
-  // the faces on the host, where a host builder needs them: material ids are the upload's
-  std::vector<ptamd_face> host_faces;
-  auto fetch_faces = [&]() -> int {
-    if (!host_faces.empty()) return PTAMD_OK;
-    host_faces.resize(n);
-    PT_HIP(hipMemcpy(host_faces.data(), d->faces, (size_t)n * sizeof(ptamd_face), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; ++i) host_faces[i].material_id = s.material_ids[i];
-    return PTAMD_OK;
-  };
-  const ptamd_light* lights = s.host_lights.data();
-  const uint32_t n_lights = (uint32_t)s.host_lights.size();
-  Bvh bvh;
-  bool host_builder = (d->flags & PTAMD_REBUILD_HOST_BUILDER) != 0u, device_built = false, device_finished = false;
-  const bool finish = (d->flags & PTAMD_REBUILD_DEVICE_FINISH) != 0u;
-  // the new tables beside the old ones; nothing of the scene changes before the move below
+  // a blocking call
+  if ((rc = rebuild_drain(ctx, s, stream)) != PTAMD_OK) return rc;
+  // the new tables beside the old ones; nothing of the scene changes before the move below.  Material ids are the upload's.
+  const bool build = !(d->flags & PTAMD_REBUILD_HOST_BUILDER);
+  BuildParams p = {};
+  FinishParams f = {};
   SceneTree fresh;
-  if (!host_builder) {
-    BuildParams p;
-    FinishParams f;
-    uint32_t n_large = 0;
-    if ((rc = rebuild_workspace(ctx, n, finish, p, f)) != PTAMD_OK || (rc = device_build(p, faces, stream, n_large, device_built)) != PTAMD_OK) return rc;
-    // PTAMD_REBUILD_DEVICE_FINISH: the tree stays where it was built, unless it turns out compact
-    if (device_built && finish && (rc = device_finish_tree(f, n_large, stream, fresh, device_finished)) != PTAMD_OK) return rc;
-    if (!device_finished) {
-      fresh = SceneTree();
-      if (device_built && (rc = host_finish_tree(p, n_large, bvh)) != PTAMD_OK) return rc;
-      if (!device_built && ((rc = fetch_faces()) != PTAMD_OK ||
-                            (rc = build_bvh_binned(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, lights, n_lights)) != PTAMD_OK))
-        return rc;
-      // a tree that takes the compact LDS layout: the skip set is chosen with rays over the tree's geometry, on the host
-      if (tree_is_compact(bvh)) { host_builder = true; device_built = false; }
-    }
-  }
-  if (host_builder) {
-    if ((rc = fetch_faces()) != PTAMD_OK || (rc = build_bvh(host_faces.data(), n, kBoxMargin, kMaxLeaf, bvh, 0u, lights, n_lights)) != PTAMD_OK) return rc;
-    if (bvh.split) { set_error("ptamd_scene_rebuild: the upload's builder pre-splits references (PTAMD_BVH_SPLIT_ALPHA): such a tree is not refitted"); return PTAMD_ERR_ARG; }
-  }
-  if (!device_finished && (rc = install_tree(ctx, bvh, n, fresh)) != PTAMD_OK) return rc;
+  uint32_t built = 0;
+  if ((build && (rc = rebuild_workspace(ctx, n, true, (d->flags & PTAMD_REBUILD_DEVICE_FINISH) != 0u, p, f, nullptr)) != PTAMD_OK) ||
+      (rc = build_fresh_tree(who, ctx, s, d->faces, n, d->flags, s.material_ids.data(), p, f, stream, fresh, built)) != PTAMD_OK)
+    return rc;
   s.tree = std::move(fresh);
-  s.cull_count.supersede();   // (drained above: a count of the old tree's is nobody's any more)
-  // positions: the refit forms records, raw boxes, planes, four-wide boxes and orders from the faces, the reduction the margins
-  RefitParams r;
-  if ((rc = refit_params(who, s, r)) != PTAMD_OK || (rc = enqueue_device_refit(s, r, faces, stream, true)) != PTAMD_OK) return rc;
+  return refit_fresh_tree(who, s, d->faces, stream, built, out);
+}
+
+int ptamd_scene_replace(ptamd_context* ctx, const ptamd_scene_replace_desc* d, ptamd_scene_rebuild_info* out)
+{
+  const char* who = "ptamd_scene_replace";
+  if (!ctx || !d) { set_error("ptamd_scene_replace: null argument"); return PTAMD_ERR_ARG; }
+  int rc = rebuild_flag_checks(who, d->flags);
+  if (rc != PTAMD_OK) return rc;
+  // (the count before the pointer is looked at)
+  const uint32_t n = d->n_faces;
+  if (n == 0) { set_error("ptamd_scene_replace: n_faces is 0 (to empty a scene, release it)"); return PTAMD_ERR_ARG; }
+  if (n >= (1u << 24)) { set_error("ptamd_scene_replace: more than 2^24 - 1 faces"); return PTAMD_ERR_LIMIT; }
+  rc = update_scene_checks(who, ctx, d->scene_id, n, d->faces, false);
+  hipStream_t stream = static_cast<hipStream_t>(d->stream);
+  if (rc != PTAMD_OK || (rc = update_capture_checks(who, ctx, stream)) != PTAMD_OK) return rc;
+  DeviceScene& s = ctx->scenes[d->scene_id];
+  if (out) std::memset(out, 0, sizeof *out);
+  if ((rc = device_array_checks(who, "faces", ctx, d->faces, (size_t)n * sizeof(ptamd_face), true)) != PTAMD_OK) return rc;
+  if (!s.materials || !s.textures || !s.texels || s.n_materials == 0) { set_error("ptamd_scene_replace: the scene has no materials for new faces to name"); return PTAMD_ERR_ARG; }
+  // a blocking call, like the rebuild
+  if ((rc = rebuild_drain(ctx, s, stream)) != PTAMD_OK) return rc;
+  // Everything sized by the count beside the old tables; nothing of the scene changes before the move below.  First the material
+  // pass (pt_reface.hip): every id checked and words 18..27 of every shading record written on the device, the compact records
+  // too (the tail is allocated whether or not the scene turns out flat: DESIGN.md §13).  The refit behind the move fills the rest.
+  const bool build = !(d->flags & PTAMD_REBUILD_HOST_BUILDER);
+  BuildParams p = {};
+  FinishParams f = {};
+  RefaceParams w;
+  std::memset(&w, 0, sizeof w);
+  if ((rc = rebuild_workspace(ctx, n, build, (d->flags & PTAMD_REBUILD_DEVICE_FINISH) != 0u, p, f, &w)) != PTAMD_OK) return rc;
+  DeviceBuffer<float4> tris_brute, shade;
+  PT_HIP(tris_brute.alloc((size_t)n * 48u));
+  PT_HIP(shade.alloc((size_t)n * (kShadeFloats * 4u + 64u)));
+  w.faces = reinterpret_cast<const float*>(d->faces);
+  w.materials = s.materials.get(); w.textures = s.textures.get(); w.texels = s.texels.get();
+  w.shade = reinterpret_cast<float*>(shade.get());
+  w.n_faces = n; w.n_materials = s.n_materials;
+  PT_HIP(launch_reface(w, stream));
+  // the result and the ids for the host's copy, in one read: the only traffic per face of a device-finished replace
+  std::vector<uint32_t> back(kRefaceResultWords + (size_t)n);
+  PT_HIP(hipMemcpyAsync(back.data(), w.result, back.size() * 4u, hipMemcpyDeviceToHost, stream));
   PT_HIP(hipStreamSynchronize(stream));
-  if ((rc = settle_margins(s, stream, who)) != PTAMD_OK || (rc = device_quality(s, stream, &s.tree.quality_built)) != PTAMD_OK) return rc;
-  if (out) {
-    out->device_builder = device_finished ? 2u : device_built ? 1u : 0u;
-    out->n_nodes = s.tree.n_nodes; out->n_nodes4 = s.tree.n_nodes4; out->depth = s.tree.depth;
-    out->quality = s.tree.quality_built;
+  if (back[1] != kRfcNoBadFace) {
+    set_error("ptamd_scene_replace: face " + std::to_string(back[1]) + " has a material_id (" + std::to_string(back[kRefaceResultWords + back[1]]) +
+              ") that is not below n_materials (" + std::to_string(s.n_materials) + ")");
+    return PTAMD_ERR_ARG;
   }
-  return PTAMD_OK;
+  SceneTree fresh;
+  uint32_t built = 0;
+  if ((rc = build_fresh_tree(who, ctx, s, d->faces, n, d->flags, nullptr, p, f, stream, fresh, built)) != PTAMD_OK) return rc;
+  // the move: tree, storage-order tables, ids, count and flatness together.  The staging of host updates was sized by the old count
+  // (every copy through it has been drained above): the next ptamd_scene_update allocates it again; the tree's pinned link slots
+  // went with the old tree.
+  s.tree = std::move(fresh);
+  s.tris_brute = std::move(tris_brute);
+  s.shade = std::move(shade);
+  s.material_ids.assign(back.begin() + kRefaceResultWords, back.end());
+  s.n_faces = n;
+  s.flat = back[0] == 0u;
+  s.d_faces = DeviceBuffer<float>();
+  s.faces_up = Upload<ptamd_face>();
+  ++s.replace_serial;
+  return refit_fresh_tree(who, s, d->faces, stream, built, out);
 }
 
 int ptamd_scene_cull_count(ptamd_context* ctx, uint32_t scene_id, uint32_t* out)

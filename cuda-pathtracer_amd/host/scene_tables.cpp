@@ -3,6 +3,7 @@
 // compares against.  No HIP: built into the library and, under sanitizers, into tests/san/rebuild_host.cpp.
 #include "ptamd_internal.h"
 #include "../csrc/pt_refit_device.h"
+#include "../csrc/pt_reface.h"
 
 #include <cstring>
 
@@ -15,11 +16,8 @@ namespace ptamd {
 static bool scene_is_flat(const ptamd_scene_desc* sc)
 {
   for (uint32_t i = 0; i < sc->n_faces; ++i) {
-    const ptamd_material& m = sc->materials[sc->faces[i].material_id];
-    const ptamd_texture_desc& dt = sc->textures[m.diffuse_spec_map];
-    uint32_t ior;
-    std::memcpy(&ior, &m.ior, 4);
-    if (dt.w != 1 || dt.h != 1 || m.normal_map >= 0 || ior != 0x3F800000u) return false;
+    const RfcMaterial m = rfc_material(sc->materials, sc->faces[i].material_id);
+    if (!rfc_flat(m, rfc_texture(sc->textures, m.diffuse_spec_map))) return false;
   }
   return true;
 }
@@ -88,6 +86,9 @@ int make_scene_tables(const ptamd_scene_desc* sc, uint32_t forms, SceneTables& t
   // storage-order {e1,e2,v0,idx} records for the brute-force variant, and the shading records
   std::vector<float>& brute = t.brute;
   std::vector<float>& shade = t.shade;
+  static_assert(sizeof(ptamd_material) == sizeof(RfcMaterial) && sizeof(ptamd_texture_desc) == sizeof(RfcTexture), "pt_reface.h reads these records");
+  const void* mats = sc->materials;
+  const void* texs = sc->textures;
   brute.assign((size_t)sc->n_faces * 12, 0.0f);
   shade.assign((size_t)sc->n_faces * kShadeFloats, 0.0f);
   for (uint32_t i = 0; i < sc->n_faces; ++i) {
@@ -98,30 +99,10 @@ int make_scene_tables(const ptamd_scene_desc* sc, uint32_t forms, SceneTables& t
     // or its one RGBA texel | normal map {..} (w = 0: none)
     float* s = &shade[(size_t)i * kShadeFloats];
     write_face_geometry(f, i, &brute[(size_t)i * 12], s);
-    std::memcpy(s + 18, &f.material_id, 4);
-    const ptamd_material& m = sc->materials[f.material_id];
-    std::memcpy(s + 19, &m.ior, 4);
-    const ptamd_texture_desc& dt = sc->textures[m.diffuse_spec_map];
-    if (dt.w == 1 && dt.h == 1) {
-      // a 1x1 diffuse+specular map (every material of indoor.obj as the reference loads it on Linux): sampleTexture can
-      // only ever return texel 0 (intersection.cuh:20-26: x = int(uv.x * 0)), so the record carries the texel itself
-      // and the kernel skips the dependent texel load; flagged in the sign bit of the material id word
-      std::memcpy(s + 20, sc->texels + dt.offset, 16);
-      const uint32_t flagged = f.material_id | 0x80000000u;
-      std::memcpy(s + 18, &flagged, 4);
-    } else {
-      const int32_t d4[4] = { dt.w, dt.h, dt.nb_chan, (int32_t)(uint32_t)dt.offset };
-      std::memcpy(s + 20, d4, 16);
-    }
-    if (m.normal_map >= 0) {
-      const ptamd_texture_desc& nt = sc->textures[m.normal_map];
-      const int32_t n4[4] = { nt.w, nt.h, nt.nb_chan, (int32_t)(uint32_t)nt.offset };
-      std::memcpy(s + 24, n4, 16);
-      uint32_t word;
-      std::memcpy(&word, s + 18, 4);
-      word |= 0x40000000u;               // bit 30 of the material id word: the record's 7th float4 (normal map) is in use
-      std::memcpy(s + 18, &word, 4);
-    }
+    // words 18..27 follow the material alone (pt_reface.h, shared with ptamd_scene_replace's kernels)
+    RfcWords w;
+    rfc_words(f.material_id, mats, texs, sc->texels, w);
+    std::memcpy(s + 18, w.shade, 40);
   }
   // flat scenes: behind the general records, the compact record of PT_RS_FLAT (pt_kernels.hip: resolve_hit), 64 bytes per face =
   // {n0, diffuse.r} {n1, diffuse.g} {n2, diffuse.b} {specular, 0, 0, 0}: three 16-byte loads and one 4-byte load per hit
@@ -129,11 +110,12 @@ int make_scene_tables(const ptamd_scene_desc* sc, uint32_t forms, SceneTables& t
   if (flat) shade.resize(shade.size() + (size_t)sc->n_faces * 16, 0.0f);
   for (uint32_t i = 0; flat && i < sc->n_faces; ++i) {
     const ptamd_face& f = sc->faces[i];
-    const float* texel = sc->texels + sc->textures[sc->materials[f.material_id].diffuse_spec_map].offset;
+    RfcWords w;
+    rfc_words(f.material_id, mats, texs, sc->texels, w);
     float* r = &shade[(size_t)sc->n_faces * kShadeFloats + (size_t)i * 16];
     write_flat_normals(f, r);
-    for (int k = 0; k < 3; ++k) r[4 * k + 3] = texel[k];
-    r[12] = texel[3];
+    for (int k = 0; k < 3; ++k) std::memcpy(r + 4 * k + 3, &w.texel[k], 4);
+    std::memcpy(r + 12, &w.texel[3], 4);
   }
   return PTAMD_OK;
 }

@@ -85,6 +85,10 @@ class SceneRebuildDesc(C.Structure):        # ptamd_scene_rebuild_desc (include/
     _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class SceneReplaceDesc(C.Structure):        # ptamd_scene_replace_desc (include/ptamd.h): faces is a DEVICE address; any count, ids are read
+    _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
+
+
 class SceneRebuildInfo(C.Structure):        # ptamd_scene_rebuild_info (include/ptamd.h)
     _fields_ = [("device_builder", C.c_uint32), ("n_nodes", C.c_uint32), ("n_nodes4", C.c_uint32), ("depth", C.c_uint32),
                 ("quality", C.c_double)]
@@ -247,6 +251,7 @@ SIGNATURES = {
     "ptamd_scene_update": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDesc)]),
     "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
     "ptamd_scene_rebuild": (C.c_int, [C.c_void_p, C.POINTER(SceneRebuildDesc), C.POINTER(SceneRebuildInfo)]),
+    "ptamd_scene_replace": (C.c_int, [C.c_void_p, C.POINTER(SceneReplaceDesc), C.POINTER(SceneRebuildInfo)]),
     "ptamd_host_scene_rebuild": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_scene_plan_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_host_scene_rebuild_plan": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -148,6 +148,30 @@ class Context:
         N.check(self._lib.ptamd_scene_rebuild(self._h, C.byref(d), C.byref(info)))
         return {n: getattr(info, n) for n, _ in N.SceneRebuildInfo._fields_}
 
+    def replace_scene_faces(self, scene_id: int, faces, stream=None, host_builder=False, device_finish=False) -> dict:
+        """ptamd_scene_replace: the scene stands for `faces` as a fresh upload of them would, under the id, materials, textures and
+        lights it has.  `faces` is a tensor as rebuild_scene_device takes it (uint8 (n, 112) or float32 (n, 28): ids travel as
+        bits) of ANY count from 1 on; material ids ARE read, and checked on the device.  The flags are rebuild_scene_device's.  A
+        blocking call.  Returns ptamd_scene_rebuild_info as a dict (device_builder, n_nodes, n_nodes4, depth, quality)."""
+        import torch
+        if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+            raise ValueError("replace_scene_faces takes a torch tensor in device memory")
+        if faces.device.index != self.device:
+            raise ValueError(f"the faces live on {faces.device}, the context on device {self.device}")
+        if not ((faces.dtype == torch.float32 and faces.dim() == 2 and faces.shape[1] == 28) or
+                (faces.dtype == torch.uint8 and faces.dim() == 2 and faces.shape[1] == 112)):
+            raise ValueError("faces must be float32 of shape (n, 28) or uint8 of shape (n, 112)")
+        if not faces.is_contiguous():
+            raise ValueError("faces must be contiguous")
+        d = N.SceneReplaceDesc()
+        d.scene_id = scene_id
+        d.faces = faces.data_ptr(); d.n_faces = faces.shape[0]
+        d.stream = _stream_handle(stream)
+        d.flags = (N.REBUILD_HOST_BUILDER if host_builder else 0) | (N.REBUILD_DEVICE_FINISH if device_finish else 0)
+        info = N.SceneRebuildInfo()
+        N.check(self._lib.ptamd_scene_replace(self._h, C.byref(d), C.byref(info)))
+        return {n: getattr(info, n) for n, _ in N.SceneRebuildInfo._fields_}
+
     def scene_rig(self, scene_id: int, host_scene, group_sizes=None) -> "SceneRig":
         """ptamd_scene_rig_create: a rig of the uploaded scene with `host_scene` (a HostScene or a FACE_DTYPE array) as its rest
         pose, cut into groups of consecutive faces; group_sizes defaults to the HostScene's mesh_sizes."""

@@ -335,6 +335,57 @@ int ptamd_host_scene_rebuild_plan(const ptamd_scene_desc* scene, const ptamd_fac
 /* Nodes of at most this many primitives are built by one workgroup each (csrc/pt_build.h: kBuildGroupPrims). */
 uint32_t ptamd_build_group_prims(void);
 
+/* ---- Another number of faces, other materials (DESIGN.md §13 "Another number of faces") --------------------------------------
+ *
+ * Every call above keeps the face count and the material of every face.  ptamd_scene_replace gives the scene NEW FACES: any count
+ * from 1 to 2^24 - 1, each with the material_id its record carries, for an object that appears, disappears, breaks apart, changes
+ * its level of detail or swaps its material.  After the call the scene stands for `faces` exactly as a fresh ptamd_upload_scene
+ * would whose descriptor is the old one with its faces replaced by these, as one mesh; its tree is the one ptamd_scene_rebuild
+ * builds with the same flags (the three cases the host builds included), and the storage order is the order of `faces`.
+ *
+ * Kept: the scene id; the material, texture and texel tables (nothing of them crosses the bus); the lights; the context's cubemaps.
+ * Changed: the face count, every per-face table, the material words of every shading record, flatness (decided again, by the rule of
+ * ptamd_scene_desc_is_flat, from the materials the NEW faces use), ptamd_scene_info, and with them LDS residency and the form a
+ * launch takes.  A replace may take a scene into the compact LDS layout or out of it; a compact result equals a fresh upload byte
+ * for byte, link table included.
+ *
+ * The material half of the shading records (words 18..27, and a flat scene's compact texels) is formed ON THE DEVICE from
+ * material_id (csrc/pt_reface.hip, the words of csrc/pt_reface.h that the upload writes too).  The same pass checks every id and
+ * decides flatness, and packs the ids into one word per face that is copied back for the host's checks (ptamd_scene_update,
+ * ptamd_scene_rig_create): with PTAMD_REBUILD_DEVICE_FINISH those 4 bytes per face are the only traffic per face of the call.
+ *
+ * It blocks as ptamd_scene_rebuild does: it waits for every reader and for `stream`, builds everything beside the old tables, and
+ * swaps only when every allocation, the build and the checks have succeeded; any refusal or failure before the swap leaves tables,
+ * links, plan, margins, quality, info, flatness and material ids untouched.
+ *
+ * Refused: everything ptamd_scene_rebuild refuses except a count that differs from the scene's; PTAMD_ERR_ARG for n_faces == 0 (to
+ * empty a scene, release it); PTAMD_ERR_LIMIT for n_faces >= 2^24, before the pointer is looked at; PTAMD_ERR_ARG for a face whose
+ * material_id >= n_materials, found on the device before anything is swapped: the message holds the word material_id and the
+ * lowest offending face index.
+ *
+ * What follows for the other calls.  ptamd_scene_update, ptamd_scene_update_device and ptamd_scene_rebuild take the NEW count from
+ * now on ("the uploaded count" in their texts), and ptamd_scene_update refuses a material_id that differs from the NEW ids.  A rig
+ * made for another count is refused at its next pose, skin or morph with PTAMD_ERR_ARG (it can still be destroyed); a rig of the
+ * same count stays usable: positions come from the rig, material words from the scene.  ptamd_denoise_temporal_motion follows faces
+ * by index, so after a replace it CUTS the history, also when the count is unchanged.  A ptamd_adaptive_state is not tracked, as
+ * after every update.  The staging buffers of ptamd_scene_update are released and allocated again by its next call.
+ *
+ * What it costs (scripts/gpu_replace.py): on the 264 832-face atrium 58 - 60 ms from its half, 17 ms with
+ * PTAMD_REBUILD_DEVICE_FINISH, against 0.7 s for release + upload.  A small textured scene that takes the compact layout is NOT
+ * replaced faster than it is uploaded again (indoor with 66 MB of texels: 7 ms against 2.6 ms): there the call stands on the kept
+ * id and the tables that stay put.
+ *
+ * The host definition needs no mirror of its own: it is ptamd_host_scene_rebuild over the descriptor of the old upload with the new
+ * faces as one mesh, rebuilt to those same faces (flags: PTAMD_REBUILD_HOST_BUILDER when the new tree is compact). */
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_face* faces;   /* DEVICE array, n_faces records, 16-byte aligned; material_id IS read */
+  uint32_t n_faces;          /* any count from 1 to 2^24 - 1: need not be the scene's */
+  void* stream;
+  uint32_t flags;            /* PTAMD_REBUILD_HOST_BUILDER / PTAMD_REBUILD_DEVICE_FINISH, as ptamd_scene_rebuild means them */
+} ptamd_scene_replace_desc;
+int ptamd_scene_replace(ptamd_context* ctx, const ptamd_scene_replace_desc* desc, ptamd_scene_rebuild_info* out /* may be NULL */);
+
 /* ---- Posing a scene from per-group transforms; moving its lights --------------------------------------------
  * The common animation is rigid: each mesh moves as a whole.  A ptamd_scene_rig keeps a scene's REST POSE on the device, cut into
  * groups of consecutive faces (group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]) in storage order; empty groups are
