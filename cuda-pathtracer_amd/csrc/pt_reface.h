@@ -111,6 +111,26 @@ struct RefaceParams {
 namespace ptamd {
 // Two kernels in stream order: the faces (one thread each), then one workgroup that folds the partials into `result`
 hipError_t launch_reface(const RefaceParams& r, hipStream_t stream);
+// ... the second of them alone, for another face pass that leaves the same partials (pt_rematerial.hip)
+hipError_t launch_reface_fold(const uint32_t* partials, uint32_t n_groups, uint32_t* result, hipStream_t stream);
 hipError_t resolve_reface_kernels();
+
+// the workgroup's OR of `not_flat` and minimum of `bad`, valid in thread 0: the one fold of every kernel that forms these two words
+__device__ __forceinline__ void rfc_fold_words(uint32_t (&so)[kRefitThreads], uint32_t (&sm)[kRefitThreads], uint32_t& not_flat, uint32_t& bad)
+{
+  so[threadIdx.x] = not_flat;
+  sm[threadIdx.x] = bad;
+  __syncthreads();
+  for (uint32_t h = kRefitThreads / 2u; h > 0u; h >>= 1) {
+    if (threadIdx.x < h) {
+      so[threadIdx.x] |= so[threadIdx.x + h];
+      const uint32_t other = sm[threadIdx.x + h];
+      if (other < sm[threadIdx.x]) sm[threadIdx.x] = other;
+    }
+    __syncthreads();
+  }
+  not_flat = so[0];
+  bad = sm[0];
+}
 }
 #endif

@@ -24,24 +24,6 @@ __device__ __forceinline__ void st4u(float* p, uint32_t a, uint32_t b, uint32_t 
   *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 }
 
-// the workgroup's OR of `not_flat` and minimum of `bad`, valid in thread 0
-__device__ __forceinline__ void fold_words(uint32_t (&so)[kRefitThreads], uint32_t (&sm)[kRefitThreads], uint32_t& not_flat, uint32_t& bad)
-{
-  so[threadIdx.x] = not_flat;
-  sm[threadIdx.x] = bad;
-  __syncthreads();
-  for (uint32_t h = kRefitThreads / 2u; h > 0u; h >>= 1) {
-    if (threadIdx.x < h) {
-      so[threadIdx.x] |= so[threadIdx.x + h];
-      const uint32_t other = sm[threadIdx.x + h];
-      if (other < sm[threadIdx.x]) sm[threadIdx.x] = other;
-    }
-    __syncthreads();
-  }
-  not_flat = so[0];
-  bad = sm[0];
-}
-
 } // namespace
 
 __global__ void __launch_bounds__(kRefitThreads) pt_reface_faces(const RefaceParams r)
@@ -79,7 +61,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_reface_faces(const RefacePar
     st4u(c + 8, 0u, 0u, 0u, w.texel[2]);
     st4u(c + 12, w.texel[3], 0u, 0u, 0u);
   }
-  fold_words(so, sm, not_flat, bad);
+  rfc_fold_words(so, sm, not_flat, bad);
   if (threadIdx.x == 0u) {
     r.partials[2u * blockIdx.x] = not_flat;
     r.partials[2u * blockIdx.x + 1u] = bad;
@@ -96,7 +78,7 @@ __global__ void __launch_bounds__(kRefitThreads) pt_reface_fold(const uint32_t* 
     const uint32_t b = partials[2u * g + 1u];
     if (b < bad) bad = b;
   }
-  fold_words(so, sm, not_flat, bad);
+  rfc_fold_words(so, sm, not_flat, bad);
   if (threadIdx.x == 0u) {
     result[0] = not_flat;
     result[1] = bad;
@@ -109,7 +91,12 @@ hipError_t launch_reface(const RefaceParams& r, hipStream_t stream)
 {
   const uint32_t groups = reface_groups(r.n_faces);
   hipLaunchKernelGGL(pt_reface_faces, dim3(groups), dim3(kRefitThreads), 0, stream, r);
-  hipLaunchKernelGGL(pt_reface_fold, dim3(1), dim3(kRefitThreads), 0, stream, r.partials, groups, r.result);
+  return launch_reface_fold(r.partials, groups, r.result, stream);
+}
+
+hipError_t launch_reface_fold(const uint32_t* partials, uint32_t n_groups, uint32_t* result, hipStream_t stream)
+{
+  hipLaunchKernelGGL(pt_reface_fold, dim3(1), dim3(kRefitThreads), 0, stream, partials, n_groups, result);
   return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include "pt_refit.h"
 #include "pt_refit_device.h"
 #include "pt_reface.h"
+#include "pt_rematerial.h"
 #include "pt_relink.h"
 #include "pt_morph.h"
 
@@ -137,6 +138,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_refit_kernels();
   if (e == hipSuccess) e = resolve_refit_device_kernels();
   if (e == hipSuccess) e = resolve_reface_kernels();
+  if (e == hipSuccess) e = resolve_rematerial_kernels();
   if (e == hipSuccess) e = resolve_rig_kernels();
   if (e == hipSuccess) e = resolve_relink_kernel();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);

@@ -3,6 +3,7 @@
 //   ptamd_context.cpp   last error, ptamd_create / ptamd_destroy, device utilities, counters, self-test, time stamps
 //   ptamd_scene.cpp     scene tables: upload (install_tree), release, reads, info and flatness queries; cubemaps; fill_scene
 //   ptamd_scene_update.cpp  what changes an uploaded scene: the updates of faces and lights, relink, rebuild, margins, quality
+//   ptamd_scene_materials.cpp  ptamd_scene_update_materials: materials, textures, texels and ids changed under a scene's id
 //   (host/scene_tables.cpp: the tables' host form and the ptamd_host_scene_* mirrors, without HIP)
 //   ptamd_rig.cpp       the scene rig: a scene posed from per-group transforms, skinned from per-corner bone weights, or morphed from
 //                       blend-shape targets, on the device
@@ -97,6 +98,13 @@ struct DeviceScene {
   ReadBack<float> margins;                       // kMarginWords floats a slot
   ReadBack<uint32_t> cull_count;                 // ptamd_scene_relink: the pairs it culled, one word a slot, on their way to tree.n_culled
   Upload<ptamd_light> lights_up;                 // ptamd_scene_update_lights: the new table's way to `lights`
+  // ptamd_scene_update_materials (ptamd_scene_materials.cpp): host copies of the two tables, by which a table the call keeps is
+  // validated against a resized blob and a texel range is known to touch no 1x1 map; the blob's size; a host range's way to `texels`
+  std::vector<ptamd_material> host_materials;
+  std::vector<ptamd_texture_desc> host_textures;
+  uint64_t n_texel_floats = 0;
+  Upload<float> texels_up;
+  size_t texels_up_bytes = 0;                    // a slot's size: a longer range drains the two slots and makes larger ones
 };
 
 struct DeviceCubemap {
@@ -238,6 +246,11 @@ int wait_for_readers(const ptamd_context* ctx, const DeviceScene& s, hipStream_t
 int device_array_checks(const char* who, const char* what, const ptamd_context* ctx, const void* p, size_t bytes, bool aligned16);
 int prepare_device_refit(const char* who, DeviceScene& s, RefitParams& r);
 int enqueue_device_refit(DeviceScene& s, RefitParams& r, const float* faces, hipStream_t stream, bool keep_links = false);
+// how the blocking calls (ptamd_scene_rebuild, _replace, _update_materials' tables path) wait before they build
+int rebuild_drain(const ptamd_context* ctx, DeviceScene& s, hipStream_t stream);
+// the material pass's part of the context's rebuild workspace for `n` faces: kRefaceResultWords result words with n id words behind
+// them (one copy brings both back), and the partials
+int material_pass_workspace(ptamd_context* ctx, uint32_t n, uint32_t** result, uint32_t** ids, uint32_t** partials);
 
 // ---- the sigmas of the denoiser and of the upsample (ptamd_denoise.cpp, ptamd_upsample.cpp)
 // sigma_n: 0 (the default, n_squarings left as it is) or a power of two in 1..256 = 2^n_squarings.  -0.0 compares equal to 0 and is

@@ -101,6 +101,12 @@ public:
     if (e == hipSuccess) valid_[slot] = true;
     return e;
   }
+  hipError_t drain() const   // the host waits for the copies out of both slots: the slots may then be replaced by larger ones
+  {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) if (valid_[i]) e = hipEventSynchronize(sent_[i].get());
+    return e;
+  }
 private:
   PinnedBuffer<T> h_[2];
   Event sent_[2];                          // the copy out of h_[i] has finished

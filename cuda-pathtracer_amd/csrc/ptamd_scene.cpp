@@ -185,6 +185,10 @@ int ptamd_upload_scene(ptamd_context* ctx, const ptamd_scene_desc* sc, uint32_t*
     for (uint32_t i = 0; i < sc->n_faces; ++i) d.material_ids[i] = sc->faces[i].material_id;
   }
   d.host_lights.assign(sc->lights, sc->lights + sc->n_lights);   // (every scene: ptamd_scene_update_lights recomputes the reach from them)
+  // ... and of what ptamd_scene_update_materials validates a new blob against and reads its skip rule from
+  d.host_materials.assign(sc->materials, sc->materials + sc->n_materials);
+  d.host_textures.assign(sc->textures, sc->textures + sc->n_textures);
+  d.n_texel_floats = sc->n_texel_floats;
   ctx->scenes.push_back(std::move(d));
   *out_scene_id = (uint32_t)ctx->scenes.size() - 1;
   return PTAMD_OK;

@@ -265,6 +265,17 @@ static int rebuild_workspace(ptamd_context* ctx, uint32_t n, bool build, bool fi
   return PTAMD_OK;
 }
 
+int material_pass_workspace(ptamd_context* ctx, uint32_t n, uint32_t** result, uint32_t** ids, uint32_t** partials)
+{
+  BuildParams p;
+  FinishParams f;
+  RefaceParams w;
+  std::memset(&w, 0, sizeof w);
+  const int rc = rebuild_workspace(ctx, n, false, false, p, f, &w);
+  *result = w.result; *ids = w.ids; *partials = w.partials;
+  return rc;
+}
+
 // The device builder (pt_build.hip) over `faces`, into the workspace.  handled = false: a node above the subtrees needs one of
 // partition's fallbacks, and the caller builds the same tree on the host.
 static int device_build(const BuildParams& p, const float* faces, hipStream_t stream, uint32_t& n_large, bool& handled)
@@ -358,7 +369,7 @@ static int rebuild_flag_checks(const char* who, uint32_t flags)
 
 // ... and how both block before they build: every reader of the scene, whatever the stream holds, and the copies earlier updates
 // left in flight
-static int rebuild_drain(const ptamd_context* ctx, DeviceScene& s, hipStream_t stream)
+int rebuild_drain(const ptamd_context* ctx, DeviceScene& s, hipStream_t stream)
 {
   int rc;
   if ((rc = prepare_margins(s)) != PTAMD_OK || (rc = wait_for_readers(ctx, s, stream)) != PTAMD_OK) return rc;

@@ -167,6 +167,10 @@ constexpr float kBoxMargin = 1e-3f; // absolute box inflation, DESIGN.md "Conser
 constexpr size_t kShadeFloats = 28;   // 7 float4 per face (pt_kernels.hip: resolve_hit).  Round 4 re-measured on the atrium: a 128-byte stride (one line per record) -1.2 %, a 64-byte hot half + 64-byte cold half (one line, 17 MB instead of 30) level, -0.6 % on textured scenes (profiles/r04_notes.md)
 constexpr uint32_t kMaxLeaf = 2;   // 2 / 3 / 4 = 10902 / 10839 / 10160 Msamples/s on the headline now that a box test costs 16 VALU and a triangle test ~67 (round 3, PTAMD_BVH_MAX_LEAF sweep: every bench configuration >= leaves of three)
 int validate_scene_desc(const ptamd_scene_desc* sc);
+// ... its rules for the texture descriptors against a blob of n_texel_floats floats, and for the materials against the texture
+// table, in `who`'s name: shared with ptamd_scene_update_materials, which brings tables of its own
+int validate_textures(const char* who, const ptamd_texture_desc* textures, uint32_t n_textures, uint64_t n_texel_floats);
+int validate_materials(const char* who, const ptamd_material* materials, uint32_t n_materials, const ptamd_texture_desc* textures, uint32_t n_textures);
 // The five tables a scene's geometry decides: the tree (binary nodes, leaf-major records, four-wide nodes), the storage-order
 // records and the shading records (flat scenes: the compact records behind them)
 struct SceneTables { Bvh bvh; std::vector<float> brute, shade; bool flat = false; };

@@ -4,6 +4,7 @@
 #include "ptamd_internal.h"
 #include "../csrc/pt_refit_device.h"
 #include "../csrc/pt_reface.h"
+#include "../csrc/pt_rematerial.h"
 
 #include <cstring>
 
@@ -60,18 +61,29 @@ int validate_scene_desc(const ptamd_scene_desc* sc)
   if (total != sc->n_faces) { set_error("ptamd_upload_scene: mesh_sizes do not sum to n_faces"); return PTAMD_ERR_ARG; }
   for (uint32_t i = 0; i < sc->n_faces; ++i)
     if (sc->faces[i].material_id >= sc->n_materials) { set_error("ptamd_upload_scene: face material_id out of range"); return PTAMD_ERR_ARG; }
-  for (uint32_t i = 0; i < sc->n_textures; ++i) {
-    const ptamd_texture_desc& t = sc->textures[i];
-    if (t.w < 1 || t.h < 1 || t.nb_chan < 1 || t.offset + (uint64_t)t.w * t.h * t.nb_chan > sc->n_texel_floats) {
-      set_error("ptamd_upload_scene: texture descriptor out of the texel blob");
+  const int rc = validate_textures("ptamd_upload_scene", sc->textures, sc->n_textures, sc->n_texel_floats);
+  return rc != PTAMD_OK ? rc : validate_materials("ptamd_upload_scene", sc->materials, sc->n_materials, sc->textures, sc->n_textures);
+}
+
+int validate_textures(const char* who, const ptamd_texture_desc* textures, uint32_t n_textures, uint64_t n_texel_floats)
+{
+  for (uint32_t i = 0; i < n_textures; ++i) {
+    const ptamd_texture_desc& t = textures[i];
+    if (t.w < 1 || t.h < 1 || t.nb_chan < 1 || t.offset + (uint64_t)t.w * t.h * t.nb_chan > n_texel_floats) {
+      set_error(std::string(who) + ": texture descriptor out of the texel blob");
       return PTAMD_ERR_ARG;
     }
   }
-  for (uint32_t i = 0; i < sc->n_materials; ++i) {
-    const ptamd_material& m = sc->materials[i];
-    if (m.diffuse_spec_map < 0 || (uint32_t)m.diffuse_spec_map >= sc->n_textures || sc->textures[m.diffuse_spec_map].nb_chan != 4 ||
-        (m.normal_map >= 0 && ((uint32_t)m.normal_map >= sc->n_textures || sc->textures[m.normal_map].nb_chan < 3))) {
-      set_error("ptamd_upload_scene: material texture id invalid (diffuse+spec must be 4-channel)");
+  return PTAMD_OK;
+}
+
+int validate_materials(const char* who, const ptamd_material* materials, uint32_t n_materials, const ptamd_texture_desc* textures, uint32_t n_textures)
+{
+  for (uint32_t i = 0; i < n_materials; ++i) {
+    const ptamd_material& m = materials[i];
+    if (m.diffuse_spec_map < 0 || (uint32_t)m.diffuse_spec_map >= n_textures || textures[m.diffuse_spec_map].nb_chan != 4 ||
+        (m.normal_map >= 0 && ((uint32_t)m.normal_map >= n_textures || textures[m.normal_map].nb_chan < 3))) {
+      set_error(std::string(who) + ": material texture id invalid (diffuse+spec must be 4-channel)");
       return PTAMD_ERR_ARG;
     }
   }
@@ -220,6 +232,32 @@ int ptamd_host_scene_rebuild_plan(const ptamd_scene_desc* sc, const ptamd_face* 
   const void* src[5] = { b.refit_groups.data(), b.refit_levels.data(), b.refit_sched.data(), b.wide_child.data(), counts };
   const uint64_t size[5] = { b.refit_groups.size() * 4u, b.refit_levels.size() * 4u, b.refit_sched.size() * 4u, b.wide_child.size() * 4u, sizeof counts };
   return sized_read(who, size[which], out, bytes, [&] { if (size[which]) std::memcpy(out, src[which], size[which]); return (int)PTAMD_OK; });
+}
+
+int ptamd_host_rematerial_table(const void* shade_in, uint32_t n_faces, const uint32_t* ids, const ptamd_material* materials, uint32_t n_materials,
+                                const ptamd_texture_desc* textures, uint32_t n_textures, const float* texels, uint64_t n_texel_floats, void* shade_out,
+                                uint32_t result[4])
+{
+  if (!result || (n_faces && (!shade_in || !shade_out)) || (n_materials && !materials) || (n_textures && !textures) || (n_texel_floats && !texels)) {
+    set_error("ptamd_host_rematerial_table: null argument or table");
+    return PTAMD_ERR_ARG;
+  }
+  // the kernel's loop (pt_rematerial.hip), face by face; its two reductions are an OR and a minimum
+  uint32_t not_flat = 0u, bad = kRfcNoBadFace;
+  const char* in = static_cast<const char*>(shade_in);
+  char* out = static_cast<char*>(shade_out);
+  for (uint32_t i = 0; i < n_faces; ++i) {
+    uint32_t old[kRmtGeneralWords], g[kRmtGeneralWords], c[kRmtCompactWords];
+    std::memcpy(old, in + (size_t)i * sizeof old, sizeof old);
+    const uint32_t id = ids ? ids[i] : rmt_kept_id(old[18]);
+    bool flat = true;
+    if (!rmt_face(old, id, n_materials, materials, textures, texels, g, c, flat) && i < bad) bad = i;
+    if (!flat) not_flat = 1u;
+    std::memcpy(out + (size_t)i * sizeof g, g, sizeof g);
+    std::memcpy(out + (size_t)n_faces * sizeof g + (size_t)i * sizeof c, c, sizeof c);
+  }
+  result[0] = not_flat; result[1] = bad; result[2] = 0u; result[3] = 0u;
+  return PTAMD_OK;
 }
 
 int ptamd_scene_desc_is_flat(const ptamd_scene_desc* sc, int32_t* out_flat)

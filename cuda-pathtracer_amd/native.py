@@ -89,6 +89,20 @@ class SceneReplaceDesc(C.Structure):        # ptamd_scene_replace_desc (include/
     _fields_ = [("scene_id", C.c_uint32), ("faces", C.c_void_p), ("n_faces", C.c_uint32), ("stream", C.c_void_p), ("flags", C.c_uint32)]
 
 
+MATERIALS_DEVICE_TEXELS = 1
+
+
+class SceneMaterialsDesc(C.Structure):      # ptamd_scene_materials_desc (include/ptamd.h): the tables are HOST arrays, material_ids a DEVICE address, texels either
+    _fields_ = [("scene_id", C.c_uint32), ("materials", C.POINTER(Material)), ("n_materials", C.c_uint32),
+                ("textures", C.POINTER(TextureDesc)), ("n_textures", C.c_uint32), ("texels", C.c_void_p),
+                ("texel_first", C.c_uint64), ("texel_count", C.c_uint64), ("n_texel_floats", C.c_uint64),
+                ("material_ids", C.c_void_p), ("stream", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class SceneMaterialsInfo(C.Structure):      # ptamd_scene_materials_info (include/ptamd.h)
+    _fields_ = [("flat_before", C.c_uint32), ("flat", C.c_uint32), ("asynchronous", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SceneRebuildInfo(C.Structure):        # ptamd_scene_rebuild_info (include/ptamd.h)
     _fields_ = [("device_builder", C.c_uint32), ("n_nodes", C.c_uint32), ("n_nodes4", C.c_uint32), ("depth", C.c_uint32),
                 ("quality", C.c_double)]
@@ -252,6 +266,9 @@ SIGNATURES = {
     "ptamd_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdateDeviceDesc)]),
     "ptamd_scene_rebuild": (C.c_int, [C.c_void_p, C.POINTER(SceneRebuildDesc), C.POINTER(SceneRebuildInfo)]),
     "ptamd_scene_replace": (C.c_int, [C.c_void_p, C.POINTER(SceneReplaceDesc), C.POINTER(SceneRebuildInfo)]),
+    "ptamd_scene_update_materials": (C.c_int, [C.c_void_p, C.POINTER(SceneMaterialsDesc), C.POINTER(SceneMaterialsInfo)]),
+    "ptamd_host_rematerial_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Material), C.c_uint32, C.POINTER(TextureDesc), C.c_uint32,
+                                              C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]),
     "ptamd_host_scene_rebuild": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_scene_plan_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_host_scene_rebuild_plan": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(Face), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import native as N
-from .scene import FACE_DTYPE, LIGHT_DTYPE, HostScene
+from .scene import FACE_DTYPE, LIGHT_DTYPE, MATERIAL_DTYPE, TEXTURE_DTYPE, HostScene
 from .native import UPSAMPLE_GUIDED, UPSAMPLE_BILINEAR
 
 POST_NONE, POST_GRAYSCALE, POST_SEPIA, POST_INVERT = 0, 1, 2, 3
@@ -171,6 +171,57 @@ class Context:
         info = N.SceneRebuildInfo()
         N.check(self._lib.ptamd_scene_replace(self._h, C.byref(d), C.byref(info)))
         return {n: getattr(info, n) for n, _ in N.SceneRebuildInfo._fields_}
+
+    def update_scene_materials(self, scene_id: int, materials=None, textures=None, texels=None, texel_first: int = 0,
+                               n_texel_floats: int = 0, material_ids=None, stream=None) -> dict:
+        """ptamd_scene_update_materials: what the scene's faces look like, changed under its id.  materials / textures: MATERIAL_DTYPE /
+        TEXTURE_DTYPE arrays that replace the tables (None: the table stays).  texels: float32 values that replace the blob's floats
+        from texel_first on, a numpy array (host) or a CUDA tensor (device, read in stream order); with n_texel_floats the blob's NEW
+        size, which texels then holds whole.  material_ids: a CUDA tensor of one 32-bit id per face (None: every face keeps its
+        id).  Texels alone: asynchronous on `stream`; anything else: a blocking call.  Returns ptamd_scene_materials_info as a dict
+        (flat_before, flat, asynchronous, reserved)."""
+        import torch
+        d = N.SceneMaterialsDesc()
+        d.scene_id = scene_id
+        keep = []
+        if materials is not None:
+            m = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE).reshape(-1)
+            keep.append(m)
+            d.materials = m.ctypes.data_as(C.POINTER(N.Material)) if len(m) else None; d.n_materials = len(m)
+        if textures is not None:
+            t = np.ascontiguousarray(textures, dtype=TEXTURE_DTYPE).reshape(-1)
+            keep.append(t)
+            d.textures = t.ctypes.data_as(C.POINTER(N.TextureDesc)) if len(t) else None; d.n_textures = len(t)
+        if texels is not None:
+            if isinstance(texels, torch.Tensor):
+                if not texels.is_cuda:
+                    raise ValueError("texels is a numpy array (host) or a tensor in device memory")
+                if texels.device.index != self.device:
+                    raise ValueError(f"the texels live on {texels.device}, the context on device {self.device}")
+                if texels.dtype != torch.float32 or not texels.is_contiguous():
+                    raise ValueError("device texels must be a contiguous float32 tensor")
+                d.texels = texels.data_ptr(); d.texel_count = texels.numel()
+                d.flags |= N.MATERIALS_DEVICE_TEXELS
+            else:
+                x = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1)
+                keep.append(x)
+                d.texels = x.ctypes.data; d.texel_count = x.size
+            d.texel_first = texel_first
+        d.n_texel_floats = n_texel_floats
+        if material_ids is not None:
+            if not isinstance(material_ids, torch.Tensor) or not material_ids.is_cuda:
+                raise ValueError("material_ids is a torch tensor in device memory")
+            if material_ids.device.index != self.device:
+                raise ValueError(f"the ids live on {material_ids.device}, the context on device {self.device}")
+            if material_ids.element_size() != 4 or material_ids.dim() != 1 or not material_ids.is_contiguous():
+                raise ValueError("material_ids must be a contiguous one-dimensional tensor of 32-bit ids")
+            if material_ids.numel() != self.scene_info(scene_id)["n_faces"]:
+                raise ValueError("material_ids must hold one id for each face of the scene")
+            d.material_ids = material_ids.data_ptr()
+        d.stream = _stream_handle(stream)
+        info = N.SceneMaterialsInfo()
+        N.check(self._lib.ptamd_scene_update_materials(self._h, C.byref(d), C.byref(info)))   # (host arrays are copied before the call returns)
+        return {n: getattr(info, n) for n, _ in N.SceneMaterialsInfo._fields_}
 
     def scene_rig(self, scene_id: int, host_scene, group_sizes=None) -> "SceneRig":
         """ptamd_scene_rig_create: a rig of the uploaded scene with `host_scene` (a HostScene or a FACE_DTYPE array) as its rest
@@ -617,6 +668,28 @@ def host_rebuild_tables(scene: HostScene, faces, host_builder=False) -> dict:
     out["scalars"] = out["scalars"].view(np.float32)
     out["quality"] = float(out["quality"].view(np.float64)[0])
     return out
+
+
+def host_rematerial_table(shade, n_faces: int, materials, textures, texels, ids=None):
+    """ptamd_host_rematerial_table (no GPU): the per-face step of ptamd_scene_update_materials over `shade` (bytes: n_faces general
+    records of 112 bytes; whatever lies behind them is not read) under the tables and `ids` (uint32 per face; None: the id in each
+    record).  Returns (bytes: n_faces general records, then n_faces compact ones; uint32[4] {not flat, lowest bad face, 0, 0})."""
+    src = np.ascontiguousarray(shade).view(np.uint8).reshape(-1)
+    if src.size < n_faces * 112:
+        raise ValueError("shade holds fewer than n_faces general records")
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE).reshape(-1)
+    t = np.ascontiguousarray(textures, dtype=TEXTURE_DTYPE).reshape(-1)
+    x = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1)
+    i = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    if i is not None and i.size != n_faces:
+        raise ValueError("ids must hold one word for each face")
+    out = np.zeros(n_faces * 176, np.uint8)
+    result = (C.c_uint32 * 4)()
+    N.check(N.load().ptamd_host_rematerial_table(src.ctypes.data, n_faces, None if i is None else i.ctypes.data,
+                                                 m.ctypes.data_as(C.POINTER(N.Material)) if len(m) else None, len(m),
+                                                 t.ctypes.data_as(C.POINTER(N.TextureDesc)) if len(t) else None, len(t),
+                                                 x.ctypes.data if x.size else None, x.size, out.ctypes.data, result))
+    return out, np.array(result[:], dtype=np.uint32)
 
 
 def _plan_tables(read) -> dict:

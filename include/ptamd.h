@@ -386,6 +386,86 @@ typedef struct {
 } ptamd_scene_replace_desc;
 int ptamd_scene_replace(ptamd_context* ctx, const ptamd_scene_replace_desc* desc, ptamd_scene_rebuild_info* out /* may be NULL */);
 
+/* ---- Other materials, other texels (DESIGN.md §13 "Other materials, other texels") --------------------------------------------
+ *
+ * Every call above keeps what a face looks like.  ptamd_scene_update_materials changes exactly that under the scene's id: the
+ * material table, the texture descriptors, the texel blob (a range of it, or a blob of another size) and the material_id of every
+ * face, in any combination, for a colour (in this format a 1x1 texel), an ior or a map that changes, a frame of an animated
+ * texture, or faces that take another material.  After the call the scene stands as a fresh ptamd_upload_scene would, given the
+ * scene's descriptor with these tables, blob and ids substituted, then taken through the same updates, rebuild or replace the scene
+ * has had.
+ *
+ * Changed: table 4 of ptamd_scene_table_read (the shading records; the compact records behind them by the size rule
+ * `flat ? +64 : 0` bytes per face), the device's material, texture and texel tables, flatness (ptamd_scene_is_flat, decided again by
+ * the rule of ptamd_scene_desc_is_flat) and with it the form a launch takes, the host's copy of the material ids.
+ * NOT changed, by a byte: tables 0 - 3, the link table, the plan, margins, quality and ptamd_scene_info; neither the scene's
+ * geometry serial nor its replace serial moves, so ptamd_denoise_temporal_motion does NOT cut its history: no face moved.  A caller
+ * that changes albedo abruptly resets the history itself.
+ *
+ * The material half of every shading record (words 18..27, the compact records' texels) is formed again ON THE DEVICE over the
+ * records the scene holds (csrc/pt_rematerial.hip; the per-face step of csrc/pt_rematerial.h, whose words are csrc/pt_reface.h's);
+ * words 0..17 are carried over, and the compact normals are taken from them.  The tree, the triangle records and the links are not
+ * read.  A face that keeps its id is read from word 18 of its record, which holds 30 bits of it: the call refuses a material table
+ * of more than 2^30 records.
+ *
+ * Two paths; out->asynchronous says which was taken.
+ *
+ * TEXELS ALONE (materials, textures and material_ids NULL, n_texel_floats 0; out->asynchronous = 1).  Asynchronous on `stream`
+ * and ordered against launches and other updates as ptamd_scene_update_lights is.  A HOST range is copied before the call returns
+ * (through pinned staging of the scene's own); a DEVICE range (PTAMD_MATERIALS_DEVICE_TEXELS) is read in stream order: whatever
+ * fills it is ordered before the call on `stream`, and it stays unmodified until the copy has run.  Flatness cannot change (no
+ * texel decides it), no id can become bad and nothing is read back.  Because a 1x1 map's texel is baked into the records, the
+ * face pass runs in place behind the copy, unless no material's 1x1 diffuse+specular map overlaps the range.  texel_count == 0
+ * succeeds and does nothing.
+ *
+ * ANYTHING ELSE (out->asynchronous = 0).  Blocks as ptamd_scene_replace does: waits for every reader and for `stream`.  The new
+ * tables are validated on the host by the upload's rules for textures and materials, against the new blob size (kept tables against
+ * a resized blob too); kept ids are checked against a smaller material count on the host before anything is launched.  New
+ * material, texture and texel buffers are made beside the old ones where they change, and always a new shading table with room
+ * for the compact records, n_faces * (112 + 64) bytes, as ptamd_scene_replace makes it; the face pass runs from the old records into
+ * the new ones; {not flat, lowest bad face} and the ids come back in one copy; only then is everything moved in together.  Any
+ * refusal or failure before the move leaves every table, the flatness and the ids as they were.
+ *
+ * Refused with PTAMD_ERR_ARG: null arguments; a released or out-of-range scene; unknown flag bits; a count without its table or a
+ * table without its count; a range that does not lie inside the blob (the new one, when n_texel_floats gives it a new size); a
+ * n_texel_floats with NULL texels, texel_first != 0 or texel_count != n_texel_floats; device pointers that are not device memory of
+ * the context's device, not aligned to 16 bytes or shorter than the call reads; a scene uploaded without materials; tables the
+ * upload would refuse, with its words; a material_id >= n_materials, found on the host for kept ids under a smaller table and on
+ * the device otherwise, before anything is moved: the message holds the word material_id and the lowest offending face index.
+ * With PTAMD_ERR_LIMIT: a capturing stream or a context that holds a captured launch; n_texel_floats >= 2^32; n_materials > 2^30.
+ * A scene whose tree is one of the knob-only forms IS accepted, as ptamd_scene_update_lights accepts it: no tree is touched.
+ *
+ * What it costs: scripts/gpu_materials.py measures both paths beside ptamd_scene_replace of the unchanged faces and beside release +
+ * upload; DESIGN.md §13 holds the figures.
+ *
+ * What follows for the other calls.  ptamd_scene_update checks material ids against the NEW ones; rigs stay valid (positions come
+ * from the rig, material words from the scene); ptamd_scene_replace forms its words from the new tables.  To give a scene new
+ * materials AND another number of faces, call this one first.
+ *
+ * The host definition needs no mirror of its own: it is a fresh upload of the changed descriptor (ptamd_host_scene_refit,
+ * ptamd_host_scene_rebuild).  ptamd_host_rematerial_table applies the per-face step the kernel applies, no device needed: shade_in
+ * holds n_faces general records (112 bytes each), ids n_faces words or NULL (word 18 of each record), shade_out receives n_faces
+ * general records and behind them n_faces compact ones (n_faces * 176 bytes; may not overlap shade_in), result the kernel's four
+ * words {1 when some face is not flat, the lowest face with a bad id or 0xFFFFFFFF, 0, 0}.  The tables are trusted as the kernel
+ * trusts them (validate them with an upload's rules first); a bad id indexes none. */
+#define PTAMD_MATERIALS_DEVICE_TEXELS 1u   /* texels is DEVICE memory, 16-byte aligned, read in stream order */
+typedef struct {
+  uint32_t scene_id;
+  const ptamd_material* materials;     uint32_t n_materials;   /* HOST; NULL (and 0): the table stays */
+  const ptamd_texture_desc* textures;  uint32_t n_textures;    /* HOST; NULL (and 0): the table stays */
+  const float* texels;                 /* HOST, or DEVICE with the flag; NULL: the blob stays */
+  uint64_t texel_first, texel_count;   /* texels[0 .. count) replace floats [first, first + count) of the blob */
+  uint64_t n_texel_floats;             /* 0: the blob keeps its size; else its NEW size: then first == 0 and count == this */
+  const uint32_t* material_ids;        /* DEVICE, n_faces words, 16-byte aligned; NULL: every face keeps its id */
+  void* stream;
+  uint32_t flags;
+} ptamd_scene_materials_desc;
+typedef struct { uint32_t flat_before, flat, asynchronous, reserved; } ptamd_scene_materials_info;
+int ptamd_scene_update_materials(ptamd_context* ctx, const ptamd_scene_materials_desc* desc, ptamd_scene_materials_info* out /* may be NULL */);
+int ptamd_host_rematerial_table(const void* shade_in, uint32_t n_faces, const uint32_t* ids /* NULL: word 18 */,
+                                const ptamd_material* materials, uint32_t n_materials, const ptamd_texture_desc* textures, uint32_t n_textures,
+                                const float* texels, uint64_t n_texel_floats, void* shade_out /* n_faces * 176 bytes */, uint32_t result[4]);
+
 /* ---- Posing a scene from per-group transforms; moving its lights --------------------------------------------
  * The common animation is rigid: each mesh moves as a whole.  A ptamd_scene_rig keeps a scene's REST POSE on the device, cut into
  * groups of consecutive faces (group g owns faces [sum(group_sizes[0..g)), + group_sizes[g]) in storage order; empty groups are
