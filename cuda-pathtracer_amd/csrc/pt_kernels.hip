@@ -27,7 +27,7 @@
 // A side unit compiles this source once more for restart kernels of its own and nothing else: pt_kernels_fma.hip (the contracted
 // instantiations, PT_FMA_BUILD) and pt_kernels_tight.hip (the flat deferring form's tight copy, PT_TIGHT_BUILD: in a unit of its own,
 // where its code cannot move the compiler's choices in the kernels of this one)
-#if defined(PT_FMA_BUILD) || defined(PT_TIGHT_BUILD)
+#if defined(PT_FMA_BUILD) || defined(PT_TIGHT_BUILD) || defined(PT_QUERY_BUILD)   /* (PT_QUERY_BUILD: pt_query.hip, for the walk functions alone) */
 #define PT_SIDE_UNIT 1
 #endif
 
@@ -3017,6 +3017,7 @@ static const void* const kBlockwiseEntries[2][2] = {
   { PT_FN(pt_megakernel_blockwise<false, false>), PT_FN(pt_megakernel_blockwise<false, true>) },
   { PT_FN(pt_megakernel_blockwise<true, false>), PT_FN(pt_megakernel_blockwise<true, true>) } };
 #endif
+#ifndef PT_QUERY_BUILD   /* (pt_query.hip names no megakernel: no entry table, no form) */
 #ifdef PT_FMA_BUILD
 constexpr bool kContracted = true;
 #else
@@ -3072,6 +3073,7 @@ uint32_t restart_wide_blocks_per_cu() { return (PT_RS4_WAVES_PER_EU * 256u) / PT
   else if (list) { f.cache_slot = kFormSlotRestartList; f.name = "restart (list form)"; }
   return f;
 }
+#endif
 
 #ifndef PT_SIDE_UNIT
 KernelForm megakernel_form(uint32_t kernel, bool lds_resident, bool stats, bool list, size_t lds_bytes, const KParams* p)
@@ -3238,7 +3240,7 @@ extern "C" void ptamd_fma_restart_form(int lds_resident, size_t lds_bytes, const
   *out = ptamd::restart_form(lds_resident != 0, false, false, lds_bytes, p);
 }
 namespace ptamd {
-#else
+#elif defined(PT_TIGHT_BUILD)
 } // namespace (ptamd_tight in this translation unit)
 // The one C entry point of pt_kernels_tight.hip: the entry of a tight form, for restart_entry_of
 extern "C" const void* ptamd_tight_restart_entry(int variant, int lds_resident)

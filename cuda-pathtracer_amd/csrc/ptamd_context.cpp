@@ -7,6 +7,7 @@
 #include "pt_rematerial.h"
 #include "pt_relink.h"
 #include "pt_morph.h"
+#include "pt_query.h"
 
 #include <cstring>
 #include <memory>
@@ -141,6 +142,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_rematerial_kernels();
   if (e == hipSuccess) e = resolve_rig_kernels();
   if (e == hipSuccess) e = resolve_relink_kernel();
+  if (e == hipSuccess) e = resolve_query_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

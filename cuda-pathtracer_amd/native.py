@@ -139,6 +139,18 @@ class SceneLightsDesc(C.Structure):         # ptamd_scene_lights_desc (include/p
     _fields_ = [("scene_id", C.c_uint32), ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class QueryDesc(C.Structure):               # ptamd_query_desc (include/ptamd.h): every pointer is a DEVICE address
+    _fields_ = [("scene_id", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32), ("walk", C.c_uint32), ("n", C.c_uint32),
+                ("rays", C.c_void_p), ("t_range", C.c_void_p), ("hits", C.c_void_p), ("uv", C.c_void_p), ("occluded", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
+QUERY_NEAREST, QUERY_ANY = 0, 1
+QUERY_NO_LIGHTS = 1
+QUERY_WALK_AUTO, QUERY_WALK_EVERY_FACE, QUERY_WALK_BINARY, QUERY_WALK_WIDE, QUERY_WALK_RESIDENT = 0, 1, 2, 3, 4
+QUERY_MAX_RAYS = 1 << 28
+
+
 class SceneQualityInfo(C.Structure):        # ptamd_scene_quality_info (include/ptamd.h)
     _fields_ = [("built", C.c_double), ("now", C.c_double)]
 
@@ -329,6 +341,9 @@ SIGNATURES = {
     "ptamd_host_origin_reach": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(Light), C.c_uint32, C.POINTER(C.c_float)]),
     "ptamd_trace_rays_queue": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.POINTER(C.c_uint32)]),
+    "ptamd_query_rays": (C.c_int, [C.c_void_p, C.POINTER(QueryDesc)]),
+    "ptamd_host_query_rays": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(Light), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptamd_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseDesc)]),
     "ptamd_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -481,6 +481,55 @@ class Context:
                                                  _stream_handle(stream), C.byref(waves)))
         return int(waves.value)
 
+    def query_rays(self, scene_id: int, rays, t_range=None, mode: str = "nearest", lights: bool = True, walk="auto", hits=None, uv=None,
+                   occluded=None, stream=None):
+        """ptamd_query_rays: nearest hit or occlusion for rays in device memory; asynchronous on `stream`.  rays float32[n, 6] =
+        {dir, origin} and t_range float32[n, 2] = {t_min, t_max} (optional) are CUDA tensors.  mode "nearest" returns (hits
+        int32[n, 4] = kind, index, t bits, 0; uv float32[n, 2]), mode "any" returns occluded (torch.bool or uint8 [n]); outputs the
+        caller did not pass are allocated.  lights=False: PTAMD_QUERY_NO_LIGHTS.  walk: "auto", "every_face", "binary", "wide", "resident"
+        or the number."""
+        import torch
+        modes = {"nearest": N.QUERY_NEAREST, "any": N.QUERY_ANY}
+        walks = {"auto": N.QUERY_WALK_AUTO, "every_face": N.QUERY_WALK_EVERY_FACE, "binary": N.QUERY_WALK_BINARY, "wide": N.QUERY_WALK_WIDE,
+                 "resident": N.QUERY_WALK_RESIDENT}
+        if mode not in modes:
+            raise ValueError('mode is "nearest" or "any"')
+        if isinstance(walk, str) and walk not in walks:
+            raise ValueError(f"walk is one of {sorted(walks)} or a number")
+
+        def device(name, t, dtypes, width):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name} must be a tensor in the memory of device {self.device}")
+            if t.dtype not in dtypes or not t.is_contiguous() or t.numel() != n * width:
+                raise ValueError(f"{name} must be contiguous, {' or '.join(str(x) for x in dtypes)}, {n} x {width}")
+            return t.data_ptr()
+
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be a float32 tensor of shape (n, 6)")
+        n = int(rays.shape[0])
+        dev = rays.device
+        d = N.QueryDesc()
+        d.scene_id, d.mode, d.flags = scene_id, modes[mode], 0 if lights else N.QUERY_NO_LIGHTS
+        d.walk = walks[walk] if isinstance(walk, str) else int(walk)
+        d.n = n
+        d.rays = device("rays", rays, (torch.float32,), 6)
+        d.t_range = device("t_range", t_range, (torch.float32,), 2) if t_range is not None else None
+        d.stream = _stream_handle(stream)
+        if mode == "any":
+            if occluded is None:
+                occluded = torch.empty(n, dtype=torch.bool, device=dev)
+            d.occluded = device("occluded", occluded, (torch.bool, torch.uint8), 1)
+            N.check(self._lib.ptamd_query_rays(self._h, C.byref(d)))
+            return occluded
+        if hits is None:
+            hits = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        if uv is None:
+            uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        d.hits = device("hits", hits, (torch.int32,), 4)
+        d.uv = device("uv", uv, (torch.float32,), 2)
+        N.check(self._lib.ptamd_query_rays(self._h, C.byref(d)))
+        return hits, uv
+
     def release_captured(self, stream=None) -> None:
         """The graphs captured on `stream` are gone: its sample slab and ring slots are no longer pinned (ptamd_release_captured)."""
         N.check(self._lib.ptamd_release_captured(self._h, _stream_handle(stream)))
@@ -744,6 +793,31 @@ def host_bvh_refit_trace(scene_a: HostScene, scene_b: HostScene, rays: np.ndarra
                                                 rays.ctypes.data_as(C.POINTER(C.c_float)), len(rays),
                                                 out[0].ctypes.data_as(C.POINTER(C.c_int32)), out[1].ctypes.data_as(C.POINTER(C.c_int32))))
     return out[0], out[1]
+
+
+def host_query_rays(faces, lights, rays, t_range=None, mode: str = "nearest", use_lights: bool = True):
+    """ptamd_host_query_rays (no GPU), the definition of Context.query_rays: every face, then every light.  faces: FACE_DTYPE array
+    (or a HostScene, whose lights are then the default), lights: LIGHT_DTYPE array or None, rays float32[n, 6], t_range
+    float32[n, 2] or None.  mode "nearest": (hits int32[n, 4], uv float32[n, 2]); mode "any": occluded uint8[n]."""
+    if isinstance(faces, HostScene):
+        lights = faces.lights if lights is None else lights
+        faces = faces.faces
+    faces = np.ascontiguousarray(faces, dtype=FACE_DTYPE)
+    lights = np.ascontiguousarray(lights if lights is not None else np.zeros(0, LIGHT_DTYPE), dtype=LIGHT_DTYPE)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = len(rays)
+    if t_range is not None:
+        t_range = np.ascontiguousarray(t_range, dtype=np.float32).reshape(-1, 2)
+        if len(t_range) != n:
+            raise ValueError("t_range must hold one {t_min, t_max} per ray")
+    if mode not in ("nearest", "any"):
+        raise ValueError('mode is "nearest" or "any"')
+    hits, uv, occ = np.zeros((n, 4), np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+    N.check(N.load().ptamd_host_query_rays(faces.ctypes.data_as(C.POINTER(N.Face)), len(faces), lights.ctypes.data_as(C.POINTER(N.Light)),
+                                           len(lights), N.QUERY_ANY if mode == "any" else N.QUERY_NEAREST, 0 if use_lights else N.QUERY_NO_LIGHTS,
+                                           rays.ctypes.data, t_range.ctypes.data if t_range is not None else None, n,
+                                           hits.ctypes.data, uv.ctypes.data, occ.ctypes.data))
+    return occ if mode == "any" else (hits, uv)
 
 
 def host_bvh_trace(scene: HostScene, rays: np.ndarray):

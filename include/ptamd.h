@@ -912,6 +912,70 @@ int ptamd_trace_rays(ptamd_context* ctx, uint32_t scene_id, uint32_t kernel,
 int ptamd_trace_rays_queue(ptamd_context* ctx, uint32_t scene_id, const float* rays_dev, uint32_t n, int32_t* out_dev, uint32_t config,
                            uint32_t refill_min, void* stream, uint32_t* out_waves_per_cu);
 
+/* ---- Ray queries from device memory: nearest hit and occlusion -------------------------------------------
+ *
+ * ptamd_query_rays answers n rays that lie in DEVICE memory against an uploaded scene, asynchronously on `stream`, and writes
+ * the answers to device memory: what a host needs for picking, line of sight, collision probes and shadow or visibility baking
+ * from the tree the update calls keep current.  ptamd_host_query_rays is its definition, no device needed: every face in
+ * storage order, then every light, the reference's intersect() search loops (intersection.cuh:179-212) with the two constants
+ * of its accept rule made per-ray.  The device result equals the host's bit for bit for EVERY bit pattern of ray and range.
+ *
+ *   rays     n * {dir.xyz, origin.xyz}, the layout of ptamd_trace_rays.  Directions need not be unit vectors; t is in units
+ *            of the direction's length.
+ *   t_range  n * {t_min, t_max}, or NULL.  Per ray lo = t_min > 0 ? t_min : 0 and limit = t_max < 100000 ? t_max : 100000:
+ *            a NaN, infinite or larger t_max means the reference's MAX_DIST (100000), a NaN or negative t_min means 0.
+ *            NULL: (0, MAX_DIST) for every ray.
+ *   accept   the search starts with best = limit.  A face is accepted when the reference's triangle test accepts it and
+ *            t < best && t > lo; with PTAMD_QUERY_NO_LIGHTS clear a light sphere is accepted, after the faces, when the
+ *            reference's sphere test returns true and t < best && t >= lo (the reference's own asymmetry).
+ *            The triangle test is ONE-SIDED, as the reference's is (det < 1e-7 rejects): a back-facing triangle neither is
+ *            hit nor occludes.
+ *   NEAREST  hits: n * {kind, index, t bits, 0}, the record of ptamd_trace_rays: kind 0 nothing (index -1, t = limit),
+ *            1 a face, 2 a light; index is the face's position in the face array the scene was last given (upload, update
+ *            or replace) or the light's.  uv (may be NULL): n * {u, v}, the barycentrics of a face hit, 0 otherwise.
+ *            With t_range == NULL and no flag the records are the reference's intersect() for every ray.
+ *   ANY      occluded: n bytes, 1 exactly when NEAREST over the same ray and range would return kind != 0, else 0.  The
+ *            walk stops at the first accepted face or sphere and never enters a box beyond limit.
+ *   walk     PTAMD_QUERY_WALK_AUTO chooses by scene and n (csrc/pt_query.h: query_auto_walk).  The others force a form:
+ *            _EVERY_FACE tests every face (the definition itself); _BINARY walks the binary tree from L2 (any scene); _WIDE the
+ *            four-wide tree with a stack in LDS (scenes that have one: ptamd_scene_info.n_nodes4 != 0); _RESIDENT stages the
+ *            scene in LDS once per persistent workgroup (scenes that are LDS-resident: ptamd_scene_info.lds_bytes_bvh <= 64 KB,
+ *            at most 896 nodes and 2047 triangle records).  The answer does not depend on the walk: PER RAY, an origin whose
+ *            max-axis |coordinate| o fails (o + extent) * 2^-21 <= margin_floor (ptamd_host_origin_reach; a NaN fails it), or
+ *            a direction with a NaN or infinite component, takes the every-face path inside the kernel.
+ *
+ * The call reads the scene's tables like ptamd_render_features: it is ordered against the scene's updates by stream order (issue
+ * it on the update's stream, or behind an event), settles margins that are pending behind ptamd_scene_update_device first and is
+ * refused with PTAMD_ERR_LIMIT where that would need a host wait inside a capture.  With margins settled it enqueues one kernel
+ * and nothing else (no allocation, no synchronisation, no state of the context written), so it can be captured into a graph and
+ * calls on different streams of one context may be in flight together.
+ * PTAMD_ERR_ARG, before anything is enqueued: null context or descriptor; a bad or released scene id; an unknown mode, flag or
+ * walk; PTAMD_QUERY_WALK_WIDE on a scene with no four-wide tree and PTAMD_QUERY_WALK_RESIDENT on one that is not LDS-resident;
+ * n > 2^28 (decided from the count alone); rays, t_range (when given) or the mode's outputs (hits for NEAREST, occluded for
+ * ANY; uv when given) that are null, not device memory of the context's device, smaller than the call reads or writes, or not
+ * aligned to their element (rays and t_range 4 bytes, uv 8, hits 16).  n == 0 is PTAMD_OK and touches nothing. */
+enum { PTAMD_QUERY_NEAREST = 0, PTAMD_QUERY_ANY = 1 };
+enum { PTAMD_QUERY_NO_LIGHTS = 1u };   /* flags */
+enum { PTAMD_QUERY_WALK_AUTO = 0, PTAMD_QUERY_WALK_EVERY_FACE = 1, PTAMD_QUERY_WALK_BINARY = 2,
+       PTAMD_QUERY_WALK_WIDE = 3, PTAMD_QUERY_WALK_RESIDENT = 4 };
+#define PTAMD_QUERY_MAX_RAYS (1u << 28)
+typedef struct {
+  uint32_t scene_id, mode, flags, walk;
+  uint32_t n;               /* <= PTAMD_QUERY_MAX_RAYS */
+  const float* rays;        /* DEVICE, n * {dir.xyz, origin.xyz} */
+  const float* t_range;     /* DEVICE, n * {t_min, t_max}, or NULL */
+  int32_t* hits;            /* DEVICE, NEAREST: n * {kind, index, t bits, 0} */
+  float* uv;                /* DEVICE, NEAREST, may be NULL: n * {u, v} */
+  uint8_t* occluded;        /* DEVICE, ANY: n bytes, 1 or 0 */
+  void* stream;
+} ptamd_query_desc;
+int ptamd_query_rays(ptamd_context* ctx, const ptamd_query_desc* desc);
+/* The definition.  Host pointers; hits / uv are written in NEAREST mode (uv may be NULL), occluded in ANY mode.  PTAMD_ERR_ARG
+ * for an unknown mode or flag, n > 2^28 and a null pointer where a count says there is something behind it. */
+int ptamd_host_query_rays(const ptamd_face* faces, uint32_t n_faces, const ptamd_light* lights, uint32_t n_lights,
+                          uint32_t mode, uint32_t flags, const float* rays, const float* t_range, uint32_t n,
+                          int32_t* hits, float* uv, uint8_t* occluded);
+
 /* Host mirror of the device BVH walk (same node/triangle records, same float operations),
  * so the builder's "equals brute force" contract can be tested without a GPU.  This is a
  * test hook for the acceleration structure only; it renders nothing.
