@@ -5,7 +5,8 @@
 // The body is compiled for what the form's launches are (pt_device.h: restart_select, restart_shipped_launch): an LDS-resident flat
 // scene with a skip table, a static camera, deferring rounds, the pools in LDS, no XCD regions, no interleaved bands, no list, no
 // stamps, no counters.  It holds none of the template body's alternatives.  Every floating-point operation of a path is the shared
-// code's (path_begin, traverse_round_tight, nearest_lights, path_post); what differs is integer, address and control work:
+// code's (path_begin, traverse_round_tight, nearest_lights, and path_post's as pt_tight_shade.h restates them: the form's shading
+// half is its own too); what differs is integer, address and control work:
 //   * park by offset: a lane that restarts forms the 32-bit byte offset of its sample behind samples_out (pt_tight_tiles.h: twelve
 //     times the sample's slot) and carries it in Path::xy, where the template's body carries x and y; Path::bk holds the bounce index
 //     alone.  The park is that offset added to the slab's base and one store: no 64-bit address arithmetic, no multiply, and the row
@@ -20,6 +21,8 @@
 // Tickets are handed out as in the template body, in the same order, from the same heads.
 #pragma once
 // (pt_tight_tiles.h, the slot arithmetic, comes in with pt_device.h, outside the namespace this header is included in)
+
+#include "pt_tight_shade.h"
 
 static_assert(PT_TILE_W == PT_TT_TILE && PT_TILE_H == PT_TT_TILE, "pt_tight_tiles.h states the tile as 8 x 8");
 
@@ -78,6 +81,7 @@ pt_megakernel_restart<true, PT_RS_FLAT_SKIP_TIGHT>(PT_KERNEL_PARAMS)
   // the two divisors of a tile's number are launch constants: their reciprocals (pt_tight_tiles.h: tight_div) are formed once per wave
   const uint32_t m_tiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)tight_div_magic(PT_KARG(p, n_tiles)));
   const uint32_t m_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)tight_div_magic(PT_KARG(p, tiles_x)));
+  const char* records = tight_records(p);   // where the hits' records lie: a launch constant too
   for (;;) {
     // ---- restart lanes without a path from the pool.  One site takes an entry; the pool's refill, all lanes active, sits in front of
     // it as the cold case.  (Leaving the loop at once where the pool had a path for every idle lane, without the second ballot, gave
@@ -151,11 +155,16 @@ pt_megakernel_restart<true, PT_RS_FLAT_SKIP_TIGHT>(PT_KERNEL_PARAMS)
         // the iteration's first variate (raytrace.cu:70) is drawn here, after the search: intersect() draws nothing, so the
         // path's random stream is the same, and r1 need not live across the walk
         const float r1 = path_pre<true>(p, st);
+        // ... and the second one (raytrace.cu:100) with it, by every lane: pt_tight_shade.h says why
+        const uint32_t v0_before = st.rng.v0;
+        const float r2 = xorwow_uniform(st.rng);
         Nearest n;
         n.t = best.t; n.u = best.u; n.v = best.v; n.idx = best.idx;
         n = nearest_lights(p, st.o, st.d, n);
-        Counters cnt = {};
-        if (path_post<false, true, true>(p, st, r1, n, cnt)) {
+        // (the walk's result is dead here, the next walk starts from a fresh one: handing it the light loop's lets the loop run on
+        // the walk's own registers, without a copy of the distance and the index in front of it)
+        best.t = n.t; best.idx = n.idx;
+        if (tight_shade(p, records, st, r1, r2, v0_before, n)) {
           tight_park(p, st.xy, st.acc);
           st.xy = PT_TIGHT_IDLE;
         }

@@ -9,7 +9,8 @@ one (PT_RS_FLAT: flat scenes under a uniform environment), VARIANT=9 / 10 the sk
 (PT_RS_FLAT_SKIP_TIGHT), which is compiled in a unit of its own, pt_kernels_tight.hip: its counts come from that unit's listing.
 The tight form's kernel body is its own (pt_tight_body.h, an explicit specialisation): its regions carry the same names, from
 anchors in that header (TIGHT_MARKS), and one more, restart_begin, which parts the restart step and the refill from the staging
-in front of them; path_post's regions are the shared function's."""
+in front of them; so is its shading half (pt_tight_shade.h), whose regions carry path_post's names, from anchors of its own
+(TIGHT_SHADE_MARKS)."""
 import os, re, sys, collections
 from kernel_listing import CSRC, listing
 SRC = os.path.join(CSRC, "pt_kernels.hip")
@@ -33,15 +34,25 @@ TIGHT_MARKS = [
     ("    if (st.xy != PT_TIGHT_IDLE) {\n      if (node == 0xFFFFu) {", "round_begin"),
     ("      traverse_round_tight(s_nodes, s_tris, reinterpret_cast<const uint32_t*>(s_mem)", "traverse_begin"),
     ("      if (node == 0xFFFFu) {\n        // the iteration's first variate", "traverse_end"),
-    ("        if (path_post<false, true, true>(p, st, r1, n, cnt)) {", "lights_end"),
     ("          tight_park(p, st.xy, st.acc);\n          st.xy = PT_TIGHT_IDLE;", "post_end"),
+]
+TIGHT_SHADE = "pt_tight_shade.h"      # the tight form's own shading half, included by its body: path_post's regions, from anchors of its own.
+# A region is named for what the shared function holds under that name: lights_end the hit's decode, resolve_end the misses' tail,
+# miss_end the BSDF sample, bsdf_end the roulette.  The tail stands in front of the decode in this source, so resolve_end comes first
+# (regions() takes the markers in the listing's order), and traverse_end, the light loop, runs up to it.
+TIGHT_SHADE_MARKS = [
+    ("  if (!found) {\n    const f3 env = mk3(", "resolve_end"),
+    ("  f3 normal, direct_light;", "lights_end"),
+    # (this marker holds the normal: without it the compiler starts the BSDF sample's reflection, 18 VALU, inside the decode's region)
+    ("  // the BSDF sample (raytrace.cu:88-120), ior 1\n", "miss_end", '"+v"(normal.x), "+v"(normal.y), "+v"(normal.z)'),
+    ("  // the roulette (raytrace.cu:183-192)\n", "bsdf_end"),
 ]
 
 
 def mark(s, marks):
-    for anchor, name in marks:
+    for anchor, name, *held in marks:   # held: output operands the marker pins, so that what is computed from them stays behind it
         assert s.count(anchor) == 1, (name, s.count(anchor))
-        s = s.replace(anchor, 'asm volatile("; PT_MARK %s" ::: "memory");\n' % name + anchor)
+        s = s.replace(anchor, 'asm volatile("; PT_MARK %s" : %s :: "memory");\n' % (name, held[0] if held else "") + anchor)
     return s
 
 
@@ -54,7 +65,10 @@ def marked_listing(tight=False):
     unit = open(os.path.join(CSRC, TIGHT_UNIT)).read()
     body = '#include "%s"\n' % TIGHT_BODY
     assert s.count(body) == 1
-    s = s.replace(body, mark(open(os.path.join(CSRC, TIGHT_BODY)).read(), TIGHT_MARKS))
+    tight = mark(open(os.path.join(CSRC, TIGHT_BODY)).read(), TIGHT_MARKS)
+    shade = '#include "%s"\n' % TIGHT_SHADE
+    assert tight.count(shade) == 1
+    s = s.replace(body, tight.replace(shade, mark(open(os.path.join(CSRC, TIGHT_SHADE)).read(), TIGHT_SHADE_MARKS)))
     include = '#include "pt_kernels.hip"\n'
     assert unit.count(include) == 1
     return listing(TIGHT_UNIT, unit.replace(include, s)).split("\n")
