@@ -234,6 +234,8 @@ int ptamd_device_alloc(ptamd_context* ctx, size_t bytes, void** out)
   if (!ctx || !out) { set_error("ptamd_device_alloc: null argument"); return PTAMD_ERR_ARG; }
   PT_HIP(hipSetDevice(ctx->device));
   PT_HIP(hipMalloc(out, bytes ? bytes : 16));
+  const int fill = alloc_fill_byte();   // tuning knob PTAMD_ALLOC_FILL: the one place a test reads the fill back
+  if (fill >= 0) PT_HIP(fill_new(*out, fill, bytes ? bytes : 16, false));
   return PTAMD_OK;
 }
 

@@ -6,10 +6,22 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ptamd_tuning.h"
+
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace ptamd {
+
+// Under PTAMD_ALLOC_FILL (ptamd_tuning.h): every byte of a new allocation set to `byte`, on the device before this returns (the
+// fill goes to the null stream, which the context's own streams do not wait for: hence the device-wide wait)
+inline hipError_t fill_new(void* p, int byte, size_t bytes, bool pinned)
+{
+  if (pinned) { std::memset(p, byte, bytes); return hipSuccess; }
+  const hipError_t e = hipMemset(p, byte, bytes);
+  return e != hipSuccess ? e : hipDeviceSynchronize();
+}
 
 // One allocation of T's: device memory (hipMalloc / hipFree) or pinned host memory (hipHostMalloc / hipHostFree)
 template <typename T, bool Pinned>
@@ -25,8 +37,9 @@ public:
     reset();
     void** p = reinterpret_cast<void**>(&p_);
     const hipError_t e = Pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-    if (e != hipSuccess) p_ = nullptr;
-    return e;
+    if (e != hipSuccess) { p_ = nullptr; return e; }
+    const int fill = alloc_fill_byte();   // tuning knob PTAMD_ALLOC_FILL; off (-1): no call beyond the allocation
+    return fill < 0 ? hipSuccess : fill_new(p_, fill, bytes, Pinned);
   }
   void reset() { if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; }
   T* get() const { return p_; }

@@ -14,6 +14,16 @@ const char* tuning_env(const char* name)
   return std::getenv(name);
 }
 
+int alloc_fill_byte()
+{
+  const char* e = tuning_env("PTAMD_ALLOC_FILL");
+  if (!e || !*e) return -1;
+  char* end = nullptr;
+  const long v = std::strtol(e, &end, 10);
+  if (*end || v < 0 || v > 255) return -1;   // (not clamped: a test that asks for a byte it cannot have runs unfilled, and says so)
+  return (int)v;
+}
+
 namespace {
 
 enum KnobKind {

@@ -1,7 +1,7 @@
 // ptamd_tuning.h — the tuning knobs a context reads once, at ptamd_create (ptamd_tuning.cpp: one table, one parser; no HIP, so
 // tests/test_tuning_knobs_cpu.py runs it on the host).  Each is an environment variable honoured only behind PTAMD_TUNING=1
 // (ptamd_internal.h: tuning_env).  The knobs read per call (PTAMD_STACK_LDS, PTAMD_TRACE_STACK, the builder's) are not here:
-// they take effect at the call that reads them.
+// they take effect at the call that reads them.  PTAMD_ALLOC_FILL, read at every allocation, has its parser below.
 #pragma once
 
 #include "ptamd.h"
@@ -39,5 +39,10 @@ struct TuningSettings {
 
 // The defaults above, then every knob the environment sets (behind PTAMD_TUNING=1)
 void read_tuning_knobs(TuningSettings& s);
+
+// PTAMD_ALLOC_FILL=<0..255>, read at each allocation (ptamd_owners.h: Buffer::alloc; ptamd_device_alloc): the byte every new
+// allocation of the library is filled with, so that a test decides what a kernel finds in memory no one has written yet.
+// -1 (off) when the knob or the gate is unset, and for an empty value, one that is no decimal number or one outside 0..255.
+int alloc_fill_byte();
 
 } // namespace ptamd

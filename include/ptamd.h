@@ -1306,7 +1306,14 @@ int ptamd_host_adaptive_select(const ptamd_adaptive_desc* desc, const uint32_t* 
 /* The frame number of the context's last ptamd_raytrace (raytrace.cu:296's `seed`): the divisor of its resolve. */
 int ptamd_get_frame_counter(ptamd_context* ctx, uint32_t* out);
 
-/* Plain device-memory helpers so that C/C++ hosts need not link HIP themselves. */
+/* Plain device-memory helpers so that C/C++ hosts need not link HIP themselves.
+ *
+ * With PTAMD_TUNING=1: PTAMD_ALLOC_FILL=<0..255> fills every allocation the library makes from then on, ptamd_device_alloc's
+ * included, with that byte before the allocating call goes on (device memory: a fill and a device-wide wait; the pinned
+ * staging slots: a memset), so that the suite decides what a kernel finds in memory nobody has written yet
+ * (tests/test_alloc_fill_gpu.py).  It is read at each allocation, not at ptamd_create.  An empty value, one that is
+ * no decimal number and one outside 0..255 leave the knob off; off, an allocation makes no call beyond the allocation itself.
+ * The fill goes to the null stream: not for calls on a capturing stream. */
 int ptamd_device_alloc(ptamd_context* ctx, size_t bytes, void** out);
 int ptamd_device_free(ptamd_context* ctx, void* p);
 int ptamd_device_memset(ptamd_context* ctx, void* p, int value, size_t bytes, void* stream);

@@ -420,9 +420,28 @@ class Rays:
 
 # ---------------------------------------------------------------- what the readers must answer, and the comparisons
 
-def expected(P, O, hs, rays, t_range, frame=True):
+_expected = {}
+
+
+def expected(P, O, hs, rays, t_range, frame=True, key=None):
     """What every reader must answer for the descriptor `hs`: the oracle's frame, the query mirror's records, and what
-    host_scene_tables states of tables 3 and 4 (the compact records behind table 4's general ones only while the scene is flat)."""
+    host_scene_tables states of tables 3 and 4 (the compact records behind table 4's general ones only while the scene is flat).
+    key: (sequence index, step) of a caller that takes a Model along a sequence of sequences(): the model is a function of the two, so
+    the answer is computed once per key and handed out again, its arrays read-only (a second run of the sequence, under other
+    contents of fresh device memory, costs device time only)."""
+    if key is not None and (key, frame) in _expected:
+        return _expected[key, frame]
+    out = _compute_expected(P, O, hs, rays, t_range, frame)
+    if key is not None:
+        for v in out.values():
+            for a in (v if isinstance(v, tuple) else (v,)):
+                if isinstance(a, np.ndarray):
+                    a.setflags(write=False)
+        _expected[key, frame] = out
+    return out
+
+
+def _compute_expected(P, O, hs, rays, t_range, frame):
     out = {}
     if frame:
         out["frame"] = O.render(O.OracleScene.from_host_scene(hs, P.cubemap_from_color()), O.camera_from_record(hs.camera), *SIZE, spp=SPP, bounces=BOUNCES)

@@ -177,7 +177,7 @@ def run_sequence(P, O, ctx, index):
             rays_np = rs.aimed_at(model.lights)
             rays = torch.from_numpy(rays_np).cuda()
         hs, lay = model.scene(), model.layout()
-        want = S.expected(P, O, hs, rays_np, rs.t_range)
+        want = S.expected(P, O, hs, rays_np, rs.t_range, key=(index, step))
         walks, resident, si = dev.allows()
         assert resident == lay["resident"], (what, si, lay)
         if info is not None:
