@@ -47,8 +47,8 @@ PT_DEV f3 normalize(f3 v) { float inv_len = 1.0f / __builtin_sqrtf(dot(v, v)); r
 #define PT_SHORT_MATH 1   /* 0: the compiler's full sqrt / division everywhere (A/B: scripts/build_variants.sh x="-DPT_SHORT_MATH=0" + scripts/gpu_ab.sh) */
 #endif
 // ---- short forms of the two IEEE operations the shading code is full of.  Each is the compiler's own expansion minus
-// the steps that are the identity inside a range; scripts/ubench/sqrt_exact.hip and rcp_exact.hip compare them with the
-// full forms on ALL 2^32 binary32 patterns on the device (0 mismatches inside the ranges stated here).
+// the steps that are the identity inside a range; tests/test_primitives_gpu.py (test_short_forms_sweep_every_pattern, through
+// ptamd_probe) compares them with the full forms on ALL 2^32 binary32 patterns on the device (0 mismatches inside the ranges stated here).
 // 1.0f / x, correctly rounded, for 2^-95 <= |x| <= 2^125: no v_div_scale / v_div_fixup (7 VALU instead of 11).
 PT_DEV float rcp_exact_in_range(float x)
 {
@@ -61,7 +61,8 @@ PT_DEV float rcp_exact_in_range(float x)
   return __builtin_fmaf(r2, y1, q1);
 }
 // sqrtf(x), correctly rounded, for x == 0, 2^-96 <= x <= +inf and NaN: v_sqrt_f32 and the "is a neighbour better" step,
-// without the 2^32 pre-scaling of small inputs and the 0 / inf fix-up (9 VALU instead of 15).
+// without the 2^32 pre-scaling of small inputs and the 0 / inf fix-up (9 VALU instead of 15).  Negative normal x and -inf give NaN
+// as the full form does (the sweep holds that too); 0 < x < 2^-96 and negative denormals are outside the claim.
 PT_DEV float sqrt_exact_in_range(float x)
 {
   float s = __builtin_amdgcn_sqrtf(x);

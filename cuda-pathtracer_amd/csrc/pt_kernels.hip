@@ -2993,6 +2993,164 @@ hipError_t launch_denoise_pass(const DenoiseParams& q, int pass, hipStream_t str
   }
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------- probe (ptamd_probe, include/ptamd.h "self-tests"; test infrastructure)
+// Hands rows of chosen inputs to the device functions above and in pt_device.h, one lane per row, and returns what they compute.  Launched by
+// nothing but ptamd_probe.  No input becomes an address: texture_idx's result is stored, env_lookup reads through its own clamps, and the only
+// loops run over the launch's arguments (the draws of XORWOW, the patterns of a sweep).
+
+// every pattern first..last through a short form and the compiler's full form; the ranges are the ones pt_device.h claims for the short forms
+PT_DEV void probe_sweep(uint32_t what, const uint32_t* in, uint32_t* out)
+{
+  const unsigned long long first = in[0], last = in[1];
+  unsigned long long bad_in = 0, bad_out = 0;
+  uint32_t first_in = 0xFFFFFFFFu, first_out = 0xFFFFFFFFu;
+  for (unsigned long long i = first + blockIdx.x * 256u + threadIdx.x; i <= last; i += (unsigned long long)gridDim.x * 256u) {
+    const uint32_t bits = (uint32_t)i;
+    const float x = u_as_f(bits);
+    float a, b;
+    bool inside;
+    if (what == PTAMD_PROBE_SWEEP_RCP) {
+      a = rcp_exact_in_range(x); b = 1.0f / x;
+      const float ax = __builtin_fabsf(x);
+      inside = ax >= 0x1p-95f && ax <= 0x1p125f;
+    } else if (what == PTAMD_PROBE_SWEEP_SQRT) {
+      a = sqrt_exact_in_range(x); b = __builtin_sqrtf(x);
+      inside = x == 0.0f || x >= 0x1p-96f || x <= -0x1p-126f || x != x;
+    } else {
+      a = rcp_exact_in_range(sqrt_exact_in_range(x)); b = 1.0f / __builtin_sqrtf(x);
+      inside = x >= 0x1p-96f && x < __builtin_inff();
+    }
+    if (f_as_u(a) == f_as_u(b) || (a != a && b != b)) continue;
+    if (inside) { ++bad_in; first_in = first_in < bits ? first_in : bits; }
+    else { ++bad_out; first_out = first_out < bits ? first_out : bits; }
+  }
+  // (the host set the row to counts of 0 and "first" words of 0xFFFFFFFF)
+  if (bad_in) { atomicAdd(reinterpret_cast<unsigned long long*>(out), bad_in); atomicMin(out + 4, first_in); }
+  if (bad_out) { atomicAdd(reinterpret_cast<unsigned long long*>(out) + 1, bad_out); atomicMin(out + 5, first_out); }
+  if (blockIdx.x == 0u && threadIdx.x == 0u) out[6] = PTAMD_PROBE_SENTINEL;
+}
+
+__global__ void __launch_bounds__(256) pt_probe_kernel(PT_KERNEL_PARAMS, uint32_t what, const uint32_t* in, uint32_t n, uint32_t* out, uint32_t in_words,
+                                                       uint32_t out_words, uint32_t arg)
+{
+  if (what >= PTAMD_PROBE_SWEEP_RCP) { probe_sweep(what, in, out); return; }
+  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+  if (row >= n) return;
+  const uint32_t* r = in + (size_t)row * in_words;
+  uint32_t* w = out + (size_t)row * out_words;
+  const bool active = r[0] != 0u;
+  const auto fl = [r](uint32_t i) { return u_as_f(r[i]); };
+  switch (what) {
+    case PTAMD_PROBE_LEAF_ORDERED: case PTAMD_PROBE_LEAF_FULL: case PTAMD_PROBE_LEAF_SMALL: case PTAMD_PROBE_LEAF_ASM: {
+      const float4 a = make_float4(fl(1), fl(2), fl(3), fl(4)), b = make_float4(fl(5), fl(6), fl(7), fl(8)), c = make_float4(fl(9), fl(10), 0.f, 0.f);
+      const f3 o = mk3(fl(11), fl(12), fl(13)), d = mk3(fl(14), fl(15), fl(16));
+      Best best = { fl(17), fl(18), fl(19), r[20] };
+      if (active) {
+        if (what == PTAMD_PROBE_LEAF_ORDERED) mt_test<true>(a, b, c, o, d, best);
+        else if (what == PTAMD_PROBE_LEAF_FULL) mt_test<false>(a, b, c, o, d, best, false);
+        else if (what == PTAMD_PROBE_LEAF_SMALL) mt_test<false>(a, b, c, o, d, best, true);
+        else mt_test_asm(a, b, make_float2(c.x, c.y), o, d, best);
+      }
+      w[1] = f_as_u(best.t); w[2] = f_as_u(best.u); w[3] = f_as_u(best.v); w[4] = best.idx;
+      break;
+    }
+    case PTAMD_PROBE_SPHERE: {
+      float t = 0.0f;
+      bool hit = false;
+      if (active) hit = intersect_sphere(mk3(fl(1), fl(2), fl(3)), mk3(fl(4), fl(5), fl(6)), mk3(fl(7), fl(8), fl(9)), fl(10), t);
+      w[1] = hit ? 1u : 0u; w[2] = f_as_u(t);
+      break;
+    }
+    case PTAMD_PROBE_WRAPPERS: {
+      float q = 0.0f, s = 0.0f;
+      f3 nv = mk3(0.0f);
+      if (active) q = rcp_hot(fl(1));
+      if (active) s = sqrt_checked(fl(2));
+      if (active) nv = normalize_hot(mk3(fl(3), fl(4), fl(5)));
+      w[1] = f_as_u(q); w[2] = f_as_u(s); w[3] = f_as_u(nv.x); w[4] = f_as_u(nv.y); w[5] = f_as_u(nv.z);
+      break;
+    }
+    case PTAMD_PROBE_MATH: {
+      float v[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+      if (active) {
+        const float x = fl(1);
+        v[0] = rcp_exact_in_range(x); v[1] = 1.0f / x;
+        v[2] = sqrt_exact_in_range(x); v[3] = __builtin_sqrtf(x);
+        v[4] = rcp_exact_in_range(sqrt_exact_in_range(x)); v[5] = 1.0f / __builtin_sqrtf(x);
+      }
+      for (int i = 0; i < 6; ++i) w[1 + i] = f_as_u(v[i]);
+      break;
+    }
+    case PTAMD_PROBE_SINCOS: {
+      float s = 0.0f, c = 0.0f;
+      if (active) pt_sincosf(fl(1), s, c);
+      w[1] = f_as_u(s); w[2] = f_as_u(c);
+      break;
+    }
+    case PTAMD_PROBE_POW: {
+      float v = 0.0f;
+      if (active) v = pt_powf(fl(1), fl(2));
+      w[1] = f_as_u(v);
+      break;
+    }
+    case PTAMD_PROBE_WANG: {
+      uint32_t h = 0u;
+      if (active) h = wang_hash(r[1]);
+      w[1] = h;
+      break;
+    }
+    case PTAMD_PROBE_XORWOW: {
+      Xorwow st = { 0u, 0u, 0u, 0u, 0u, 0u };
+      if (active) {
+        xorwow_init(st, r[1]);
+        for (uint32_t k = 0; k < arg; ++k) w[7u + k] = f_as_u(xorwow_uniform(st));
+      } else {
+        for (uint32_t k = 0; k < arg; ++k) w[7u + k] = 0u;
+      }
+      w[1] = st.v0; w[2] = st.v1; w[3] = st.v2; w[4] = st.v3; w[5] = st.v4; w[6] = st.d;
+      break;
+    }
+    case PTAMD_PROBE_TEXEL: {
+      int idx = 0;
+      if (active) {
+        TexDesc tex;
+        tex.w = (int32_t)r[1]; tex.h = (int32_t)r[2]; tex.nb_chan = (int32_t)r[3]; tex.pad = 0u; tex.offset = 0u;
+        idx = texture_idx(tex, fl(4), fl(5));
+      }
+      w[1] = (uint32_t)idx;
+      break;
+    }
+    case PTAMD_PROBE_ENV: {
+      f3 c = mk3(0.0f);
+      if (active) c = env_lookup(p, mk3(fl(1), fl(2), fl(3)));
+      w[1] = f_as_u(c.x); w[2] = f_as_u(c.y); w[3] = f_as_u(c.z);
+      break;
+    }
+    case PTAMD_PROBE_OUTPUT: {
+      uint32_t px = 0u;
+      if (active) px = output_pixel(mk3(fl(1), fl(2), fl(3)), r[4], arg != 0u, p.gamma_table);
+      w[1] = px;
+      break;
+    }
+    default: {   // PTAMD_PROBE_F2U
+      uint32_t v = 0u;
+      if (active) v = pt_f2u(fl(1));
+      w[1] = v;
+      break;
+    }
+  }
+  w[0] = PTAMD_PROBE_SENTINEL;
+}
+
+// in_words / out_words: ptamd_probe_layout's; blocks: the grid (rows / 256 rounded up; a sweep's own)
+hipError_t launch_probe(const KParams& p, uint32_t what, const uint32_t* in_dev, uint32_t n, uint32_t* out_dev, uint32_t in_words, uint32_t out_words,
+                        uint32_t arg, hipStream_t stream)
+{
+  const uint32_t blocks = what >= PTAMD_PROBE_SWEEP_RCP ? 4096u : (n + 255u) / 256u;
+  hipLaunchKernelGGL(pt_probe_kernel, dim3(blocks), dim3(256), 0, stream, p, what, in_dev, n, out_dev, in_words, out_words, arg);
+  return hipGetLastError();
+}
 #endif
 
 // ---------------------------------------------------------------- launchers
@@ -3173,6 +3331,7 @@ hipError_t resolve_kernels()
     PT_FN(pt_trace_rays_wide_kernel<0>), PT_FN(pt_trace_rays_wide_kernel<1>), PT_FN(pt_trace_rays_wide_kernel<2>),
     PT_FN(pt_features_kernel<1>), PT_FN(pt_features_kernel<2>),
     PT_FN(pt_denoise_kernel<0>), PT_FN(pt_denoise_kernel<1>), PT_FN(pt_denoise_kernel<2>), PT_FN(pt_denoise_kernel<3>),
+    PT_FN(pt_probe_kernel),
   };
   resolve(others, sizeof others / sizeof others[0]);
   return e;

@@ -40,6 +40,9 @@ hipError_t launch_resolve(const KParams& p, hipStream_t stream);
 // gamma step of the tonemap as a table (pt_kernels.hip: gamma_byte): 258 floats, and its exhaustive check
 hipError_t build_gamma_table(float* table_dev, hipStream_t stream);
 hipError_t launch_gamma_selftest(const float* table_dev, uint32_t first, uint32_t count, unsigned long long* out_dev, hipStream_t stream);
+// the probe of the device functions (pt_kernels.hip: pt_probe_kernel; ptamd_probe): rows of in_words words in, rows of out_words words out
+hipError_t launch_probe(const KParams& p, uint32_t what, const uint32_t* in_dev, uint32_t n, uint32_t* out_dev, uint32_t in_words, uint32_t out_words,
+                        uint32_t arg, hipStream_t stream);
 // Resolves every kernel entry point of the code object (setupFunctionTables' role: fail early when the device image is unusable).
 hipError_t resolve_kernels();
 // walk-only kernel fed from a ray queue (pt_kernels.hip: pt_trace_queue_kernel): shape of a configuration, launch

@@ -200,6 +200,49 @@ int ptamd_gamma_table_selftest(ptamd_context* ctx, uint64_t* out_checked, uint64
   return PTAMD_OK;
 }
 
+int ptamd_probe_layout(uint32_t what, uint32_t arg, uint32_t* out_in_words, uint32_t* out_out_words)
+{
+  // {input words (with `active`), output words (with the sentinel)} per PTAMD_PROBE_* number; XORWOW's output grows by its draws
+  static const uint32_t kWords[PTAMD_PROBE_COUNT][2] = {
+    { 21, 5 }, { 21, 5 }, { 21, 5 }, { 21, 5 }, { 11, 3 }, { 6, 6 }, { 2, 7 }, { 2, 3 }, { 3, 2 }, { 2, 2 }, { 2, 7 }, { 6, 2 }, { 4, 4 }, { 5, 2 }, { 2, 2 },
+    { 2, 8 }, { 2, 8 }, { 2, 8 },
+  };
+  if (!out_in_words || !out_out_words || what >= PTAMD_PROBE_COUNT) { set_error("ptamd_probe_layout: bad argument"); return PTAMD_ERR_ARG; }
+  const bool arg_ok = what == PTAMD_PROBE_XORWOW ? (arg >= 1u && arg <= 8192u) : (what == PTAMD_PROBE_OUTPUT ? arg <= 1u : (what == PTAMD_PROBE_ENV || arg == 0u));
+  if (!arg_ok) { set_error("ptamd_probe_layout: bad arg for this probe"); return PTAMD_ERR_ARG; }
+  *out_in_words = kWords[what][0];
+  *out_out_words = kWords[what][1] + (what == PTAMD_PROBE_XORWOW ? arg : 0u);
+  return PTAMD_OK;
+}
+
+int ptamd_probe(ptamd_context* ctx, uint32_t what, const void* in_dev, uint32_t n, void* out_dev, uint32_t arg)
+{
+  if (!ctx || !in_dev || !out_dev) { set_error("ptamd_probe: null argument"); return PTAMD_ERR_ARG; }
+  uint32_t in_words = 0, out_words = 0;
+  if (ptamd_probe_layout(what, arg, &in_words, &out_words) != PTAMD_OK) { set_error("ptamd_probe: bad what or arg"); return PTAMD_ERR_ARG; }
+  const bool sweep = what >= PTAMD_PROBE_SWEEP_RCP;
+  if (n == 0 || n > (1u << 24) || (sweep && n != 1u)) { set_error("ptamd_probe: n out of range"); return PTAMD_ERR_ARG; }
+  if ((uintptr_t)in_dev % 4u || (uintptr_t)out_dev % (sweep ? 8u : 4u)) { set_error("ptamd_probe: misaligned pointer"); return PTAMD_ERR_ARG; }
+  if (what == PTAMD_PROBE_ENV && arg >= ctx->cubemaps.size()) { set_error("ptamd_probe: cubemap id out of range"); return PTAMD_ERR_ARG; }
+  if (what == PTAMD_PROBE_OUTPUT && arg == 1u && !ctx->d_gamma) { set_error("ptamd_probe: the context has no gamma table"); return PTAMD_ERR_ARG; }
+  PT_HIP(hipSetDevice(ctx->device));
+  KParams p = {};
+  p.gamma_table = ctx->d_gamma.get();
+  if (what == PTAMD_PROBE_ENV) {
+    const DeviceCubemap& cm = ctx->cubemaps[arg];
+    p.cubemap = cm.faces.get(); p.cubemap_size = cm.size;
+    p.env_uniform = cm.uniform ? 1u : 0u; p.env_r = cm.color[0]; p.env_g = cm.color[1]; p.env_b = cm.color[2];
+  }
+  if (sweep) {   // counts of 0, "first" words of 0xFFFFFFFF, which the kernel lowers with atomicMin
+    PT_HIP(hipMemsetAsync(out_dev, 0, 8 * sizeof(uint32_t), nullptr));
+    PT_HIP(hipMemsetAsync(static_cast<uint32_t*>(out_dev) + 4, 0xFF, 2 * sizeof(uint32_t), nullptr));
+  }
+  const hipError_t e = launch_probe(p, what, static_cast<const uint32_t*>(in_dev), n, static_cast<uint32_t*>(out_dev), in_words, out_words, arg, nullptr);
+  if (e != hipSuccess) return hip_fail("ptamd_probe", e);
+  PT_HIP(hipDeviceSynchronize());
+  return PTAMD_OK;
+}
+
 int ptamd_set_timeline(ptamd_context* ctx, uint32_t max_waves)
 {
   if (!ctx) { set_error("ptamd_set_timeline: null context"); return PTAMD_ERR_ARG; }

@@ -149,6 +149,10 @@ QUERY_NEAREST, QUERY_ANY = 0, 1
 QUERY_NO_LIGHTS = 1
 QUERY_WALK_AUTO, QUERY_WALK_EVERY_FACE, QUERY_WALK_BINARY, QUERY_WALK_WIDE, QUERY_WALK_RESIDENT = 0, 1, 2, 3, 4
 QUERY_MAX_RAYS = 1 << 28
+# ptamd_probe (include/ptamd.h, "self-tests"): PTAMD_PROBE_* in the header's order
+PROBES = ("leaf_ordered", "leaf_full", "leaf_small", "leaf_asm", "sphere", "wrappers", "math", "sincos", "pow", "wang", "xorwow", "texel", "env", "output",
+          "f2u", "sweep_rcp", "sweep_sqrt", "sweep_rsqrt")
+PROBE_SENTINEL = 0x50524F42
 
 
 class SceneQualityInfo(C.Structure):        # ptamd_scene_quality_info (include/ptamd.h)
@@ -328,6 +332,8 @@ SIGNATURES = {
     "ptamd_device_error_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_phase_cycles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ptamd_gamma_table_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ptamd_probe": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "ptamd_probe_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ptamd_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
                                    C.POINTER(C.c_int32)]),
     "ptamd_host_bvh_trace": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,

@@ -573,6 +573,25 @@ class Context:
         N.check(self._lib.ptamd_gamma_table_selftest(self._h, C.byref(n), C.byref(bad)))
         return n.value, bad.value
 
+    def probe(self, what, rows: np.ndarray, arg: int = 0) -> np.ndarray:
+        """ptamd_probe: runs the device function `what` (a name of native.PROBES or its number) on rows uint32[n, in_words] — word 0 of a
+        row is `active`, 64 consecutive rows are one wave — and returns uint32[n, out_words]: word 0 the sentinel, then the results (the
+        header's table).  A sweep takes rows [[first, last]] and returns the 8-word record.  The output buffer enters filled with 0xCD
+        bytes, so a lane that wrote nothing shows.  Synchronises."""
+        import torch
+        what = N.PROBES.index(what) if isinstance(what, str) else int(what)
+        wi, wo = C.c_uint32(), C.c_uint32()
+        N.check(self._lib.ptamd_probe_layout(what, arg, C.byref(wi), C.byref(wo)))
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if rows.ndim != 2 or rows.shape[1] != wi.value:
+            raise ValueError(f"rows must be uint32[n, {wi.value}] for this probe")
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(rows.view(np.int32)).to(dev)
+        d_out = torch.full((rows.shape[0], wo.value), -842150451, dtype=torch.int32, device=dev)   # 0xCDCDCDCD
+        torch.cuda.synchronize(dev)
+        N.check(self._lib.ptamd_probe(self._h, what, d_in.data_ptr(), rows.shape[0], d_out.data_ptr(), arg))
+        return d_out.cpu().numpy().view(np.uint32)
+
     def device_error_count(self) -> int:
         """Protocol time-outs of the split kernel since creation (0 unless there is a bug); synchronises."""
         v = C.c_uint64()

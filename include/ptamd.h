@@ -883,6 +883,69 @@ int ptamd_scene_is_flat(ptamd_context* ctx, uint32_t scene_id, uint32_t cubemap_
  * a non-zero count means frames rendered by PTAMD_KERNEL_BVH_SPLIT are incomplete). */
 int ptamd_device_error_count(ptamd_context* ctx, uint64_t* out);
 
+/* ---- self-tests: entries that exist for the test suite; nothing on the render path calls them ---- */
+
+/* Test hook.  Hands chosen inputs to the device functions the kernels are made of — the library's own, not copies — and returns what
+ * they compute (tests/test_primitives_gpu.py compares that with the oracle bit for bit).  Synchronous on the null stream.
+ *
+ * Row probes (every `what` below PTAMD_PROBE_SWEEP_RCP): in_dev holds n rows of in_words 32-bit words, out_dev receives n rows of
+ * out_words words (ptamd_probe_layout), one lane per row; rows 64 k .. 64 k + 63 are the lanes 0..63 of one wave.  Word 0 of an input
+ * row is `active`: the function is called inside `if (active)`, so hand-written code is entered with the EXEC mask the rows compose
+ * and the per-wave switches (wave_all) see exactly the active lanes.  After the call EVERY lane writes PTAMD_PROBE_SENTINEL to word 0
+ * of its output row and its results behind it (an inactive lane: the leaf probes' `best` as it came in, zeros elsewhere).
+ *
+ *   what            input row (after `active`)                                     output row (after the sentinel)
+ *   LEAF_ORDERED    e1.xyz e2.xyz v0.xyz idx | o.xyz | d.xyz | best.t u v idx      best.t u v idx          mt_test<true>
+ *   LEAF_FULL       (same)                                                         (same)                  mt_test<false>, small_det 0
+ *   LEAF_SMALL      (same)                                                         (same)                  mt_test<false>, small_det 1
+ *   LEAF_ASM        (same)                                                         (same)                  mt_test_asm
+ *   SPHERE          o.xyz | d.xyz | centre.xyz | radius^2                          hit (0/1), t            intersect_sphere (t enters as 0)
+ *   WRAPPERS        x_rcp | x_sqrt | v.xyz                                         rcp_hot, sqrt_checked, normalize_hot.xyz
+ *   MATH            x                                                              rcp_exact_in_range, 1.0f / x, sqrt_exact_in_range, sqrtf,
+ *                                                                                  rcp_exact(sqrt_exact(x)), 1.0f / sqrtf(x)
+ *   SINCOS          x                                                              sin, cos                pt_sincosf
+ *   POW             x | y                                                          pt_powf(x, y)
+ *   WANG            a                                                              wang_hash(a)
+ *   XORWOW          seed                                                           state v0..v4 d after the draws, then `arg` variates
+ *   TEXEL           w | h | channels | uv.x | uv.y                                 texture_idx (returned, never used as an address)
+ *   ENV             dir.xyz                                                        env_lookup.rgb of cubemap `arg` (reads through its own clamps)
+ *   OUTPUT          radiance.rgb | post_id                                         output_pixel; arg 1: with the context's gamma table
+ *   F2U             x                                                              pt_f2u(x)
+ * The LEAF_SMALL and LEAF_ASM forms are entered by the renderer only with finite record coordinates of at most 1e8 and directions
+ * that are unit vectors or hold NaN; the caller keeps to that domain.
+ *
+ * Sweeps (PTAMD_PROBE_SWEEP_*): n == 1; the input row is {first, last}, binary32 patterns, both inclusive; every pattern between
+ * them goes through the short form and the compiler's full form of pt_device.h (RCP: rcp_exact_in_range(x) against 1.0f / x; SQRT:
+ * sqrt_exact_in_range(x) against sqrtf(x); RSQRT: their composition against 1.0f / sqrtf(x)).  The output row is 8 words (8-byte
+ * aligned): mismatches inside the range the header claims for the short form (64 bits), mismatches outside it (64 bits), the first
+ * mismatching pattern inside, the first outside (0xFFFFFFFF with a count of 0: none), PTAMD_PROBE_SENTINEL, 0.  NaN equals NaN.
+ *
+ * `arg`: XORWOW the number of draws (1..8192), ENV a cubemap id, OUTPUT 0 or 1, 0 for everything else.  n is 1..2^24.  A bad `what`,
+ * n, arg, a null or misaligned pointer: PTAMD_ERR_ARG, nothing is launched or written. */
+#define PTAMD_PROBE_LEAF_ORDERED 0u
+#define PTAMD_PROBE_LEAF_FULL 1u
+#define PTAMD_PROBE_LEAF_SMALL 2u
+#define PTAMD_PROBE_LEAF_ASM 3u
+#define PTAMD_PROBE_SPHERE 4u
+#define PTAMD_PROBE_WRAPPERS 5u
+#define PTAMD_PROBE_MATH 6u
+#define PTAMD_PROBE_SINCOS 7u
+#define PTAMD_PROBE_POW 8u
+#define PTAMD_PROBE_WANG 9u
+#define PTAMD_PROBE_XORWOW 10u
+#define PTAMD_PROBE_TEXEL 11u
+#define PTAMD_PROBE_ENV 12u
+#define PTAMD_PROBE_OUTPUT 13u
+#define PTAMD_PROBE_F2U 14u
+#define PTAMD_PROBE_SWEEP_RCP 15u
+#define PTAMD_PROBE_SWEEP_SQRT 16u
+#define PTAMD_PROBE_SWEEP_RSQRT 17u
+#define PTAMD_PROBE_COUNT 18u
+#define PTAMD_PROBE_SENTINEL 0x50524F42u
+int ptamd_probe(ptamd_context* ctx, uint32_t what, const void* in_dev, uint32_t n, void* out_dev, uint32_t arg);
+/* Words per input and per output row of a probe (host only; PTAMD_ERR_ARG for a bad `what` or `arg`). */
+int ptamd_probe_layout(uint32_t what, uint32_t arg, uint32_t* out_in_words, uint32_t* out_out_words);
+
 /* Test hook.  The resolve pass reads the byte the reference's gamma + store sequence (raytrace.cu:262-268: powf(c, 1/2.2),
  * c * 255 through a truncating conversion) produces off a 256-step table built once per context with that very sequence
  * (PTAMD_GAMMA_TABLE=0: no table).  This compares the table form with the sequence itself for every binary32 value the

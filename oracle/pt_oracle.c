@@ -264,12 +264,29 @@ float or_xorwow_uniform(uint32_t st[6])
 
 /* ------------------------------------------------------------------ textures */
 
-/* IX:20-65 nearest texel, no filtering */
+/* cvt.rzi.s32.f32, what IX:23-24's float -> int initialisations compile to in device code: NaN -> 0, values beyond the range of
+ * int saturate, else truncate.  (A C cast is undefined there; x86 would answer INT_MIN for all three.) */
+static inline int32_t or_f2i(float v)
+{
+  if (!(v == v)) return 0;
+  if (v >= 2147483648.0f) return INT32_MAX;
+  if (v <= -2147483648.0f) return INT32_MIN;
+  return (int32_t)v;
+}
+
+/* IX:20-65 nearest texel, no filtering.  The index arithmetic is 32-bit two's complement (mad.lo.s32), stated here on unsigned words */
 static inline int texture_idx(const or_texture* tex, or_f2 uv)
 {
-  int x = (int)(uv.x * (float)(tex->w - 1));
-  int y = (int)(uv.y * (float)(tex->h - 1));
-  return (y * tex->w + x) * tex->nb_chan;
+  int32_t x = or_f2i(uv.x * (float)(tex->w - 1));
+  int32_t y = or_f2i(uv.y * (float)(tex->h - 1));
+  return (int32_t)(((uint32_t)y * (uint32_t)tex->w + (uint32_t)x) * (uint32_t)tex->nb_chan);
+}
+
+int32_t or_texture_idx(int32_t w, int32_t h, int32_t nb_chan, float uvx, float uvy)
+{
+  or_texture tex = { w, h, nb_chan, 0, 0 };
+  or_f2 uv = { uvx, uvy };
+  return texture_idx(&tex, uv);
 }
 
 /* texCubemap(cubemap_ref, x, y, z) with cudaFilterModeLinear, normalised coordinates
@@ -817,4 +834,77 @@ int or_render(const or_scene* sc, const or_camera* cam, uint32_t width, uint32_t
   free(jobs);
   free(th);
   return 0;
+}
+
+/* ------------------------------------------------------------------ batch forms (tests/primitive_cases.py)
+ * Plain loops over the functions above, for the tests that hand them 10^5 values and more; nothing is restated. */
+
+void or_wang_hash_batch(const uint32_t* a, uint32_t n, uint32_t* out)
+{
+  for (uint32_t i = 0; i < n; ++i) out[i] = or_wang_hash(a[i]);
+}
+
+void or_sincosf_batch(const float* x, uint32_t n, float* s, float* c)
+{
+  for (uint32_t i = 0; i < n; ++i) or_sincosf(x[i], &s[i], &c[i]);
+}
+
+void or_powf_batch(const float* x, const float* y, uint32_t n, float* out)
+{
+  for (uint32_t i = 0; i < n; ++i) out[i] = or_powf(x[i], y[i]);
+}
+
+/* faces: n x 9 floats (three vertices); rays: n x {dir.xyz, origin.xyz}; hit: n; tuv: n x {t, u, v}, written for hits only */
+void or_intersect_triangle_batch(const float* faces, const float* rays, uint32_t n, int32_t* hit, float* tuv)
+{
+  for (uint32_t i = 0; i < n; ++i) {
+    or_face f;
+    memset(&f, 0, sizeof f);
+    memcpy(f.vertices, faces + (size_t)i * 9, 9 * sizeof(float));
+    or_f3 normal;
+    or_f2 uv;
+    or_ray r;
+    memcpy(&r.dir, rays + (size_t)i * 6, 3 * sizeof(float));
+    memcpy(&r.origin, rays + (size_t)i * 6 + 3, 3 * sizeof(float));
+    hit[i] = intersect_triangle(&f, &normal, &uv, &r, &tuv[i * 3], &tuv[i * 3 + 1], &tuv[i * 3 + 2]);
+  }
+}
+
+/* rays: n x {dir.xyz, origin.xyz}; spheres: n x {centre.xyz, radius}; t: n, left as it is where IX:140-155 does not write it */
+void or_intersect_sphere_batch(const float* rays, const float* spheres, uint32_t n, int32_t* hit, float* t)
+{
+  for (uint32_t i = 0; i < n; ++i) {
+    or_light l;
+    memset(&l, 0, sizeof l);
+    memcpy(&l.vec, spheres + (size_t)i * 4, 3 * sizeof(float));
+    l.radius = spheres[(size_t)i * 4 + 3];
+    or_ray r;
+    memcpy(&r.dir, rays + (size_t)i * 6, 3 * sizeof(float));
+    memcpy(&r.origin, rays + (size_t)i * 6 + 3, 3 * sizeof(float));
+    hit[i] = intersect_sphere(&r, &l, &t[i]);
+  }
+}
+
+void or_texture_idx_batch(const int32_t* whc, const float* uv, uint32_t n, int32_t* out)
+{
+  for (uint32_t i = 0; i < n; ++i) out[i] = or_texture_idx(whc[i * 3], whc[i * 3 + 1], whc[i * 3 + 2], uv[i * 2], uv[i * 2 + 1]);
+}
+
+/* xyz: n x 3, the arguments of texCubemap (RT:60,197 pass -z); out: n x 4 */
+void or_tex_cubemap_batch(const or_scene* sc, const float* xyz, uint32_t n, float* out)
+{
+  for (uint32_t i = 0; i < n; ++i) or_tex_cubemap(sc, xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], out + (size_t)i * 4);
+}
+
+/* RT:259-268 from the averaged radiance on: exposure, gamma, post-process, pack.  rad: n x 3; out: n */
+void or_output_batch(const float* rad, const uint32_t* post_id, uint32_t n, uint32_t* out)
+{
+  const float g = 1.0f / 2.2f;
+  for (uint32_t i = 0; i < n; ++i) {
+    float e[3], q[3];
+    or_exposure(rad + (size_t)i * 3, e);
+    e[0] = or_powf(e[0], g); e[1] = or_powf(e[1], g); e[2] = or_powf(e[2], g);
+    or_post_process(post_id[i], e, q);
+    out[i] = or_pack_rgba(q);
+  }
 }

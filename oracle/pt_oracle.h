@@ -115,6 +115,18 @@ void     or_tex_cubemap(const or_scene* sc, float x, float y, float z, float out
 uint32_t or_pack_rgba(const float rad[3]);                           /* raytrace.cu:231-232,266-268 */
 void     or_post_process(uint32_t post_id, const float in[3], float out[3]); /* raytrace.cu:327-352 */
 
+int32_t  or_texture_idx(int32_t w, int32_t h, int32_t nb_chan, float uvx, float uvy);  /* intersection.cuh:20-26 */
+
+/* ---- batch forms of the primitives: plain loops over the functions above (tests/primitive_cases.py) ---- */
+void or_wang_hash_batch(const uint32_t* a, uint32_t n, uint32_t* out);
+void or_sincosf_batch(const float* x, uint32_t n, float* s, float* c);
+void or_powf_batch(const float* x, const float* y, uint32_t n, float* out);
+void or_intersect_triangle_batch(const float* faces, const float* rays, uint32_t n, int32_t* hit, float* tuv);
+void or_intersect_sphere_batch(const float* rays, const float* spheres, uint32_t n, int32_t* hit, float* t);
+void or_texture_idx_batch(const int32_t* whc, const float* uv, uint32_t n, int32_t* out);
+void or_tex_cubemap_batch(const or_scene* sc, const float* xyz, uint32_t n, float* out);
+void or_output_batch(const float* rad, const uint32_t* post_id, uint32_t n, uint32_t* out);
+
 /*
  * One reference raytrace()+kernel() launch (raytrace.cu:212-325) restricted to surface rows
  * [y0, y1).  hash_seed = WangHash(frame_nb) is computed by the caller exactly as

@@ -117,6 +117,16 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                               C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
                               C.c_int32]
     lib.or_last_stats.argtypes = [C.POINTER(C.c_uint64)]
+    lib.or_texture_idx.restype = C.c_int32
+    lib.or_texture_idx.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float]
+    p, n = C.c_void_p, C.c_uint32
+    for name, argtypes in (("or_wang_hash_batch", [p, n, p]), ("or_sincosf_batch", [p, n, p, p]), ("or_powf_batch", [p, p, n, p]),
+                           ("or_intersect_triangle_batch", [p, p, n, p, p]), ("or_intersect_sphere_batch", [p, p, n, p, p]),
+                           ("or_texture_idx_batch", [p, p, n, p]), ("or_output_batch", [p, p, n, p])):
+        getattr(lib, name).restype = None
+        getattr(lib, name).argtypes = argtypes
+    lib.or_tex_cubemap_batch.restype = None
+    lib.or_tex_cubemap_batch.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_uint32, C.c_void_p]
     return lib
 
 
