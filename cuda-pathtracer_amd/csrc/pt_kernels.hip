@@ -27,7 +27,7 @@
 // A side unit compiles this source once more for restart kernels of its own and nothing else: pt_kernels_fma.hip (the contracted
 // instantiations, PT_FMA_BUILD) and pt_kernels_tight.hip (the flat deferring form's tight copy, PT_TIGHT_BUILD: in a unit of its own,
 // where its code cannot move the compiler's choices in the kernels of this one)
-#if defined(PT_FMA_BUILD) || defined(PT_TIGHT_BUILD) || defined(PT_QUERY_BUILD)   /* (PT_QUERY_BUILD: pt_query.hip, for the walk functions alone) */
+#if defined(PT_FMA_BUILD) || defined(PT_TIGHT_BUILD) || defined(PT_QUERY_BUILD) || defined(PT_RADIANCE_BUILD)   /* (PT_QUERY_BUILD: pt_query.hip, for the walk functions alone; PT_RADIANCE_BUILD: pt_radiance.hip, for those and the shading half) */
 #define PT_SIDE_UNIT 1
 #endif
 
@@ -3175,7 +3175,7 @@ static const void* const kBlockwiseEntries[2][2] = {
   { PT_FN(pt_megakernel_blockwise<false, false>), PT_FN(pt_megakernel_blockwise<false, true>) },
   { PT_FN(pt_megakernel_blockwise<true, false>), PT_FN(pt_megakernel_blockwise<true, true>) } };
 #endif
-#ifndef PT_QUERY_BUILD   /* (pt_query.hip names no megakernel: no entry table, no form) */
+#if !defined(PT_QUERY_BUILD) && !defined(PT_RADIANCE_BUILD)   /* (pt_query.hip and pt_radiance.hip name no megakernel: no entry table, no form) */
 #ifdef PT_FMA_BUILD
 constexpr bool kContracted = true;
 #else

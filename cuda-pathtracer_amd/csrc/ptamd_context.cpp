@@ -8,6 +8,7 @@
 #include "pt_relink.h"
 #include "pt_morph.h"
 #include "pt_query.h"
+#include "pt_radiance.h"
 
 #include <cstring>
 #include <memory>
@@ -143,6 +144,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_rig_kernels();
   if (e == hipSuccess) e = resolve_relink_kernel();
   if (e == hipSuccess) e = resolve_query_kernels();
+  if (e == hipSuccess) e = resolve_radiance_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

@@ -149,6 +149,15 @@ QUERY_NEAREST, QUERY_ANY = 0, 1
 QUERY_NO_LIGHTS = 1
 QUERY_WALK_AUTO, QUERY_WALK_EVERY_FACE, QUERY_WALK_BINARY, QUERY_WALK_WIDE, QUERY_WALK_RESIDENT = 0, 1, 2, 3, 4
 QUERY_MAX_RAYS = 1 << 28
+
+
+class RadianceDesc(C.Structure):            # ptamd_radiance_desc (include/ptamd.h): every pointer is a DEVICE address
+    _fields_ = [("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32), ("n", C.c_uint32), ("bounces", C.c_uint32), ("rng_skip", C.c_uint32),
+                ("walk", C.c_uint32), ("flags", C.c_uint32), ("groups", C.c_uint32), ("rays", C.c_void_p), ("seeds", C.c_void_p),
+                ("radiance", C.c_void_p), ("status", C.c_void_p), ("stream", C.c_void_p)]
+
+
+RADIANCE_WALK_AUTO, RADIANCE_WALK_EVERY_FACE, RADIANCE_WALK_BINARY, RADIANCE_WALK_RESIDENT = 0, 1, 2, 3
 # ptamd_probe (include/ptamd.h, "self-tests"): PTAMD_PROBE_* in the header's order
 PROBES = ("leaf_ordered", "leaf_full", "leaf_small", "leaf_asm", "sphere", "wrappers", "math", "sincos", "pow", "wang", "xorwow", "texel", "env", "output",
           "f2u", "sweep_rcp", "sweep_sqrt", "sweep_rsqrt")
@@ -350,6 +359,8 @@ SIGNATURES = {
     "ptamd_query_rays": (C.c_int, [C.c_void_p, C.POINTER(QueryDesc)]),
     "ptamd_host_query_rays": (C.c_int, [C.POINTER(Face), C.c_uint32, C.POINTER(Light), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptamd_query_radiance": (C.c_int, [C.c_void_p, C.POINTER(RadianceDesc)]),
+    "ptamd_host_radiance_seeds": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "ptamd_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseDesc)]),
     "ptamd_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),

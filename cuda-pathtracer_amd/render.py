@@ -530,6 +530,46 @@ class Context:
         N.check(self._lib.ptamd_query_rays(self._h, C.byref(d)))
         return hits, uv
 
+    def query_radiance(self, scene_id: int, cubemap_id: int, rays, seeds, bounces: int = 3, rng_skip: int = 0, walk="auto", groups: int = 0,
+                       radiance=None, status=None, stream=None):
+        """ptamd_query_radiance: the light along rays in device memory, the renderer's static radiance() per ray; asynchronous on
+        `stream`.  rays float32[n, 6] = {dir, origin} and seeds (int32 or uint32 [n], ray i's generator seed) are CUDA tensors.
+        Returns (radiance float32[n, 3], not clamped; status uint8[n]: 1 traced, 0 refused for a NaN or infinite component); outputs
+        the caller did not pass are allocated.  rng_skip: uniforms discarded after seeding (2 reproduces a renderer sample, with
+        radiance_seeds).  walk: "auto", "every_face", "binary", "resident" or the number; groups: the resident form's workgroups."""
+        import torch
+        walks = {"auto": N.RADIANCE_WALK_AUTO, "every_face": N.RADIANCE_WALK_EVERY_FACE, "binary": N.RADIANCE_WALK_BINARY,
+                 "resident": N.RADIANCE_WALK_RESIDENT}
+        if isinstance(walk, str) and walk not in walks:
+            raise ValueError(f"walk is one of {sorted(walks)} or a number")
+
+        def device(name, t, dtypes, width):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name} must be a tensor in the memory of device {self.device}")
+            if t.dtype not in dtypes or not t.is_contiguous() or t.numel() != n * width:
+                raise ValueError(f"{name} must be contiguous, {' or '.join(str(x) for x in dtypes)}, {n} x {width}")
+            return t.data_ptr()
+
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be a float32 tensor of shape (n, 6)")
+        n = int(rays.shape[0])
+        dev = rays.device
+        d = N.RadianceDesc()
+        d.scene_id, d.cubemap_id, d.n, d.bounces, d.rng_skip = scene_id, cubemap_id, n, int(bounces), int(rng_skip)
+        d.walk = walks[walk] if isinstance(walk, str) else int(walk)
+        d.flags, d.groups = 0, int(groups)
+        d.rays = device("rays", rays, (torch.float32,), 6)
+        d.seeds = device("seeds", seeds, (torch.int32, getattr(torch, "uint32", torch.int32)), 1)
+        if radiance is None:
+            radiance = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        d.radiance = device("radiance", radiance, (torch.float32,), 3)
+        d.status = device("status", status, (torch.uint8, torch.bool), 1)
+        d.stream = _stream_handle(stream)
+        N.check(self._lib.ptamd_query_radiance(self._h, C.byref(d)))
+        return radiance, status
+
     def release_captured(self, stream=None) -> None:
         """The graphs captured on `stream` are gone: its sample slab and ring slots are no longer pinned (ptamd_release_captured)."""
         N.check(self._lib.ptamd_release_captured(self._h, _stream_handle(stream)))
@@ -1442,6 +1482,14 @@ def interleaved_rows(height: int, ranks: int, rank: int, band_rows: int) -> int:
 
 def wang_hash(a: int) -> int:
     return N.load().ptamd_wang_hash(a & 0xFFFFFFFF)
+
+
+def radiance_seeds(width: int, height: int, frame_nb: int) -> np.ndarray:
+    """ptamd_host_radiance_seeds (no GPU): uint32[height, width], the generator seeds ptamd_raytrace gives the pixels of frame
+    `frame_nb`, row y of the array = surface row y (as Context.render_features orders its rays)."""
+    out = np.zeros((int(height), int(width)), dtype=np.uint32)
+    N.check(N.load().ptamd_host_radiance_seeds(int(width), int(height), int(frame_nb) & 0xFFFFFFFF, out.ctypes.data))
+    return out
 
 
 class FrameRenderer:

@@ -1039,6 +1039,64 @@ int ptamd_host_query_rays(const ptamd_face* faces, uint32_t n_faces, const ptamd
                           uint32_t mode, uint32_t flags, const float* rays, const float* t_range, uint32_t n,
                           int32_t* hits, float* uv, uint8_t* occluded);
 
+/* ---- Radiance queries for rays in device memory -------------------------------------------------------------
+ *
+ * ptamd_query_radiance returns the light along n rays that lie in DEVICE memory: the integrator of ptamd_raytrace (textures,
+ * normal maps, refraction, light spheres, the cubemap, the XORWOW stream) without its pinhole camera and pixel grid, asynchronously
+ * on `stream`.  What a host needs for light probes, irradiance and lightmap baking, reflection probes, other camera models and
+ * sparse or foveated sampling.
+ *
+ *   definition  for a ray whose six floats are all finite: seed the generator with seeds[i] (curand_init(seeds[i], 0, 0)), draw and
+ *               discard rng_skip uniforms, run the reference's static radiance() (raytrace.cu:64-207, as oracle/pt_oracle.c:
+ *               radiance states it with is_static = 1) on the ray with `bounces` iterations, write the returned acc, NOT clamped.
+ *               A ray with a NaN or infinite component is refused: its radiance is three zeros, its status 0, nothing is traced
+ *               (the oracle's float-to-int casts are undefined there: there is nothing to equal).
+ *   no mirror   there is no ptamd_host_query_radiance.  The shading half is device code and the product may not link the oracle:
+ *               the ORACLE is the definition, exactly as it is for ptamd_raytrace.  The device result equals it bit for bit.
+ *   rays        n * {dir.xyz, origin.xyz}, the layout of ptamd_query_rays.  Directions need not be unit vectors: the integrator's
+ *               own bounce directions are not.
+ *   seeds       n.  A renderer sample of pixel (x, y) in frame f is the aperture-0 camera ray (ptamd_render_features: rays_dev)
+ *               with seed ptamd_host_radiance_seeds' and rng_skip = 2 (the renderer's two camera_dof draws); the accumulator adds
+ *               min(max(out, 0), 1) per channel.
+ *   radiance    n * 3 floats.  status (may be NULL): n bytes, 1 traced, 0 refused.
+ *   walk        PTAMD_RADIANCE_WALK_AUTO chooses by scene and n (csrc/pt_radiance.h: radiance_auto_walk).  The others force a form:
+ *               _EVERY_FACE tests every face for every segment (the definition itself); _BINARY walks the binary tree from L2 (any
+ *               scene); _RESIDENT stages the scene in LDS once per persistent workgroup and refills the lanes of a wave as their
+ *               paths end (scenes that are LDS-resident, as PTAMD_QUERY_WALK_RESIDENT asks).  The answer does not depend on the walk:
+ *               PER SEGMENT, an origin whose max-axis |coordinate| o fails (o + extent) * 2^-21 <= margin_floor, or a direction
+ *               with a NaN, infinite or larger-than-2^100 component, is tested against every face inside the kernel.
+ *   groups      the resident form only: the number of persistent workgroups; 0 = the library's choice.  For tests and measurements.
+ *
+ * The call reads the scene's tables like ptamd_query_rays: ordered against the scene's updates by stream order, margins pending
+ * behind ptamd_scene_update_device settled first (PTAMD_ERR_LIMIT where that would need a host wait inside a capture).  With
+ * margins settled it enqueues one kernel and nothing else (no allocation, no synchronisation, no state of the context written), so
+ * it can be captured into a graph and calls on different streams of one context may be in flight together.
+ * PTAMD_ERR_ARG, before anything is enqueued or written: null context or descriptor; a bad or released scene id; a bad cubemap id; an
+ * unknown walk; flags != 0; bounces outside 1..1024; rng_skip > 16; n > 2^28 (decided from the count alone);
+ * PTAMD_RADIANCE_WALK_RESIDENT on a scene that is not LDS-resident; rays, seeds, radiance or status (when given) that are null, not
+ * device memory of the context's device, smaller than the call reads or writes, or not aligned to their element (4 bytes; status
+ * 1).  n == 0 is PTAMD_OK and touches nothing. */
+enum { PTAMD_RADIANCE_WALK_AUTO = 0, PTAMD_RADIANCE_WALK_EVERY_FACE = 1,
+       PTAMD_RADIANCE_WALK_BINARY = 2, PTAMD_RADIANCE_WALK_RESIDENT = 3 };
+typedef struct {
+  uint32_t scene_id, cubemap_id;
+  uint32_t n;              /* <= PTAMD_QUERY_MAX_RAYS */
+  uint32_t bounces;        /* 1..1024: iterations of the raytrace.cu:67 loop, as ptamd_launch.bounces of a static launch */
+  uint32_t rng_skip;       /* 0..16: uniforms drawn and discarded after seeding, before the path (2 = the renderer's camera_dof draws) */
+  uint32_t walk, flags;    /* flags: none defined yet, must be 0 */
+  uint32_t groups;         /* resident form only: number of persistent workgroups; 0 = the library's choice.  For tests and measurements */
+  const float*    rays;    /* DEVICE, n * {dir.xyz, origin.xyz}: the layout of ptamd_query_rays */
+  const uint32_t* seeds;   /* DEVICE, n: ray i's generator is curand_init(seeds[i], 0, 0), as a pixel's is hash_seed + tid */
+  float*   radiance;       /* DEVICE, n * 3 floats: what radiance() returns, NOT clamped */
+  uint8_t* status;         /* DEVICE, optional, n bytes: 1 traced, 0 refused */
+  void* stream;
+} ptamd_radiance_desc;
+int ptamd_query_radiance(ptamd_context* ctx, const ptamd_radiance_desc* desc);
+/* The seeds ptamd_raytrace gives the pixels of a width x height frame in frame frame_nb, surface row order (row 0 = top, index
+ * y * width + x): WangHash(frame_nb) + tid, tid from the reference's 16x16 launch geometry with its padded grid
+ * (raytrace.cu:227-229).  Host pointers, no device needed.  PTAMD_ERR_ARG for a side outside 1..65536 or a null seeds_out. */
+int ptamd_host_radiance_seeds(uint32_t width, uint32_t height, uint32_t frame_nb, uint32_t* seeds_out);
+
 /* Host mirror of the device BVH walk (same node/triangle records, same float operations),
  * so the builder's "equals brute force" contract can be tested without a GPU.  This is a
  * test hook for the acceleration structure only; it renders nothing.
