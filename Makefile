@@ -9,8 +9,8 @@ ARCH     ?= gfx950
 HIPFLAGS := $(EXTRA_HIPFLAGS) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -fno-vectorize -Iinclude -I$(PKG)/host -I$(PKG)/csrc \
             -Wall -Wextra -Wno-unused-parameter
 LIB      := $(PKG)/libptamd.so
-SRCS     := $(PKG)/csrc/pt_kernels.hip $(PKG)/csrc/pt_kernels_fma.hip $(PKG)/csrc/pt_kernels_tight.hip $(PKG)/csrc/pt_denoise_temporal.hip $(PKG)/csrc/pt_denoise_motion.hip $(PKG)/csrc/pt_adaptive.hip $(PKG)/csrc/pt_upsample.hip $(PKG)/csrc/pt_refit.hip $(PKG)/csrc/pt_refit_device.hip $(PKG)/csrc/pt_reface.hip $(PKG)/csrc/pt_rematerial.hip $(PKG)/csrc/pt_relink.hip $(PKG)/csrc/pt_build.hip $(PKG)/csrc/pt_finish.hip $(PKG)/csrc/pt_rig.hip $(PKG)/csrc/pt_query.hip $(PKG)/csrc/pt_radiance.hip $(PKG)/csrc/ptamd_context.cpp $(PKG)/csrc/ptamd_scene.cpp $(PKG)/csrc/ptamd_scene_update.cpp $(PKG)/csrc/ptamd_scene_materials.cpp $(PKG)/csrc/ptamd_rig.cpp $(PKG)/csrc/ptamd_launch.cpp $(PKG)/csrc/ptamd_denoise.cpp $(PKG)/csrc/ptamd_adaptive.cpp $(PKG)/csrc/ptamd_upsample.cpp $(PKG)/csrc/ptamd_tuning.cpp $(PKG)/csrc/ptamd_query.cpp $(PKG)/csrc/ptamd_radiance.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_builder.cpp $(PKG)/host/bvh_walks.cpp $(PKG)/host/skip_links.cpp $(PKG)/host/scene_tables.cpp $(PKG)/host/pose.cpp $(PKG)/host/skin.cpp $(PKG)/host/morph.cpp $(PKG)/host/query.cpp $(PKG)/host/radiance.cpp $(PKG)/host/image_decode.cpp $(PKG)/host/image_png.cpp $(PKG)/host/image_resize.cpp
-HDRS     := include/ptamd.h $(PKG)/host/ptamd_internal.h $(PKG)/csrc/pt_device.h $(PKG)/csrc/pt_round.h $(PKG)/csrc/pt_tight_tiles.h $(PKG)/csrc/pt_tight_body.h $(PKG)/csrc/pt_tight_shade.h $(PKG)/csrc/pt_launch.h $(PKG)/csrc/pt_denoise.h $(PKG)/csrc/pt_denoise_temporal.h $(PKG)/csrc/pt_denoise_motion.h $(PKG)/csrc/pt_adaptive.h $(PKG)/csrc/pt_upsample.h $(PKG)/csrc/pt_refit.h $(PKG)/csrc/pt_refit_device.h $(PKG)/csrc/pt_reface.h $(PKG)/csrc/pt_rematerial.h $(PKG)/csrc/pt_relink.h $(PKG)/csrc/pt_build.h $(PKG)/csrc/pt_finish.h $(PKG)/csrc/pt_pose.h $(PKG)/csrc/pt_skin.h $(PKG)/csrc/pt_morph.h $(PKG)/csrc/pt_query.h $(PKG)/csrc/pt_query_search.h $(PKG)/csrc/pt_radiance.h $(PKG)/csrc/ptamd_host.h $(PKG)/csrc/ptamd_owners.h $(PKG)/csrc/ptamd_tuning.h
+SRCS     := $(PKG)/csrc/pt_kernels.hip $(PKG)/csrc/pt_kernels_fma.hip $(PKG)/csrc/pt_kernels_tight.hip $(PKG)/csrc/pt_denoise_temporal.hip $(PKG)/csrc/pt_denoise_motion.hip $(PKG)/csrc/pt_adaptive.hip $(PKG)/csrc/pt_upsample.hip $(PKG)/csrc/pt_refit.hip $(PKG)/csrc/pt_refit_device.hip $(PKG)/csrc/pt_reface.hip $(PKG)/csrc/pt_rematerial.hip $(PKG)/csrc/pt_relink.hip $(PKG)/csrc/pt_build.hip $(PKG)/csrc/pt_finish.hip $(PKG)/csrc/pt_rig.hip $(PKG)/csrc/pt_query.hip $(PKG)/csrc/pt_radiance.hip $(PKG)/csrc/pt_gather.hip $(PKG)/csrc/ptamd_context.cpp $(PKG)/csrc/ptamd_scene.cpp $(PKG)/csrc/ptamd_scene_update.cpp $(PKG)/csrc/ptamd_scene_materials.cpp $(PKG)/csrc/ptamd_rig.cpp $(PKG)/csrc/ptamd_launch.cpp $(PKG)/csrc/ptamd_denoise.cpp $(PKG)/csrc/ptamd_adaptive.cpp $(PKG)/csrc/ptamd_upsample.cpp $(PKG)/csrc/ptamd_tuning.cpp $(PKG)/csrc/ptamd_query.cpp $(PKG)/csrc/ptamd_radiance.cpp $(PKG)/csrc/ptamd_gather.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_builder.cpp $(PKG)/host/bvh_walks.cpp $(PKG)/host/skip_links.cpp $(PKG)/host/scene_tables.cpp $(PKG)/host/pose.cpp $(PKG)/host/skin.cpp $(PKG)/host/morph.cpp $(PKG)/host/query.cpp $(PKG)/host/radiance.cpp $(PKG)/host/gather.cpp $(PKG)/host/image_decode.cpp $(PKG)/host/image_png.cpp $(PKG)/host/image_resize.cpp
+HDRS     := include/ptamd.h $(PKG)/host/ptamd_internal.h $(PKG)/csrc/pt_device.h $(PKG)/csrc/pt_round.h $(PKG)/csrc/pt_tight_tiles.h $(PKG)/csrc/pt_tight_body.h $(PKG)/csrc/pt_tight_shade.h $(PKG)/csrc/pt_launch.h $(PKG)/csrc/pt_denoise.h $(PKG)/csrc/pt_denoise_temporal.h $(PKG)/csrc/pt_denoise_motion.h $(PKG)/csrc/pt_adaptive.h $(PKG)/csrc/pt_upsample.h $(PKG)/csrc/pt_refit.h $(PKG)/csrc/pt_refit_device.h $(PKG)/csrc/pt_reface.h $(PKG)/csrc/pt_rematerial.h $(PKG)/csrc/pt_relink.h $(PKG)/csrc/pt_build.h $(PKG)/csrc/pt_finish.h $(PKG)/csrc/pt_pose.h $(PKG)/csrc/pt_skin.h $(PKG)/csrc/pt_morph.h $(PKG)/csrc/pt_query.h $(PKG)/csrc/pt_query_search.h $(PKG)/csrc/pt_radiance.h $(PKG)/csrc/pt_gather.h $(PKG)/csrc/ptamd_host.h $(PKG)/csrc/ptamd_owners.h $(PKG)/csrc/ptamd_tuning.h
 # identity of the build: EVERY source and header the library is compiled from + the flags, in this order (the host half decides what
 # the device executes too: leaf size, launch geometry and slab sizing in ptamd_launch.cpp, the tree's shape in bvh_builder.cpp).
 # profiles/pmc_*.json carry the id of the build their counters were collected on; bench.py refuses to price a roofline with counters

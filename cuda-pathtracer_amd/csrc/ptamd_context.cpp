@@ -9,6 +9,7 @@
 #include "pt_morph.h"
 #include "pt_query.h"
 #include "pt_radiance.h"
+#include "pt_gather.h"
 
 #include <cstring>
 #include <memory>
@@ -145,6 +146,7 @@ int ptamd_setup_function_tables(ptamd_context* ctx)
   if (e == hipSuccess) e = resolve_relink_kernel();
   if (e == hipSuccess) e = resolve_query_kernels();
   if (e == hipSuccess) e = resolve_radiance_kernels();
+  if (e == hipSuccess) e = resolve_gather_kernels();
   if (e != hipSuccess) return hip_fail("ptamd_setup_function_tables: device code object", e);
   return PTAMD_OK;
 }

@@ -158,6 +158,17 @@ class RadianceDesc(C.Structure):            # ptamd_radiance_desc (include/ptamd
 
 
 RADIANCE_WALK_AUTO, RADIANCE_WALK_EVERY_FACE, RADIANCE_WALK_BINARY, RADIANCE_WALK_RESIDENT = 0, 1, 2, 3
+
+
+class GatherDesc(C.Structure):              # ptamd_gather_desc (include/ptamd.h): every pointer is a DEVICE address
+    _fields_ = [("scene_id", C.c_uint32), ("cubemap_id", C.c_uint32), ("n", C.c_uint32), ("samples", C.c_uint32), ("block", C.c_uint32),
+                ("mode", C.c_uint32), ("bounces", C.c_uint32), ("walk", C.c_uint32), ("flags", C.c_uint32), ("groups", C.c_uint32),
+                ("offset", C.c_float), ("points", C.c_void_p), ("seeds", C.c_void_p), ("out", C.c_void_p), ("partials", C.c_void_p),
+                ("status", C.c_void_p), ("stream", C.c_void_p)]
+
+
+GATHER_HEMISPHERE, GATHER_SPHERE_SH9 = 0, 1
+GATHER_MAX_SAMPLES, GATHER_MAX_BLOCK, GATHER_DEFAULT_BLOCK = 65536, 4096, 64
 # ptamd_probe (include/ptamd.h, "self-tests"): PTAMD_PROBE_* in the header's order
 PROBES = ("leaf_ordered", "leaf_full", "leaf_small", "leaf_asm", "sphere", "wrappers", "math", "sincos", "pow", "wang", "xorwow", "texel", "env", "output",
           "f2u", "sweep_rcp", "sweep_sqrt", "sweep_rsqrt")
@@ -361,6 +372,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptamd_query_radiance": (C.c_int, [C.c_void_p, C.POINTER(RadianceDesc)]),
     "ptamd_host_radiance_seeds": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "ptamd_gather_radiance": (C.c_int, [C.c_void_p, C.POINTER(GatherDesc)]),
+    "ptamd_host_gather_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptamd_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseDesc)]),
     "ptamd_render_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera), C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -570,6 +570,64 @@ class Context:
         N.check(self._lib.ptamd_query_radiance(self._h, C.byref(d)))
         return radiance, status
 
+    def gather_radiance(self, scene_id: int, cubemap_id: int, points, seeds, samples: int, block: int = 0, mode="hemisphere", bounces: int = 3,
+                        offset: float = 0.03, walk="auto", groups: int = 0, out=None, status=None, partials=None, stream=None):
+        """ptamd_gather_radiance: per point the mean of `samples` radiance samples drawn, traced and summed on the device;
+        asynchronous on `stream`.  points float32[n, 6] = {position, normal} and seeds (int32 or uint32 [n]; space them by at least
+        `samples`) are CUDA tensors.  mode "hemisphere" returns out float32[n, 3] (times pi: irradiance), "sphere_sh9" float32[n, 27]
+        (coefficient-major; times 4 pi: SH coefficients).  block: the samples one partial sum holds (0 = 64), part of the result's
+        definition.  Returns (out, status uint8[n]: 1 gathered, 0 refused for a NaN or infinite float); out, status and the
+        workspace partials (float32, n * ceil(samples / block) * W, needed with more than one block) are allocated when not passed.
+        walk, groups: as query_radiance."""
+        import torch
+        modes = {"hemisphere": N.GATHER_HEMISPHERE, "sphere_sh9": N.GATHER_SPHERE_SH9}
+        walks = {"auto": N.RADIANCE_WALK_AUTO, "every_face": N.RADIANCE_WALK_EVERY_FACE, "binary": N.RADIANCE_WALK_BINARY,
+                 "resident": N.RADIANCE_WALK_RESIDENT}
+        if isinstance(mode, str) and mode not in modes:
+            raise ValueError(f"mode is one of {sorted(modes)} or a number")
+        if isinstance(walk, str) and walk not in walks:
+            raise ValueError(f"walk is one of {sorted(walks)} or a number")
+        samples, block = int(samples), int(block)
+        if not 1 <= samples <= N.GATHER_MAX_SAMPLES or not 0 <= block <= N.GATHER_MAX_BLOCK:
+            raise ValueError(f"samples is 1..{N.GATHER_MAX_SAMPLES}, block 0..{N.GATHER_MAX_BLOCK}")
+
+        def device(name, t, dtypes, count):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name} must be a tensor in the memory of device {self.device}")
+            if t.dtype not in dtypes or not t.is_contiguous() or t.numel() != count:
+                raise ValueError(f"{name} must be contiguous, {' or '.join(str(x) for x in dtypes)}, {count} elements")
+            return t.data_ptr()
+
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 6:
+            raise ValueError("points must be a float32 tensor of shape (n, 6)")
+        n = int(points.shape[0])
+        dev = points.device
+        d = N.GatherDesc()
+        d.scene_id, d.cubemap_id, d.n, d.samples, d.block, d.bounces = scene_id, cubemap_id, n, samples, block, int(bounces)
+        d.mode = modes[mode] if isinstance(mode, str) else int(mode)
+        d.walk = walks[walk] if isinstance(walk, str) else int(walk)
+        d.flags, d.groups, d.offset = 0, int(groups), float(offset)
+        width = 27 if d.mode == N.GATHER_SPHERE_SH9 else 3
+        n_blocks = -(-samples // (block or N.GATHER_DEFAULT_BLOCK))
+        d.points = device("points", points, (torch.float32,), n * 6)
+        d.seeds = device("seeds", seeds, (torch.int32, getattr(torch, "uint32", torch.int32)), n)
+        if out is None:
+            out = torch.empty((n, width), dtype=torch.float32, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        if partials is None and n_blocks > 1:
+            partials = torch.empty(n * n_blocks * width, dtype=torch.float32, device=dev)
+        d.out = device("out", out, (torch.float32,), n * width)
+        d.status = device("status", status, (torch.uint8, torch.bool), n)
+        if partials is not None:
+            if not isinstance(partials, torch.Tensor) or not partials.is_cuda or partials.dtype != torch.float32 or not partials.is_contiguous() \
+                    or (n_blocks > 1 and partials.numel() < n * n_blocks * width):
+                raise ValueError(f"partials must be a contiguous float32 tensor of the device with at least {n * n_blocks * width} elements")
+            d.partials = partials.data_ptr()
+        d.stream = _stream_handle(stream)
+        N.check(self._lib.ptamd_gather_radiance(self._h, C.byref(d)))
+        return out, status
+
     def release_captured(self, stream=None) -> None:
         """The graphs captured on `stream` are gone: its sample slab and ring slots are no longer pinned (ptamd_release_captured)."""
         N.check(self._lib.ptamd_release_captured(self._h, _stream_handle(stream)))
@@ -1490,6 +1548,27 @@ def radiance_seeds(width: int, height: int, frame_nb: int) -> np.ndarray:
     out = np.zeros((int(height), int(width)), dtype=np.uint32)
     N.check(N.load().ptamd_host_radiance_seeds(int(width), int(height), int(frame_nb) & 0xFFFFFFFF, out.ctypes.data))
     return out
+
+
+def gather_rays(points, seeds, samples: int, mode="hemisphere", offset: float = 0.03):
+    """ptamd_host_gather_rays (no GPU), the ray side of gather_radiance's definition: points float32[n, 6], seeds uint32[n] ->
+    (rays float32[n * samples, 6] = {dir, origin}, seeds uint32[n * samples], weights float32[n * samples, 9] or None), sample s of
+    point i at row i * samples + s: what Context.query_radiance takes with rng_skip = 2.  A refused point's rays are NaN."""
+    modes = {"hemisphere": N.GATHER_HEMISPHERE, "sphere_sh9": N.GATHER_SPHERE_SH9}
+    m = modes[mode] if isinstance(mode, str) else int(mode)
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    n, samples = len(points), int(samples)
+    if len(seeds) != n:
+        raise ValueError("one seed per point")
+    if not 1 <= samples <= N.GATHER_MAX_SAMPLES:
+        raise ValueError(f"samples is 1..{N.GATHER_MAX_SAMPLES}")
+    rays = np.zeros((n * samples, 6), dtype=np.float32)
+    seeds_out = np.zeros(n * samples, dtype=np.uint32)
+    weights = np.zeros((n * samples, 9), dtype=np.float32) if m == N.GATHER_SPHERE_SH9 else None
+    N.check(N.load().ptamd_host_gather_rays(points.ctypes.data, seeds.ctypes.data, n, samples, m, float(offset), rays.ctypes.data,
+                                            seeds_out.ctypes.data, weights.ctypes.data if weights is not None else None))
+    return rays, seeds_out, weights
 
 
 class FrameRenderer:

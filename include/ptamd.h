@@ -1097,6 +1097,79 @@ int ptamd_query_radiance(ptamd_context* ctx, const ptamd_radiance_desc* desc);
  * (raytrace.cu:227-229).  Host pointers, no device needed.  PTAMD_ERR_ARG for a side outside 1..65536 or a null seeds_out. */
 int ptamd_host_radiance_seeds(uint32_t width, uint32_t height, uint32_t frame_nb, uint32_t* seeds_out);
 
+/* ---- Radiance gathered per point on the device -----------------------------------------------------------------
+ *
+ * ptamd_gather_radiance takes n points with a normal and one seed a point, in DEVICE memory, and returns per point the mean of
+ * `samples` radiance samples (3 floats), or its projection on the nine real spherical harmonics of bands 0..2 (27 floats): the
+ * step from one sample of ptamd_query_radiance to a converged value at a point, for light probes, irradiance and lightmap baking.
+ * Directions are drawn, paths traced and samples summed in the lane; no ray, seed or per-sample result goes to memory.
+ *
+ *   refusal     a point with a NaN or infinite float among its six is refused: its W outputs are zeros, its status 0, nothing traced.
+ *   sample s    of point i: the generator is curand_init(seeds[i] + s, 0, 0), the sum in 32-bit wrap-around; u1 and u2 are its
+ *               first two uniforms; the direction d follows from them by mode; the origin is point + d * offset (a multiply, then
+ *               an add); the sample L is what ptamd_query_radiance defines for the ray {d, origin} with that seed and rng_skip = 2,
+ *               its refusal included: a generated ray with a NaN or infinite component gives three zeros and still counts in the
+ *               divisor.  A host spaces the seeds of its points by at least `samples`, as the renderer's hash_seed + tid spaces a
+ *               frame's pixels by one: closer seeds make two points share generators.
+ *   HEMISPHERE  the integrator's own diffuse bounce about the normal AS GIVEN, not normalised (raytrace.cu:106-123, operation for
+ *               operation as oracle/pt_oracle.c: radiance states it): phi = (float)(2.0 * pi * (double)u2); sin_t = sqrtf(u1);
+ *               cos_t = sqrtf(1 - u1); axis = (double)fabsf(n.x) > .1 ? (0, 1, 0) : (1, 0, 0); u = normalize(cross(axis, n));
+ *               v = cross(n, u); d = normalize(v * sin_t * cos(phi) + u * sin(phi) * sin_t + n * cos_t), sin and cos the build's
+ *               defined sincos.  x_s = L, W = 3 words.  (A zero normal gives NaN directions: every sample is refused, the result zeros.)
+ *   SPHERE_SH9  uniform on the sphere, the normal unused: z = 1.0f - 2.0f * u1; r = sqrtf(1.0f - z * z); phi as above;
+ *               d = (r * cos(phi), r * sin(phi), z).  The weights, in binary32 on d's components x, y, z, in the written order:
+ *               Y0 = 0.282095f; Y1 = 0.488603f * y; Y2 = 0.488603f * z; Y3 = 0.488603f * x; Y4 = 1.092548f * (x * y);
+ *               Y5 = 1.092548f * (y * z); Y6 = 0.315392f * (3.0f * (z * z) - 1.0f); Y7 = 1.092548f * (x * z);
+ *               Y8 = 0.546274f * (x * x - y * y).  x_s[k][c] = L_c * Y_k, W = 27 words, coefficient-major (k * 3 + channel).
+ *   sum         per word, in binary32 and unfused.  Block b holds samples b * B .. min(S, (b + 1) * B) - 1;
+ *               P_b = ((0.0f + x_bB) + x_bB+1) + ...;  T = ((0.0f + P_0) + P_1) + ...;  out = T / (float)S.
+ *               B (`block`) is part of the definition: it fixes the association, and it is what lets one point's samples spread
+ *               over lanes.  The host multiplies by pi for irradiance (HEMISPHERE: the cosine-weighted mean) or by 4 pi for SH
+ *               coefficients (SPHERE_SH9: the uniform mean).
+ *   partials    the call's workspace, n * ceil(S / B) * W floats of the caller's: the call allocates nothing.  Not read or
+ *               written when ceil(S / B) == 1 (it may be NULL then).
+ *   walk, groups  as ptamd_radiance_desc's; PTAMD_RADIANCE_WALK_AUTO chooses by scene and the number of work units
+ *               n * ceil(S / B) (csrc/pt_gather.h: gather_auto_walk).  The result depends on neither.
+ *
+ * The call behaves as ptamd_query_radiance does: a reader of the scene's tables ordered by stream order, pending margins settled
+ * first (PTAMD_ERR_LIMIT where that would need a host wait inside a capture); then it enqueues one kernel, or two when
+ * ceil(S / B) > 1 (the second sums the partials), and nothing else: no allocation, no synchronisation, no state of the context
+ * written.  It can be captured into a graph, and calls on different streams may be in flight together (each with partials of its own).
+ * PTAMD_ERR_ARG, before anything is enqueued or written: everything ptamd_query_radiance refuses (null context or descriptor, a bad
+ * or released scene id, a bad cubemap id, an unknown walk, flags != 0, bounces outside 1..1024, n > 2^28, PTAMD_RADIANCE_WALK_RESIDENT
+ * on a scene that is not LDS-resident); samples outside 1..65536; block above 4096; an unknown mode; an offset that is NaN or
+ * infinite; n * ceil(S / B) > 2^28 (decided from the counts alone); points, seeds, out, status (when given) or partials (when
+ * ceil(S / B) > 1) that are null, not device memory of the context's device, smaller than the call reads or writes, or not aligned
+ * to their element (4 bytes; status 1).  n == 0 is PTAMD_OK and touches nothing. */
+enum { PTAMD_GATHER_HEMISPHERE = 0, PTAMD_GATHER_SPHERE_SH9 = 1 };
+#define PTAMD_GATHER_MAX_SAMPLES 65536u
+#define PTAMD_GATHER_MAX_BLOCK   4096u
+typedef struct {
+  uint32_t scene_id, cubemap_id;
+  uint32_t n;            /* points, <= PTAMD_QUERY_MAX_RAYS */
+  uint32_t samples;      /* S: 1..PTAMD_GATHER_MAX_SAMPLES per point */
+  uint32_t block;        /* B: samples one partial sum holds, 1..PTAMD_GATHER_MAX_BLOCK; 0 = 64.  Part of the definition (above) */
+  uint32_t mode;         /* PTAMD_GATHER_* */
+  uint32_t bounces;      /* 1..1024, as ptamd_radiance_desc.bounces */
+  uint32_t walk, flags;  /* PTAMD_RADIANCE_WALK_*; flags must be 0 */
+  uint32_t groups;       /* resident form only, as ptamd_radiance_desc.groups */
+  float    offset;       /* finite; a sample's origin is point + direction * offset (the reference steps 0.03 off a surface) */
+  const float*    points;   /* DEVICE, n * {position.xyz, normal.xyz} */
+  const uint32_t* seeds;    /* DEVICE, n */
+  float*   out;             /* DEVICE, n * W floats; W = 3 (HEMISPHERE) or 27 (SH9: coefficient-major, k*3 + channel) */
+  float*   partials;        /* DEVICE, n * ceil(S/B) * W floats of workspace; may be NULL when ceil(S/B) == 1 */
+  uint8_t* status;          /* DEVICE, optional, n bytes: 1 gathered, 0 refused */
+  void* stream;
+} ptamd_gather_desc;
+int ptamd_gather_radiance(ptamd_context* ctx, const ptamd_gather_desc* desc);
+/* The definition's ray side.  Host pointers, no device needed: rays_out n * S * {dir.xyz, origin.xyz} and seeds_out n * S, sample s
+ * of point i at index i * S + s, as ptamd_query_radiance takes them with rng_skip = 2; weights_out n * S * 9, the Y_k of each
+ * direction (SPHERE_SH9 only, else it may be NULL).  A refused point's rays are six NaNs each (rays ptamd_query_radiance refuses),
+ * its weights zeros.  PTAMD_ERR_ARG, with nothing written, for an unknown mode, samples outside 1..65536, an offset that is not
+ * finite, n > 2^28 and a null pointer where n > 0 says there is something behind it. */
+int ptamd_host_gather_rays(const float* points, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t mode,
+                           float offset, float* rays_out, uint32_t* seeds_out, float* weights_out);
+
 /* Host mirror of the device BVH walk (same node/triangle records, same float operations),
  * so the builder's "equals brute force" contract can be tested without a GPU.  This is a
  * test hook for the acceleration structure only; it renders nothing.
